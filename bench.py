@@ -2,6 +2,7 @@
 """bench.py -- env steps/s of the HIP hot path (BASELINE.json metric), one JSON line on rank 0.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--grid G] [--launch many|seq|graph|eager] [--mode env|a2c]
+                  [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one batched MobiEnvironment.step() over all envs of a rank (mobile_env.py:150-194).
@@ -12,7 +13,7 @@ env bench -- only the barrier / max-reduce of the timing.  `python bench.py --gp
 ranks (one process per GPU, spawned before anything touches the GPU) and fails loudly if fewer than N joined.
 
 --launch  how the K steps reach the GPU.  Every form computes the same steps bit for bit (tests/test_step_many_gpu.py) and writes
-          all nine outputs of every step; the line reports the other forms under "other_launch_forms":
+          all nine outputs of every step; a --full line reports the other forms under "other_launch_forms":
             many   (default) uavenv_step_many: <= 100 consecutive steps per launch, walker / group / UAV state carried in registers
                    between them (the benchmark's actions are resident in HBM and do not depend on observations, which is the
                    case this entry point exists for).  A 4096-env single-step kernel lasts 8 us whatever launches it, 5.8 us of it
@@ -23,7 +24,13 @@ ranks (one process per GPU, spawned before anything touches the GPU) and fails l
             eager  one ctypes call per step (round 1's bench)
 --mode a2c  BASELINE configs[2] (N=1) / configs[3] (N=8): 8192 envs per GPU, MLP actor-critic, 50-step rollouts, one update per
             rollout with ONE flat RCCL all-reduce of the 80.8 MB gradient inside the timed region (a2c_single_thread.py:107-133).
-            The default (env) run appends the same measurement as the "a2c" object of its line unless --no-a2c.
+            A --full env run appends the same measurement as the "a2c" object of its line unless --no-a2c.
+--full      env mode: everything beyond the headline -- the other launch forms, G = 200, the A2C leg, the CPU baseline and the
+            roofline block (with its launch-timing repeat of the timed steps).  A plain run sets up, warms up, times the K steps,
+            writes the outputs if asked and prints the line: metric, value, unit, higher_is_better, dtype, ms_per_step (wall time of
+            one timed step), steps, warmup, config.
+--dump-outputs DIR  env mode: the nine outputs of the timed path's last step as DIR/<name>.npy (float32 / float64), for comparing
+            two builds output for output: with the same arguments the inputs (env seed, action pool) are the same from run to run.
 """
 import argparse
 import json
@@ -44,6 +51,7 @@ SIMD_ISSUE_HZ = 2.4e9 / 4.0   # one VALU wave-instruction per 4 cycles per SIMD 
 CHUNK = 100                   # steps per captured graph / per uavenv_step_many launch (divides MAXSTEP = 2000)
 A2C_ENVS, A2C_ROLLOUT = 8192, 50
 PREWARM_STEPS = 400           # untimed steps on a scratch env right before the headline measurement (clock ramp; see measure_env)
+PREWARM_SECONDS = 0.3         # then this long of the headline's own launch form on the scratch env (see measure_env)
 CPU_THREAD_CAP = 16           # cpu_baseline threads: the CPU share of a one-GPU job on this pool (stated in the line)
 
 
@@ -230,7 +238,7 @@ def parse_args(argv):
     ap.add_argument("--chunk", type=int, default=CHUNK, help="steps per uavenv_step_many launch / per captured graph (default 100; profiling "
                     "runs use 20 to repeat the launch shape of the driver's --steps 20 call)")
     ap.add_argument("--grid", type=int, default=GRID, help="grid cells per side (100 = every reference script; 200 = the class default, "
-                    "mobile_env.py:37; the default run also reports G = 200 under other_grids)")
+                    "mobile_env.py:37; a --full run also reports G = 200 under other_grids)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-a2c", action="store_true", help="env mode: skip the appended A2C / gradient all-reduce measurement")
     ap.add_argument("--no-alt", action="store_true", help="env mode: skip the secondary eager / step_many measurements")
@@ -244,7 +252,21 @@ def parse_args(argv):
                     "census / barrier / max-reduce and rank 0 prints a line marked rehearsal (value null).  CPU test of the launcher")
     ap.add_argument("--n-bs", type=int, default=N_BS, help="secondary measurements only (default = BASELINE workload)")
     ap.add_argument("--n-ue", type=int, default=N_UE, help="secondary measurements only (default = BASELINE workload)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="env mode: also run everything beyond the headline -- the other launch forms, "
+                    "G = 200, the appended A2C measurement, the CPU baseline and the roofline block with its launch-timing repeat of the "
+                    "timed steps (--no-alt / --no-a2c / --no-cpu-baseline still drop a part).  Without it a run sets up, warms up, times "
+                    "the K steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="env mode: after the timed steps write the nine outputs of the "
+                    "timed path's last step (rank 0's envs) as DIR/<name>.npy, float32 / float64 (integers as float64), at most 64 MB in all "
+                    "(beyond that a fixed, seeded sample of env rows, listed in DIR/env_index.npy)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs is not None and args.mode != "env":
+        ap.error("--dump-outputs is an env-mode option")
+    return args
 
 
 def init_dist(args, rank, local_rank, world):
@@ -295,6 +317,8 @@ class EnvRun:
         self.tape = torch.empty((self.chunk, env.n_envs), dtype=torch.int64, device=env.device)
         self.graphs = {}
         self.many_out = {}
+        self._snapped = False
+        self.keep_last = False    # compile(): keep the last step's outputs of the one-kernel-per-step forms from a trailing reset (dumps)
         self.max_step = int(env.cfg.max_step)
         self.t = 0            # steps since the last reset (the constructor's reset counts as one)
         self.cursor = 0       # next pool row
@@ -345,9 +369,15 @@ class EnvRun:
         import ctypes as C
         import functools
 
+        import torch
+
         env, prog = self.env, []
         stream = C.c_void_p(env._stream())
-        for n, reset_after in self.plan(n_steps):
+        segs = self.plan(n_steps)
+        self._snapped = False
+        for i, (n, reset_after) in enumerate(segs):
+            self.last_n = n
+            self._ready(n)
             if getattr(self, "_staged", False):
                 self._staged = False
             else:
@@ -367,13 +397,37 @@ class EnvRun:
                 prog.extend(functools.partial(env.step, self.tape[t]) for t in range(n))
             self.t += n
             if reset_after:
+                if self.keep_last and self.launch != "many" and i == len(segs) - 1:
+                    # the steps end on a reset, which rewrites env.out: one device copy of the output arena before it keeps the
+                    # last step's outputs for last_outputs() (the multi-step form's output blocks are not touched by a reset)
+                    if getattr(self, "_snap", None) is None:
+                        self._snap = torch.empty_like(env._arena)
+                    prog.append(functools.partial(self._snap.copy_, env._arena))
+                    self._snapped = True
                 prog.append(env.reset)
                 self.t = 0
         return prog
 
+    def last_outputs(self):
+        """Copies of the last step's outputs after the last compiled program has run: its block of the multi-step output, or env.out
+        for the one-kernel-per-step forms -- taken before a trailing reset when keep_last was set for compile()."""
+        if self.launch == "many":
+            return {k: v[self.last_n - 1].clone() for k, v in self.many_out[self.last_n].items()}
+        if self._snapped:
+            return {name: self._snap[o:o + nbytes].view(dt).view(shape).clone() for name, dt, shape, o, nbytes in self.env._arena_specs}
+        return {k: v.clone() for k, v in self.env.out.items()}
+
+    def _ready(self, n):
+        """prepare() a segment length met only now: where the reset boundary falls depends on the steps already taken, so a later pass
+        over the same step count (the launch-timing repeat, a warm-up loop) may cut segments that prepare(sizes) did not see.  run() and
+        compile() call it; neither runs inside a timed region."""
+        if (self.launch == "many" and n not in self.many_out) or (self.launch == "graph" and n not in self.graphs):
+            self.prepare([n])
+
     def run(self, n_steps):
         env = self.env
         for n, reset_after in self.plan(n_steps):
+            self._ready(n)
             if getattr(self, "_staged", False):
                 self._staged = False
             else:
@@ -427,7 +481,10 @@ def timed(fn, dist, dev, keep_busy=None, events=True):
     return elapsed, (ev0.elapsed_time(ev1) if events else None)   # an RCCL barrier costs tens of microseconds, a 20-step region lasts 0.1 ms)
 
 
-def measure_env(args, env, launch, K, W, dist, dev, reduce_dev, rank, scratch=None):
+def measure_env(args, env, launch, K, W, dist, dev, reduce_dev, rank, scratch=None, launch_timing=True, keep_outputs=False):
+    """launch_timing: for the multi-step form, repeat the K steps with per-dispatch timing to get the kernel's own duration (the
+    roofline's figures; a plain run skips it and gets gpu_ms None).  keep_outputs: info["outputs"] = copies of what the timed path
+    left for its caller, taken right after the timed region."""
     import torch
 
     from drl_uav_cellularnet_amd.sharding import gather_over_ranks, max_over_ranks
@@ -445,17 +502,29 @@ def measure_env(args, env, launch, K, W, dist, dev, reduce_dev, rank, scratch=No
         # the clock ramp.  PREWARM_STEPS eager steps, untimed, immediately before the measured env's own W warm-up steps.
         for t in range(PREWARM_STEPS):
             scratch.step(pool[t % n_pool])
+        rs = EnvRun(scratch, launch, pool, chunk=ck)
+        rs.prepare(sizes)
         if launch == "many":
             # ... and the scratch env through the SAME launch form and call sizes as the measured one: a multi-step call of another size
             # may take another code path of the kernel (a rotation schedule's pieces, section 4d), and the first execution of a path pays
             # its instruction fetch from memory -- 20-30 us, which a 20-step timed region (0.1 ms) would otherwise carry
-            rs = EnvRun(scratch, launch, pool, chunk=ck)
-            rs.prepare(sizes)
             for n in sorted(set(sizes)):
                 for _ in range(3):
                     rs.run(n)
+        # Then PREWARM_SECONDS of the same launch form on the scratch env, one synchronised call after another: without it a 20-step
+        # headline with no other launch form ahead of it read 5.60-5.87 us per step, with it 5.17-5.41 (profiles/plain_headline_prewarm_ab.txt).
+        scratch.reset()
+        rs.t = 0
+        n0, t0 = max(sizes), time.perf_counter()
+        while time.perf_counter() - t0 < PREWARM_SECONDS:
+            if rs.t + n0 > rs.max_step:
+                scratch.reset()
+                rs.t = 0
+            rs.run(n0)
+            torch.cuda.synchronize()
     r.run(W)
     r.stage(K)
+    r.keep_last = keep_outputs
     prog = r.compile(K)
 
     results = []
@@ -474,6 +543,7 @@ def measure_env(args, env, launch, K, W, dist, dev, reduce_dev, rank, scratch=No
                 scratch.step(pool[t % n_pool])
     many = launch == "many"
     elapsed, gpu_ms = timed(go, dist, dev, keep_busy=busy, events=not many)
+    outputs = r.last_outputs() if keep_outputs else None
     kernels = launched_kernels(census0, _capi.launch_census())          # the instantiation(s) the timed region really launched
     if many:                                                             # (the keep-busy single steps on the scratch env fall between the two
         kernels = [k for k in kernels if "MANY=1" in k]                  #  census snapshots: they are not the region's)
@@ -483,14 +553,15 @@ def measure_env(args, env, launch, K, W, dist, dev, reduce_dev, rank, scratch=No
     if bad:
         _capi.check(bad[0])
     launch_us = None
-    if many:
+    if many and launch_timing:
         # The multi-step kernel's own duration: the SAME K steps once more, every dispatch carrying its start / stop events
         # (uavenv_launch_timing: hipExtLaunchKernelGGL, the dispatch packet's timestamps) -- live in this process, on the launch stream,
         # but outside the wall-clock region above, which therefore holds nothing but the K steps.
         env.launch_timing(True)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        repeat = r.compile(K)                                            # (built before e0: it may prepare a segment length first met here)
         e0.record()
-        for f in r.compile(K):
+        for f in repeat:
             f()
         e1.record()
         torch.cuda.synchronize()
@@ -500,8 +571,11 @@ def measure_env(args, env, launch, K, W, dist, dev, reduce_dev, rank, scratch=No
             gpu_ms = sum(launch_us) * 1e-3                               # device time of the K steps' launches (tape copies / resets excluded)
         else:                                                            # (a multi-pass handle runs a multi-step call as single-step launches:
             gpu_ms, launch_us = e0.elapsed_time(e1), None                #  no multi-step dispatch to time -- stream events around the repeat)
-    per_rank = gather_over_ranks([elapsed, gpu_ms], device=reduce_dev)   # every rank's own clock: a straggler must be visible
-    elapsed, gpu_ms = max_over_ranks([elapsed, gpu_ms], device=reduce_dev)          # slowest rank
+    no_gpu_ms = gpu_ms is None                                           # (multi-step form without the launch-timing repeat)
+    per_rank = gather_over_ranks([elapsed, float("nan") if no_gpu_ms else gpu_ms], device=reduce_dev)   # every rank's own clock: a straggler must be visible
+    elapsed, gpu_ms = max_over_ranks([elapsed, float("nan") if no_gpu_ms else gpu_ms], device=reduce_dev)          # slowest rank
+    if no_gpu_ms:
+        gpu_ms = None
     sched = None
     if launch == "many":                                                   # how the library runs a call of this many steps on this handle
         import ctypes as C
@@ -510,8 +584,35 @@ def measure_env(args, env, launch, K, W, dist, dev, reduce_dev, rank, scratch=No
         env._lib.uavenv_debug_rotation_info(env._h, min(ck, K), C.byref(nl), C.byref(sl))
         sched = {"form": SCHEDULE_NAMES.get(nl.value, "?"), "dispatches_per_call": max(1, nl.value), "wavefronts_per_dispatch": sl.value or None}
     return elapsed, gpu_ms, {"kernels": kernels, "per_rank_elapsed_s": [p[0] for p in per_rank],
-                             "per_rank_gpu_ms": [p[1] for p in per_rank], "schedule": sched, "device_error": env.device_error(),
-                             "launch_us": launch_us}
+                             "per_rank_gpu_ms": None if no_gpu_ms else [p[1] for p in per_rank], "schedule": sched,
+                             "device_error": env.device_error(), "launch_us": launch_us, "outputs": outputs}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outputs, out_dir, seed=SEED):
+    """outputs: name -> device tensor [n_envs, ...].  Writes out_dir/<name>.npy, floating outputs in their own width (float32 /
+    float64), integer ones as float64 (exact).  If the whole would exceed DUMP_LIMIT_BYTES, the same fixed, seeded sample of env rows
+    is taken from every output and its indices are written as out_dir/env_index.npy.  -> list of the names written."""
+    import numpy as np
+
+    arrs = {}
+    for k, v in outputs.items():
+        a = v.cpu().numpy()
+        arrs[k] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    n_envs = next(iter(arrs.values())).shape[0]
+    per_env = sum(a.nbytes // max(1, a.shape[0]) for a in arrs.values())
+    idx = None
+    if per_env * n_envs > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (per_env + 8)                          # (+ 8: the row's entry in env_index)
+        idx = np.sort(np.random.RandomState(seed).choice(n_envs, size=keep, replace=False))
+        arrs = {k: a[idx] for k, a in arrs.items()}
+        arrs["env_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in sorted(arrs.items()):
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrs)
 
 
 def measure_a2c(args, dist, dev, reduce_dev, rank, world, envs, rollouts, rollout_len=A2C_ROLLOUT):
@@ -783,8 +884,9 @@ def main(argv=None):
     # pre-warm, and the A2C leg LAST: measured on one box, a 20-step headline region ran at 5.6e8 env-steps/s when the A2C leg
     # (TunableOp, BLAS handles, a captured graph, a side stream, several GB of buffers) came before it and at 6.5-6.7e8 when it
     # comes after.  Every measurement has its own env, its own W warm-up steps and its own bracketed timed region.
+    # A plain run (no --full) measures the headline alone: set-up, its pre-warm and W warm-up steps, the K timed steps, the line.
     alt, grids = {}, {}
-    if not args.no_alt:                                # secondary: the other launch forms on the same box, same K / W
+    if args.full and not args.no_alt:                  # secondary: the other launch forms on the same box, same K / W
         for other in (("eager", "many", "graph", "seq") if world == 1 else ("seq",)):   # N > 1: the one-kernel-per-step form only
             if other != args.launch:
                 el, gm, info = measure_env(args, make_env(), other, K, W, dist, dev, reduce_dev, rank)
@@ -795,15 +897,20 @@ def main(argv=None):
             grids["200"] = {"value": whole_job_rate(E * K, world, el), "unit": "env-steps/s", "us_per_step_gpu": gm * 1e3 / K,
                             "launch": args.launch, "note": "same workload on a 200 x 200 grid: compact outputs do not grow with G (the dense "
                             "observation would: 800 000 B per env-step instead of 200 000)"}
-    elapsed, gpu_ms, info = measure_env(args, make_env(), args.launch, K, W, dist, dev, reduce_dev, rank, scratch=make_env())
+    elapsed, gpu_ms, info = measure_env(args, make_env(), args.launch, K, W, dist, dev, reduce_dev, rank, scratch=make_env(),
+                                        launch_timing=args.full, keep_outputs=args.dump_outputs is not None)
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(info["outputs"], args.dump_outputs)
+    info["outputs"] = None
     a2c = None
-    if not args.no_a2c and baseline_shape:
+    if args.full and not args.no_a2c and baseline_shape:
         try:
             a2c = measure_a2c(args, dist, dev, reduce_dev, rank, world, A2C_ENVS, args.a2c_rollouts)
         except Exception as ex:                        # the headline line must survive a failure of the appended measurement
             a2c = {"error": "%s: %s" % (type(ex).__name__, ex)}
 
-    if rank == 0:
+    roof = None                          # the roofline block: --full only (its kernel time comes from the launch-timing repeat)
+    if rank == 0 and args.full:
         per_step_s = gpu_ms * 1e-3 / K   # average per-step device time (HIP events on the launch stream around the timed region)
         b_step = algorithmic_bytes_per_env_step(n_ue, n_bs, len(groups))
         achieved = b_step * E / per_step_s / 1e9
@@ -853,6 +960,7 @@ def main(argv=None):
             roof["per"] = "GPU"
             roof["whole_node_algorithmic_GBps"] = achieved * world
             roof["whole_node_peak_GBps"] = HBM_PEAK_GBPS * world
+    if rank == 0:
         form = {"seq": "one kernel per step, launches issued by one C call (uavenv_step_seq) per <=100 steps",
                 "graph": "one kernel per step, hipGraph replay of <=100-step chunks",
                 "eager": "one kernel launch per step from Python",
@@ -863,12 +971,14 @@ def main(argv=None):
             "unit": "env-steps/s", "n_gpus": n_ranks, "steps": K, "warmup": W,
             "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f64", "data": "synthetic", "launch": args.launch, "prewarm_steps_on_scratch_env": PREWARM_STEPS,
+            "prewarm_seconds_on_scratch_env": PREWARM_SECONDS, "full": args.full,
             "config": {"workload": "%d batched envs/GPU, %d UAV x %d UE (groups %s), G=%d, HIP step(), compact outputs, "
                                    "on-device Philox, %s" % (E, n_bs, n_ue, ",".join(str(g) for g in groups), grid, form),
                        "envs_per_gpu": E, "n_bs": n_bs, "n_ue": n_ue, "grid": grid, "parallelism": "env-shard x%d" % world},
             "per_rank_elapsed_s": info["per_rank_elapsed_s"], "per_rank_gpu_ms": info["per_rank_gpu_ms"],
-            "roofline": roof,
         }
+        if roof is not None:
+            line["roofline"] = roof
         if alt:
             line["other_launch_forms"] = alt
             if "seq" in alt:             # one kernel launch per step (what a closed-loop caller, e.g. the A2C rollout, gets)
@@ -877,7 +987,7 @@ def main(argv=None):
             line["other_grids"] = grids
         if a2c is not None:
             line["a2c"] = a2c
-        if world == 1 and not args.no_cpu_baseline and baseline_shape:
+        if args.full and world == 1 and not args.no_cpu_baseline and baseline_shape:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
     if dist is not None:

@@ -17,7 +17,7 @@ else
   for round in ${UAVENV_AB_ROUNDS:-1 2 3}; do
     for v in "${VARIANTS[@]}"; do
       name=${v%%:*}
-      UAVENV_LIB=$OUT/libuavenv_$name.so python3 $R/bench.py --steps 1500 --warmup 100 --no-cpu-baseline "${@:2}" 2>/dev/null | tail -1 | \
+      UAVENV_LIB=$OUT/libuavenv_$name.so python3 $R/bench.py --full --steps 1500 --warmup 100 --no-cpu-baseline "${@:2}" 2>/dev/null | tail -1 | \
         python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('round $round  $name  %.3f us  %.1f M env-steps/s' % (d['roofline']['avg_launch_us'], d['value']/1e6))"
     done
   done

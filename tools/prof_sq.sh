@@ -3,13 +3,14 @@
 set -e
 TAG=$1; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}
+D=$R/${PROF_OUT:-prof_out}/$TAG      # output folder (PROF_OUT relative to the repo root)
 export TMPDIR=/tmp
-mkdir -p $R/gpurun_out/$TAG
+mkdir -p $D
 cd /tmp
-rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU --output-format csv -d $R/gpurun_out/$TAG/sq1 -- python3 $R/bench.py --steps 60 --warmup 20 --no-cpu-baseline "$@" > $R/gpurun_out/$TAG/sq1.log 2>&1
-rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SMEM SQ_WAIT_INST_LDS --output-format csv -d $R/gpurun_out/$TAG/sq2 -- python3 $R/bench.py --steps 60 --warmup 20 --no-cpu-baseline "$@" > $R/gpurun_out/$TAG/sq2.log 2>&1
+rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU --output-format csv -d $D/sq1 -- python3 $R/bench.py --full --steps 60 --warmup 20 --no-cpu-baseline "$@" > $D/sq1.log 2>&1
+rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SMEM SQ_WAIT_INST_LDS --output-format csv -d $D/sq2 -- python3 $R/bench.py --full --steps 60 --warmup 20 --no-cpu-baseline "$@" > $D/sq2.log 2>&1
 cd $R
-python3 - "$R/gpurun_out/$TAG" <<'PY'
+python3 - "$D" <<'PY'
 import csv, glob, os, sys
 d = sys.argv[1]
 for sub in ("sq1", "sq2"):

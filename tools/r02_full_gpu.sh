@@ -12,8 +12,8 @@ tail -2 $O/smoke.log
 timeout -k 10 300 python tools/bench_shim.py > $O/bench_shim.json 2> $O/bench_shim.err
 echo "shim rc=$?" | tee -a $O/status.txt
 cat $O/bench_shim.json
-timeout -k 10 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 echo "bench default rc=$?" | tee -a $O/status.txt
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench_driver_style.err
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench_driver_style.err
 echo "bench driver-style rc=$?" | tee -a $O/status.txt
 cat $O/status.txt

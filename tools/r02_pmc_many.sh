@@ -4,7 +4,7 @@ O=$R/gpurun_out/r02e
 mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp
-A="--no-cpu-baseline --no-a2c --no-alt"
+A="--full --no-cpu-baseline --no-a2c --no-alt"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_many -- python3 $R/bench.py --steps 2000 --warmup 100 $A > $O/trace_many.log 2>&1
 echo "trace many rc=$?" | tee -a $O/status.txt
 for c in FETCH_SIZE WRITE_SIZE; do
@@ -25,6 +25,6 @@ cd $R
 find $O -name "*_kernel_trace.csv" -size +5M -delete
 python3 tools/pmc_digest.py $O > $O/digest.txt 2>&1
 grep -E "packed<4, 2, true, true, true, true>|multipass<16, 2|== " $O/digest.txt | cut -c1-200
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench_driver_style.err
-timeout -k 10 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench_driver_style.err
+timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 cat $O/status.txt

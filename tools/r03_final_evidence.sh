@@ -18,6 +18,6 @@ done
 cd $R
 find $O -name "*_kernel_trace.csv" -size +3M -delete; find $O -name "*agent_info.csv" -delete
 python3 tools/pmc_digest.py $O > $O/digest.txt 2>&1
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench_driver_style.err; echo "bench driver rc=$?" | tee -a $O/status.txt
-timeout -k 10 300 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?" | tee -a $O/status.txt
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench_driver_style.err; echo "bench driver rc=$?" | tee -a $O/status.txt
+timeout -k 10 300 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?" | tee -a $O/status.txt
 cat $O/status.txt

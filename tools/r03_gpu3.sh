@@ -9,7 +9,7 @@ rc=$?
 echo "tests rc=$rc" | tee -a $O/status.txt
 tail -8 $O/tests.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 200 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 200 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 echo "bench rc=$?" | tee -a $O/status.txt
 tail -c 3000 $O/bench_default.json
 ROUNDS=3 timeout -k 10 200 python tools/r03_many_ab.py > $O/many_ab.json 2> $O/many_ab.err

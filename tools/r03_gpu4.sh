@@ -7,7 +7,7 @@ cd $R
 timeout -k 10 900 python -m pytest tests -q -m gpu -x > $O/tests.log 2>&1
 rc=$?; echo "tests rc=$rc" | tee -a $O/status.txt; tail -6 $O/tests.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 300 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 echo "bench rc=$?" | tee -a $O/status.txt
 python - <<'PY'
 import json,os

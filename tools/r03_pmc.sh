@@ -6,7 +6,7 @@ O=$R/gpurun_out/r03e
 mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp
-A="--no-cpu-baseline --no-a2c --no-alt"
+A="--full --no-cpu-baseline --no-a2c --no-alt"
 SQ="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY"
 run() {   # tag, trace steps, pmc steps, bench args...
   local tag=$1 ts=$2 ps=$3; shift 3

@@ -7,9 +7,9 @@ cd $R
 timeout -k 10 1100 python -m pytest tests -q -m gpu -x -rs > $O/tests.log 2>&1
 rc=$?; echo "tests rc=$rc" | tee -a $O/status.txt; tail -4 $O/tests.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 echo "bench rc=$?" | tee -a $O/status.txt
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench_driver_style.err
+timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench_driver_style.err
 echo "bench 20 rc=$?" | tee -a $O/status.txt
 python - <<'PY'
 import json,os,sys

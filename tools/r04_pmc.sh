@@ -8,7 +8,7 @@ O=$R/gpurun_out/${1:-r04e}
 mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp
-A="--no-cpu-baseline --no-a2c --no-alt"
+A="--full --no-cpu-baseline --no-a2c --no-alt"     # --full: the launch-timing repeat the manifest counts
 SQ="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY"
 echo '{"runs": [' > $O/runs.json
 first=1

@@ -10,7 +10,9 @@ mkdir -p $O
 A="--no-a2c --no-alt --no-cpu-baseline"
 run() { # tag dir args...
   local tag=$1 dir=$2; shift 2
-  (cd $dir && timeout -k 10 300 python bench.py $A "$@" 2>> $O/err.log | tail -1 > $O/$tag.json)
+  local full=""
+  [ "$dir" = "$R" ] && full="--full"   # (this tree prints roofline only with --full; the round-3 bench.py has no such option and always printed it)
+  (cd $dir && timeout -k 10 300 python bench.py $A $full "$@" 2>> $O/err.log | tail -1 > $O/$tag.json)
   python -c "
 import json;d=json.loads(open('$O/$tag.json').read());print('$tag', '%.4g'%d['value'], 'us/step gpu', d['roofline']['avg_step_us'])"
 }
