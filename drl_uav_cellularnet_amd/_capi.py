@@ -67,7 +67,7 @@ _lib = None
 
 
 def lib_path():
-    """In-tree library; UAVENV_LIB overrides it (A/B runs of kernel build variants, see tools/ab_variants.sh)."""
+    """In-tree library; UAVENV_LIB overrides it (A/B runs of kernel build variants)."""
     return os.environ.get("UAVENV_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib",
                                                         "libuavenv.so")
 

@@ -384,19 +384,15 @@ class A2CRunner:
         # no order between the heads, are slower (every cross-stream edge of the graph costs ~9 us, every node of a two-stream graph ~5).
         # True = when each half still fills the chip (>= 4096 envs), "force" = whenever the batch can be cut (tests).
         self._halves = None
-        self._pipe_streams = []
+        self._pipe_stream = None
         import os as _os
 
-        # UAVAGENT_PIPE_MODE (A/B runs, tools/ab_collect.py): "alternate" = the parts' heads run one after the other (events), everything
-        # else free; "free" = no cross-stream order at all; "stagger" = free, but part p starts p gathers late.  UAVAGENT_PIPE_PARTS: 2..8.
-        self.pipeline_mode = _os.environ.get("UAVAGENT_PIPE_MODE", "alternate")
-        n_parts = int(_os.environ.get("UAVAGENT_PIPE_PARTS", "2"))
-        if pipeline_halves and self.dev.type == "cuda" and self.fused_head and self.fused_obs and 2 <= n_parts <= 8:
-            unit = 16                                                 # the head's 16-row tiles stay whole (a part of a batch runs on 16-row
-            per = (env.n_envs // n_parts + unit - 1) // unit * unit   #  workgroups: 8192 envs = 2 x 256 tiles = one workgroup per CU and half)
-            cuts = [min(i * per, env.n_envs) for i in range(n_parts)] + [env.n_envs]
-            if all(cuts[i] < cuts[i + 1] for i in range(n_parts)) and (pipeline_halves == "force" or env.n_envs >= 4096):
-                self._halves = tuple((cuts[i], cuts[i + 1]) for i in range(n_parts))
+        if pipeline_halves and self.dev.type == "cuda" and self.fused_head and self.fused_obs:
+            # the cut lies on a multiple of the head's 16-row tiles (half a batch runs on 16-row workgroups: 8192 envs = 2 x 256 tiles = one
+            # workgroup per CU and half)
+            mid = min((env.n_envs // 2 + 15) // 16 * 16, env.n_envs)
+            if 0 < mid < env.n_envs and (pipeline_halves == "force" or env.n_envs >= 4096):
+                self._halves = ((0, mid), (mid, env.n_envs))
         # persistent_rollout (GPU, fused_head + fused_obs, the reference's 4 UAVs and <= 64 UEs): the whole rollout as TWO persistent kernel
         # launches on two streams -- uavagent_actor_head_gated_f32 (the policy) and uavenv_rollout_gated (env step + next observation's first
         # layer) -- that hand 16-env blocks to each other through step counters in device memory (include/uavenv.h has the protocol): no kernel
@@ -405,8 +401,6 @@ class A2CRunner:
         # timeout makes collect() restore the state the rollout started from and collect it again with the per-step launches.  "auto" = from 4096 envs on; True = whenever the shapes allow (tests); the first
         # collect() proves on a CLONE of the env state that the two kernels do run side by side, and falls back to pipeline_halves if not.
         self._persistent = False
-        if _os.environ.get("UAVAGENT_PERSISTENT") in ("0", "1"):          # A/B runs (tools, bench): overrides the argument
-            persistent_rollout = _os.environ["UAVAGENT_PERSISTENT"] == "1"
         self._persist_stream = None
         self._persistent_proven = False
         self._persist_same_stream = _os.environ.get("UAVAGENT_PERSIST_SAME_STREAM", "0") == "1"
@@ -562,31 +556,41 @@ class A2CRunner:
         """Eager launches: one trial rollout on a CLONE of the env state shows whether the two persistent kernels run side by side on the
         streams this runner uses (the stream -> hardware-queue mapping is fixed when a stream is created); if not, the per-step launches take
         over for good.  (The captured form has the same trial in _capture.)"""
-        env = self.env
-        state = torch.empty(env._lay.total_bytes, dtype=torch.uint8, device=self.dev)
-        env.copy_state_to(state)
-        keep = {k: v.clone() for k, v in env.out.items()}
-        keep_idx = self.idx_buf[self.T].clone()
+        restore = self._snapshot()
         refused = None
         try:
             self._rollout_steps()
         except Exception as ex:                        # an entry point refused the shapes before launching anything
             refused = ex
         torch.cuda.synchronize(self.dev)
-        failed = refused is not None or self._persistent_failed()
-        if failed:
-            import warnings
-            from . import _agent_capi as A
-
-            warnings.warn("A2CRunner: the persistent rollout kernels did not run side by side (eager trial: %s); using the per-step launches "
-                          "instead" % ("refused: %s" % refused if refused is not None else "a gate wait timed out"))
-            self._persistent = False
-            A.device_error_clear()
-        env.copy_state_from(state)                     # (also clears the env handle's device-error word)
-        for k, v in keep.items():
-            env.out[k].copy_(v)
-        self.idx_buf[self.T].copy_(keep_idx)
+        if refused is not None or self._persistent_failed():
+            self._give_up_persistent("eager trial: %s" % ("refused: %s" % refused if refused is not None else "a gate wait timed out"))
+        restore()
         self._persistent_proven = True
+
+    def _snapshot(self):
+        """Copies what a trial rollout changes -- the env state, env.out and idx_buf[T] -- and returns the function that puts them back."""
+        env = self.env
+        state = torch.empty(env._lay.total_bytes, dtype=torch.uint8, device=self.dev)
+        env.copy_state_to(state)
+        keep = {k: v.clone() for k, v in env.out.items()}
+        keep_idx = self.idx_buf[self.T].clone()
+
+        def restore():
+            env.copy_state_from(state)                 # (also clears the env handle's device-error word)
+            for k, v in keep.items():
+                env.out[k].copy_(v)
+            self.idx_buf[self.T].copy_(keep_idx)
+        return restore
+
+    def _give_up_persistent(self, why):
+        """The two persistent kernels did not run side by side: the per-step launches take over for good."""
+        import warnings
+        from . import _agent_capi as A
+
+        warnings.warn("A2CRunner: the persistent rollout kernels did not run side by side (%s); using the per-step launches instead" % why)
+        self._persistent = False
+        A.device_error_clear()
 
     def _persistent_failed(self):
         """True when a gated launch gave up on the device (both libraries keep a sticky word in host-mapped memory)."""
@@ -595,59 +599,48 @@ class A2CRunner:
         return A.device_error() != 0 or self.env.device_error() != 0
 
     def _rollout_steps_pipelined(self):
-        """The T-step loop with the batch cut in parts, one stream each (see pipeline_halves in __init__).  Per part and step: first
-        layer from the observation the part's previous step left (gather), actor head, env step of the part's envs
-        (uavenv_step_range).  Cross-stream order in mode "alternate": head(part p, step t) after head(part p - 1, t), head(part 0, t + 1)
-        after head(last part, t).  Capturable: the extra streams fork from and join the calling stream through events."""
+        """The T-step loop with the batch cut in two halves, one stream each (see pipeline_halves in __init__).  Per half and step: first
+        layer from the observation the half's previous step left (gather), actor head, env step of the half's envs
+        (uavenv_step_range).  The heads alternate: head(half 1, t) after head(half 0, t), head(half 0, t + 1) after head(half 1, t); everything
+        else overlaps them.  Capturable: the second stream forks from and joins the calling stream through events."""
         from . import _agent_capi as A
 
         env, T, net, fw, wt = self.env, self.T, self.net, self._fwd, self._wt
         self.idx_buf[0].copy_(self.idx_buf[T])
         main = torch.cuda.current_stream(self.dev)
-        P = len(self._halves)
-        while len(self._pipe_streams) < P - 1:
+        if self._pipe_stream is None:
             # (normal priority.  A high-priority stream would have a hardware queue of its own -- with a dozen streams alive in one process the
             #  side stream can end up in the calling stream's queue, where the halves run one after the other: 8.8-10.3 instead of 4.4 ms in a
             #  five-runner A/B process, profiles/r04fd_ab_collect_five_runners_in_one_process.json -- but the captured graph then runs the rollout in
             #  12.9 ms: profiles/r04gu_ab_bench_a2c_pipelined_on_a_high_priority_stream.txt)
-            self._pipe_streams.append(torch.cuda.Stream(device=self.dev))
-        streams = [main] + self._pipe_streams[:P - 1]
+            self._pipe_stream = torch.cuda.Stream(device=self.dev)
+        side = self._pipe_stream
         fork = torch.cuda.Event()
         fork.record(main)
-        for st in streams[1:]:
-            st.wait_event(fork)
+        side.wait_event(fork)
         obs = env.observation()
-        alternate, stagger = self.pipeline_mode == "alternate", self.pipeline_mode == "stagger"
-        last_head = None                                              # event behind the head issued last (mode "alternate")
-        first_gather = [None] * P
+        last_head = None                                              # event behind the head issued last
         for t in range(T):
-            for h, ((lo, hi), st) in enumerate(zip(self._halves, streams)):
+            for (lo, hi), st in zip(self._halves, (main, side)):
                 with torch.cuda.stream(st):
-                    if t == 0 and h > 0 and stagger:                 # part h starts when part h - 1 has done its first gather, then runs free
-                        st.wait_event(first_gather[h - 1])
                     if t == 0:
                         A.sparse_rows_sum(self.idx_buf[0][lo:hi], net.a_w1, net.a_b1, net.c_w1, net.c_b1, relu6=True, out_a=fw["h1a"][0][lo:hi],
                                           out_c=fw["h1c"][0][lo:hi])
-                        if stagger:
-                            first_gather[h] = torch.cuda.Event()
-                            first_gather[h].record(st)
                     else:
                         A.first_layer_from_obs({k: v[lo:hi] for k, v in obs.items()}, self.G, net.a_w1, net.a_b1, net.c_w1, net.c_b1,
                                                fw["h1a"][t][lo:hi], fw["h1c"][t][lo:hi], idx_out=self.idx_buf[t][lo:hi])
-                    if alternate and last_head is not None:
+                    if last_head is not None:
                         st.wait_event(last_head)                     # the heads run one after the other; everything else overlaps them
                     A.actor_head(fw["h1a"][t][lo:hi], wt["a_w2t"], net.a_b2, wt["a_w3t"], wt["a_b3p"], self.u_buf[t][lo:hi], net.n_action,
                                  fw["h2a"][t][lo:hi], self._logits_pad[t][lo:hi], self.act_buf[t][lo:hi])
-                    if alternate:
-                        last_head = torch.cuda.Event()
-                        last_head.record(st)
+                    last_head = torch.cuda.Event()
+                    last_head.record(st)
                     env.step_range(self.act_buf[t], lo, hi - lo, reward_out=self.rew_buf[t])
                     if t == T - 1:
                         A.obs_indices({k: v[lo:hi] for k, v in obs.items()}, self.G, self.B, out=self.idx_buf[T][lo:hi])
-        for st in streams[1:]:
-            join = torch.cuda.Event()
-            join.record(st)
-            main.wait_event(join)
+        join = torch.cuda.Event()
+        join.record(side)
+        main.wait_event(join)
 
     @torch.no_grad()
     def collect(self):
@@ -721,27 +714,7 @@ class A2CRunner:
     def _capture(self):
         """hipGraph of the rollout loop.  A warm-up pass on a side stream first (rocBLAS handles / workspaces), on a CLONE of the
         env state so that capturing changes nothing the caller can observe."""
-        env = self.env
-        state = torch.empty(env._lay.total_bytes, dtype=torch.uint8, device=self.dev)
-        env.copy_state_to(state)
-        keep = {k: v.clone() for k, v in env.out.items()}
-        keep_idx = self.idx_buf[self.T].clone()
-        def restore():
-            env.copy_state_from(state)                 # (also clears the env handle's device-error word)
-            for k, v in keep.items():
-                env.out[k].copy_(v)
-            self.idx_buf[self.T].copy_(keep_idx)
-
-        def give_up_persistent(where):
-            import warnings
-            from . import _agent_capi as A
-
-            warnings.warn("A2CRunner: the persistent rollout kernels did not run side by side (%s: a gate wait timed out); using the "
-                          "per-step launches instead" % where)
-            self._persistent = False
-            A.device_error_clear()
-            restore()
-
+        restore = self._snapshot()
         s = torch.cuda.Stream(device=self.dev)
         for attempt in range(2):
             s.wait_stream(torch.cuda.current_stream(self.dev))
@@ -756,7 +729,8 @@ class A2CRunner:
             torch.cuda.current_stream(self.dev).wait_stream(s)
             torch.cuda.synchronize(self.dev)
             if self._persistent and (refused is not None or self._persistent_failed()):
-                give_up_persistent("eager warm-up pass" + (", refused: %s" % refused if refused is not None else ""))
+                self._give_up_persistent("eager warm-up pass" + (", refused: %s" % refused if refused is not None else "") + ": a gate wait timed out")
+                restore()
                 continue
             restore()
             # capture_error_mode="thread_local": with torch.distributed initialised, RCCL's watchdog thread polls events while this
@@ -769,7 +743,8 @@ class A2CRunner:
                 g.replay()
                 torch.cuda.synchronize(self.dev)
                 if self._persistent_failed():
-                    give_up_persistent("trial replay of the captured graph")
+                    self._give_up_persistent("trial replay of the captured graph: a gate wait timed out")
+                    restore()
                     continue
                 restore()
                 self._persistent_proven = True

@@ -14,13 +14,13 @@ SRC = os.path.join(PKG_DIR, "csrc", "uavenv_capi.hip")
 ENV_SRCS = [SRC, os.path.join(PKG_DIR, "csrc", "uavenv_gated.hip")]     # one object per translation unit: a change to one does not rebuild the other
 ENV_HDRS = [os.path.join(PKG_DIR, "csrc", f) for f in ("uavenv_kernels.h", "uavenv_handle.h", "philox.h", "lean_math.h", "intdiv.h",
                                                         "state_layout.h")] + [os.path.join(ROOT, "include", "uavenv.h")]
-ENV_EXTRA = {"uavenv_gated.hip": [os.path.join(PKG_DIR, "csrc", "uavenv_gated_kernel.h")]}      # headers of one translation unit only
+ENV_EXTRA = {"uavenv_gated.hip": [os.path.join(PKG_DIR, "csrc", f) for f in ("uavenv_gated_kernel.h", "rollout_gate.h")]}      # headers of one translation unit only
 DEPS = ENV_SRCS + ENV_HDRS + [h for hs in ENV_EXTRA.values() for h in hs]
 LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB = os.path.join(LIB_DIR, "libuavenv.so")
 AGENT_SRCS = [os.path.join(PKG_DIR, "csrc", f) for f in ("agent_kernels.hip", "agent_learner.hip", "agent_gemm.hip")]
 AGENT_SRC = AGENT_SRCS[0]
-AGENT_DEPS = AGENT_SRCS + [os.path.join(PKG_DIR, "csrc", "agent_common.h"), os.path.join(ROOT, "include", "uavagent.h")]
+AGENT_DEPS = AGENT_SRCS + [os.path.join(PKG_DIR, "csrc", f) for f in ("agent_common.h", "rollout_gate.h")] + [os.path.join(ROOT, "include", "uavagent.h")]
 AGENT_LIB = os.path.join(LIB_DIR, "libuavagent.so")
 ARCH = "gfx950"
 
@@ -56,7 +56,7 @@ def build_agent(force=False, verbose=False):
     return AGENT_LIB
 
 
-def build(force=False, verbose=False, extra_flags=()):
+def build(force=False, verbose=False):
     build_agent(force=force, verbose=verbose)
     if not force and not needs_build():
         return LIB
@@ -65,8 +65,7 @@ def build(force=False, verbose=False, extra_flags=()):
     os.makedirs(obj_dir, exist_ok=True)
     # -amdgpu-kernarg-preload-count: leading scalar kernel arguments arrive in SGPRs at wave launch (the packed env
     # kernel starts its global loads from them while the parameter struct is still being fetched)
-    flags = ["-O3", "-std=c++17", "--offload-arch=" + ARCH, "-fPIC", "-Wall", "-Wno-unused-function", "-mllvm", "-amdgpu-kernarg-preload-count=16",
-             *extra_flags]
+    flags = ["-O3", "-std=c++17", "--offload-arch=" + ARCH, "-fPIC", "-Wall", "-Wno-unused-function", "-mllvm", "-amdgpu-kernarg-preload-count=16"]
     tag = os.path.join(obj_dir, "flags.txt")
     same_flags = os.path.isfile(tag) and open(tag).read() == " ".join(flags)
     objs = []

@@ -27,6 +27,7 @@
 
 #include "../../include/uavagent.h"
 #include "agent_common.h"
+#include "rollout_gate.h"
 
 namespace {
 
@@ -99,14 +100,6 @@ template <> struct TnPlan<20> {          // a 320-wide tile of a wider J: 13 x 2
 
 constexpr int kTnBK = 32;       // rows of M per chunk = 8 k-steps of 4
 
-// Diagnostic build (-DUAVGEMM_STAMPS, tools/r03_gemm_stamps.sh): s_memtime at the phase boundaries of gemm_tn_kernel, summed per wavefront
-// into 4 counters behind the slabs (total, prologue, MFMA phases, chunk boundaries).  Values go to that buffer only, never to an output.
-#ifdef UAVGEMM_STAMPS
-#define GEMM_STAMP(var) do { __builtin_amdgcn_sched_barrier(0); var = __builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define GEMM_STAMP(var) do { } while (0)
-#endif
-
 // The 8 k-steps of one chunk for one wavefront: an NR x NC block rectangle at (pa, pb) + NX single blocks at (pxa[i], pxb[i]).  The
 // pointers are this lane's element of k row q of the tiles (row strides kNP / BJP); every k-step offset is an immediate of the ds_read.
 // Fragments of k-step s + 1 are read while the MFMAs of k-step s issue, ONE LDS read ahead of each MFMA, in exactly the order written
@@ -148,16 +141,13 @@ __device__ __forceinline__ void tn_ksteps(const float *pa, const float *pb, cons
 template <int PLAN, bool BVEC>
 __global__ __launch_bounds__(512, 1) void gemm_tn_kernel(const float *__restrict__ A, int n_i, const float *__restrict__ B, long long ldb,
                                                           int n_j, long long M, long long rows_per_split, int n_jt, int n_split,
-                                                          f32x4 *__restrict__ slabs, int dbg) {
+                                                          f32x4 *__restrict__ slabs) {
     using P = TnPlan<PLAN>;
     constexpr int NCB = P::NCB, BJP = P::BJP, NR = P::NR, NC = P::NC, NX = P::NX, NBLKW = P::NBLKW;
     constexpr int A_TILE = kTnBK * kNP, B_TILE = kTnBK * BJP;
     __shared__ __attribute__((aligned(16))) float lds[2 * (A_TILE + B_TILE)];
     float *const sA = lds, *const sB = lds + 2 * A_TILE;
 
-    unsigned long long ts0 = 0, ts1 = 0, tsa = 0, tsb = 0, tsc = 0, t_mfma = 0, t_bound = 0;
-    (void)ts0; (void)ts1; (void)tsa; (void)tsb; (void)tsc; (void)t_mfma; (void)t_bound;
-    GEMM_STAMP(ts0);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (wave-uniform: scalar branches)
     const int r = lane & 15, q = lane >> 4;
     // workgroup -> (split, J tile): the J tiles of one split read the same rows of A, so they sit on one XCD (ids = xcd mod 8) and
@@ -254,29 +244,15 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_kernel(const float *__restrict
 
     if (n_chunks > 0) { load_chunk(0); store_chunk(0, 0); }
     __syncthreads();
-    GEMM_STAMP(ts1);
-    tsc = ts1;
-#ifdef UAVGEMM_STAMPS
-    if ((dbg & 1) && wave >= 4) __builtin_amdgcn_s_setprio(1);
-    if ((dbg & 8) && wave < 4) __builtin_amdgcn_s_setprio(1);
-    const bool skip = ((dbg & 2) && wave >= 4) || ((dbg & 4) && wave < 4);
-#else
-    (void)dbg;
-    constexpr bool skip = false;
-#endif
     for (int c = 0; c < n_chunks; ++c) {
         const int buf = c & 1;
-        tsa = tsc;
         if (c + 1 < n_chunks) load_chunk(c + 1);                           // in flight behind this chunk's MFMAs
         const float *tA = sA + buf * A_TILE, *tB = sB + buf * B_TILE;
 #pragma unroll
         for (int i = 0; i < NX; ++i) { pxa[i] = tA + oxa[i]; pxb[i] = tB + oxb[i]; }
-        if (!skip) tn_ksteps<NR, NC, NX, BJP, P::XONECOL>(tA + oa, tB + ob, pxa, pxb, acc, accx);
-        GEMM_STAMP(tsb);
+        tn_ksteps<NR, NC, NX, BJP, P::XONECOL>(tA + oa, tB + ob, pxa, pxb, acc, accx);
         if (c + 1 < n_chunks) store_chunk(buf ^ 1, c + 1);
         __syncthreads();
-        GEMM_STAMP(tsc);
-        t_mfma += tsb - tsa; t_bound += tsc - tsb;
     }
 
     // ---- one slab per workgroup, in fragment order (coalesced 16-byte stores): [wave][block][lane], blocks of a wave = its rectangle
@@ -288,14 +264,6 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_kernel(const float *__restrict
         for (int c = 0; c < NC; ++c) dst[(i * NC + c) * 64] = acc[i][c];
 #pragma unroll
     for (int i = 0; i < NX; ++i) dst[(NR * NC + i) * 64] = accx[i];
-#ifdef UAVGEMM_STAMPS
-    unsigned long long ts2;
-    GEMM_STAMP(ts2);
-    if (lane == 0) {
-        unsigned long long *d = reinterpret_cast<unsigned long long *>(slabs + (long long)n_split * n_jt * 8 * NBLKW * 64) + ((long long)blockIdx.x * 8 + wave) * 4;
-        d[0] = ts2 - ts0; d[1] = ts1 - ts0; d[2] = t_mfma; d[3] = t_bound;
-    }
-#endif
 }
 
 // Second pass of dW: 64 accumulator fragments (J tile, wave, block, lane) per workgroup, each summed over the splits by four threads (a
@@ -570,9 +538,6 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_nt_kernel(const float *__res
     constexpr int LDS_FLOATS = (2 * (A_TILE + W_TILE) > 4 * 16 * LDC) ? 2 * (A_TILE + W_TILE) : 4 * 16 * LDC;
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
     float *const sA = lds, *const sW = lds + 2 * A_TILE;
-    unsigned long long ts0 = 0, ts1 = 0, tsa = 0, tsb = 0, tsc = 0, t_mfma = 0, t_bound = 0, ts2 = 0, ts3 = 0;
-    (void)ts0; (void)ts1; (void)tsa; (void)tsb; (void)tsc; (void)t_mfma; (void)t_bound; (void)ts2; (void)ts3;
-    GEMM_STAMP(ts0);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, q = lane >> 4;
     const long long m0 = (long long)blockIdx.x * BM;
@@ -627,11 +592,8 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_nt_kernel(const float *__res
     __syncthreads();
     const int fa = (wave * (16 * RBW) + r) * kNtLD + 4 * q, fw = r * kNtLD + 4 * q;    // this lane's 16-byte piece of the first 16 k
     const int fa5 = (wave * (16 * RBW) + r) * kNtLD + 16 + q, fw5 = r * kNtLD + 16 + q;  // and its element of the fifth k-step
-    GEMM_STAMP(ts1);
-    tsc = ts1;
     for (int c = 0; c < n_chunks; ++c) {
         const int buf = c & 1;
-        tsa = tsc;
         if (c + 1 < n_chunks) load_chunk(c + 1);
         const float *tA = sA + buf * A_TILE, *tW = sW + buf * W_TILE;
         // reads in issue order: a128[*], w128[0 .. AHEAD-1]; then one read ahead of each column block (sched_barrier pins the order, see
@@ -659,13 +621,9 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_nt_kernel(const float *__res
                 }
             }
         }
-        GEMM_STAMP(tsb);
         if (c + 1 < n_chunks) store_chunk(buf ^ 1, c + 1);
         __syncthreads();
-        GEMM_STAMP(tsc);
-        t_mfma += tsb - tsa; t_bound += tsc - tsb;
     }
-    GEMM_STAMP(ts2);
 
     // ---- epilogue through LDS (see gemm_rows_vec_kernel): 16 rows x NB * 16 columns per wave and round, one whole row per instruction ----
     float *E = lds + wave * (16 * LDC);
@@ -726,14 +684,6 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_nt_kernel(const float *__res
             *reinterpret_cast<float4 *>(col_partial + (long long)blockIdx.x * kNP + n0 + lane * 4) = t;
         }
     }
-#ifdef UAVGEMM_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    GEMM_STAMP(ts3);
-    if (col_partial != nullptr && lane == 0 && blockIdx.y == 0) {
-        unsigned long long *d = reinterpret_cast<unsigned long long *>(col_partial + (long long)gridDim.x * kNP) + ((long long)blockIdx.x * 4 + wave) * 6;
-        d[0] = ts3 - ts0; d[1] = ts1 - ts0; d[2] = t_mfma; d[3] = t_bound; d[4] = ts3 - ts2; d[5] = ts0;
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1105,10 +1055,6 @@ __global__ __launch_bounds__(kRsThr, 1) void gemm_rows_resident_kernel(const flo
 // workgroup per CU --, 1 (16 rows, wave = column eighth w) for HALF a batch, so that it still spreads over every CU (A2CRunner(pipeline_halves)):
 // the time of a workgroup is mostly its stream of W2^T + W3^T (672 KB) and does not shrink with the number of workgroups.
 constexpr int kHdH = 200, kHdNP = 640, kHdWaves = 8, kHdThr = kHdWaves * 64;
-#ifdef UAVGEMM_STAMPS
-__device__ unsigned long long *g_head_dbg;   // [workgroups][8 waves][10]: s_memtime stamps of actor_head_kernel (tools/head_stamps.py sets it)
-#endif
-__device__ int g_head_no_stagger;      // A/B switch (UAVAGENT_HEAD_STAGGER=0 sets it to 1 through uavagent_actor_head_f32): every wave issues at the chunk's start
 constexpr int kHdW2Rows = 256, kHdW2Pass = kHdW2Rows * 10 / kHdThr;                              // 2560 float4: 5 passes
 constexpr int kHdW3Rows = 320;                                                                  // (rows of a phase-1 ring stage: 256 used)
 constexpr int kHdStageF = kHdW3Rows * kGlBK;                                                    // 12 800 floats per ring stage (phase 1's two)
@@ -1180,10 +1126,7 @@ __device__ __forceinline__ void actor_head_tile(float *lds, const long long m0, 
     float *const ring3 = sH1;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, q = lane >> 4, rb = (RB == 2) ? (wave & 1) : 0, qt = (RB == 2) ? (wave >> 1) : wave;   // row block, column group
-    const bool stagger_first = (wave < 4) || g_head_no_stagger;      // (waves w and w + 4 share a SIMD)
-    unsigned long long hs0 = 0, hs1 = 0, hs2 = 0, hs3 = 0, hs4 = 0, hs5 = 0, hs6 = 0, hs7 = 0, hs_b = 0, hs_t = 0, hs_wait = 0, hs_first = 0;
-    (void)hs0; (void)hs1; (void)hs2; (void)hs3; (void)hs4; (void)hs5; (void)hs6; (void)hs7; (void)hs_b; (void)hs_t; (void)hs_wait; (void)hs_first;
-    GEMM_STAMP(hs0);
+    const bool stagger_first = wave < 4;      // (waves w and w + 4 share a SIMD)
     // the uniforms of this wave's rows, loaded NOW: read where the draw needs them, each was a global round trip (~2 000 cycles by the stamps)
     // in the middle of a dependent chain, once per row
     float u_row[kHdRows / kHdWaves];
@@ -1239,13 +1182,9 @@ __device__ __forceinline__ void actor_head_tile(float *lds, const long long m0, 
     for (int c = 0; c < NCB1; ++c) acc1[c] = f32x4{0.f, 0.f, 0.f, 0.f};
     const float *pa1 = sH1 + (rb * 16 + r) * kHdH;
     auto chunk2 = [&](auto set_c, int c) {
-        GEMM_STAMP(hs_b);
         wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        GEMM_STAMP(hs_t);
-        hs_wait += hs_t - hs_b;
-        if (c == 0) hs_first = hs_t;
         // The stagger: after the barrier both waves of a SIMD would issue their 5 LDS-DMA instructions at once (60-185 cycles of issue each,
         // MI355X_MICROARCH.md) and leave the matrix pipe idle meanwhile; waves 0-3 issue at the start of the chunk, waves 4-7 in its middle
         // (under their partner's MFMAs and vice versa).  Per wave the order of its loads is unchanged, so the counted waits still hold.
@@ -1264,9 +1203,7 @@ __device__ __forceinline__ void actor_head_tile(float *lds, const long long m0, 
             for (int t = 0; t < 4; ++t) sH2[(rb * 16 + 4 * q + t) * kHdH + col] = fminf(fmaxf(acc1[cb][t] + bv, 0.0f), 6.0f);
         }
     }
-    GEMM_STAMP(hs1);                                   // phase 1's MFMAs done, h2 written to LDS
     __syncthreads();                                   // (every wave is past the ring's last read too: phase 2 may refill it)
-    GEMM_STAMP(hs2);
 
     // ---- phase 2: logits = h2 @ W3 + b3 in three PARTS of 256 / 256 / 128 policy columns x 5 chunks of 40 k; wave = 16 rows x 4 / 4 / 2 of a
     // part's 16 / 16 / 8 column blocks.  Stages of 256 rows x 40 k (40 KB): three of them fit [h1 tile | ring], so chunk p + 2 is issued when
@@ -1314,16 +1251,12 @@ __device__ __forceinline__ void actor_head_tile(float *lds, const long long m0, 
     const float *pa2 = sH2 + (rb * 16 + r) * kHdH;
     // chunk p3 has landed once at most the loads of chunk p3 + 1 are outstanding (5 per wave; in part 2: 3 for waves 0-3, 2 for the others)
     auto land3 = [&](int p3) {
-        GEMM_STAMP(hs_b);
         if (p3 + 1 >= 15) wait_vmcnt<0>();
         else if (p3 + 1 < 10) wait_vmcnt<kHdP3Pass>();
         else if (wave < 4) wait_vmcnt<3>();
         else wait_vmcnt<2>();
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        GEMM_STAMP(hs_t);
-        hs_wait += hs_t - hs_b;
-        if (p3 == 0) hs3 = hs_t;                       // phase 2's first chunk has landed (h2 store + two chunk issues lie before)
     };
     auto chunk3 = [&](auto set_c, auto ncb_c, int p3, f32x4 (&acc)[decltype(ncb_c)::value]) {       // SET = parity of p3: chunk p3 + 2 is issued here
         constexpr int NCB = decltype(ncb_c)::value;
@@ -1337,7 +1270,6 @@ __device__ __forceinline__ void actor_head_tile(float *lds, const long long m0, 
     chunk3(set0_t{}, n4_t{}, 0, accA); chunk3(set1_t{}, n4_t{}, 1, accA); chunk3(set0_t{}, n4_t{}, 2, accA); chunk3(set1_t{}, n4_t{}, 3, accA); chunk3(set0_t{}, n4_t{}, 4, accA);
     chunk3(set1_t{}, n4_t{}, 5, accB); chunk3(set0_t{}, n4_t{}, 6, accB); chunk3(set1_t{}, n4_t{}, 7, accB); chunk3(set0_t{}, n4_t{}, 8, accB); chunk3(set1_t{}, n4_t{}, 9, accB);
     chunk3(set0_t{}, n2_t{}, 10, accC); chunk3(set1_t{}, n2_t{}, 11, accC); chunk3(set0_t{}, n2_t{}, 12, accC); chunk3(set1_t{}, n2_t{}, 13, accC); chunk3(set0_t{}, n2_t{}, 14, accC);
-    GEMM_STAMP(hs4);                                   // phase 2's MFMAs done
     __syncthreads();                                   // the ring is free: it becomes the [32][640] logits tile
 
     // ---- phase 3: + bias -> logits tile in LDS; coalesced store; one wave samples 4 rows ----
@@ -1360,7 +1292,6 @@ __device__ __forceinline__ void actor_head_tile(float *lds, const long long m0, 
         for (int t = 0; t < 4; ++t) sL[(rb * 16 + 4 * q + t) * kHdNP + colC] = accC[cb][t] + bC;
     }
     __syncthreads();
-    GEMM_STAMP(hs5);                                   // logits tile in LDS
     {
         const int rows = (int)(n_rows - m0 < kHdRows ? n_rows - m0 : kHdRows);
 #pragma unroll 5
@@ -1369,7 +1300,6 @@ __device__ __forceinline__ void actor_head_tile(float *lds, const long long m0, 
             if (row < rows) *reinterpret_cast<float4 *>(logits + (m0 + row) * ldl + c4 * 4) = *reinterpret_cast<const float4 *>(sL + row * kHdNP + c4 * 4);
         }
     }
-    GEMM_STAMP(hs6);                                   // logits stores issued
     constexpr int PER = 10;                            // sample_actions_kernel<10>: lane l owns columns 10 l .. 10 l + 9
 #pragma unroll
     for (int i = 0; i < kHdRows / kHdWaves; ++i) {
@@ -1423,14 +1353,6 @@ __device__ __forceinline__ void actor_head_tile(float *lds, const long long m0, 
             else action[m] = a;
         }
     }
-#ifdef UAVGEMM_STAMPS
-    GEMM_STAMP(hs7);
-    if (g_head_dbg != nullptr && lane == 0) {
-        unsigned long long *d = g_head_dbg + ((long long)blockIdx.x * kHdWaves + wave) * 10;
-        d[0] = hs0; d[1] = hs_first - hs0; d[2] = hs1 - hs0; d[3] = hs2 - hs0; d[4] = hs3 - hs0; d[5] = hs4 - hs0; d[6] = hs5 - hs0; d[7] = hs6 - hs0; d[8] = hs7 - hs0;
-        d[9] = hs_wait;
-    }
-#endif
 }
 
 template <int RB>
@@ -1450,42 +1372,11 @@ __global__ __launch_bounds__(kHdThr, 1) void actor_head_kernel(const float *__re
 // wait until gate_obs[b] >= t + 1 (h1[t] of the block's rows is in memory), one 16-row tile exactly as actor_head_kernel<1> computes it
 // (same bits), actions stored through, s_waitcnt vmcnt(0), gate_act[b] = t + 1.  No kernel boundary, graph node or host call between a
 // step's kernels any more (a2c_single_thread.py:113-118 is a loop over independent workers).  Every wait is bounded: after spin_us the
-// wave stores kGateErr in the library's host-mapped error word and leaves (uavagent_device_error).  At most UAVAGENT_GATE_VGPRS = 112
-// VGPRs (amdgpu_num_vgpr): two of this kernel's waves and two of the env kernel's (<= 144 VGPRs each) share a SIMD's 512.
+// wave stores rollout_gate::kErrGate in the library's host-mapped error word and leaves (uavagent_device_error).  At most
+// rollout_gate::kPolicyVgprs = 112 VGPRs (amdgpu_num_vgpr): two of this kernel's waves and two of the env kernel's (<= 144 VGPRs each)
+// share a SIMD's 512.
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr uint32_t kGateErr = 0x47415445u;      // "GATE"
-#ifdef UAVAGENT_GATE_STAMPS     /* diagnostic build (tools/gated_timeline.py): s_memrealtime of pair 0's events, same buffer as the env kernel's stamps */
-__device__ unsigned long long *g_hgate_dbg;   // [T][2 halves][8]: slot 0 = h1 seen, 1 = actions published
-#define HGATE_STAMP(t, half, k) do { if (g_hgate_dbg != nullptr && pair == 0 && threadIdx.x == 0) g_hgate_dbg[((t) * 2 + (half)) * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define HGATE_STAMP(t, half, k) do { } while (0)
-#endif
-__device__ __forceinline__ bool head_gate_wait(uint32_t *word, uint32_t need, uint32_t *err, uint32_t spin_us) {
-    const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
-    const unsigned long long budget = (unsigned long long)spin_us * 100ull;           // s_memrealtime ticks at 100 MHz
-    bool ok = false;
-    for (;;) {
-        uint32_t v = 0u;
-        if ((threadIdx.x & 63) == 0) v = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((uint32_t)__builtin_amdgcn_readfirstlane((int)v) >= need) { ok = true; break; }
-        if (__builtin_amdgcn_s_memrealtime() - t_start > budget) break;
-        __builtin_amdgcn_s_sleep(8);
-    }
-    if (!ok && (threadIdx.x & 63) == 0) __hip_atomic_store(err, kGateErr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    asm volatile("" ::: "memory");
-    return ok;
-}
-#ifdef UAVAGENT_GATE_NOCAP      /* timing experiment: the kernel without its register cap (such a build cannot run beside its partner) */
-#define UAVAGENT_GATE_CAP
-#else
-#ifndef UAVAGENT_GATE_VGPRS
-#define UAVAGENT_GATE_VGPRS 112     /* this kernel's share of a SIMD lane's 512 registers is 2 x this; the env kernel has the rest: 144
-                                     * (uavenv_gated_kernel.h).  112 + 144 against 128 + 128: the pair 3.75-3.78 against 3.86 ms per rollout, same box
-                                     * (profiles/r04gz_gated_pair_vgpr_split_sweep.txt): the env side is the one the rollout waits for */
-#endif
-#define UAVAGENT_GATE_CAP __attribute__((amdgpu_num_vgpr(UAVAGENT_GATE_VGPRS / 2)))   /* (gfx90a and later: the attribute counts VGPR + AGPR pairs) */
-#endif
-__global__ __launch_bounds__(kHdThr) UAVAGENT_GATE_CAP void actor_head_gated_kernel(const float *__restrict__ h1, const float *__restrict__ w2t, const float *__restrict__ b2,
+__global__ __launch_bounds__(kHdThr) __attribute__((amdgpu_num_vgpr(rollout_gate::kPolicyVgprs / 2))) void actor_head_gated_kernel(const float *__restrict__ h1, const float *__restrict__ w2t, const float *__restrict__ b2,
                                                                       const float *__restrict__ w3t, const float *__restrict__ b3p,
                                                                       const float *__restrict__ uni, long long n_rows, int n_steps, int n_act,
                                                                       float *__restrict__ h2_out, float *__restrict__ logits, long long ldl,
@@ -1507,8 +1398,7 @@ __global__ __launch_bounds__(kHdThr) UAVAGENT_GATE_CAP void actor_head_gated_ker
             for (int half = 0; half < 2; ++half) {
                 const int blk = 2 * pair + half;
                 if (blk >= n_blocks) continue;
-                if (!head_gate_wait(gate_obs + blk, (uint32_t)t + 1u, err, spin_us)) return;
-                HGATE_STAMP(t, half, 0);
+                if (!rollout_gate::wait(gate_obs + blk, (uint32_t)t + 1u, err, spin_us)) return;
                 __syncthreads();                             // every wave has left the previous tile's LDS
                 // (the weights' base pointers pass through an empty asm: otherwise hipcc hoists the per-lane LDS-DMA source pointers of every
                 //  tile -- 40 VGPRs -- out of the step loop and, capped at 96 VGPRs, spills them)
@@ -1519,17 +1409,10 @@ __global__ __launch_bounds__(kHdThr) UAVAGENT_GATE_CAP void actor_head_gated_ker
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the actions have left
                 __syncthreads();
                 if (threadIdx.x == 0) __hip_atomic_store(gate_act + blk, (uint32_t)t + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                HGATE_STAMP(t, half, 1);
             }
         }
     }
 }
-
-#ifdef UAVGEMM_STAMPS
-extern "C" int uavagent_debug_set_head_stamps(void *dev_ptr) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_head_dbg), &dev_ptr, sizeof(void *)) == hipSuccess ? 0 : -1;
-}
-#endif
 
 template <bool NT, bool VEC, int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_rows_kernel(const float *__restrict__ A, long long lda, const float *__restrict__ W, long long ldw,
@@ -1653,9 +1536,6 @@ TnShape tn_shape(long long M, int n_j) {
     if (s.n_split < 1) s.n_split = 1;
     const int nblkw = (s.plan == 13) ? TnPlan<13>::NBLKW : TnPlan<20>::NBLKW;
     s.ws_bytes = (size_t)s.n_split * s.n_jt * 8 * nblkw * 64 * sizeof(f32x4);
-#ifdef UAVGEMM_STAMPS
-    s.ws_bytes += (size_t)s.n_split * s.n_jt * 8 * 4 * sizeof(unsigned long long);
-#endif
     return s;
 }
 }  // namespace
@@ -1710,14 +1590,10 @@ extern "C" int uavagent_gemm_tn_f32(const float *a, const float *b, int64_t m_ro
     // stride) -- they must hold finite values (the learner keeps its [M, 625] logits in rows of 640 with a zero tail)
     const bool bvec = aligned16(b) && (ldb % 4 == 0) && (ldb >= ((n_j + 3) & ~3));
     const dim3 grid((unsigned)(s.n_split * s.n_jt)), blk(512);
-    int dbg = 0;
-#ifdef UAVGEMM_STAMPS
-    if (const char *e = std::getenv("UAVGEMM_DBG")) dbg = std::atoi(e);     // diagnostic build only: read per call
-#endif
 #define UAV_TN(PLAN_)                                                                                                                        \
     do {                                                                                                                                     \
-        if (bvec) hipLaunchKernelGGL((gemm_tn_kernel<PLAN_, true>), grid, blk, 0, st, a, n_i, b, (long long)ldb, n_j, (long long)m_rows, s.rows_per_split, s.n_jt, s.n_split, slabs, dbg); \
-        else hipLaunchKernelGGL((gemm_tn_kernel<PLAN_, false>), grid, blk, 0, st, a, n_i, b, (long long)ldb, n_j, (long long)m_rows, s.rows_per_split, s.n_jt, s.n_split, slabs, dbg);    \
+        if (bvec) hipLaunchKernelGGL((gemm_tn_kernel<PLAN_, true>), grid, blk, 0, st, a, n_i, b, (long long)ldb, n_j, (long long)m_rows, s.rows_per_split, s.n_jt, s.n_split, slabs); \
+        else hipLaunchKernelGGL((gemm_tn_kernel<PLAN_, false>), grid, blk, 0, st, a, n_i, b, (long long)ldb, n_j, (long long)m_rows, s.rows_per_split, s.n_jt, s.n_split, slabs);    \
         const int n_items = s.n_jt * 8 * TnPlan<PLAN_>::NBLKW * 64;                                                                          \
         hipLaunchKernelGGL((gemm_tn_reduce<PLAN_>), dim3((n_items + 63) / 64), dim3(256), 0, st, slabs, s.n_split, s.n_jt, n_i, n_j, c, (long long)ldc, dbias_out); \
     } while (0)
@@ -1753,14 +1629,6 @@ extern "C" int uavagent_actor_head_f32(const float *h1, const float *w2t, const 
     if (n_rows == 0) return UAVAGENT_OK;
     // 32-row workgroups while they give every CU one (a whole rollout batch of 8192 rows on 256 CUs); 16-row workgroups for fewer rows (half a
     // batch on its own stream): the time of a workgroup is its weight stream, so fewer, larger workgroups would only leave CUs idle
-    {   // A/B switch of the DMA stagger, read once per process
-        static const int no_stagger = [] { const char *e = getenv("UAVAGENT_HEAD_STAGGER"); return (e && e[0] == '0') ? 1 : 0; }();
-        static bool pushed = false;
-        if (!pushed && no_stagger) {
-            if (hipMemcpyToSymbol(HIP_SYMBOL(g_head_no_stagger), &no_stagger, sizeof(int)) != hipSuccess) return fail3(UAVAGENT_E_HIP, "actor_head: hipMemcpyToSymbol failed");
-        }
-        pushed = true;
-    }
     const char *force_env = getenv("UAVAGENT_HEAD_RB");          // tests / A-B runs: 1 or 2 forces the tile height (read per call)
     const int force_rb = force_env ? atoi(force_env) : 0;
     const int n_cu = cu_count_of_current_device();
@@ -1776,12 +1644,6 @@ extern "C" int uavagent_actor_head_f32(const float *h1, const float *w2t, const 
     if (hipGetLastError() != hipSuccess) return fail3(UAVAGENT_E_HIP, "actor_head: launch failed");
     return UAVAGENT_OK;
 }
-
-#ifdef UAVAGENT_GATE_STAMPS
-extern "C" int uavagent_debug_set_gate_stamps(void *dev_ptr) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_hgate_dbg), &dev_ptr, sizeof(void *)) == hipSuccess ? 0 : -1;
-}
-#endif
 
 // ---- the gated head's error word: host-mapped, one per process (allocated by uavagent_gate_prepare, never inside a launch) ----
 static uint32_t *g_gate_err_host = nullptr, *g_gate_err_dev = nullptr;
@@ -1833,15 +1695,8 @@ extern "C" int uavagent_actor_head_gated_f32(const float *h1, const float *w2t, 
 
 extern "C" size_t uavagent_gemm_rows_workspace_bytes(int64_t m_rows) {
     if (m_rows < 1) return 0;
-    size_t b = (size_t)((m_rows + 63) / 64) * kNP * sizeof(float);          // one partial row per workgroup of the 64-row kernels (the most)
-#ifdef UAVGEMM_STAMPS
-    b += (size_t)((m_rows + 63) / 64) * 4 * 6 * sizeof(unsigned long long);
-#endif
-    return b;
+    return (size_t)((m_rows + 63) / 64) * kNP * sizeof(float);          // one partial row per workgroup of the 64-row kernels (the most)
 }
-
-// UAVAGENT_ROWS_RESIDENT=0 (read once): the update's K = 200 GEMMs on version 4's 128-row workgroups instead of the resident-W kernel (A/B runs)
-static const bool g_rows_resident = [] { const char *e = getenv("UAVAGENT_ROWS_RESIDENT"); return e ? e[0] != '0' : true; }();
 
 extern "C" int uavagent_gemm_rows_f32(const float *a, int64_t lda, const float *w, int64_t ldw, int32_t w_transposed, int64_t m_rows, int32_t k,
                                       int32_t n, const float *bias, int32_t relu6, const float *relu6_mask_h, int64_t ldh, float *c, int64_t ldc,
@@ -1888,7 +1743,7 @@ extern "C" int uavagent_gemm_rows_f32(const float *a, int64_t lda, const float *
         else if (epi == 1) hipLaunchKernelGGL((gemm_rows_glds_kernel<BM_, NB_, NS_, 1>), g2, b2, 0, st, a, (long long)lda, w, (long long)ldw, (int)k, (int)n, (long long)m_rows, bias, (int)relu6, relu6_mask_h, (long long)ldh, c, (long long)ldc, colp); \
         else hipLaunchKernelGGL((gemm_rows_glds_kernel<BM_, NB_, NS_, 2>), g2, b2, 0, st, a, (long long)lda, w, (long long)ldw, (int)k, (int)n, (long long)m_rows, bias, (int)relu6, relu6_mask_h, (long long)ldh, c, (long long)ldc, colp); \
     } while (0)
-    if (w_transposed && vec && k == kRsK && n > kRsNBA * 16 && n <= 208 && m_rows > 32768 && g_rows_resident) {
+    if (w_transposed && vec && k == kRsK && n > kRsNBA * 16 && n <= 208 && m_rows > 32768) {
         // W^T resident in LDS, persistent workgroups (gemm_rows_resident_kernel): the update's 200-wide layers
         const int n_cu = cu_count_of_current_device();          // per device: a process may drive several
         const int nA = (n_cu * kRsNBA + (kRsNBA + kRsNBB) / 2) / (kRsNBA + kRsNBB) < n_cu ? (n_cu * kRsNBA + (kRsNBA + kRsNBB) / 2) / (kRsNBA + kRsNBB) : n_cu - 1;

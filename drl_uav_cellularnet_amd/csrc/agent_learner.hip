@@ -701,10 +701,8 @@ extern "C" int uavagent_a2c_loss_grad(float *logits_inout, int64_t ld_logits, co
     const long long *ac = reinterpret_cast<const long long *>(actions);
 #define UAVAGENT_LOSS(P_) hipLaunchKernelGGL((a2c_loss_grad_kernel<P_>), dim3(kLossBlocks), dim3(256), 0, s, logits_inout, v, v_target, ac, \
                                              (long long)m_rows, (int)n_actions, (long long)ld_logits, beta, inv_m, dv_out, colp, lossp)
-    // rows that start 16-byte aligned (the learner's: ld 640): the float4 form; UAVAGENT_LOSS_SCALAR=1 keeps the first form (A/B runs)
-    const char *force_scalar = getenv("UAVAGENT_LOSS_SCALAR");
-    const bool vec = ((reinterpret_cast<uintptr_t>(logits_inout) & 15) == 0) && ((ld_logits & 3) == 0) && (ld_logits >= ((n_actions + 3) & ~3)) &&
-                     !(force_scalar && force_scalar[0] == '1');
+    // rows that start 16-byte aligned (the learner's: ld 640): the float4 form
+    const bool vec = ((reinterpret_cast<uintptr_t>(logits_inout) & 15) == 0) && ((ld_logits & 3) == 0) && (ld_logits >= ((n_actions + 3) & ~3));
 #define UAVAGENT_LOSSV(P_) hipLaunchKernelGGL((a2c_loss_grad_vec_kernel<P_>), dim3(kLossBlocks), dim3(256), 0, s, logits_inout, v, v_target, ac, \
                                               (long long)m_rows, (int)n_actions, (long long)ld_logits, beta, inv_m, dv_out, colp, lossp)
     if (vec) {

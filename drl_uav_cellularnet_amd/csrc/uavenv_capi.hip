@@ -933,15 +933,6 @@ extern "C" int uavenv_lean_math_eval(int op, const double *a_dev, const double *
     return UAVENV_OK;
 }
 
-#ifdef UAVENV_STAMPS
-// Diagnostic builds only (not in include/uavenv.h): where the kernels drop their s_memtime stamps.
-extern "C" int uavenv_debug_set_stamp_buffer(uavenv_t *h, void *dev_ptr) {
-    if (!h) return fail(UAVENV_E_INVALID, "debug_set_stamp_buffer: null handle");
-    h->kp.dbg = (unsigned long long *)dev_ptr;
-    return UAVENV_OK;
-}
-#endif
-
 extern "C" int uavenv_state_layout(const uavenv_t *h, UavEnvStateLayout *layout) {
     if (!h || !layout) return fail(UAVENV_E_INVALID, "state_layout: null argument");
     *layout = h->lay;

@@ -58,9 +58,3 @@ extern "C" int uavenv_rollout_gated(uavenv_t *h, const UavEnvGatedRollout *r, co
     return UAVENV_OK;
 }
 
-
-#ifdef UAVENV_GATE_STAMPS
-extern "C" int uavenv_debug_set_gate_stamps(void *dev_ptr) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(uavk::g_gate_dbg), &dev_ptr, sizeof(void *)) == hipSuccess ? 0 : -1;
-}
-#endif

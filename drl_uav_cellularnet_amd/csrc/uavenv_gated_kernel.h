@@ -1,6 +1,7 @@
 // libuavenv: the gated rollout kernel (uavenv_rollout_gated, include/uavenv.h).  Included by uavenv_gated.hip only; the step body it runs
 // is env_packed_body of uavenv_kernels.h.
 #pragma once
+#include "rollout_gate.h"
 #include "uavenv_kernels.h"
 
 namespace uavk {
@@ -14,7 +15,7 @@ namespace uavk {
 //     gate_obs[b] >= t + 1   "the encoded observation BEFORE step t of block b's envs is in out_a[t] / out_c[t]"  (set here, awaited there;
 //                             t = 0 is the caller's: it encodes the observation the rollout starts from and presets the word to 1)
 // and the protocol of sched_hand_off_*: payload in coherent stores -> s_waitcnt vmcnt(0) -> the word; the reader polls ONE lane, bounded,
-// and loads the payload coherently after it.  A wait that does not end within the budget stores kDevErrGate in the handle's error word
+// and loads the payload coherently after it.  A wait that does not end within the budget stores rollout_gate::kErrGate in the handle's error word
 // and the wavefront leaves the kernel; the host then fails every later call (UAVENV_E_DEVICE), it never hangs.
 //
 // A workgroup of 8 wavefronts owns a PAIR of blocks (32 envs) for the whole rollout and alternates between them: while the policy
@@ -30,7 +31,7 @@ namespace uavk {
 // wavefronts at <= 96 VGPRs beside the policy kernel's 2 x 112: the pair 4.43-4.54 against 3.75 ms, the step body spills 68 registers at 96; one wavefront per (env, table) with all 24 pieces
 // issued at once: the same time as 16 at once; every second pair starting 8-36 us late so that the CUs' encoder phases do not coincide: 1 %;
 // non-temporal table loads: the encoder alone 4.19 instead of 3.13 ms per rollout.)
-// Launch: min(pairs, CUs) workgroups of kGateWaves = 8 wavefronts, at most UAVENV_GATE_VGPRS = 144 VGPRs (amdgpu_num_vgpr, which counts register
+// Launch: min(pairs, CUs) workgroups of kGateWaves = 8 wavefronts, at most rollout_gate::kEnvVgprs = 144 VGPRs (amdgpu_num_vgpr, which counts register
 // PAIRS on gfx90a and later); the partner at most 112: one workgroup of each fills a CU's register file exactly (2 x 144 + 2 x 112 per SIMD lane), and that is how an idle chip is filled -- one pair per
 // CU.  Residency: nothing here DEPENDS on that placement.  Pairs of blocks are claimed from a counter in arrival order by both kernels, so
 // whichever workgroups are resident hold the lowest unfinished pairs on both sides; if the dispatcher ever puts two of these workgroups on one
@@ -40,27 +41,10 @@ namespace uavk {
 // profiles/r04g_gated_kernels_alone_vgpr_caps.txt.)
 // ================================================================================================
 constexpr int kGateRows = 16, kGateWaves = 8;
-#ifndef UAVENV_GATE_UNR24
-#define UAVENV_GATE_UNR24 8      /* rows (x tables) in flight per wavefront at 24 nodes; 12: A/B build */
-#endif
 // What the step body loads coherently (env_packed_body's HO bits): the ACTIONS -- another kernel wrote them.  Not the env state and not the
 // observation the encoder reads back: only wavefronts of this workgroup touch them during the launch, they share one CU and its L1 (work-group
-// scope needs no cache bypass on gfx950), and the launch boundary took care of everything older.  UAVENV_GATE_COHERENT_STATE=1 (build flag,
-// A/B): state and observation past the L1 as well.
-#ifdef UAVENV_GATE_COHERENT_STATE
-constexpr int kGateHO = 5;
-#define GATE_OBS_LOAD(ptr) __hip_atomic_load(ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#else
+// scope needs no cache bypass on gfx950), and the launch boundary took care of everything older.
 constexpr int kGateHO = 4;
-#define GATE_OBS_LOAD(ptr) (*(ptr))
-#endif
-#ifdef UAVENV_GATE_STAMPS       /* diagnostic build (tools/gated_timeline.py): s_memrealtime (100 MHz, one clock for the whole chip) of pair 0's events */
-__device__ unsigned long long *g_gate_dbg;    // [T][2 halves][8]: slot 2 = actions seen, 3 = env step done (outputs in L2), 4 = encoded rows published
-#define GATE_STAMP(t, half, k) do { if (g_gate_dbg != nullptr && pair == 0 && threadIdx.x == 0) g_gate_dbg[((t) * 2 + (half)) * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define GATE_STAMP(t, half, k) do { } while (0)
-#endif
-constexpr uint32_t kDevErrGate = 0x47415445u;      // "GATE": error word of a gate wait that timed out
 struct GatedParams {
     int T, n_blocks;
     const long long *actions;      // [T][N]
@@ -73,22 +57,6 @@ struct GatedParams {
     long long n_rows;
     int H4, relu6, G;
 };
-
-__device__ __forceinline__ bool gate_wait(uint32_t *word, uint32_t need, const KParams &p) {
-    const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
-    const unsigned long long budget = (unsigned long long)p.sched_spin_us * 100ull;           // s_memrealtime ticks at 100 MHz
-    bool ok = false;
-    for (;;) {
-        uint32_t v = 0u;
-        if ((threadIdx.x & 63) == 0) v = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((uint32_t)__builtin_amdgcn_readfirstlane((int)v) >= need) { ok = true; break; }
-        if (__builtin_amdgcn_s_memrealtime() - t_start > budget) break;
-        __builtin_amdgcn_s_sleep(8);
-    }
-    if (!ok && (threadIdx.x & 63) == 0) __hip_atomic_store(p.sched_err, kDevErrGate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    asm volatile("" ::: "memory");
-    return ok;
-}
 
 __device__ __forceinline__ void enc_fma4(float4 &s, const float4 &v, float w) {
     s.x = __builtin_fmaf(v.x, w, s.x); s.y = __builtin_fmaf(v.y, w, s.y); s.z = __builtin_fmaf(v.z, w, s.z); s.w = __builtin_fmaf(v.w, w, s.w);
@@ -125,14 +93,14 @@ __device__ __forceinline__ void encode_env(const GatedParams &g, const OutPtrs &
         int x, y, pl;
         if (k < B) {     // (written by other wavefronts of this workgroup a moment ago: see kGateHO)
             union { unsigned long long w; int2 c; } q;
-            q.w = GATE_OBS_LOAD(reinterpret_cast<const unsigned long long *>(obs.bs_xy) + (me * B + k));
+            q.w = *(reinterpret_cast<const unsigned long long *>(obs.bs_xy) + (me * B + k));
             x = q.c.x; y = q.c.y; pl = 0;
         } else {
             const long long iu = me * U + (k - B);
             union { uint32_t w; short2 c; } q;
-            q.w = GATE_OBS_LOAD(reinterpret_cast<const uint32_t *>(obs.ue_xy) + iu);
+            q.w = *(reinterpret_cast<const uint32_t *>(obs.ue_xy) + iu);
             x = q.c.x; y = q.c.y;
-            pl = 1 + (int)GATE_OBS_LOAD(obs.serving + iu);
+            pl = 1 + (int)obs.serving[iu];
         }
         const bool ok = x >= 0 && x < g.G && y >= 0 && y < g.G && pl >= 0 && pl <= B;
         mine = ok ? ((long long)pl * g.G + x) * g.G + y : -1ll;
@@ -190,16 +158,8 @@ __device__ __forceinline__ void encode_env(const GatedParams &g, const OutPtrs &
     if (NS > 1) one_env(std::integral_constant<int, (NS > 1 ? 1 : 0)>{});
 }
 
-#ifdef UAVENV_GATE_NOCAP        /* timing experiment: the kernel without its register cap (such a build cannot run beside its partner) */
-#define UAVENV_GATE_CAP
-#else
-#ifndef UAVENV_GATE_VGPRS
-#define UAVENV_GATE_VGPRS 144       /* this kernel's share of a SIMD lane's 512 registers is 2 x this; the policy kernel has the rest (112) */
-#endif
-#define UAVENV_GATE_CAP __attribute__((amdgpu_num_vgpr(UAVENV_GATE_VGPRS / 2)))       /* (gfx90a and later: the attribute counts VGPR + AGPR pairs) */
-#endif
 template <int BT, bool PLC, int KT, bool TWO>
-__global__ __launch_bounds__(64 * kGateWaves) UAVENV_GATE_CAP void env_kernel_gated(char *blob, const int8_t *gid_of_u, long long N, int U, int EPW, int Gr, int B_rt,
+__global__ __launch_bounds__(64 * kGateWaves) __attribute__((amdgpu_num_vgpr(rollout_gate::kEnvVgprs / 2))) void env_kernel_gated(char *blob, const int8_t *gid_of_u, long long N, int U, int EPW, int Gr, int B_rt,
                                                                                      int lane_magic, const GatedParams g, const KParams p) {
     __shared__ int s_bs[kGateWaves][kMaxEpw][2 * kMaxBs];
     __shared__ int s_pair;
@@ -221,8 +181,7 @@ __global__ __launch_bounds__(64 * kGateWaves) UAVENV_GATE_CAP void env_kernel_ga
                 if (blk >= g.n_blocks) continue;
                 const int e_lo = blk * kGateRows;
                 const int e_hi = (long long)(e_lo + kGateRows) < N ? e_lo + kGateRows : (int)N;
-                if (!gate_wait(g.gate_act + blk, (uint32_t)t + 1u, p)) return;
-                GATE_STAMP(t, half, 2);
+                if (!rollout_gate::wait(g.gate_act + blk, (uint32_t)t + 1u, p.sched_err, p.sched_spin_us)) return;
                 const int w_lo = e_lo / EPW, n_w = (e_hi - 1) / EPW - w_lo + 1;
                 for (int w = wave; w < n_w; w += kGateWaves) {
                     env_packed_body<BT, MODE_STEP, PLC, true, false, false, kGateHO>(blob, g.actions + (long long)t * N, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, p,
@@ -231,17 +190,15 @@ __global__ __launch_bounds__(64 * kGateWaves) UAVENV_GATE_CAP void env_kernel_ga
                 }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wavefront's output stores are in the L2
                 __syncthreads();
-                GATE_STAMP(t, half, 3);
                 const bool gather = t + 1 < g.T;
                 // (UNR as in sparse_rows_sum_kernel: 24 = 3 x 8, 44 = 11 x 4; at 24 nodes a wavefront takes its two envs of the block, m and m + 8, at once)
                 constexpr int NS = (KT > 0 && 2 * KT <= 64) ? 2 : 1;
                 for (int m = e_lo + wave; m < e_hi; m += NS * kGateWaves)
-                    encode_env<KT, (KT == 44 ? 4 : UAVENV_GATE_UNR24), TWO, NS>(g, p.out, m, kGateWaves, (NS > 1 && m + kGateWaves < e_hi) ? 2 : 1, U, BT, N, t + 1, gather);
+                    encode_env<KT, (KT == 44 ? 4 : 8), TWO, NS>(g, p.out, m, kGateWaves, (NS > 1 && m + kGateWaves < e_hi) ? 2 : 1, U, BT, N, t + 1, gather);
                 if (gather) {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the encoded rows have left
                     __syncthreads();
                     if (threadIdx.x == 0) __hip_atomic_store(g.gate_obs + blk, (uint32_t)t + 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    GATE_STAMP(t, half, 4);
                 }
             }
             if (g.reward != nullptr) po.reward += N;

@@ -39,10 +39,7 @@
 
 namespace uavk {
 
-#ifndef UAVENV_WAVES_PER_BLOCK
-#define UAVENV_WAVES_PER_BLOCK 4   // wavefronts per workgroup of the env kernels (build-time knob for A/B runs)
-#endif
-constexpr int kWavesPerBlock = UAVENV_WAVES_PER_BLOCK;
+constexpr int kWavesPerBlock = 4;   // wavefronts per workgroup of the env kernels
 constexpr int kMaxGroups = 16;
 constexpr int kMaxBs = 32;
 constexpr int kMaxEpw = 8;  // env instances per wavefront (packed kernel)
@@ -105,7 +102,7 @@ struct KParams {
     const double *inj_theta, *inj_group, *inj_fading;
     const long long *actions; const uint8_t *mask; const int16_t *trace_xy; int n_ticks;
     OutPtrs out;
-    unsigned long long *dbg;   // diagnostic builds only (UAVENV_STAMPS): [waves][8] s_memtime stamps
+    unsigned long long *dbg;   // unused; kept so that the kernarg offsets (and with them the generated code) stay as they are
     const int4 *sched;         // multi-step launches: work descriptors [launch waves][kSchedPieces] {env-wavefront, first step, steps,
                                // SCHED_* bits} of a rotation schedule (uavenv_capi.hip: rotation_plan), or null = wave w runs
                                // env-wavefront w, all steps
@@ -213,21 +210,6 @@ __device__ __forceinline__ StatePtrs state_from_params(const KParams &p) {
     return s;
 }
 
-// In-kernel phase stamps (diagnostic build -DUAVENV_STAMPS only; MI355X guide, "In-kernel stamps"): one asm
-// statement per stamp with its own lgkmcnt(0), scheduling barriers around it.  Values go to p.dbg, never to outputs.
-#ifdef UAVENV_STAMPS
-#define UAV_STAMP(var)                                                             \
-    do {                                                                           \
-        __builtin_amdgcn_sched_barrier(0);                                         \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var)::"memory"); \
-        __builtin_amdgcn_sched_barrier(0);                                         \
-    } while (0)
-#define UAV_DRAIN_VM() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#else
-#define UAV_STAMP(var) do { } while (0)
-#define UAV_DRAIN_VM() do { } while (0)
-#endif
-
 // Kernarg warm-up.  hipcc loads kernarg fields lazily, one scalar-load batch per block that first uses them, and the
 // phase stamps (gpurun_out/stamps_*.log) show a cold kernarg fetch costing ~1900 ticks (~1 us):
 // the kernarg block is rewritten for every launch, so the first touch of each 64-byte line misses every cache.
@@ -236,7 +218,6 @@ __device__ __forceinline__ StatePtrs state_from_params(const KParams &p) {
 // of them); the later lazy loads then hit the scalar cache.
 template <int BYTES>
 __device__ __forceinline__ void kernarg_warm() {
-#ifndef UAVENV_NO_KERNARG_WARM
     typedef const __attribute__((address_space(4))) unsigned int *kptr_t;
     kptr_t ka = (kptr_t)__builtin_amdgcn_kernarg_segment_ptr();
     // All loads are consumed by ONE asm statement, so they are issued back to back and waited for once.  (One asm per
@@ -248,7 +229,6 @@ __device__ __forceinline__ void kernarg_warm() {
     for (int i = 0; i < 16; ++i) v[i] = (i < LINES) ? ka[i * 16] : 0u;
     asm volatile("" ::"s"(v[0]), "s"(v[1]), "s"(v[2]), "s"(v[3]), "s"(v[4]), "s"(v[5]), "s"(v[6]), "s"(v[7]), "s"(v[8]),
                  "s"(v[9]), "s"(v[10]), "s"(v[11]), "s"(v[12]), "s"(v[13]), "s"(v[14]), "s"(v[15]));
-#endif
 }
 
 // ================================================================================================
@@ -752,9 +732,6 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
                                                 const OutPtrs *po = nullptr) {
     constexpr bool LDC = (HO & 1) != 0, STC = (HO & 2) != 0, ACC = (HO & 4) != 0;
     const OutPtrs &pout = po != nullptr ? *po : p.out;
-    unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, ts4 = 0, ts5 = 0, ts6 = 0;
-    (void)ts0; (void)ts1; (void)ts2; (void)ts3; (void)ts4; (void)ts5; (void)ts6;
-    UAV_STAMP(ts0);                                   // wave start
     const int lane = threadIdx.x & 63;
     const int B = uav_count<BT, FAST>(B_rt);
     const StatePtrs st = state_from_blob(blob, N, U, B, Gr);
@@ -781,7 +758,6 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
     const bool bown = (MODE != MODE_WARMUP) && live && (ul < B);     // this lane owns UAV `ul`
     const bool gown = (has_mobility(MODE)) && live && (ul < Gr);     // this lane owns RPGM group `ul`
 
-    UAV_STAMP(ts1);                                   // first kernarg words arrived, lane bookkeeping done
     // ================= load phase: every global read of the launch, issued before any dependent work ======
     constexpr bool REG_MOVE = (BT <= 8);   // serial BS_move in registers; n_act^B <= 9^8 always fits 32 bits here
     int bx = 0, by = 0;                    // the UAV this lane OWNS (store phase)
@@ -839,17 +815,7 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
     const LeanCoef C = lm_make_coef<PIN>();   // polynomial coefficients, pinned in VGPRs once per kernel (lean_math.h)
     const HotConst H = make_hot<PIN>(p);      // hot kernarg doubles, pinned in VGPRs (frees ~30 SGPRs)
     const double MAXC = H.maxc;
-    UAV_DRAIN_VM();
-    UAV_STAMP(ts2);                                   // every load of the load phase has returned
     // ================= compute ===============================================================================
-#ifdef UAVENV_SKELETON   // diagnostic build (tools/ab_variants.sh): load phase + store phase only, to measure the fixed floor
-    double sum_cur = 0.0, cur = x + y + hu + ogx + ogy + ogfl + ogv + ogc + ogs + (double)(bx + by + bsx[0] + bsy[0] + bsx[BT - 1] + bsy[BT - 1] + (int)act + (int)apw + gid);
-    int n_outage = (int)(prev_out & 1ull) + serving + r0 + r1 + r2 + depth;
-    unsigned long long ob = prev_out;
-    tick += 1u;
-    OutPtrs om = p.out;
-    (void)bs_row; (void)slot_mask; (void)n_ticks; (void)MAXC; (void)hu_inj; (void)C; (void)H; (void)om;
-#else
     // One loop body serves all launch kinds: warm-up = n_ticks mobility ticks (no UAV move, no channel update); reset / step =
     // exactly one iteration (compile-time trip count, the loop folds away); multi-step (MANY) = n_ticks whole steps, each
     // storing its outputs, with walker / group / UAV state carried in registers.
@@ -897,7 +863,6 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
             }
         }
 
-        if (!MANY) UAV_STAMP(ts3);                        // UAV move done
         // ---- mobility: next(self.mm); walker and group state stay in registers across ticks ----
         if (has_mobility(MODE)) {
             const bool aggregating = agg != 0;
@@ -941,7 +906,6 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
         if (MODE == MODE_WARMUP) continue;                // warm-up: mobility only
         if (has_mobility(MODE)) { ix = (int)x; iy = (int)y; }                            // .astype(int), mobile_env.py:154-155
 
-        if (!MANY) UAV_STAMP(ts4);                        // mobility done
         // ---- channel update (one per reset / step; Philox time = the tick just executed) ------------------
         {
             double pg[BT];
@@ -983,8 +947,6 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
         }
     }
     if (MODE == MODE_WARMUP) { ix = (int)x; iy = (int)y; }                               // cells after the last warm-up tick
-#endif  // UAVENV_SKELETON
-    UAV_STAMP(ts5);                                   // channel update done
 
     // ================= store phase: state, then outputs ==========================================================
     if (live) {
@@ -1014,16 +976,6 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
         // (MANY: outputs of the LAST step + the record; depth / step_n are the values that step started from)
         env_finish<MODE, FAST, true, true, STC>(p, MANY ? om : pout, st, ew, erec, tick, agg, deagg, depth, step_n, sum_cur, n_outage);
     }
-#ifdef UAVENV_STAMPS
-    UAV_STAMP(ts6);                                   // all stores issued (not yet acknowledged)
-    UAV_DRAIN_VM();
-    unsigned long long ts7 = 0;
-    UAV_STAMP(ts7);                                   // all stores acknowledged
-    if (p.dbg != nullptr && lane == 0) {
-        unsigned long long *d = p.dbg + ((long long)blockIdx.x * kWavesPerBlock + wave) * 8;
-        d[0] = ts0; d[1] = ts1; d[2] = ts2; d[3] = ts3; d[4] = ts4; d[5] = ts5; d[6] = ts6; d[7] = ts7;
-    }
-#endif
 }
 
 // ---- hand-off between the two wavefronts that share a split job of a one-launch schedule -----------------------------------------
@@ -1187,17 +1139,9 @@ __device__ __forceinline__ int tail_items(int U, int B) {
     return (R > 0 && (HB & (HB - 1)) == 0 && HB >= 2 && R * HB <= 64) ? HB : 0;
 }
 
-#ifndef UAVENV_MP_VGPR_PTRS
-#define UAVENV_MP_VGPR_PTRS 1   // build knob (A/B runs), see env_kernel_multipass
-#endif
-#ifndef UAVENV_MP_SGPR_COEF
-#define UAVENV_MP_SGPR_COEF 2   // build knob (A/B runs): 0 none, 1 = exp2 coefficients pinned in SGPRs, 2 = + sincospi, 3 = + log
-#endif
-#ifndef UAVENV_MP_WAVES
-#define UAVENV_MP_WAVES 3     // occupancy the register allocator must allow (waves per SIMD): 3 -> <= 168 VGPRs, 4 -> <= 128
-#endif
+// amdgpu_waves_per_eu(3): the occupancy the register allocator must allow (waves per SIMD): 3 -> <= 168 VGPRs, 4 -> <= 128
 template <int BT, int MODE, bool PLC, bool FAST>
-__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_per_eu(UAVENV_MP_WAVES)))
+__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_per_eu(3)))
 void env_kernel_multipass(const KParams p) {
     const StatePtrs st = state_from_params(p);
     constexpr bool PRE = FAST && has_mobility(MODE);
@@ -1216,20 +1160,12 @@ void env_kernel_multipass(const KParams p) {
     // Polynomial coefficients in SGPR PAIRS (lm_pin_sgpr): a float64 literal cannot be an operand, so every use of an unpinned
     // coefficient costs a v_mov_b64 (50 of the 300 instructions of a fading iteration); VGPR pinning costs occupancy (above); a Horner
     // step fma(p, r, c_k) may read one scalar operand, so SGPR-resident coefficients cost nothing per use.  The scalar file only has room
-    // once the pass loop's seven pointers live in VGPRs (UAVENV_MP_VGPR_PTRS).  One box, 8192 envs of 16 x 200
+    // once the pass loop's seven pointers live in VGPRs (below).  One box, 8192 envs of 16 x 200
     // (profiles/r02c_config5_multipass_v2.txt): none 150.5 us; exp2 146.4; exp2 + pointers 145.0; exp2 + sincospi + pointers 142.3
     // (shipped); + log coefficients 146.8 (the scalar file overflows again).
     LeanCoef C = lm_make_coef<false>();
-#if UAVENV_MP_SGPR_COEF >= 1
     for (int k = 0; k < 13; ++k) lm_pin_sgpr(C.e2[k]);     // exp2: evaluated twice per fading iteration
-#endif
-#if UAVENV_MP_SGPR_COEF >= 2
     for (int k = 0; k < 8; ++k) { lm_pin_sgpr(C.sp[k]); lm_pin_sgpr(C.cp[k]); }
-#endif
-#if UAVENV_MP_SGPR_COEF >= 3
-    for (int k = 0; k < 7; ++k) lm_pin_sgpr(C.lg[k]);
-    lm_pin_sgpr(C.ln2_hi); lm_pin_sgpr(C.ln2_lo);
-#endif
     const HotConst H = make_hot<false>(p);
 
     const int U = p.U, B = uav_count<BT, FAST>(p.B), Gr = p.Gr;
@@ -1286,9 +1222,8 @@ void env_kernel_multipass(const KParams p) {
     const int depth = erec.fifo_depth, step_n = erec.step_n;
     double sum_cur = 0.0;
     int n_outage = 0;
-#if UAVENV_MP_VGPR_PTRS
     // The pointers the pass loop uses, as (uniform) VGPR pairs: 14 SGPRs fewer live across the fading loop, where the scalar
-    // file is wanted for polynomial coefficients (UAVENV_MP_SGPR_COEF); an access then forms its address with one v_lshl_add_u64.
+    // file is wanted for polynomial coefficients (above); an access then forms its address with one v_lshl_add_u64.
     UeAux *const pv_aux = vgpr_ptr(st.ue_aux);
     UePos *const pv_pos = vgpr_ptr(st.ue_pos);
     unsigned long long *const pv_bits = vgpr_ptr(st.out_bits);
@@ -1296,15 +1231,6 @@ void env_kernel_multipass(const KParams p) {
     int16_t *const pv_oxy = vgpr_ptr(p.out.ue_xy);
     int8_t *const pv_osrv = vgpr_ptr(p.out.serving);
     float *const pv_osinr = vgpr_ptr(p.out.cur_sinr);
-#else
-    UeAux *const pv_aux = st.ue_aux;
-    UePos *const pv_pos = st.ue_pos;
-    unsigned long long *const pv_bits = st.out_bits;
-    const int8_t *const pv_gid = p.gid_of_u;
-    int16_t *const pv_oxy = p.out.ue_xy;
-    int8_t *const pv_osrv = p.out.serving;
-    float *const pv_osinr = p.out.cur_sinr;
-#endif
 
     for (int it = 0; it < n_ticks; ++it) {
         const bool aggregating = agg != 0;

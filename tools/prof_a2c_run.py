@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A few whole A2C iterations (collect + update) at BASELINE config 3 for rocprofv3 (tools/r03_pmc_a2c.sh)."""
+"""A few whole A2C iterations (collect + update) at BASELINE config 3 for rocprofv3."""
 import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

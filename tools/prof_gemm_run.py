@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A few launches of each hand-written GEMM for rocprofv3 (tools/r03_gemm_prof.sh)."""
+"""A few launches of each hand-written GEMM for rocprofv3."""
 import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
