@@ -323,14 +323,15 @@ class A2CRunner:
 
     On a GPU the rollout loop is ONE hipGraph (per step three kernels: first layer fed from the env's compact observation + the actor's
     head (layer 2, policy head, action draw) + env step) and the update is a hand-derived backward pass on libuavagent's kernels
-    (float32 MFMA GEMMs with fused epilogues, loss gradient, table gradient, RMSProp).  Every fusion has a switch
-    (``hip_gemms``, ``fused_head``, ``fused_obs``, ``overlap_dw``, ``overlap_allreduce``) whose other setting is the form it replaced; the
-    tests compare the two bit for bit where the arithmetic is the same and to tolerance where it is not.  ``update_reference`` is the same
-    update through autograd."""
+    (float32 MFMA GEMMs with fused epilogues, loss gradient, table gradient, RMSProp).  Each switch
+    (``hip_gemms``, ``fused_head``, ``fused_obs``, ``overlap_allreduce``, ``pipeline_halves``, ``persistent_rollout``) turns on a fused or
+    overlapped form where the shapes and the process group allow it; its other setting is the form that still serves the rest, and the tests
+    compare the two bit for bit where the arithmetic is the same and to tolerance where it is not.  ``update_reference`` is the same update
+    through autograd."""
 
     def __init__(self, env, net=None, rollout=50, gamma=GAMMA, beta=ENTROPY_BETA, lr_a=LR_A, lr_c=LR_C, seed=6,
                  update_chunk=65536, first_state="obs", collect_launch="graph", fused_update=True, tune_gemms=False, hip_gemms=True,
-                 overlap_allreduce=True, fused_head=True, overlap_dw=False, fused_obs=True, early_sort=True, pipeline_halves=True, force_exchange=False,
+                 overlap_allreduce=True, fused_head=True, fused_obs=True, pipeline_halves=True, force_exchange=False,
                  persistent_rollout="auto"):
         self.env = env
         self.dev = env.device
@@ -363,13 +364,6 @@ class A2CRunner:
         self.force_exchange = bool(force_exchange)
         # fused_head: layer 2, the policy head and the action draw of a rollout step as ONE kernel (uavagent_actor_head_f32)
         self.fused_head = bool(fused_head) and self.hip_gemms and 576 < self.net.n_action <= 640
-        # overlap_dw (one rank, hip_gemms): the three dW GEMMs (MFMA bound, 1.6 ms at config 3) run on a side stream beside the
-        # first-layer table gradient (sort + indexed row sums: memory bound, 2.4 ms) instead of between the dX GEMMs.  Off by default:
-        # side by side each runs that much slower (rocprofv3: the gather 2.2 -> 3.2 ms, a dW GEMM 0.33 -> up to 2.1 ms); the update takes
-        # the same 6.9 ms either way (tools/ab_update.py)
-        self.overlap_dw = bool(overlap_dw)
-        # early_sort (hip_gemms): the table gradient's sort of the (row, sample) pairs starts on a side stream before the update's forward pass
-        self.early_sort = bool(early_sort)
         # fused_obs: steps 1 .. T-1 of a rollout build their index list inside the first layer's kernel (uavagent_first_layer_from_obs_f32)
         # instead of a separate obs_indices launch after every env step
         self.fused_obs = bool(fused_obs) and env.nBS + env.nUE <= 64
@@ -385,8 +379,6 @@ class A2CRunner:
         # True = when each half still fills the chip (>= 4096 envs), "force" = whenever the batch can be cut (tests).
         self._halves = None
         self._pipe_stream = None
-        import os as _os
-
         if pipeline_halves and self.dev.type == "cuda" and self.fused_head and self.fused_obs:
             # the cut lies on a multiple of the head's 16-row tiles (half a batch runs on 16-row workgroups: 8192 envs = 2 x 256 tiles = one
             # workgroup per CU and half)
@@ -403,8 +395,8 @@ class A2CRunner:
         self._persistent = False
         self._persist_stream = None
         self._persistent_proven = False
-        self._persist_same_stream = _os.environ.get("UAVAGENT_PERSIST_SAME_STREAM", "0") == "1"
-        self._gate_spin_us = int(_os.environ.get("UAVAGENT_GATE_SPIN_US", "0"))     # 0 = the library's 2 s
+        self._persist_same_stream = False            # test hook: both persistent kernels in ONE queue, i.e. never side by side
+        self._gate_spin_us = 0                       # test hook: the policy kernel's wait budget; 0 = the library's 2 s
         if (persistent_rollout and self.dev.type == "cuda" and self.fused_head and self.fused_obs and env.nBS == 4 and env.nUE <= 64
                 and env.n_envs % 4 == 0 and "cur_sinr_f64" not in env.out and (persistent_rollout is True or env.n_envs >= 4096)):
             self._persistent = True
@@ -475,6 +467,39 @@ class A2CRunner:
         else:
             out.copy_(obs_to_indices(self.env.observation(), self.G, self.B))
 
+    def _first_layer(self, t, lo, hi):
+        """Both trunks' first layers (relu6) for the rows [lo, hi) of step t (GPU): gathered from idx_buf[t] at t = 0 or without fused_obs,
+        else with the index list built from the observation step t - 1 left behind, inside the gather (and stored to idx_buf[t])."""
+        from . import _agent_capi as A
+
+        net, fw = self.net, self._fwd
+        if t == 0 or not self.fused_obs:
+            # both trunks in one gather (tried twice, round 2 and round 3: the critic's half on a second stream beside the actor's GEMMs is
+            # SLOWER, 6.3-6.4 against 5.5 ms per rollout: two 800-byte gathers cost more than one of 1600)
+            A.sparse_rows_sum(self.idx_buf[t][lo:hi], net.a_w1, net.a_b1, net.c_w1, net.c_b1, relu6=True, out_a=fw["h1a"][t][lo:hi],
+                              out_c=fw["h1c"][t][lo:hi])
+        else:
+            A.first_layer_from_obs({k: v[lo:hi] for k, v in self.env.observation().items()}, self.G, net.a_w1, net.a_b1, net.c_w1, net.c_b1,
+                                   fw["h1a"][t][lo:hi], fw["h1c"][t][lo:hi], idx_out=self.idx_buf[t][lo:hi])
+
+    def _policy(self, t, lo, hi):
+        """The actor's layer 2, policy head and action draw for the rows [lo, hi) of step t (GPU)."""
+        from . import _agent_capi as A
+
+        net, fw, wt = self.net, self._fwd, self._wt
+        h1a, h2a, logits = fw["h1a"][t][lo:hi], fw["h2a"][t][lo:hi], fw["logits"][t][lo:hi]
+        u, act = self.u_buf[t][lo:hi], self.act_buf[t][lo:hi]
+        if self.fused_head:      # one launch, 32 rows per workgroup
+            A.actor_head(h1a, wt["a_w2t"], net.a_b2, wt["a_w3t"], wt["a_b3p"], u, net.n_action, h2a, self._logits_pad[t][lo:hi], act)
+        elif wt is not None:     # float32 MFMA kernels, bias / relu6 fused, 64-row workgroups (8192 rows fill the chip)
+            A.gemm_rows(h1a, wt["a_w2t"], h2a, w_transposed=True, bias=net.a_b2, relu6=True)
+            A.gemm_rows(h2a, wt["a_w3t"], self._logits_pad[t][lo:hi], w_transposed=True, bias=wt["a_b3p"])
+            A.sample_actions(logits, u, out=act)
+        else:
+            torch.addmm(net.a_b2, h1a, net.a_w2, out=h2a).clamp_(0.0, 6.0)
+            torch.addmm(net.a_b3, h2a, net.a_w3, out=logits)
+            A.sample_actions(logits, u, out=act)
+
     def _rollout_steps(self):
         """The T-step loop: choose_action (main.py:165-169) -> env.step -> next observation.  No host synchronisation, no
         allocation visible to the caller: capturable."""
@@ -482,41 +507,18 @@ class A2CRunner:
             return self._rollout_steps_persistent()
         if self._halves is not None:
             return self._rollout_steps_pipelined()
-        env, T, net = self.env, self.T, self.net
+        env, T, N = self.env, self.T, self.env.n_envs
         self.idx_buf[0].copy_(self.idx_buf[T])
         cuda = self.dev.type == "cuda"
-        if cuda:
-            from . import _agent_capi as A
-        fw = self._fwd
-        wt = self._wt if cuda else None
-        fused_obs = cuda and self.fused_obs
         for t in range(T):
-            if cuda and fused_obs and t > 0:
-                # the index list of step t is built from the observation step t - 1 left behind, inside the gather (and stored)
-                A.first_layer_from_obs(env.observation(), self.G, net.a_w1, net.a_b1, net.c_w1, net.c_b1, fw["h1a"][t], fw["h1c"][t],
-                                       idx_out=self.idx_buf[t])
-            elif cuda:
-                # both trunks' first layers in one gather (tried twice, round 2 and round 3: the critic's half on a second stream beside
-                # the actor's GEMMs is SLOWER, 6.3-6.4 against 5.5 ms per rollout: two 800-byte gathers cost more than one of 1600)
-                A.sparse_rows_sum(self.idx_buf[t], net.a_w1, net.a_b1, net.c_w1, net.c_b1, relu6=True, out_a=fw["h1a"][t],
-                                  out_c=fw["h1c"][t])
             if cuda:
-                if wt is not None and self.fused_head:      # layer 2 + policy head + action draw: one launch, 32 rows per workgroup
-                    A.actor_head(fw["h1a"][t], wt["a_w2t"], net.a_b2, wt["a_w3t"], wt["a_b3p"], self.u_buf[t], net.n_action,
-                                 fw["h2a"][t], self._logits_pad[t], self.act_buf[t])
-                elif wt is not None:     # float32 MFMA kernels, bias / relu6 fused, 64-row workgroups (8192 rows fill the chip)
-                    A.gemm_rows(fw["h1a"][t], wt["a_w2t"], fw["h2a"][t], w_transposed=True, bias=net.a_b2, relu6=True)
-                    A.gemm_rows(fw["h2a"][t], wt["a_w3t"], self._logits_pad[t], w_transposed=True, bias=wt["a_b3p"])
-                    A.sample_actions(fw["logits"][t], self.u_buf[t], out=self.act_buf[t])
-                else:
-                    torch.addmm(net.a_b2, fw["h1a"][t], net.a_w2, out=fw["h2a"][t]).clamp_(0.0, 6.0)
-                    torch.addmm(net.a_b3, fw["h2a"][t], net.a_w3, out=fw["logits"][t])
-                    A.sample_actions(fw["logits"][t], self.u_buf[t], out=self.act_buf[t])
+                self._first_layer(t, 0, N)
+                self._policy(t, 0, N)
             else:
-                prob = net.actor_only(self.idx_buf[t])
+                prob = self.net.actor_only(self.idx_buf[t])
                 self.act_buf[t] = sample_actions(prob, uniforms=self.u_buf[t])
             env.step(self.act_buf[t], reward_out=self.rew_buf[t])
-            if not fused_obs or t == T - 1:
+            if not (cuda and self.fused_obs) or t == T - 1:
                 self._indices_into(self.idx_buf[t + 1])
 
     def _rollout_steps_persistent(self):
@@ -527,7 +529,7 @@ class A2CRunner:
         env, T, net, fw, wt = self.env, self.T, self.net, self._fwd, self._wt
         env.copy_state_to(self._persist_state)       # one 11 MB device copy per rollout: what collect() falls back on if a kernel gives up
         self.idx_buf[0].copy_(self.idx_buf[T])
-        A.sparse_rows_sum(self.idx_buf[0], net.a_w1, net.a_b1, net.c_w1, net.c_b1, relu6=True, out_a=fw["h1a"][0], out_c=fw["h1c"][0])
+        self._first_layer(0, 0, env.n_envs)
         self._gate_obs.fill_(1)
         self._gate_act.zero_()
         self._gate_claim.zero_()
@@ -537,9 +539,7 @@ class A2CRunner:
             # the queue of the (normal-priority) stream the policy kernel is launched on -- two kernels that wait for each other must never sit
             # behind one another in ONE queue (that ends in the bounded waits' error code, and in the fallback of _prove_persistent)
             self._persist_stream = torch.cuda.Stream(device=self.dev, priority=-1)
-        side = self._persist_stream
-        if self._persist_same_stream:                # test hook (UAVAGENT_PERSIST_SAME_STREAM=1): both kernels in ONE queue, i.e. never side by side
-            side = main
+        side = main if self._persist_same_stream else self._persist_stream
         fork = torch.cuda.Event()
         fork.record(main)
         side.wait_event(fork)
@@ -553,42 +553,48 @@ class A2CRunner:
         main.wait_event(join)
 
     def _prove_persistent(self):
-        """Eager launches: one trial rollout on a CLONE of the env state shows whether the two persistent kernels run side by side on the
+        """Eager launches: one trial rollout on a snapshot of the env state shows whether the two persistent kernels run side by side on the
         streams this runner uses (the stream -> hardware-queue mapping is fixed when a stream is created); if not, the per-step launches take
         over for good.  (The captured form has the same trial in _capture.)"""
-        restore = self._snapshot()
-        refused = None
-        try:
-            self._rollout_steps()
-        except Exception as ex:                        # an entry point refused the shapes before launching anything
-            refused = ex
-        torch.cuda.synchronize(self.dev)
-        if refused is not None or self._persistent_failed():
-            self._give_up_persistent("eager trial: %s" % ("refused: %s" % refused if refused is not None else "a gate wait timed out"))
-        restore()
+        self._trial("eager trial", self._rollout_steps)
         self._persistent_proven = True
 
-    def _snapshot(self):
-        """Copies what a trial rollout changes -- the env state, env.out and idx_buf[T] -- and returns the function that puts them back."""
-        env = self.env
+    def _trial(self, what, run):
+        """Runs ``run`` (a rollout: the eager launches or the replay of their captured graph) on what a rollout changes -- the env state,
+        env.out and idx_buf[T] -- synchronises and puts all three back.  Persistent form: returns whether its two kernels ran side by side;
+        they did not when an entry point refused the launch or a gated wait timed out, and then the per-step launches take over for good."""
+        env, T = self.env, self.T
         state = torch.empty(env._lay.total_bytes, dtype=torch.uint8, device=self.dev)
         env.copy_state_to(state)
-        keep = {k: v.clone() for k, v in env.out.items()}
-        keep_idx = self.idx_buf[self.T].clone()
-
-        def restore():
+        keep_out = {k: v.clone() for k, v in env.out.items()}
+        keep_idx = self.idx_buf[T].clone()
+        why = None
+        try:
+            run()
+        except Exception as ex:                        # (persistent form: an entry point refused the shapes before launching anything)
+            if not self._persistent:
+                raise
+            why = "refused: %s" % ex
+        finally:
+            torch.cuda.synchronize(self.dev)
+            if why is None and self._persistent and self._persistent_failed():
+                why = "a gate wait timed out"
             env.copy_state_from(state)                 # (also clears the env handle's device-error word)
-            for k, v in keep.items():
+            for k, v in keep_out.items():
                 env.out[k].copy_(v)
-            self.idx_buf[self.T].copy_(keep_idx)
-        return restore
+            self.idx_buf[T].copy_(keep_idx)
+        if why is not None:
+            self._give_up_persistent("A2CRunner: the persistent rollout kernels did not run side by side (%s: %s); using the per-step launches "
+                                     "instead" % (what, why))
+        return why is None
 
-    def _give_up_persistent(self, why):
-        """The two persistent kernels did not run side by side: the per-step launches take over for good."""
+    def _give_up_persistent(self, message):
+        """The persistent rollout is abandoned (warning ``message``): the per-step launches take over for good.  Clears the policy
+        library's error word; the caller's restore of the env state clears the env handle's."""
         import warnings
         from . import _agent_capi as A
 
-        warnings.warn("A2CRunner: the persistent rollout kernels did not run side by side (%s); using the per-step launches instead" % why)
+        warnings.warn(message)
         self._persistent = False
         A.device_error_clear()
 
@@ -605,7 +611,7 @@ class A2CRunner:
         else overlaps them.  Capturable: the second stream forks from and joins the calling stream through events."""
         from . import _agent_capi as A
 
-        env, T, net, fw, wt = self.env, self.T, self.net, self._fwd, self._wt
+        env, T = self.env, self.T
         self.idx_buf[0].copy_(self.idx_buf[T])
         main = torch.cuda.current_stream(self.dev)
         if self._pipe_stream is None:
@@ -618,26 +624,19 @@ class A2CRunner:
         fork = torch.cuda.Event()
         fork.record(main)
         side.wait_event(fork)
-        obs = env.observation()
         last_head = None                                              # event behind the head issued last
         for t in range(T):
             for (lo, hi), st in zip(self._halves, (main, side)):
                 with torch.cuda.stream(st):
-                    if t == 0:
-                        A.sparse_rows_sum(self.idx_buf[0][lo:hi], net.a_w1, net.a_b1, net.c_w1, net.c_b1, relu6=True, out_a=fw["h1a"][0][lo:hi],
-                                          out_c=fw["h1c"][0][lo:hi])
-                    else:
-                        A.first_layer_from_obs({k: v[lo:hi] for k, v in obs.items()}, self.G, net.a_w1, net.a_b1, net.c_w1, net.c_b1,
-                                               fw["h1a"][t][lo:hi], fw["h1c"][t][lo:hi], idx_out=self.idx_buf[t][lo:hi])
+                    self._first_layer(t, lo, hi)
                     if last_head is not None:
                         st.wait_event(last_head)                     # the heads run one after the other; everything else overlaps them
-                    A.actor_head(fw["h1a"][t][lo:hi], wt["a_w2t"], net.a_b2, wt["a_w3t"], wt["a_b3p"], self.u_buf[t][lo:hi], net.n_action,
-                                 fw["h2a"][t][lo:hi], self._logits_pad[t][lo:hi], self.act_buf[t][lo:hi])
+                    self._policy(t, lo, hi)
                     last_head = torch.cuda.Event()
                     last_head.record(st)
                     env.step_range(self.act_buf[t], lo, hi - lo, reward_out=self.rew_buf[t])
                     if t == T - 1:
-                        A.obs_indices({k: v[lo:hi] for k, v in obs.items()}, self.G, self.B, out=self.idx_buf[T][lo:hi])
+                        A.obs_indices({k: v[lo:hi] for k, v in env.observation().items()}, self.G, self.B, out=self.idx_buf[T][lo:hi])
         join = torch.cuda.Event()
         join.record(side)
         main.wait_event(join)
@@ -673,16 +672,13 @@ class A2CRunner:
             # something else kept one of them off the chip for longer than the spin budget).  Nothing is lost: the rollout started from the
             # state snapshot _rollout_steps_persistent took, the uniforms are still in u_buf -- restore, switch to the per-step launches for
             # good, and collect this rollout again: same results as if the persistent kernels had finished.
-            import warnings
-            from . import _agent_capi as _A2
+            from . import _agent_capi as A
 
-            warnings.warn("A2CRunner.collect: a persistent rollout kernel gave up waiting for its partner (device error words: policy 0x%08x, env "
-                          "0x%08x); the rollout is collected again with the per-step launches, which this runner uses from now on"
-                          % (_A2.device_error(), env.device_error()))
-            _A2.device_error_clear()
+            self._give_up_persistent("A2CRunner.collect: a persistent rollout kernel gave up waiting for its partner (device error words: policy "
+                                     "0x%08x, env 0x%08x); the rollout is collected again with the per-step launches, which this runner uses from "
+                                     "now on" % (A.device_error(), env.device_error()))
             env.copy_state_from(self._persist_state)                                 # (also clears the env handle's device-error word)
             self.idx_buf[T].copy_(self.idx_buf[0])
-            self._persistent = False
             self._graph = None                                                       # (the next collect() captures the per-step form)
             self._rollout_steps()
             done = env.out["done"].bool()
@@ -712,41 +708,29 @@ class A2CRunner:
             wt["a_b3p"][:net.n_action].copy_(net.a_b3)
 
     def _capture(self):
-        """hipGraph of the rollout loop.  A warm-up pass on a side stream first (rocBLAS handles / workspaces), on a CLONE of the
-        env state so that capturing changes nothing the caller can observe."""
-        restore = self._snapshot()
+        """hipGraph of the rollout loop.  A warm-up pass on a side stream first (rocBLAS handles / workspaces) and, for the persistent form,
+        one trial replay of the graph, both through _trial: capturing changes nothing the caller can observe.  If either trial shows the
+        persistent kernels not side by side, the per-step launches are captured instead."""
         s = torch.cuda.Stream(device=self.dev)
-        for attempt in range(2):
+
+        def warm_up():
             s.wait_stream(torch.cuda.current_stream(self.dev))
-            refused = None
             with torch.cuda.stream(s):
-                try:
-                    self._rollout_steps()
-                except Exception as ex:                    # (persistent form: an entry point refused the shapes before launching anything)
-                    if not self._persistent:
-                        raise
-                    refused = ex
+                self._rollout_steps()
             torch.cuda.current_stream(self.dev).wait_stream(s)
-            torch.cuda.synchronize(self.dev)
-            if self._persistent and (refused is not None or self._persistent_failed()):
-                self._give_up_persistent("eager warm-up pass" + (", refused: %s" % refused if refused is not None else "") + ": a gate wait timed out")
-                restore()
+
+        for _ in range(2):                                # (a failed trial switches to the per-step launches, which have no trial to fail)
+            if not self._trial("eager warm-up pass", warm_up):
                 continue
-            restore()
             # capture_error_mode="thread_local": with torch.distributed initialised, RCCL's watchdog thread polls events while this
             # thread captures; in the default "global" mode that invalidates the capture.
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
                 self._rollout_steps()
             if self._persistent:
-                # a graph's parallel branches need not run at the same time; the two persistent kernels must: one trial replay on the clone
-                g.replay()
-                torch.cuda.synchronize(self.dev)
-                if self._persistent_failed():
-                    self._give_up_persistent("trial replay of the captured graph: a gate wait timed out")
-                    restore()
+                # a graph's parallel branches need not run at the same time; the two persistent kernels must: one trial replay
+                if not self._trial("trial replay of the captured graph", g.replay):
                     continue
-                restore()
                 self._persistent_proven = True
             self._graph = g
             return
@@ -758,34 +742,11 @@ class A2CRunner:
             return self.update_fused(idx_buf, act_buf, rew_buf, boot)
         return self.update_reference(idx_buf, act_buf, rew_buf, boot)
 
-    def _allreduce(self):
-        """Mean of the flat gradient over ranks: ONE all-reduce (RCCL over xGMI with backend nccl) straight on the buffer the
-        backward pass wrote; the 1 / world_size is folded into the optimiser step.  -> (elements reduced, g_scale)."""
-        import torch.distributed as dist
-
-        if not (dist.is_available() and dist.is_initialized()) or (dist.get_world_size() == 1 and not self.force_exchange):
-            return self.flat.n_real, 1.0
-        if self.flat.g.is_cuda and dist.get_backend() == "gloo":      # rehearsal on a one-GPU box (several ranks share the
-            host = self.flat.g.cpu()                                  # card, RCCL refuses that): reduce through the host
-            dist.all_reduce(host, op=dist.ReduceOp.SUM)
-            self.flat.g.copy_(host)
-        else:
-            dist.all_reduce(self.flat.g, op=dist.ReduceOp.SUM)
-        return self.flat.n_real, 1.0 / dist.get_world_size()
-
-    @staticmethod
-    def _world():
-        import torch.distributed as dist
-
-        return dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
-
     def _exchanging(self):
         """True when an update ends in a collective: more than one rank, or force_exchange with an initialised process group."""
         import torch.distributed as dist
 
-        if self._world() > 1:
-            return True
-        return self.force_exchange and dist.is_available() and dist.is_initialized()
+        return dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or self.force_exchange)
 
     def _allreduce_bucket(self, lo, hi, async_op=False):
         """Sum of flat.g[lo:hi] over ranks, in place.  nccl (RCCL): returns the work handle when async_op; gloo with CUDA tensors (the
@@ -799,6 +760,16 @@ class A2CRunner:
             buf.copy_(host)
             return None
         return dist.all_reduce(buf, op=dist.ReduceOp.SUM, async_op=async_op)
+
+    def _allreduce(self, hi=None):
+        """Sum of flat.g[:hi] over ranks (default: the whole flat gradient, ONE all-reduce -- RCCL over xGMI with backend nccl -- straight on
+        the buffer the backward pass wrote).  -> the 1 / world_size the optimiser step folds in; 1.0 when the update ends in no collective."""
+        import torch.distributed as dist
+
+        if not self._exchanging():
+            return 1.0
+        self._allreduce_bucket(0, self.flat.n_flat if hi is None else hi)
+        return 1.0 / dist.get_world_size()
 
     def _ensure_update_buffers(self, M, K):
         from . import _agent_capi as A
@@ -826,9 +797,42 @@ class A2CRunner:
                               "ws_cs": A.gemm_rows_workspace(M, dev)})
             if self._exchanging() and self.overlap_allreduce:    # one table gradient per trunk: each needs its g rows contiguous
                 self._upd.update({"g_a": f(M, H), "g_c": f(M, H)})
-            elif self.overlap_dw:                                # the critic's dh2 beside the actor's: both outlive the dX chain
-                self._upd["dh_c"] = f(M, H)
         return self._upd
+
+    def _actor_backward(self, b, g):
+        """The actor trunk backwards from d logits (in b["logits"]): dW3; dh2a = relu6'(h2a) * (dlogits @ W3^T); dW2 + db2;
+        g = relu6'(h1a) * (dh2a @ W2^T), the rows the first-layer table gradient sums, + db1."""
+        from . import _agent_capi as A
+
+        net, gv, H = self.net, self.flat.gv, HIDDEN
+        if self.hip_gemms:
+            b["w3p"][:, :net.n_action].copy_(net.a_w3)
+            A.gemm_tn(b["h2a"], b["logits"], gv["a_w3"], b["ws_tn_a"])
+            A.gemm_rows(b["logits_pad"], b["w3p"], b["dh"], w_transposed=True, relu6_mask_h=b["h2a"])
+            A.gemm_tn(b["h1a"], b["dh"], gv["a_w2"], b["ws_tn_h"], dbias_out=gv["a_b2"])
+            A.gemm_rows(b["dh"], net.a_w2, g, w_transposed=True, relu6_mask_h=b["h1a"], colsum_out=gv["a_b1"], workspace=b["ws_cs"])
+        else:
+            torch.mm(b["h2a"].t(), b["logits"], out=gv["a_w3"])
+            torch.mm(b["logits"], net.a_w3.t(), out=b["dh"])
+            A.relu6_bwd(b["dh"], b["h2a"], b["dh"], H, gv["a_b2"], b["ws_relu"])
+            torch.mm(b["h1a"].t(), b["dh"], out=gv["a_w2"])
+            torch.mm(b["dh"], net.a_w2.t(), out=b["h2a"])                 # h2a is free now: reuse it for d h1a
+            A.relu6_bwd(b["h2a"], b["h1a"], g, g.stride(0), gv["a_b1"], b["ws_relu"])
+
+    def _critic_backward(self, b, g):
+        """The critic trunk backwards from dv (in b["dv"]): the value head's outer product + relu6' + db2 + dw3 in one streaming kernel;
+        dW2; g = relu6'(h1c) * (dh2c @ W2^T), the rows the first-layer table gradient sums, + db1."""
+        from . import _agent_capi as A
+
+        net, gv, H = self.net, self.flat.gv, HIDDEN
+        A.relu6_bwd(None, b["h2c"], b["dh"], H, gv["c_b2"], b["ws_relu"], dv=b["dv"], w3=net.c_w3, dw3_out=gv["c_w3"])
+        if self.hip_gemms:
+            A.gemm_tn(b["h1c"], b["dh"], gv["c_w2"], b["ws_tn_h"])
+            A.gemm_rows(b["dh"], net.c_w2, g, w_transposed=True, relu6_mask_h=b["h1c"], colsum_out=gv["c_b1"], workspace=b["ws_cs"])
+        else:
+            torch.mm(b["h1c"].t(), b["dh"], out=gv["c_w2"])
+            torch.mm(b["dh"], net.c_w2.t(), out=b["h2c"])
+            A.relu6_bwd(b["h2c"], b["h1c"], g, g.stride(0), gv["c_b1"], b["ws_relu"])
 
     @torch.no_grad()
     def update_fused(self, idx_buf, act_buf, rew_buf, boot):
@@ -844,28 +848,24 @@ class A2CRunner:
         M, H = T * N, HIDDEN
         b = self._ensure_update_buffers(M, K)
         target = A.nstep_returns(rew_buf.contiguous(), boot.contiguous(), self.gamma, out=b["target"].view(T, N)).reshape(M)
-        idx, act = idx_buf.reshape(M, K), act_buf.reshape(M)
+        idx, act = idx_buf.reshape(M, K).contiguous(), act_buf.reshape(M)
         gv = fl.gv
         hip = self.hip_gemms
-        # The table gradient's sort needs only idx: on the side stream, beside the forward pass and the dX chain (hip path; one sort
-        # serves both trunks' sums when they are exchanged separately).
-        early_sort = hip and self.early_sort and idx.is_contiguous()
-        if early_sort:
-            main = torch.cuda.current_stream(self.dev)
-            if self._side is None:
-                self._side = torch.cuda.Stream(device=self.dev)
-            self._side.wait_stream(main)
-            with torch.cuda.stream(self._side):
-                A.rows_grad_sort(idx, 2 * H, net.n_state, b["ws_rows"])
-            sorted_ev = torch.cuda.Event()
-            sorted_ev.record(self._side)
+        main = torch.cuda.current_stream(self.dev)
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=self.dev)
+        side = self._side
+        # The table gradient's sort needs only idx: on the side stream, beside the forward pass and the dX chain (one sort serves both
+        # trunks' sums when they are exchanged separately).
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            A.rows_grad_sort(idx, 2 * H, net.n_state, b["ws_rows"])
+        sorted_ev = torch.cuda.Event()
+        sorted_ev.record(side)
 
         def table_grad(g, dw0, dw1):
-            if early_sort:
-                torch.cuda.current_stream(self.dev).wait_event(sorted_ev)
-                A.rows_grad_sums((M, K), g, H, net.n_state, dw0, dw1, b["ws_rows"])
-            else:
-                A.rows_grad(idx, g, H, net.n_state, dw0, dw1, b["ws_rows"])
+            main.wait_event(sorted_ev)
+            A.rows_grad_sums((M, K), g, H, net.n_state, dw0, dw1, b["ws_rows"])
         # forward: the actor's activations and both first layers were computed by the rollout itself, with these very weights
         reuse = b["own"] and self._fwd_valid and idx_buf.data_ptr() == self.idx_buf.data_ptr()
         if not reuse:
@@ -888,107 +888,48 @@ class A2CRunner:
         # loss and its gradient w.r.t. logits / v (logits are overwritten); d a_b3, d c_b3
         A.a2c_loss_grad(b["logits"], b["v"], target, act, self.beta, b["dv"], gv["a_b3"], b["loss"], b["ws_loss"])
         gv["c_b3"].copy_(b["loss"][2:3].to(torch.float32))
-        overlap = hip and ("g_a" in b)
-        rows_done = False
+        two_buckets = "g_a" in b
         ae = fl.actor_end
         ev = lambda: torch.cuda.Event(enable_timing=True)
-        e_c0 = e_c1 = None
-        work_c = None
-        if overlap:
+        if two_buckets:
             # ---- more than one rank: critic trunk first, its half of the gradient on the wire while the actor trunk runs ----
-            A.relu6_bwd(None, b["h2c"], b["dh"], H, gv["c_b2"], b["ws_relu"], dv=b["dv"], w3=net.c_w3, dw3_out=gv["c_w3"])
-            A.gemm_tn(b["h1c"], b["dh"], gv["c_w2"], b["ws_tn_h"])
-            A.gemm_rows(b["dh"], net.c_w2, b["g_c"], w_transposed=True, relu6_mask_h=b["h1c"], colsum_out=gv["c_b1"], workspace=b["ws_cs"])
+            self._critic_backward(b, b["g_c"])
             table_grad(b["g_c"], gv["c_w1"], None)
-            main = torch.cuda.current_stream(self.dev)
-            if self._side is None:
-                self._side = torch.cuda.Stream(device=self.dev)
             ready = torch.cuda.Event()
             ready.record(main)
             e_c0, e_c1 = ev(), ev()
-            with torch.cuda.stream(self._side):
-                self._side.wait_event(ready)
-                e_c0.record(self._side)
+            with torch.cuda.stream(side):
+                side.wait_event(ready)
+                e_c0.record(side)
                 work_c = self._allreduce_bucket(ae, fl.n_flat, async_op=True)
                 if work_c is not None:
                     work_c.wait()                                  # (the SIDE stream waits; the main stream goes on with the actor)
-                e_c1.record(self._side)
-            b["w3p"][:, :net.n_action].copy_(net.a_w3)
-            A.gemm_tn(b["h2a"], b["logits"], gv["a_w3"], b["ws_tn_a"])
-            A.gemm_rows(b["logits_pad"], b["w3p"], b["dh"], w_transposed=True, relu6_mask_h=b["h2a"])
-            A.gemm_tn(b["h1a"], b["dh"], gv["a_w2"], b["ws_tn_h"], dbias_out=gv["a_b2"])
-            A.gemm_rows(b["dh"], net.a_w2, b["g_a"], w_transposed=True, relu6_mask_h=b["h1a"], colsum_out=gv["a_b1"], workspace=b["ws_cs"])
+                e_c1.record(side)
+            self._actor_backward(b, b["g_a"])
             table_grad(b["g_a"], gv["a_w1"], None)
-        elif hip and "dh_c" in b:
-            # The dX chain first (every product the table gradient waits for), then the three dW GEMMs on a side stream WHILE the main
-            # stream sorts the (row, sample) pairs and sums the indexed rows.  Same kernels on the same operands as the branch below:
-            # the gradient is bit-identical (tests/test_learner_kernels_gpu.py).
-            b["w3p"][:, :net.n_action].copy_(net.a_w3)
-            A.gemm_rows(b["logits_pad"], b["w3p"], b["dh"], w_transposed=True, relu6_mask_h=b["h2a"])
-            A.gemm_rows(b["dh"], net.a_w2, b["gcat"][:, :H], w_transposed=True, relu6_mask_h=b["h1a"], colsum_out=gv["a_b1"],
-                        workspace=b["ws_cs"])
-            A.relu6_bwd(None, b["h2c"], b["dh_c"], H, gv["c_b2"], b["ws_relu"], dv=b["dv"], w3=net.c_w3, dw3_out=gv["c_w3"])
-            A.gemm_rows(b["dh_c"], net.c_w2, b["gcat"][:, H:], w_transposed=True, relu6_mask_h=b["h1c"], colsum_out=gv["c_b1"],
-                        workspace=b["ws_cs"])
-            main = torch.cuda.current_stream(self.dev)
-            if self._side is None:
-                self._side = torch.cuda.Stream(device=self.dev)
-            self._side.wait_stream(main)
-            with torch.cuda.stream(self._side):
-                A.gemm_tn(b["h2a"], b["logits"], gv["a_w3"], b["ws_tn_a"])
-                A.gemm_tn(b["h1a"], b["dh"], gv["a_w2"], b["ws_tn_h"], dbias_out=gv["a_b2"])
-                A.gemm_tn(b["h1c"], b["dh_c"], gv["c_w2"], b["ws_tn_h"])
-            table_grad(b["gcat"], gv["a_w1"], gv["c_w1"])
-            main.wait_stream(self._side)
-            rows_done = True
-        elif hip:
-            # actor trunk backwards: dW3; dh2a = relu6'(h2a) * (dlogits @ W3^T); dW2 + db2; dh1a = relu6'(h1a) * (dh2a @ W2^T) + db1
-            b["w3p"][:, :net.n_action].copy_(net.a_w3)
-            A.gemm_tn(b["h2a"], b["logits"], gv["a_w3"], b["ws_tn_a"])
-            A.gemm_rows(b["logits_pad"], b["w3p"], b["dh"], w_transposed=True, relu6_mask_h=b["h2a"])
-            A.gemm_tn(b["h1a"], b["dh"], gv["a_w2"], b["ws_tn_h"], dbias_out=gv["a_b2"])
-            A.gemm_rows(b["dh"], net.a_w2, b["gcat"][:, :H], w_transposed=True, relu6_mask_h=b["h1a"], colsum_out=gv["a_b1"],
-                        workspace=b["ws_cs"])
-            # critic trunk backwards (the value head's outer product + relu6' + db2 + dw3 stay one streaming kernel)
-            A.relu6_bwd(None, b["h2c"], b["dh"], H, gv["c_b2"], b["ws_relu"], dv=b["dv"], w3=net.c_w3, dw3_out=gv["c_w3"])
-            A.gemm_tn(b["h1c"], b["dh"], gv["c_w2"], b["ws_tn_h"])
-            A.gemm_rows(b["dh"], net.c_w2, b["gcat"][:, H:], w_transposed=True, relu6_mask_h=b["h1c"], colsum_out=gv["c_b1"],
-                        workspace=b["ws_cs"])
         else:
-            # actor trunk backwards
-            torch.mm(b["h2a"].t(), b["logits"], out=gv["a_w3"])
-            torch.mm(b["logits"], net.a_w3.t(), out=b["dh"])
-            A.relu6_bwd(b["dh"], b["h2a"], b["dh"], H, gv["a_b2"], b["ws_relu"])
-            torch.mm(b["h1a"].t(), b["dh"], out=gv["a_w2"])
-            torch.mm(b["dh"], net.a_w2.t(), out=b["h2a"])                 # h2a is free now: reuse it for d h1a
-            A.relu6_bwd(b["h2a"], b["h1a"], b["gcat"], 2 * H, gv["a_b1"], b["ws_relu"])
-            # critic trunk backwards
-            A.relu6_bwd(None, b["h2c"], b["dh"], H, gv["c_b2"], b["ws_relu"], dv=b["dv"], w3=net.c_w3, dw3_out=gv["c_w3"])
-            torch.mm(b["h1c"].t(), b["dh"], out=gv["c_w2"])
-            torch.mm(b["dh"], net.c_w2.t(), out=b["h2c"])
-            A.relu6_bwd(b["h2c"], b["h1c"], b["gcat"][:, H:], 2 * H, gv["c_b1"], b["ws_relu"])
-        # first-layer tables: both in one sorted pass (one rank, or no overlap)
-        if not overlap and not rows_done:
+            # one rank, or one bucket: both trunks' first-layer gradient rows side by side, both tables in one sorted pass
+            self._actor_backward(b, b["gcat"][:, :H])
+            self._critic_backward(b, b["gcat"][:, H:])
             table_grad(b["gcat"], gv["a_w1"], gv["c_w1"])
         # synchronise and step
         ev0, ev1 = ev(), ev()
         ev0.record()
-        if overlap:
-            self._allreduce_bucket(0, ae)                              # the actor's half, behind its backward pass
-            torch.cuda.current_stream(self.dev).wait_stream(self._side)     # ... and the critic's half has landed
-            n_red, g_scale = fl.n_real, 1.0 / self._world()
+        if two_buckets:
+            g_scale = self._allreduce(ae)                              # the actor's half, behind its backward pass
+            main.wait_stream(side)                                     # ... and the critic's half has landed
         else:
-            n_red, g_scale = self._allreduce()
+            g_scale = self._allreduce()
         ev1.record()
         A.rmsprop_tf1(fl.w[:ae], fl.ms[:ae], fl.g[:ae], self.lr_a, g_scale=g_scale)
         A.rmsprop_tf1(fl.w[ae:], fl.ms[ae:], fl.g[ae:], self.lr_c, g_scale=g_scale)
         loss = b["loss"].cpu()                                        # (synchronises)
         self.stats = {"a_loss": float(loss[0]), "c_loss": float(loss[1]), "mean_reward": float(rew_buf.mean()),
-                      "grad_elems": n_red, "running_r": self.running_r, "allreduce_ms": ev0.elapsed_time(ev1),
-                      "forward_reused": bool(reuse), "hip_gemms": bool(hip), "dw_on_side_stream": bool(rows_done),
+                      "grad_elems": fl.n_real, "running_r": self.running_r, "allreduce_ms": ev0.elapsed_time(ev1),
+                      "forward_reused": bool(reuse), "hip_gemms": bool(hip),
                       # two buckets (critic trunk, then actor trunk): the first one's time is hidden behind the actor's backward pass
-                      "allreduce_overlapped_ms": e_c0.elapsed_time(e_c1) if overlap else None,
-                      "allreduce_buckets": [4 * (fl.n_flat - ae), 4 * ae] if overlap else None}
+                      "allreduce_overlapped_ms": e_c0.elapsed_time(e_c1) if two_buckets else None,
+                      "allreduce_buckets": [4 * (fl.n_flat - ae), 4 * ae] if two_buckets else None}
         return self.stats
 
     def update_reference(self, idx_buf, act_buf, rew_buf, boot):
@@ -1008,12 +949,12 @@ class A2CRunner:
             ((a_loss + c_loss) * w).backward()                # disjoint parameter sets: same grads as two backward()s
             a_tot += float(a_loss.detach()) * w
             c_tot += float(c_loss.detach()) * w
-        n_red, g_scale = self._allreduce()
+        g_scale = self._allreduce()
         if g_scale != 1.0:
             self.flat.g.mul_(g_scale)
         self.opt_a.step()
         self.opt_c.step()
-        self.stats = {"a_loss": a_tot, "c_loss": c_tot, "mean_reward": float(rew_buf.mean()), "grad_elems": n_red,
+        self.stats = {"a_loss": a_tot, "c_loss": c_tot, "mean_reward": float(rew_buf.mean()), "grad_elems": self.flat.n_real,
                       "running_r": self.running_r, "allreduce_ms": None}
         return self.stats
 

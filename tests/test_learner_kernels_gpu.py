@@ -91,25 +91,6 @@ def test_rollout_with_index_lists_built_in_the_gather_is_the_same_rollout():
         assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("kw", [{"overlap_dw": True}, {"early_sort": False}, {"overlap_dw": True, "early_sort": False}], ids=lambda k: "+".join(sorted(k)))
-def test_update_stream_variants_leave_the_same_parameters(kw):
-    """The update's optional side-stream forms (dW GEMMs beside the table gradient; the table gradient's sort before the forward pass)
-    run the same kernels on the same operands in another order of issue: parameters and RMSProp accumulators bit for bit."""
-    torch = _torch()
-    from drl_uav_cellularnet_amd import BatchedMobiEnv
-    from drl_uav_cellularnet_amd.agent import A2CRunner
-
-    outs = []
-    for k in ({}, kw):
-        env = BatchedMobiEnv(1024, nBS=4, nUE=20, grid_n=100, groups=[5, 5, 5, 5])
-        r = A2CRunner(env, rollout=40, **k)                            # 40 960 samples: the update's large-M kernels
-        for _ in range(2):
-            r.train_rollout()
-        assert r.stats["dw_on_side_stream"] == bool(k.get("overlap_dw", False))
-        outs.append((r.flat.w.clone(), r.flat.ms.clone()))
-    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
-
-
 def test_sample_actions_kernel_is_the_inverse_cdf_draw():
     torch = _torch()
     from drl_uav_cellularnet_amd import _agent_capi as A
@@ -622,18 +603,17 @@ def test_persistent_rollout_with_a_ragged_last_block_equals_the_per_step_rollout
 
 
 @pytest.mark.parametrize("launch", ["eager", "graph"])
-def test_persistent_rollout_falls_back_when_its_kernels_cannot_run_side_by_side(launch, monkeypatch):
-    """The two persistent rollout kernels wait for each other, so they must run at the same time.  With both in ONE stream (test hook) the
-    first waits in vain: every wait is bounded, the trial on a clone of the env state sees the error words, and the runner goes on with the
-    per-step launches -- same results as a runner that never tried, nothing hangs, the env handle is usable."""
+def test_persistent_rollout_falls_back_when_its_kernels_share_one_stream(launch, monkeypatch):
+    """The two persistent rollout kernels wait for each other, so they must run at the same time.  With both in ONE stream (the runner's
+    _persist_same_stream hook) the first waits in vain: every wait is bounded, the trial on a snapshot of the env state sees the error words,
+    and the runner goes on with the per-step launches -- same results as a runner that never tried, nothing hangs, the env handle is usable."""
     torch = _torch()
     import warnings
 
-    monkeypatch.setenv("UAVAGENT_PERSIST_SAME_STREAM", "1")
-    monkeypatch.setenv("UAVAGENT_GATE_SPIN_US", "30000")           # 30 ms
     monkeypatch.setenv("UAVENV_HANDOFF_SPIN_US", "30000")          # (read in uavenv_create)
     r1, r2 = _twin_runners(torch, 256, 5, first=dict(collect_launch=launch, persistent_rollout=True, pipeline_halves=False),
                            second=dict(collect_launch="eager", persistent_rollout=False, pipeline_halves=False))
+    r1._persist_same_stream, r1._gate_spin_us = True, 30000        # 30 ms
     assert r1._persistent
     with warnings.catch_warnings(record=True) as w:
         warnings.simplefilter("always")
