@@ -292,7 +292,8 @@ class FlatParams:
     ALIGN = 64   # floats
 
     def __init__(self, net):
-        params = [getattr(net, k) for k in PARAM_ORDER]
+        order = getattr(net, "PARAM_ORDER", PARAM_ORDER)              # the net's own order (CnnACNet) or the MLP's
+        params = [getattr(net, k) for k in order]
         dev = params[0].device
         offs, off = [], 0
         for p in params:
@@ -300,13 +301,13 @@ class FlatParams:
             off += (p.numel() + self.ALIGN - 1) // self.ALIGN * self.ALIGN
         self.n_flat = off
         self.n_real = sum(p.numel() for p in params)
-        self.actor_end = offs[N_ACTOR_PARAMS]               # [0, actor_end) actor trunk, [actor_end, n_flat) critic trunk
+        self.actor_end = offs[getattr(net, "N_ACTOR_PARAMS", N_ACTOR_PARAMS)]   # [0, actor_end) actor trunk, [actor_end, n_flat) critic trunk
         self.w = torch.zeros(off, dtype=torch.float32, device=dev)
         self.g = torch.zeros(off, dtype=torch.float32, device=dev)
         self.ms = torch.ones(off, dtype=torch.float32, device=dev)    # TF1: accumulator initialised to ones (main.py:300-301)
         self.gv = {}
         with torch.no_grad():
-            for k, p, o in zip(PARAM_ORDER, params, offs):
+            for k, p, o in zip(order, params, offs):
                 view = self.w[o:o + p.numel()].view_as(p)
                 view.copy_(p)
                 p.data = view
@@ -333,22 +334,8 @@ class A2CRunner:
                  update_chunk=65536, first_state="obs", collect_launch="graph", fused_update=True, tune_gemms=False, hip_gemms=True,
                  overlap_allreduce=True, fused_head=True, fused_obs=True, pipeline_halves=True, force_exchange=False,
                  persistent_rollout="auto"):
-        self.env = env
-        self.dev = env.device
-        self.gemm_tuning = enable_gemm_tuning() if (tune_gemms and self.dev.type == "cuda") else False
-        self.G, self.B = env.grid_n, env.nBS
-        self.net = (net if net is not None else ACNet(env.observation_space_dim, env.action_space_dim, seed=seed)).to(self.dev)
-        self.flat = FlatParams(self.net)
-        self.lr_a, self.lr_c = float(lr_a), float(lr_c)
-        self.opt_a = TFRMSProp(self.net.actor_params(), lr_a)       # reference path only; shares FlatParams' accumulators
-        self.opt_c = TFRMSProp(self.net.critic_params(), lr_c)
-        for opt, keys in ((self.opt_a, PARAM_ORDER[:N_ACTOR_PARAMS]), (self.opt_c, PARAM_ORDER[N_ACTOR_PARAMS:])):
-            opt.ms = [self._ms_view(k) for k in keys]
-        self.T, self.gamma, self.beta = int(rollout), float(gamma), float(beta)
-        self.update_chunk = int(update_chunk)
-        self.gen = torch.Generator(device=self.dev).manual_seed(int(seed) + 1000 * int(env.env_id_base + 1))
-        if first_state not in ("obs", "zeros"):
-            raise ValueError("first_state must be 'obs' or 'zeros'")
+        self._init_common(env, net if net is not None else ACNet(env.observation_space_dim, env.action_space_dim, seed=seed), rollout, gamma,
+                          beta, lr_a, lr_c, seed, update_chunk, first_state, tune_gemms)
         if collect_launch not in ("graph", "eager"):
             raise ValueError("collect_launch must be 'graph' or 'eager'")
         self.collect_launch = collect_launch
@@ -400,13 +387,7 @@ class A2CRunner:
         if (persistent_rollout and self.dev.type == "cuda" and self.fused_head and self.fused_obs and env.nBS == 4 and env.nUE <= 64
                 and env.n_envs % 4 == 0 and "cur_sinr_f64" not in env.out and (persistent_rollout is True or env.n_envs >= 4096)):
             self._persistent = True
-        N, T, K = env.n_envs, self.T, env.nBS + env.nUE
-        # rollout buffers (persistent: the captured graph holds their addresses).  idx_buf[t] = observation BEFORE step t,
-        # idx_buf[T] = the state the rollout ended in (bootstrap value; copied to slot 0 when the next rollout starts).
-        self.idx_buf = torch.empty((T + 1, N, K), dtype=torch.int64, device=self.dev)
-        self.act_buf = torch.empty((T, N), dtype=torch.int64, device=self.dev)
-        self.rew_buf = torch.empty((T, N), dtype=torch.float32, device=self.dev)
-        self.u_buf = torch.empty((T, N), dtype=torch.float32, device=self.dev)
+        N, T = env.n_envs, self.T
         # Forward activations of the rollout, kept for the update: between collect() and update() the weights do not change, so
         # relu6(first layer) of both trunks, the actor's second layer and its logits for sample (t, n) ARE the update's forward
         # pass for that sample -- the update only adds the critic's second layer and value head.  (2 GB at 8192 envs x 50 steps.)
@@ -434,6 +415,39 @@ class A2CRunner:
             from . import _agent_capi as _A
 
             _A.gate_prepare()
+        self._graph = None
+        self._upd = None
+
+    NET_KIND = "mlp"
+
+    def _init_common(self, env, net, rollout, gamma, beta, lr_a, lr_c, seed, update_chunk, first_state, tune_gemms):
+        """What every runner over a BatchedMobiEnv sets up (A2CRunner and cnn_agent.CnnA2CRunner): the net in FlatParams with its two
+        TF1 RMSProp views, the rollout buffers, the first state, the episode bookkeeping and the action-sampling generator."""
+        self.env = env
+        self.dev = env.device
+        self.gemm_tuning = enable_gemm_tuning() if (tune_gemms and self.dev.type == "cuda") else False
+        self.G, self.B = env.grid_n, env.nBS
+        self.net = net.to(self.dev)
+        self.flat = FlatParams(self.net)
+        self.lr_a, self.lr_c = float(lr_a), float(lr_c)
+        self.opt_a = TFRMSProp(self.net.actor_params(), lr_a)       # reference path only; shares FlatParams' accumulators
+        self.opt_c = TFRMSProp(self.net.critic_params(), lr_c)
+        order = getattr(self.net, "PARAM_ORDER", PARAM_ORDER)
+        n_actor = getattr(self.net, "N_ACTOR_PARAMS", N_ACTOR_PARAMS)
+        for opt, keys in ((self.opt_a, order[:n_actor]), (self.opt_c, order[n_actor:])):
+            opt.ms = [self._ms_view(k) for k in keys]
+        self.T, self.gamma, self.beta = int(rollout), float(gamma), float(beta)
+        self.update_chunk = int(update_chunk)
+        self.gen = torch.Generator(device=self.dev).manual_seed(int(seed) + 1000 * int(env.env_id_base + 1))
+        if first_state not in ("obs", "zeros"):
+            raise ValueError("first_state must be 'obs' or 'zeros'")
+        N, T, K = env.n_envs, self.T, env.nBS + env.nUE
+        # rollout buffers (persistent: the captured graph holds their addresses).  idx_buf[t] = observation BEFORE step t,
+        # idx_buf[T] = the state the rollout ended in (bootstrap value; copied to slot 0 when the next rollout starts).
+        self.idx_buf = torch.empty((T + 1, N, K), dtype=torch.int64, device=self.dev)
+        self.act_buf = torch.empty((T, N), dtype=torch.int64, device=self.dev)
+        self.rew_buf = torch.empty((T, N), dtype=torch.float32, device=self.dev)
+        self.u_buf = torch.empty((T, N), dtype=torch.float32, device=self.dev)
         # first_state: "obs" = the observation the constructor's channel update produced; "zeros" = what the reference's first
         # work() call sees, the all-zero env.state of a never-reset env (a2c_single_thread.py:143,155): no non-zero cell, i.e.
         # every index is -1 = "no row" and the first layer returns its bias.
@@ -444,9 +458,8 @@ class A2CRunner:
         self.running_r = None                                          # GLOBAL_RUNNING_R EMA, :169-172
         self.last_episode_return = None
         self.stats = {}
-        self._graph = None
-        self._upd = None
         self._tuning_frozen = False
+        self._fwd_valid = False
 
     def _ms_view(self, key):
         p = getattr(self.net, key)
@@ -684,6 +697,12 @@ class A2CRunner:
             done = env.out["done"].bool()
             any_done = bool(done.any())
         self._fwd_valid = self._fwd is not None
+        return self._end_rollout(done, any_done)
+
+    def _end_rollout(self, done, any_done):
+        """After the T steps: episode returns, the bootstrap value v(s_T) (0 where done), the masked reset of the finished envs.
+        -> (idx [T,N,K], actions [T,N], rewards [T,N], bootstrap [N]), views of persistent buffers valid until the next collect()."""
+        env, T = self.env, self.T
         self.ep_r += self.rew_buf.sum(dim=0)
         boot = self.net.critic_only(self.idx_buf[T]).squeeze(1)                      # :173-176
         boot = torch.where(done, torch.zeros_like(boot), boot)                       # value_estimate = 0 when done
@@ -943,7 +962,7 @@ class A2CRunner:
         a_tot = c_tot = 0.0
         for s in range(0, M, self.update_chunk):
             e = min(M, s + self.update_chunk)
-            a_prob, v = self.net(idx[s:e])
+            a_prob, v = self._reference_forward(idx[s:e])
             a_loss, c_loss = a2c_losses(a_prob, v, act[s:e], target[s:e], self.beta)
             w = (e - s) / M                                   # mean over the whole batch = weighted mean of chunks
             ((a_loss + c_loss) * w).backward()                # disjoint parameter sets: same grads as two backward()s
@@ -957,6 +976,10 @@ class A2CRunner:
         self.stats = {"a_loss": a_tot, "c_loss": c_tot, "mean_reward": float(rew_buf.mean()), "grad_elems": self.flat.n_real,
                       "running_r": self.running_r, "allreduce_ms": None}
         return self.stats
+
+    def _reference_forward(self, idx):
+        """(a_prob, v) with autograd, for update_reference."""
+        return self.net(idx)
 
     def train_rollout(self):
         stats = self.update(*self.collect())
@@ -982,6 +1005,8 @@ class A2CRunner:
     def load_state_dict(self, sd):
         env = self.env
         shape = (sd["n_envs"], sd["n_bs"], sd["n_ue"], sd["grid_n"], sd["rollout"])
+        if sd.get("net", "mlp") != self.NET_KIND:
+            raise ValueError("checkpoint holds a %s network, this runner trains a %s one" % (sd.get("net", "mlp"), self.NET_KIND))
         if sd.get("format") != 1 or shape != (env.n_envs, env.nBS, env.nUE, env.grid_n, self.T):
             raise ValueError("checkpoint was written for another configuration: %r" % (shape,))
         with torch.no_grad():
@@ -1006,20 +1031,25 @@ def save_actor_npz(net, path):
     six arrays are stored under names, so loading never needs allow_pickle."""
     import numpy as np
 
-    np.savez(path, **{k: getattr(net, k).detach().cpu().numpy() for k in ACTOR_KEYS})
+    np.savez(path, **{k: getattr(net, k).detach().cpu().numpy() for k in getattr(net, "ACTOR_KEYS", ACTOR_KEYS)})
 
 
 def load_actor_npz(net, path):
     """Inverse of save_actor_npz (main_test.py:11-26 assigns the six arrays to the actor variables in order)."""
     import numpy as np
 
+    keys = getattr(net, "ACTOR_KEYS", ACTOR_KEYS)
     with np.load(path, allow_pickle=False) as z:
-        missing = [k for k in ACTOR_KEYS if k not in z.files]
+        missing = [k for k in keys if k not in z.files]
         if missing:
+            other = "CNN" if "a_conv1_k" in z.files else ("MLP" if "a_w1" in z.files else None)
+            if other is not None:
+                raise ValueError("%s holds a %s actor, the network is %s (train and evaluate with the same --net)" % (
+                    path, other, "a CNN (CnnACNet)" if keys is not ACTOR_KEYS else "an MLP (ACNet)"))
             raise ValueError("not an actor checkpoint written by save_actor_npz (missing %s); the reference's own "
                              "Global_A_PARA.npz is a pickled object array and is not loaded" % missing)
         with torch.no_grad():
-            for k in ACTOR_KEYS:
+            for k in keys:
                 p = getattr(net, k)
                 a = torch.as_tensor(z[k])
                 if tuple(a.shape) != tuple(p.shape):

@@ -1,4 +1,5 @@
-"""Builds libuavenv.so (env kernels + C ABI) and libuavagent.so (the learner's sparse first layer) for gfx950 with hipcc, in-tree.
+"""Builds libuavenv.so (env kernels + C ABI), libuavagent.so (the learner's sparse first layer) and libuavcnn.so (the CNN
+actor-critic's convolution and dense kernels) for gfx950 with hipcc, in-tree.
 
 ``python -m drl_uav_cellularnet_amd.build`` or ``__graft_entry__.build()``.  hipcc cross-compiles
 without a GPU; the built library is git-ignored but travels to the GPU box with the tree.
@@ -22,6 +23,9 @@ AGENT_SRCS = [os.path.join(PKG_DIR, "csrc", f) for f in ("agent_kernels.hip", "a
 AGENT_SRC = AGENT_SRCS[0]
 AGENT_DEPS = AGENT_SRCS + [os.path.join(PKG_DIR, "csrc", f) for f in ("agent_common.h", "rollout_gate.h")] + [os.path.join(ROOT, "include", "uavagent.h")]
 AGENT_LIB = os.path.join(LIB_DIR, "libuavagent.so")
+CNN_SRCS = [os.path.join(PKG_DIR, "csrc", "cnn_kernels.hip")]
+CNN_DEPS = CNN_SRCS + [os.path.join(ROOT, "include", "uavcnn.h")]
+CNN_LIB = os.path.join(LIB_DIR, "libuavcnn.so")
 ARCH = "gfx950"
 
 
@@ -56,8 +60,22 @@ def build_agent(force=False, verbose=False):
     return AGENT_LIB
 
 
+def build_cnn(force=False, verbose=False):
+    """libuavcnn.so (include/uavcnn.h): used by cnn_agent.py for CUDA tensors; independent of the other two libraries."""
+    if not force and not _stale(CNN_LIB, CNN_DEPS):
+        return CNN_LIB
+    os.makedirs(LIB_DIR, exist_ok=True)
+    cmd = [hipcc_path(), "-O3", "-std=c++17", "--offload-arch=" + ARCH, "-fPIC", "-shared", "-Wall", "-Wno-unused-function",
+           "-o", CNN_LIB] + CNN_SRCS
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return CNN_LIB
+
+
 def build(force=False, verbose=False):
     build_agent(force=force, verbose=verbose)
+    build_cnn(force=force, verbose=verbose)
     if not force and not needs_build():
         return LIB
     os.makedirs(LIB_DIR, exist_ok=True)

@@ -33,13 +33,18 @@ def make_trace(n_rows=10001, n_ue=40, grid=100, seed=0x7ACE):
     return rows
 
 
-def run_test(trace, out_dir, actor_npz=None, max_step=2000, n_bs=4, n_ue=40, grid=100, seed=0x5EED, area_every=500):
+def run_test(trace, out_dir, actor_npz=None, max_step=2000, n_bs=4, n_ue=40, grid=100, seed=0x5EED, area_every=500, net="mlp"):
     from drl_uav_cellularnet_amd import MobiEnvironment
     from drl_uav_cellularnet_amd.agent import ACNet, load_actor_npz, obs_to_indices
 
     os.makedirs(out_dir, exist_ok=True)
     test_env = MobiEnvironment(n_bs, n_ue, grid, "read_trace", trace, seed=seed)       # main_test.py:51
-    net = ACNet(test_env.observation_space_dim, test_env.action_space_dim)
+    if net == "cnn":                                                                     # netType='CNN' (main.py:88-140)
+        from drl_uav_cellularnet_amd.cnn_agent import CnnACNet
+
+        net = CnnACNet(n_bs, grid, test_env.action_space_dim)
+    else:
+        net = ACNet(test_env.observation_space_dim, test_env.action_space_dim)
     if actor_npz:
         load_actor_npz(net, actor_npz)                                                   # main_test.py:11-26
     net = net.to(test_env._env.device)
@@ -77,6 +82,7 @@ if __name__ == "__main__":
     ap.add_argument("--trace-rows", type=int, default=10001)
     ap.add_argument("--actor", default=None)
     ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--net", choices=("mlp", "cnn"), default="mlp", help="the network the actor file was trained with")
     a = ap.parse_args()
     if a.make_trace:
         np.save(a.make_trace, make_trace(a.trace_rows))
@@ -84,6 +90,6 @@ if __name__ == "__main__":
         sys.exit(0)
     tr = np.load(a.trace, allow_pickle=False) if a.trace else make_trace(a.steps + 2)
     t0 = time.time()
-    res = run_test(tr, a.out, a.actor, a.steps)
+    res = run_test(tr, a.out, a.actor, a.steps, net=a.net)
     print("eval: %d step_test calls in %.1f s, mean reward %.4f, mean outage fraction %.4f -> %s" % (
         len(res["reward"]), time.time() - t0, float(res["reward"].mean()), float(res["outage_fraction"].mean()), a.out))

@@ -62,6 +62,8 @@ def main():
                     "4096 workers on); per-step: the pipelined per-step launches (same results bit for bit)")
     ap.add_argument("--no-gemm-tuning", action="store_true", help="leave PyTorch's TunableOp off (library default; this tool turns the "
                     "shipped per-shape GEMM picks on: a resumed run is bit-identical only if it makes the same choice as the original)")
+    ap.add_argument("--net", choices=("mlp", "cnn"), default="mlp", help="the reference's netType: MLP (agent.ACNet) or CNN "
+                    "(cnn_agent.CnnACNet, one process only)")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -80,8 +82,13 @@ def main():
 
     base, _ = shard_for_rank(rank, world, a.workers)
     env = BatchedMobiEnv(a.workers, nBS=4, nUE=a.n_ue, grid_n=a.grid, device=dev, env_id_base=base)
-    runner = A2CRunner(env, rollout=a.rollout, first_state=a.first_state, tune_gemms=not a.no_gemm_tuning,
-                       persistent_rollout="auto" if a.rollout_form == "auto" else False)
+    if a.net == "cnn":
+        from drl_uav_cellularnet_amd.cnn_agent import CnnA2CRunner
+
+        runner = CnnA2CRunner(env, rollout=a.rollout, first_state=a.first_state)
+    else:
+        runner = A2CRunner(env, rollout=a.rollout, first_state=a.first_state, tune_gemms=not a.no_gemm_tuning,
+                           persistent_rollout="auto" if a.rollout_form == "auto" else False)
     per_episode = int(env.cfg.max_step) // a.rollout                       # a2c_single_thread.py:108
     returns, t0, first_ep = [], time.time(), 0
     ckpt = os.path.join(a.out, "checkpoint_rank%d.pt" % rank)
