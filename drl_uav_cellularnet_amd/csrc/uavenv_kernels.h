@@ -582,20 +582,32 @@ __device__ __forceinline__ void fifo_handover(const HotConst &H, int depth, int 
     if (remain && changed && (bestS - cur > H.ho_thr)) serving = best;        // :155-167
 }
 
+// The kernarg constants of env_finish.  PINNED (the pinned multi-step kernels): held in VGPRs for the whole launch.  Read from the
+// kernarg block they arrive as part of one 16-dword scalar load whose whole tuple was spilled, and the head lane's block of EVERY step
+// reloaded all of it (16 v_readlane, 5 of them needed) -- with one wavefront per SIMD nobody hides those issue slots.
+struct FinConst { double inv_U, inv_U20; int max_step; };
+template <bool PINNED>
+__device__ __forceinline__ FinConst fin_const(const KParams &p) {
+    FinConst k = {p.inv_U, p.inv_U20, p.max_step};
+    if (PINNED) { lm_pin<true>(k.inv_U); lm_pin<true>(k.inv_U20); asm volatile("" : "+v"(k.max_step)); }
+    return k;
+}
+
 // Per-env scalars and outputs after a step / reset: reward (mobile_env.py:163-189), done (:186-187).
 // `rec` is the env's record as loaded at kernel entry: fields a mode does not own keep their value (the aggregation counters in
 // the trace modes, depth and step count during warm-up), and the whole record goes back with one 32-byte store.
 // `o`: where this step's outputs go (p.out, or the current step's block of a multi-step launch).  REC = false: outputs only
 // (steps 0 .. T-2 of a multi-step launch; the record is stored once, after the last step).
+// `K`: the three kernarg constants used here (FinConst).
 template <int MODE, bool FAST, bool REC = true, bool OUTS = true, bool COH = false>
-__device__ __forceinline__ void env_finish(const KParams &p, const OutPtrs &o, const StatePtrs &st, uint32_t e, EnvRec rec, uint32_t tick,
+__device__ __forceinline__ void env_finish(const FinConst &K, const OutPtrs &o, const StatePtrs &st, uint32_t e, EnvRec rec, uint32_t tick,
                                            int agg, int deagg, int depth, int step_n, double sum_cur, int n_outage) {
     rec.tick = tick;
     if (has_mobility(MODE)) { rec.agg = agg; rec.deagg = deagg; }
     if (is_reset(MODE)) {
         rec.fifo_depth = 1;                                    // bestBS_buf = [current_BS] (channel.py:115)
         rec.step_n = 0;                                        // mobile_env.py:146
-        const double mean = sum_cur * p.inv_U;
+        const double mean = sum_cur * K.inv_U;
         if (OUTS && UAV_OUT(o.step_n)) stx(o.step_n, e, 0);
         if (OUTS && UAV_OUT(o.reward)) stx(o.reward, e, 0.f);
         if (OUTS && UAV_OUT64(o.reward_f64)) stx(o.reward_f64, e, 0.0);
@@ -606,15 +618,15 @@ __device__ __forceinline__ void env_finish(const KParams &p, const OutPtrs &o, c
     }
     if (is_step(MODE)) {
         rec.fifo_depth = depth < 3 ? depth + 1 : depth;
-        const double mean = sum_cur * p.inv_U;                // channel.py:216 (np.mean; <= 1 ulp from sum/U)
-        const double r0 = sum_cur * p.inv_U20;                // mobile_env.py:165  mean / 20
-        const double r1 = -((double)n_outage * p.inv_U);      // mobile_env.py:167  -1.0 * nOut / nUE
+        const double mean = sum_cur * K.inv_U;                // channel.py:216 (np.mean; <= 1 ulp from sum/U)
+        const double r0 = sum_cur * K.inv_U20;                // mobile_env.py:165  mean / 20
+        const double r1 = -((double)n_outage * K.inv_U);      // mobile_env.py:167  -1.0 * nOut / nUE
         double reward = (0.0 + r0) + r1;                      // sum(r_dissect)
         if (-1.0 > reward) reward = -1.0;                     // max(.., -1)  mobile_env.py:189
         step_n += 1;                                          // mobile_env.py:181
         rec.step_n = step_n;
         if (OUTS && UAV_OUT(o.step_n)) stx(o.step_n, e, step_n);
-        if (OUTS && UAV_OUT(o.done)) stx(o.done, e, (uint8_t)(step_n >= p.max_step));
+        if (OUTS && UAV_OUT(o.done)) stx(o.done, e, (uint8_t)(step_n >= K.max_step));
         if (OUTS && UAV_OUT(o.reward)) stx(o.reward, e, (float)reward);
         if (OUTS && UAV_OUT64(o.reward_f64)) stx(o.reward_f64, e, reward);
         if (OUTS && UAV_OUT(o.mean_sinr)) stx(o.mean_sinr, e, (float)mean);
@@ -709,6 +721,19 @@ static __global__ __launch_bounds__(256) void init_kernel(InitParams p) {   // (
     if (u == 0) p.env[e] = EnvRec{0u, p.agg_init, p.deagg_len, 0, 0, 0, 0, 0};
 }
 
+// Multi-step launches: retire every outstanding load HERE, with a wait the compiler's wait-count pass can see (a builtin; an asm
+// string it cannot read).  The output stores of a step sit in `if (live)` / `if (bown)` / `if (head)` blocks that are skipped by
+// branches, so at a later use of a loaded value the pass cannot tell how many stores follow the load and waits for vmcnt(0) --
+// which at run time waits for the acknowledgement of the stores just issued.  The step loop had two such waits per step: for the
+// prefetched action at the loop latch, and for the pre-loop st.out_bits load, whose pending mark survived the loop header, at
+// the first use of prev_out.  Nothing reads the outputs back, and a wavefront alone on its SIMD has nobody
+// to hide those waits behind.  Called before the loop and before the first output store of a step, the wait finds only loads that
+// are at least a step body old and stores of the previous step; from there to the back edge no load is pending, so no wait follows
+// (tests/test_many_loop_listing.py holds that in the listing).
+__device__ __forceinline__ void many_retire_loads() {
+    __builtin_amdgcn_s_waitcnt(0x0F70);   // gfx9 encoding of vmcnt(0); expcnt and lgkmcnt left open
+}
+
 // ================================================================================================
 // Packed env kernel: U <= 64, EPW = p.epw env instances per wavefront (slots of U lanes), one pass.
 // Host guarantees U >= max(B, Gr) (owner lanes live inside the slot) and EPW*U <= 64.
@@ -760,6 +785,11 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
 
     // ================= load phase: every global read of the launch, issued before any dependent work ======
     constexpr bool REG_MOVE = (BT <= 8);   // serial BS_move in registers; n_act^B <= 9^8 always fits 32 bits here
+    // Pinned multi-step launches whose lanes all hold all B == BT cells of their env: the HEAD lane stores a step's bs_xy block (8 B
+    // contiguous bytes) from bsx[] / bsy[], and the owner lanes select the cell they write back to the state once, after the last step --
+    // not in every step (B selects on SGPR-pair conditions that were spill reloads: 6 v_readlane + 8 v_cndmask per step at B = 4).
+    // Pinned only: the unpinned kernel got SLOWER with it (65 536 envs: 45.1-45.3 against 44.0-44.3 us per step).
+    constexpr bool HEAD_BS = MANY && FAST && REG_MOVE && PIN;
     int bx = 0, by = 0;                    // the UAV this lane OWNS (store phase)
     int bsx[BT], bsy[BT];                  // all UAV cells of this lane's env (rx_power reads them)
     long long act = 0, apw = 1;
@@ -825,6 +855,9 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
     unsigned long long ob = 0ull;
     OutPtrs om = p.out;                                // MANY: the current step's output blocks (dead code otherwise)
     if (MANY) out_skip_steps<FAST>(om, t0, N, U, B);
+    // MANY: no wait on a store inside the step loop (many_retire_loads).  The first step needs every load of the load phase anyway.
+    if (MANY) many_retire_loads();
+    const FinConst K = fin_const<MANY && PIN>(p);
     for (int it = 0; it < n_ticks; ++it) {
         long long act_next = 0;
         if (MANY) {                                    // prefetch the next step's action: its round trip hides behind this step
@@ -835,9 +868,11 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
         if (MODE != MODE_WARMUP) {
             if (REG_MOVE) {
                 if (is_step(MODE)) bs_move_serial<BT, FAST>(p, (unsigned)act, bsx, bsy);
+                if (!HEAD_BS) {
 #pragma unroll
-                for (int b = 0; b < BT; ++b)
-                    if (ul == b) { bx = bsx[b]; by = bsy[b]; }             // the cell this lane writes back
+                    for (int b = 0; b < BT; ++b)
+                        if (ul == b) { bx = bsx[b]; by = bsy[b]; }         // the cell this lane writes back
+                }
             } else {
                 // cooperative form for B > 8: one UAV per lane, sequential rounds, UAV cells staged in LDS
                 if (is_step(MODE)) {
@@ -929,24 +964,38 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
         }
         if (MANY) {
             // ---- this step's outputs (block `it` of every output array), then the hand-over to the next step ------------
+            many_retire_loads();                                  // outstanding: the prefetch, a step body old, and the previous step's stores
+            act = act_next;                                       // (BS_move, the only reader of `act`, is done; after the last step: unused)
             if (live) {
                 if (UAV_OUT(om.ue_xy)) { stx(om.ue_xy, 2u * iu32, (int16_t)ix); stx(om.ue_xy, 2u * iu32 + 1u, (int16_t)iy); }
                 if (UAV_OUT(om.serving)) stx(om.serving, iu32, (int8_t)serving);
                 if (UAV_OUT(om.cur_sinr)) stx(om.cur_sinr, iu32, (float)cur);
                 if (UAV_OUT64(om.cur_sinr_f64)) stx(om.cur_sinr_f64, iu32, cur);
             }
-            if (bown) { if (UAV_OUT(om.bs_xy)) { stx(om.bs_xy, 2u * ib32, bx); stx(om.bs_xy, 2u * ib32 + 1u, by); } }
+            if (HEAD_BS) {
+                if (head) {
+#pragma unroll
+                    for (int b = 0; b < BT; ++b) {
+                        const uint32_t c = 2u * (e32 * (uint32_t)BT + (uint32_t)b);
+                        stx(om.bs_xy, c, bsx[b]); stx(om.bs_xy, c + 1u, bsy[b]);
+                    }
+                }
+            } else if (bown) { if (UAV_OUT(om.bs_xy)) { stx(om.bs_xy, 2u * ib32, bx); stx(om.bs_xy, 2u * ib32 + 1u, by); } }
             if (it + 1 < n_ticks) {
-                if (head) env_finish<MODE, FAST, false>(p, om, st, e32, erec, tick, agg, deagg, depth, step_n, sum_cur, n_outage);
+                if (head) env_finish<MODE, FAST, false>(K, om, st, e32, erec, tick, agg, deagg, depth, step_n, sum_cur, n_outage);
                 out_next_step<FAST>(om, N, U, B);
                 prev_out = ob;                                    // channel.py:173  self.ue_out = new_out
                 depth = depth < 3 ? depth + 1 : depth;            // bestBS_buf grows to hoBufDepth, then shifts (:148-153)
                 step_n += 1;                                      // mobile_env.py:181
-                act = act_next;
             }
         }
     }
     if (MODE == MODE_WARMUP) { ix = (int)x; iy = (int)y; }                               // cells after the last warm-up tick
+    if (HEAD_BS) {
+#pragma unroll
+        for (int b = 0; b < BT; ++b)
+            if (ul == b) { bx = bsx[b]; by = bsy[b]; }                                   // the cell this lane writes back
+    }
 
     // ================= store phase: state, then outputs ==========================================================
     if (live) {
@@ -974,7 +1023,7 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
         const uint32_t ew = block_local<!PIN>(e32);
         if (MODE != MODE_WARMUP) stx_c<STC>(st.out_bits, ew, ob);                                // :116 / :173
         // (MANY: outputs of the LAST step + the record; depth / step_n are the values that step started from)
-        env_finish<MODE, FAST, true, true, STC>(p, MANY ? om : pout, st, ew, erec, tick, agg, deagg, depth, step_n, sum_cur, n_outage);
+        env_finish<MODE, FAST, true, true, STC>(K, MANY ? om : pout, st, ew, erec, tick, agg, deagg, depth, step_n, sum_cur, n_outage);
     }
 }
 
@@ -1409,7 +1458,7 @@ void env_kernel_multipass(const KParams p) {
         tick += 1u;
     }
     if (has_mobility(MODE) && gown) st.grp[e * Gr + lane] = GrpRec{ogx, ogy, ogfl, ogv, ogc, ogs};
-    if (lane == 0) env_finish<MODE, FAST>(p, p.out, st, (uint32_t)e, erec, tick, agg, deagg, depth, step_n, sum_cur, n_outage);
+    if (lane == 0) env_finish<MODE, FAST>(fin_const<false>(p), p.out, st, (uint32_t)e, erec, tick, agg, deagg, depth, step_n, sum_cur, n_outage);
 }
 
 // ================================================================================================
