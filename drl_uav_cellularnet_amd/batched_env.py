@@ -388,6 +388,60 @@ class BatchedMobiEnv:
         4096-env batch, uavenv_step_many_prepare): the first call with a new n_steps would otherwise build it, synchronously."""
         _capi.check(self._lib.uavenv_step_many_prepare(self._h, int(n_steps)))
 
+    # ---- the SINR-gradient baseline controller (gradient.py) -------------------------------------------
+    def gradient_actions(self, ue_xy=None, theta_u=None, group_u=None, fading=None, side_means=False, look=False):
+        """Choose_Act_Gradient (gradient.py:14-37) for every env in one launch (uavenv_gradient_actions): look one step ahead with
+        every UAV staying, then send each UAV towards the side whose UEs have the lowest mean serving SINR.  The env is NOT
+        modified: no state, none of ``self.out``.  ``ue_xy`` [N, U, 2]: the trace cells of the step (read_trace), else the next
+        mobility tick.  Returns int64 [N] joint actions; with ``side_means`` also float64 [N, B, 4] (NaN = empty side); with
+        ``look`` also the look-ahead step's outputs, a dict of fresh tensors named like ``self.out``."""
+        N, U, B = self.n_envs, self.nUE, self.nBS
+        xptr = None
+        if ue_xy is not None:
+            x = torch.as_tensor(ue_xy).to(device=self.device, dtype=torch.int16).contiguous()
+            if x.numel() != N * U * 2:
+                raise ValueError("ue_xy must be [N, U, 2]")
+            self._trace_keep = x
+            xptr = x.data_ptr()
+        acts = torch.empty(N, dtype=torch.int64, device=self.device)
+        means = torch.empty((N, B, 4), dtype=torch.float64, device=self.device) if side_means else None
+        lo, lref = None, None
+        if look:
+            lo = {k: torch.empty_like(v) for k, v in self.out.items()}
+            lst = self.out_struct_for(lo)
+            lref = C.byref(lst)
+        rc = self._lib.uavenv_gradient_actions(self._h, xptr, self._inject(theta_u, group_u, fading), acts.data_ptr(),
+                                               means.data_ptr() if side_means else None, lref, self._stream())
+        if rc:
+            _capi.check(rc)
+        res = (acts,) + ((means,) if side_means else ()) + ((lo,) if look else ())
+        return res[0] if len(res) == 1 else res
+
+    def step_gradient(self, n_steps, out=None, actions_out=None):
+        """``n_steps`` x [gradient_actions(); step(those actions)] issued by one C call (uavenv_step_gradient; group mobility,
+        on-device randomness).  Returns (actions int64 [T, N], dict of [T, ...] tensors as step_many returns); ``self.out`` holds
+        the last step's results.  ``out`` / ``actions_out``: the results of an earlier call with the same T, to be overwritten
+        (no allocation: capturable in a graph).  Bit-identical to the loop of the two calls."""
+        T = int(n_steps)
+        if actions_out is None:
+            actions_out = torch.empty((T, self.n_envs), dtype=torch.int64, device=self.device)
+        elif not (actions_out.dtype == torch.int64 and tuple(actions_out.shape) == (T, self.n_envs) and actions_out.is_contiguous()
+                  and actions_out.device == self.device):
+            raise ValueError("actions_out must be a contiguous int64 [T, n_envs] tensor on the env's device")
+        if out is None:
+            out = {k: torch.empty((T,) + tuple(v.shape), dtype=v.dtype, device=self.device) for k, v in self.out.items()}
+        elif set(out) != set(self.out) or any(out[k].shape != (T,) + tuple(v.shape) or not out[k].is_contiguous()
+                                              for k, v in self.out.items()):
+            raise ValueError("out must be a dict returned by step_gradient / step_many for the same number of steps")
+        st = self.out_struct_for(out)
+        rc = self._lib.uavenv_step_gradient(self._h, T, actions_out.data_ptr(), C.byref(st), self._stream())
+        if rc:
+            _capi.check(rc)
+        if T > 0:
+            for k, v in self.out.items():
+                v.copy_(out[k][T - 1])
+        return actions_out, out
+
     def step_trace(self, actions, ue_xy, fading=None):
         """MobiEnvironment.step_test with mobility_model == 'read_trace' (mobile_env.py:196-233)."""
         a = self._actions(actions)

@@ -20,6 +20,7 @@ using uavenv_internal::fail;
 using uavenv_internal::poisoned;
 using uavenv_internal::fill_call;
 using uavenv_internal::call_is_fast;
+using uavenv_internal::out_block;
 
 static_assert(UAVENV_MAX_GROUPS == kMaxGroups && UAVENV_MAX_BS == kMaxBs, "header / kernel bounds differ");
 
@@ -587,7 +588,7 @@ extern "C" int uavenv_step_range(uavenv_t *h, const int64_t *actions_dev, int64_
 }
 
 // Output block of step t in the [T][...] arrays of a multi-step call (uavenv_step_many); null members stay null.
-static UavEnvOut out_block(const UavEnvOut &o, long long t, long long N, long long U, long long B) {
+UavEnvOut uavenv_internal::out_block(const UavEnvOut &o, long long t, long long N, long long U, long long B) {
     UavEnvOut r = o;
     if (r.reward_dev) r.reward_dev += t * N;
     if (r.done_dev) r.done_dev += t * N;

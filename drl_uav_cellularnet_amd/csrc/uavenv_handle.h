@@ -1,5 +1,6 @@
 // Internal to libuavenv (not installed): the handle and the helpers shared by its translation units (uavenv_capi.hip: everything but
-// the gated rollout; uavenv_gated.hip: uavenv_rollout_gated and its kernel instantiations, a file of its own so that neither rebuilds the other).
+// the gated rollout and the gradient policy; uavenv_gated.hip: uavenv_rollout_gated and its kernel instantiations; uavenv_gradient.hip:
+// uavenv_gradient_actions / uavenv_step_gradient and the look-ahead kernels -- files of their own so that none rebuilds the others).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -51,6 +52,7 @@ int fail(int code, const std::string &msg);            // sets uavenv_last_error
 int poisoned(const uavenv *h, const char *what);
 void fill_call(uavk::KParams &p, const UavEnvInject *inj, const UavEnvOut *out);
 bool call_is_fast(const uavk::KParams &p);
+UavEnvOut out_block(const UavEnvOut &o, long long t, long long N, long long U, long long B);   // block t of [T][...] outputs; null members stay null
 }  // namespace uavenv_internal
 
 #define HIP_TRY(expr)                                                                              \

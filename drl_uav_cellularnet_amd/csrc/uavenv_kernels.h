@@ -636,6 +636,77 @@ __device__ __forceinline__ void env_finish(const FinConst &K, const OutPtrs &o, 
     if (REC) stx_c<COH>(st.env, e, rec);
 }
 
+// Choose_Act_Gradient's rule (gradient.py:26-34) for the env of one slot, from the serving SINR of a look-ahead step: per UAV b the mean
+// of `cur` over the walkers with x > bx, x <= bx, y > by, y <= by (dir_grad, :27-31; an empty side is NaN), digit_b = np.nanargmin of the
+// four (the first minimum), joint action = sum digit_b n_act^(B-1-b) (:34).  Every walker covers one of x > bx / x <= bx, so a minimum exists.
+// Mapping: the walkers' (cur, cell) go through LDS once; then ONE LANE PER SIDE (side 4 b + k on lane 4 b + k of the slot, in passes of U
+// sides when 4 B > U) walks its env's U walkers in index order -- broadcast LDS reads, no cross-lane traffic -- and adds cur_j or +0.0.
+// The order of the additions depends on U alone, so a side sum is a function of the selected SET: two sides that select the same
+// walkers (all of them right of AND above a UAV) give bit-equal means and the tie goes to the lower digit, as in NumPy, where both
+// are the same np.mean of the same array.  All 4 B means, counts and divisions of an env run side by side in its lanes; the head lane
+// only picks the digits.  (First form: 4 B segmented shuffle reductions and 4 B divisions one after the other, 18.3 us against 13.3 us
+// for the step kernel itself at 4096 envs x 4 x 40)
+struct LookArgs {
+    long long *actions_out;   // [N]
+    double *side_means;       // [N,B,4] or null
+};
+struct LookLds {              // per wavefront
+    double cur[64];           // cur_sinr of the walker on each lane
+    short x[64], y[64];       // its cell (cells are int16 in the state)
+    double mean[256];         // [slot][4 B] side means: EPW * 4 B <= 4 * EPW * U <= 256
+};
+template <int BT>
+__device__ __forceinline__ void side_rule(const LookArgs &lk, LookLds &L, int B, int U, int n_act, int lane, int slot, int base, int ul, bool live,
+                                          bool head, uint32_t e32, int ix, int iy, double cur, const int (&bsx)[BT], const int (&bsy)[BT]) {
+    L.cur[lane] = cur;
+    L.x[lane] = (short)ix;
+    L.y[lane] = (short)iy;
+    __builtin_amdgcn_wave_barrier();
+    const int n_side = 4 * B;
+    const int rb = live ? base : 0;                       // (lanes past the last slot: any row inside the arrays; they store nothing)
+    const int mrow = live ? slot * n_side : 0;
+    for (int s0 = 0; s0 < n_side; s0 += U) {              // uniform
+        const int sd = s0 + ul;                           // this lane's side
+        const bool mine = live && sd < n_side;
+        const int b = sd >> 2, k = sd & 3;
+        int thr = 0;                                      // the UAV coordinate this side compares with
+#pragma unroll
+        for (int bb = 0; bb < BT; ++bb)
+            if (bb == b) thr = (k < 2) ? bsx[bb] : bsy[bb];
+        const short *coord = (k >= 2 ? L.y : L.x) + rb;   // the walker coordinate it compares
+        const bool le = (k & 1) != 0;
+        double sum = 0.0;
+        int cnt = 0;
+        for (int j = 0; j < U; ++j) {                     // walkers in index order: the fixed shape of every side sum
+            const double cj = L.cur[rb + j];
+            const bool in = ((int)coord[j] > thr) != le;
+            sum = fma(cj, in ? 1.0 : 0.0, sum);          // sum + cj or sum + 0, exactly (cf. sinr_db_px): one select, not two
+            cnt += in ? 1 : 0;
+        }
+        const double mean = cnt > 0 ? sum / (double)cnt : __builtin_nan("");   // IEEE division, as np.mean's
+        if (mine) {
+            L.mean[mrow + sd] = mean;
+            if (lk.side_means != nullptr) lk.side_means[(size_t)e32 * (size_t)n_side + (size_t)sd] = mean;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (head) {
+        unsigned long long a = 0ull;
+        for (int b = 0; b < B; ++b) {
+            int digit = 0;
+            double lowest = 0.0;
+            bool have = false;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const double m = L.mean[mrow + 4 * b + k];
+                if (m == m && (!have || m < lowest)) { lowest = m; digit = k; have = true; }   // np.nanargmin: NaNs skipped, first minimum
+            }
+            a = a * (unsigned long long)n_act + (unsigned long long)digit;
+        }
+        lk.actions_out[e32] = (long long)a;
+    }
+}
+
 // Multi-step launches (uavenv_step_many): every output array holds one block per step, [T][...]; the pointers move on by one
 // block after each step (uniform 64-bit adds on the scalar unit).  A null (skipped) output stays null.
 template <bool FAST>
@@ -750,11 +821,16 @@ __device__ __forceinline__ void many_retire_loads() {
 // bit 1 = another wavefront continues this piece's job (state STORED coherently); 0 everywhere else.  Bit 2 (the gated rollout kernel,
 // env_kernel_gated): the ACTIONS are loaded coherently too -- another kernel wrote them while this one was running.
 // `po` (single-step launches): where the outputs go instead of p.out (the gated rollout kernel moves the reward pointer on per step).
-template <int BT, int MODE, bool PLC, bool FAST, bool PIN, bool MANY, int HO = 0>
+// LOOK (uavenv_gradient_actions, env_kernel_look in uavenv_gradient_kernel.h): the step with every UAV staying (digit 4 everywhere: no action is
+// read, BS_move is skipped), computed exactly as above and then DROPPED: no store to the state; the step's outputs go to whichever members of
+// `pout` are non-null (tested at run time even when FAST, which here only selects the arithmetic variant the real step would run), and
+// the SINR-gradient rule (side_rule) turns cur_sinr into the joint action of `lk`.  LOOK = false is the code as it was.
+template <int BT, int MODE, bool PLC, bool FAST, bool PIN, bool MANY, int HO = 0, bool LOOK = false>
 __device__ __forceinline__ void env_packed_body(char *blob, const long long *actions, const int8_t *gid_of_u, long long N, int U, int EPW,
                                                 int Gr, int B_rt, int lane_magic, const KParams &p, int (*s_bs)[kMaxEpw][2 * kMaxBs],
                                                 const int wave, const long long ew, const int t0, const int nt, const int e_lo, const int e_hi,
-                                                const OutPtrs *po = nullptr) {
+                                                const OutPtrs *po = nullptr, const LookArgs *lk = nullptr, LookLds *ll = nullptr) {
+    static_assert(!LOOK || (is_step(MODE) && !MANY && !PIN && HO == 0), "the look-ahead is one plain step");
     constexpr bool LDC = (HO & 1) != 0, STC = (HO & 2) != 0, ACC = (HO & 4) != 0;
     const OutPtrs &pout = po != nullptr ? *po : p.out;
     const int lane = threadIdx.x & 63;
@@ -802,11 +878,11 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
 #pragma unroll
             for (int b = 0; b < BT; ++b)
                 if (b < B) { const int2 q = is_reset(MODE) ? ldx(cells, c0 + (uint32_t)b) : ldx_c<LDC>(cells, c0 + (uint32_t)b); bsx[b] = q.x; bsy[b] = q.y; }
-            if (is_step(MODE)) act = ldx_c<ACC>(actions, e32);
+            if (is_step(MODE) && !LOOK) act = ldx_c<ACC>(actions, e32);
         } else if (bown) {
             if (is_reset(MODE)) { bx = p.bs_init[2 * ul]; by = p.bs_init[2 * ul + 1]; }
             else { const int2 q = ldx_c<LDC>(reinterpret_cast<const int2 *>(st.bs_xy), ib32); bx = q.x; by = q.y; }
-            if (is_step(MODE)) { act = ldx_c<ACC>(actions, e32); apw = p.act_pow[ul]; }
+            if (is_step(MODE) && !LOOK) { act = ldx_c<ACC>(actions, e32); apw = p.act_pow[ul]; }
         }
     }
     const EnvRec erec = ldx_c<LDC>(st.env, e32);                      // tick, phase counters, FIFO depth, step count: one record
@@ -867,7 +943,7 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
         // ---- UAV move: Decimal_to_Base_N + BS_move (ue_mobility.py:191-271,310-336) ---------------
         if (MODE != MODE_WARMUP) {
             if (REG_MOVE) {
-                if (is_step(MODE)) bs_move_serial<BT, FAST>(p, (unsigned)act, bsx, bsy);
+                if (is_step(MODE) && !LOOK) bs_move_serial<BT, FAST>(p, (unsigned)act, bsx, bsy);
                 if (!HEAD_BS) {
 #pragma unroll
                     for (int b = 0; b < BT; ++b)
@@ -875,7 +951,7 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
                 }
             } else {
                 // cooperative form for B > 8: one UAV per lane, sequential rounds, UAV cells staged in LDS
-                if (is_step(MODE)) {
+                if (is_step(MODE) && !LOOK) {
                     int dig = 0;
                     if (bown) dig = action_digit(p, act, apw, ul);
                     for (int i = 0; i < B; ++i) {  // sequential: UAV i sees the already-moved UAVs j < i
@@ -995,6 +1071,19 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
 #pragma unroll
         for (int b = 0; b < BT; ++b)
             if (ul == b) { bx = bsx[b]; by = bsy[b]; }                                   // the cell this lane writes back
+    }
+
+    if (LOOK) {   // look-ahead: the requested outputs of the dropped step, then the rule; the state is left as it was loaded
+        if (live) {
+            if (pout.ue_xy != nullptr) { stx(pout.ue_xy, 2u * iu32, (int16_t)ix); stx(pout.ue_xy, 2u * iu32 + 1u, (int16_t)iy); }
+            if (pout.serving != nullptr) stx(pout.serving, iu32, (int8_t)serving);
+            if (pout.cur_sinr != nullptr) stx(pout.cur_sinr, iu32, (float)cur);
+            if (pout.cur_sinr_f64 != nullptr) stx(pout.cur_sinr_f64, iu32, cur);
+        }
+        if (bown && pout.bs_xy != nullptr) { stx(pout.bs_xy, 2u * ib32, bx); stx(pout.bs_xy, 2u * ib32 + 1u, by); }
+        if (head) env_finish<MODE, false, false>(K, pout, st, e32, erec, tick, agg, deagg, depth, step_n, sum_cur, n_outage);
+        side_rule<BT>(*lk, *ll, B, U, p.n_act, lane, slot, base, ul, live, head, e32, ix, iy, cur, bsx, bsy);
+        return;
     }
 
     // ================= store phase: state, then outputs ==========================================================

@@ -1,6 +1,10 @@
 """The reference's hand-written "SINR-gradient" controller (gradient.py:14-37) on top of the drop-in MobiEnvironment:
 a policy-free, deterministic-given-the-seed end-to-end driver (SURVEY.md section 8 f, row 3).  Host-side logic only;
-every env operation (deepcopy, step_test) goes through the HIP path."""
+every env operation (deepcopy, step_test) goes through the HIP path.
+
+For a batch the controller itself is a HIP kernel (BatchedMobiEnv.gradient_actions / step_gradient); here are its NumPy statement of
+the rule (side_rule) and the same decision built from a twin handle and the ordinary step (gradient_actions_reference), which is what
+the kernel is tested and timed against and what serves the shapes the kernel refuses (n_ue > 64)."""
 import warnings
 from copy import deepcopy
 
@@ -47,3 +51,49 @@ def run_gradient_policy(env, n_steps, reset_every=2000):
         if (step + 1) % reset_every == 0:
             env.reset()
     return np.array(rewards), np.array(actions)
+
+
+def side_rule(cur_sinr, ue_xy, bs_xy, n_act=5):
+    """The rule of gradient.py:26-34 for a batch, in NumPy float64: cur_sinr [N, U], ue_xy [N, U, 2], bs_xy [N, B, 2] ->
+    (side means [N, B, 4] with NaN for an empty side, joint actions int64 [N]).  Per env and UAV it is side_means() and
+    np.nanargmin, so each mean is the very np.mean the reference takes."""
+    cur = np.asarray(cur_sinr, np.float64)
+    ue, bs = np.asarray(ue_xy), np.asarray(bs_xy)
+    N, B = bs.shape[0], bs.shape[1]
+    means = np.empty((N, B, 4))
+    actions = np.empty(N, np.int64)
+    for e in range(N):
+        a = 0
+        for b in range(B):
+            means[e, b] = side_means(cur[e], ue[e], bs[e, b])
+            a = a * n_act + int(np.nanargmin(means[e, b]))               # most significant digit -> UAV 0 (:34)
+        actions[e] = a
+    return means, actions
+
+
+def gradient_actions_reference(env, twin, side_means=False):
+    """choose_act_gradient for every env of a BatchedMobiEnv, from the pieces the env has always had: ``twin`` (a second
+    BatchedMobiEnv of the same shape, seed and env_id_base, e.g. ``env.clone()``, kept by the caller) takes a copy of the state,
+    steps once with every UAV staying, and the rule runs as torch ops on the twin's outputs.  ``env`` is not modified.  Any shape,
+    n_ue > 64 included.  Returns int64 [N] on the device (and the side means [N, B, 4] float64 when asked)."""
+    import torch
+
+    buf = getattr(twin, "_gradient_state_buf", None)
+    if buf is None:
+        buf = twin._gradient_state_buf = torch.empty(env._lay.total_bytes, dtype=torch.uint8, device=env.device)
+        twin._gradient_stay = torch.full((env.n_envs,), env.N_ACT ** env.nBS - 1, dtype=torch.int64, device=env.device)
+    env.copy_state_to(buf)
+    twin.copy_state_from(buf)
+    twin.step(twin._gradient_stay)
+    o = twin.out
+    cur = o["cur_sinr_f64"] if "cur_sinr_f64" in o else o["cur_sinr"].double()            # [N, U]
+    ue, bs = o["ue_xy"].int(), o["bs_xy"]                                                  # [N, U, 2], [N, B, 2]
+    gt_x = ue[:, None, :, 0] > bs[:, :, None, 0]                                           # [N, B, U]
+    gt_y = ue[:, None, :, 1] > bs[:, :, None, 1]
+    sel = torch.stack((gt_x, ~gt_x, gt_y, ~gt_y), dim=2)                                   # [N, B, 4, U]
+    cnt = sel.sum(-1)
+    means = (sel * cur[:, None, None, :]).sum(-1) / cnt                                    # 0 / 0 = NaN: an empty side
+    digit = torch.where(cnt > 0, means, torch.full_like(means, float("inf"))).argmin(-1)   # nanargmin (no side mean is infinite)
+    w = env.N_ACT ** torch.arange(env.nBS - 1, -1, -1, device=env.device, dtype=torch.int64)
+    actions = (digit * w).sum(-1)
+    return (actions, means) if side_means else actions

@@ -23,14 +23,16 @@
 extern "C" {
 #endif
 
-#define UAVENV_ABI_VERSION 7   /* 2: state blob = arrays of records (UavEnvStateLayout); 3: + uavenv_step_many, uavenv_step_seq;
+#define UAVENV_ABI_VERSION 8   /* 2: state blob = arrays of records (UavEnvStateLayout); 3: + uavenv_step_many, uavenv_step_seq;
                                 * 4: + uavenv_sinr_area_at, uavenv_step_many_packed / uavenv_unpack_outputs, uavenv_debug_variant_* (launch census), uavenv_debug_rotation_info,
                                 *      uavenv_step_many_prepare;
                                 * 5: + UAVENV_E_DEVICE, uavenv_device_error (one-launch rotation schedule with bounded hand-offs), uavenv_step_range,
                                 *      uavenv_launch_timing / uavenv_launch_times_us;
                                 * 6: - uavenv_step_many_packed / uavenv_unpack_outputs (ABI 4's packed output records: no benefit once measured
                                 *      under the one-launch schedule, removed with their 24 kernel instantiations per shape);
-                                * 7: + uavenv_rollout_gated / UavEnvGatedRollout (a whole rollout as one persistent launch beside a persistent policy kernel) */
+                                * 7: + uavenv_rollout_gated / UavEnvGatedRollout (a whole rollout as one persistent launch beside a persistent policy kernel);
+                                * 8: + uavenv_gradient_actions (the SINR-gradient baseline's decision from a look-ahead step that commits nothing),
+                                *      uavenv_step_gradient */
 #define UAVENV_MAX_GROUPS 16
 #define UAVENV_MAX_BS 32
 
@@ -270,6 +272,21 @@ typedef struct UavEnvGatedRollout {
     int32_t enc_relu6;
 } UavEnvGatedRollout;
 int uavenv_rollout_gated(uavenv_t *h, const UavEnvGatedRollout *r, const UavEnvOut *out, void *stream);
+
+/* Choose_Act_Gradient (gradient.py:14-37) for every env; the state is not modified.  One launch: the step the env would take next with no
+ * UAV moving (step_test(624) on a deep copy in the reference: the mobility tick or the trace cells, that tick's fading draws, cur_sinr of the
+ * serving UAV before any handover -- bit-identical to uavenv_step with the all-stay action on a copy of the handle), then per UAV the mean
+ * cur_sinr of the UEs with x > bx, x <= bx, y > by, y <= by (NaN for an empty side), digit = the first minimum of the four, joint action =
+ * sum digit_b n_act^(B-1-b).  With on-device randomness the look-ahead sees the draws of the tick the real step will execute.
+ * ue_xy_in_dev: NULL = group mobility (the next tick), else [N,U,2] trace cells (read_trace, mobile_env.py:202-203).
+ * actions_out_dev [N] int64 (required); side_means_dev [N,B,4] float64 or NULL; look_out: the look-ahead step's outputs, or NULL.
+ * n_ue <= 64 (the packed kernels) and n_act == 5; UAVENV_E_INVALID otherwise, before any launch. */
+int uavenv_gradient_actions(uavenv_t *h, const int16_t *ue_xy_in_dev, const UavEnvInject *inj, int64_t *actions_out_dev,
+                            double *side_means_dev, const UavEnvOut *look_out, void *stream);
+/* n_steps x [uavenv_gradient_actions; uavenv_step with those actions] issued by ONE host call (group mobility, on-device randomness):
+ * actions_out_dev [n_steps, N]; `out` in uavenv_step_many's layout (block t = what step t returned).  No host synchronisation,
+ * capturable in a hipGraph, no allocation.  Bit-identical to the two-call loop by definition: it is that loop. */
+int uavenv_step_gradient(uavenv_t *h, int n_steps, int64_t *actions_out_dev, const UavEnvOut *out, void *stream);
 
 /* Sticky device-side error of a handle: *code = 0, or the word a kernel left when it gave up (0x48414e44 "HAND": a wavefront of a
  * one-launch schedule waited longer than the spin budget for the wavefront that runs the first steps of the same envs -- never seen
