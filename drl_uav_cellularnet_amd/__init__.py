@@ -4,7 +4,7 @@ SamKnightGit/DRL_UAV_CellularNet: MobiEnvironment.step/reset + LTEChannel DL SIN
 Importing the package does not need a GPU; constructing an env does (no CPU fallback)."""
 from ._capi import UavEnvError  # noqa: F401
 
-__all__ = ["BatchedMobiEnv", "MobiEnvironment", "UavEnvError"]
+__all__ = ["BatchedMobiEnv", "MobiEnvironment", "GreedyEvaluator", "UavEnvError"]
 
 
 def __getattr__(name):  # lazy: torch is only imported when an env class is requested
@@ -14,4 +14,7 @@ def __getattr__(name):  # lazy: torch is only imported when an env class is requ
     if name == "MobiEnvironment":
         from .mobile_env import MobiEnvironment
         return MobiEnvironment
+    if name == "GreedyEvaluator":
+        from .evaluate import GreedyEvaluator
+        return GreedyEvaluator
     raise AttributeError(name)

@@ -18,7 +18,7 @@ EXPORTS = ("uavagent_abi_version", "uavagent_last_error", "uavagent_sparse_rows_
            "uavagent_rows_grad_workspace_bytes", "uavagent_rows_grad_f32", "uavagent_rows_grad_sort", "uavagent_rows_grad_sums_f32", "uavagent_nstep_returns_f32", "uavagent_rmsprop_tf1",
            "uavagent_gemm_rows_f32", "uavagent_gemm_rows_workspace_bytes", "uavagent_gemm_tn_workspace_bytes", "uavagent_gemm_tn_f32",
            "uavagent_debug_tn_plan_check", "uavagent_actor_head_f32", "uavagent_actor_head_gated_f32", "uavagent_gate_prepare",
-           "uavagent_device_error", "uavagent_device_error_clear")
+           "uavagent_device_error", "uavagent_device_error_clear", "uavagent_actor_head_greedy_f32", "uavagent_argmax_rows_f32")
 ABI_VERSION = 5
 
 _lib = None
@@ -44,6 +44,7 @@ _PROF_KEYS = {
     "uavagent_gemm_rows_f32": lambda a: "M=%d,K=%d,N=%d%s" % (a[5], a[6], a[7], ",relu6_mask" if a[10] else (",bias" if a[8] else "")),
     "uavagent_gemm_tn_f32": lambda a: "M=%d,I=%d,J=%d" % (a[2], a[3], a[4]),
     "uavagent_actor_head_f32": lambda a: "rows=%d" % a[6],
+    "uavagent_actor_head_greedy_f32": lambda a: "rows=%d" % a[5],
     "uavagent_first_layer_from_obs_f32": lambda a: "rows=%d" % a[9],
     "uavagent_sparse_rows_sum_f32": lambda a: "rows=%d" % a[7],
     "uavagent_rows_grad_sums_f32": lambda a: "M=%d,K=%d" % (a[1], a[2]),
@@ -118,6 +119,8 @@ def load():
         "uavagent_gemm_tn_f32": [_P, _P, _I64, _I32, _I32, _I64, _P, _I64, _P, _P, C.c_size_t, _P],
         "uavagent_actor_head_f32": [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _I64, _P, _P],
         "uavagent_actor_head_gated_f32": [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _I64, _P, _P, _P, _P, C.c_uint32, _P],
+        "uavagent_actor_head_greedy_f32": [_P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _I64, _P, _P],
+        "uavagent_argmax_rows_f32": [_P, _I64, _I64, _I32, _P, _P],
         "uavagent_gate_prepare": [],
         "uavagent_device_error": [C.POINTER(C.c_uint32)],
         "uavagent_device_error_clear": [],
@@ -430,6 +433,42 @@ def actor_head(h1, w2t, b2, w3t_padded, b3_padded, uniforms, n_actions, h2_out, 
                                             _stream(h1.device))
     _check(rc, "uavagent_actor_head_f32")
     return actions_out
+
+
+def actor_head_greedy(h1, w2t, b2, w3t_padded, b3_padded, n_actions, h2_out, logits_pad_out, actions_out):
+    """actor_head with argmax(logits) in place of the draw (uavagent_actor_head_greedy_f32; evaluate.greedy_reference states the rule):
+    same h2 and logits bits as actor_head, no uniforms."""
+    for t, what in ((h1, "h1"), (w2t, "w2t"), (b2, "b2"), (w3t_padded, "w3t_padded"), (b3_padded, "b3_padded"), (h2_out, "h2_out")):
+        _f32c(t, what)
+    N, H = h1.shape
+    if tuple(w2t.shape) != (H, H) or w3t_padded.shape[1] != H or w3t_padded.shape[0] != b3_padded.numel() or tuple(h2_out.shape) != (N, H):
+        raise UavAgentError("actor_head_greedy: shapes do not agree")
+    if actions_out.dtype != torch.int64 or actions_out.numel() != N or not actions_out.is_contiguous() or logits_pad_out.shape[0] != N:
+        raise UavAgentError("actor_head_greedy: one logits row and one contiguous int64 action per row of h1")
+    if b2.numel() != H:
+        raise UavAgentError("actor_head_greedy: b2 must have %d elements" % H)
+    _same_device("actor_head_greedy", h1, w2t, b2, w3t_padded, b3_padded, h2_out, logits_pad_out, actions_out)
+    with torch.cuda.device(h1.device):
+        rc = load().uavagent_actor_head_greedy_f32(_ptr(h1), _ptr(w2t), _ptr(b2), _ptr(w3t_padded), _ptr(b3_padded), N, H, int(n_actions),
+                                                   _ptr(h2_out), _ptr(logits_pad_out), _row_stride(logits_pad_out, "logits_pad_out"),
+                                                   _ptr(actions_out), _stream(h1.device))
+    _check(rc, "uavagent_actor_head_greedy_f32")
+    return actions_out
+
+
+def argmax_rows(logits, out=None):
+    """First maximum of every row (uavagent_argmax_rows_f32): logits float32 [N, A <= 1024], possibly a column slice of a wider buffer
+    (rows contiguous); returns int64 [N]."""
+    ld = _row_stride(logits, "logits")
+    N, A = logits.shape
+    if out is None:
+        out = torch.empty((N,), dtype=torch.int64, device=logits.device)
+    elif out.dtype != torch.int64 or out.numel() != N or not out.is_contiguous() or out.device != logits.device:
+        raise UavAgentError("argmax_rows: out must be a contiguous int64 [N] tensor on the device of logits")
+    with torch.cuda.device(logits.device):
+        rc = load().uavagent_argmax_rows_f32(_ptr(logits), ld, N, A, _ptr(out), _stream(logits.device))
+    _check(rc, "uavagent_argmax_rows_f32")
+    return out
 
 
 def gate_prepare():

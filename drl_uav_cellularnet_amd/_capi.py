@@ -49,7 +49,12 @@ class UavEnvGatedRollout(C.Structure):      # include/uavenv.h
                 ("enc_rows", C.c_int64), ("enc_hidden", C.c_int32), ("enc_relu6", C.c_int32)]
 
 
-ABI_VERSION = 8   # UAVENV_ABI_VERSION of include/uavenv.h this binding is written against (tests/test_capi_load.py compares the three)
+class UavEnvEvalAcc(C.Structure):           # include/uavenv.h
+    _fields_ = [(n, _P) for n in ("reward_sum_dev", "mean_sinr_sum_dev", "n_out_sum_dev", "steps_dev", "sinr_hist_dev", "sinr_nan_dev")] + [
+        ("lo", C.c_double), ("inv_width", C.c_double), ("bins", C.c_int32)]
+
+
+ABI_VERSION = 9   # UAVENV_ABI_VERSION of include/uavenv.h this binding is written against (tests/test_capi_load.py compares the three)
 STATE_FIELDS = ("ue_pos", "ue_aux", "grp", "env", "bs_xy", "out_bits")   # arrays of records, include/uavenv.h
 
 
@@ -58,7 +63,7 @@ class UavEnvStateLayout(C.Structure):
 
 
 EXPORTS = ("uavenv_abi_version", "uavenv_last_error", "uavenv_default_config", "uavenv_create", "uavenv_destroy",
-           "uavenv_init", "uavenv_warmup", "uavenv_reset", "uavenv_reset_trace", "uavenv_step", "uavenv_step_range", "uavenv_rollout_gated", "uavenv_gradient_actions", "uavenv_step_gradient", "uavenv_step_many", "uavenv_step_seq", "uavenv_step_trace",
+           "uavenv_init", "uavenv_warmup", "uavenv_reset", "uavenv_reset_trace", "uavenv_step", "uavenv_step_range", "uavenv_rollout_gated", "uavenv_gradient_actions", "uavenv_step_gradient", "uavenv_eval_accumulate", "uavenv_step_many", "uavenv_step_seq", "uavenv_step_trace",
            "uavenv_obs_dense", "uavenv_obs_dense_update", "uavenv_sinr_area", "uavenv_sinr_area_at",
            "uavenv_debug_variant_count", "uavenv_debug_variant_info", "uavenv_debug_variant_reset", "uavenv_debug_rotation_info", "uavenv_step_many_prepare", "uavenv_device_error", "uavenv_launch_timing", "uavenv_launch_times_us", "uavenv_debug_schedule",
            "uavenv_state_layout", "uavenv_get_state", "uavenv_set_state", "uavenv_philox4x32_10", "uavenv_lean_math_eval")
@@ -101,6 +106,7 @@ def load():
     lib.uavenv_rollout_gated.argtypes = [_P, C.POINTER(UavEnvGatedRollout), C.POINTER(UavEnvOut), _P]
     lib.uavenv_gradient_actions.argtypes = [_P, _P, C.POINTER(UavEnvInject), _P, _P, C.POINTER(UavEnvOut), _P]
     lib.uavenv_step_gradient.argtypes = [_P, C.c_int, _P, C.POINTER(UavEnvOut), _P]
+    lib.uavenv_eval_accumulate.argtypes = [_P, C.POINTER(UavEnvOut), C.POINTER(UavEnvEvalAcc), _P]
     lib.uavenv_step_range.argtypes = [_P, _P, C.c_int64, C.c_int64, C.POINTER(UavEnvInject), C.POINTER(UavEnvOut), _P]
     lib.uavenv_step_many.argtypes = [_P, _P, C.c_int, C.POINTER(UavEnvOut), _P]
     lib.uavenv_step_seq.argtypes = [_P, _P, C.c_int, C.POINTER(UavEnvOut), _P]

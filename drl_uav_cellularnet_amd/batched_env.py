@@ -47,6 +47,44 @@ _REC_DTYPES = {
 assert [_REC_DTYPES[k].itemsize for k in ("ue_pos", "ue_aux", "grp", "env")] == [16, 16, 48, 32]
 
 
+class EvalAccumulators:
+    """The caller-owned side of uavenv_eval_accumulate (UavEnvEvalAcc): device tensors ``reward_sum`` / ``mean_sinr_sum`` float64 [N],
+    ``n_out_sum`` int64 [N], ``steps`` int32 [N], ``sinr_hist`` int64 [bins], ``sinr_nan`` int64 [1].  Bin b of the histogram counts
+    floor((cur_sinr - lo) * inv_width) == b, the first and last bin also everything below / above the range; inv_width = bins / (hi - lo)."""
+
+    NAMES = ("reward_sum", "mean_sinr_sum", "n_out_sum", "steps", "sinr_hist", "sinr_nan")
+
+    def __init__(self, env, hist=(-50.0, 100.0, 150)):
+        lo, hi, bins = float(hist[0]), float(hist[1]), int(hist[2])
+        if not (np.isfinite(lo) and np.isfinite(hi) and hi > lo and 1 <= bins <= 1024):
+            raise ValueError("hist must be (lo, hi, bins) with finite lo < hi and 1 <= bins <= 1024")
+        N, dev = env.n_envs, env.device
+        self.lo, self.hi, self.bins, self.inv_width = lo, hi, bins, bins / (hi - lo)
+        self.reward_sum = torch.zeros(N, dtype=torch.float64, device=dev)
+        self.mean_sinr_sum = torch.zeros(N, dtype=torch.float64, device=dev)
+        self.n_out_sum = torch.zeros(N, dtype=torch.int64, device=dev)
+        self.steps = torch.zeros(N, dtype=torch.int32, device=dev)
+        self.sinr_hist = torch.zeros(bins, dtype=torch.int64, device=dev)
+        self.sinr_nan = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._struct = _capi.UavEnvEvalAcc()
+        for n in self.NAMES:
+            setattr(self._struct, n + "_dev", getattr(self, n).data_ptr())
+        self._struct.lo, self._struct.inv_width, self._struct.bins = lo, self.inv_width, bins
+        self._ref = C.byref(self._struct)
+
+    def zero_(self):
+        for n in self.NAMES:
+            getattr(self, n).zero_()
+        return self
+
+    def tensors(self):
+        return {n: getattr(self, n) for n in self.NAMES}
+
+    def hist_edges(self):
+        """float64 [bins + 1]: bin b covers [edges[b], edges[b + 1])."""
+        return self.lo + np.arange(self.bins + 1, dtype=np.float64) / self.inv_width
+
+
 class BatchedMobiEnv:
     N_ACT = 5  # mobile_env.py:21
     WARMUP_TICKS = 200  # mobile_env.py:77-79
@@ -441,6 +479,20 @@ class BatchedMobiEnv:
             for k, v in self.out.items():
                 v.copy_(out[k][T - 1])
         return actions_out, out
+
+    # ---- evaluation totals (main_test.py:46-113 for a whole batch) ------------------------------------
+    def eval_accumulators(self, hist=(-50.0, 100.0, 150)):
+        """Zeroed accumulators for eval_accumulate(): ``hist`` = (lo, hi, bins) of the serving-SINR histogram in dB (default: the
+        range of plot_sinr_map, mobile_env.py:252, in 1 dB bins)."""
+        return EvalAccumulators(self, hist)
+
+    def eval_accumulate(self, acc):
+        """Fold the outputs of the last step (``self.out``) into ``acc`` (uavenv_eval_accumulate): one launch, no synchronisation.
+        Per env reward_sum / mean_sinr_sum (float64, the float64 outputs when the env has them), n_out_sum, steps; over all envs
+        the histogram of cur_sinr and the count of NaNs."""
+        rc = self._lib.uavenv_eval_accumulate(self._h, self._out_ref, acc._ref, self._stream())
+        if rc:
+            _capi.check(rc)
 
     def step_trace(self, actions, ue_xy, fading=None):
         """MobiEnvironment.step_test with mobility_model == 'read_trace' (mobile_env.py:196-233)."""

@@ -13,4 +13,21 @@ __attribute__((visibility("hidden"))) int fail(int code, const std::string &msg)
 // a row's ~800 instructions were half expf (10 per lane, ~40 instructions each).  Underflow to 0 is the exact limit.
 #ifdef __HIPCC__
 __device__ __forceinline__ float draw_exp(float x_minus_max) { return __builtin_amdgcn_exp2f(x_minus_max * 1.4426950408889634f); }
+
+// The GREEDY choice (uavagent_argmax_rows_f32 and the greedy head's fused pick: one rule, stated once): the first index whose value no other
+// exceeds.  A lane feeds its columns in ASCENDING order to greedy_take -- strict >, so of equal values the lower index stays; a NaN is never
+// taken -- and greedy_wave reduces the 64 (value, index) pairs (equal values: the lower index) to the row's answer in every lane.  bi < 0 =
+// nothing taken yet; a row of NaNs only (or no columns) gives 0.
+__device__ __forceinline__ void greedy_take(float &bv, int &bi, float v, int c) {
+    if (v == v && (bi < 0 || v > bv)) { bv = v; bi = c; }
+}
+__device__ __forceinline__ int greedy_wave(float bv, int bi) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(bv, off, 64);
+        const int oi = __shfl_xor(bi, off, 64);
+        if (oi >= 0 && (bi < 0 || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+    }
+    return bi < 0 ? 0 : bi;
+}
 #endif

@@ -1113,7 +1113,9 @@ __device__ __forceinline__ void head_chunk(const float *pa, const float *pw, int
 // One tile (16 RB rows from h1 to the action) of the head; `lds` = the workgroup's HdPlan<RB>::LdsF floats, m0 = the tile's first row.
 // COH (the gated kernel below): h1 was written by ANOTHER kernel while this one was running and the actions are read by it -- the h1 tile is
 // loaded past this CU's L1 (LDS-DMA with sc1) and the actions are stored through (agent-scope atomics).
-template <int RB, bool COH>
+// GREEDY (uavagent_actor_head_greedy_f32, the evaluation loop of main_test.py:68): phases 0-2 and the logits store are the same code; the
+// action is argmax(logits) by greedy_take / greedy_wave (agent_common.h) instead of the draw -- no exp, no scan, `uni` is not read.
+template <int RB, bool COH, bool GREEDY = false>
 __device__ __forceinline__ void actor_head_tile(float *lds, const long long m0, const float *__restrict__ h1, const float *__restrict__ w2t,
                                                 const float *__restrict__ b2, const float *__restrict__ w3t, const float *__restrict__ b3p,
                                                 const float *__restrict__ uni, long long n_rows, int n_act,
@@ -1133,7 +1135,7 @@ __device__ __forceinline__ void actor_head_tile(float *lds, const long long m0, 
 #pragma unroll
     for (int i = 0; i < kHdRows / kHdWaves; ++i) {
         const long long m = m0 + wave * (kHdRows / kHdWaves) + i;
-        u_row[i] = uni[m < n_rows ? m : 0];
+        if constexpr (!GREEDY) u_row[i] = uni[m < n_rows ? m : 0];
     }
     using set0_t = std::integral_constant<int, 0>;
     using set1_t = std::integral_constant<int, 1>;
@@ -1307,46 +1309,59 @@ __device__ __forceinline__ void actor_head_tile(float *lds, const long long m0, 
         const long long m = m0 + lr;
         if (m >= n_rows) break;
         const float *row = sL + lr * kHdNP;
-        float v[PER];
-        float mx = -3.0e38f;
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int c = lane * PER + k;
-            v[k] = (c < n_act) ? row[c] : -3.0e38f;
-            mx = fmaxf(mx, v[k]);
-        }
-        mx = wave_max_g(mx);
-        float loc = 0.f;
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int c = lane * PER + k;
-            v[k] = (c < n_act) ? draw_exp(v[k] - mx) : 0.f;
-            loc += v[k];
-        }
-        float incl = loc;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const float t = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += t;
-        }
-        const float total = __shfl(incl, 63, 64);
-        const float target = u_row[i] * total;
-        const unsigned long long over = __ballot(incl > target);
-        int a = n_act - 1;
-        if (over != 0ull) {
-            // every lane walks its OWN PER values from its own exclusive prefix; the walk of the lane that holds the crossing is the answer
-            // (the same sums in the same order as walking that lane's values by broadcast, without ten dependent cross-lane reads)
-            const int first = __ffsll((long long)over) - 1;
-            float c = incl - loc;
-            int fk = -1;
+        int a;
+        if constexpr (GREEDY) {
+            // the padding columns [n_act, 640) hold b3's zeros: they are never fed, so they cannot win over negative logits
+            float bv = 0.f;
+            int bi = -1;
 #pragma unroll
             for (int k = 0; k < PER; ++k) {
-                c += v[k];
-                if (fk < 0 && c > target) fk = k;
+                const int c = lane * PER + k;
+                if (c < n_act) greedy_take(bv, bi, row[c], c);
             }
-            fk = __shfl(fk, first, 64);
-            a = fk < 0 ? first * PER + PER - 1 : first * PER + fk;
-            if (a > n_act - 1) a = n_act - 1;
+            a = greedy_wave(bv, bi);
+        } else {
+            float v[PER];
+            float mx = -3.0e38f;
+#pragma unroll
+            for (int k = 0; k < PER; ++k) {
+                const int c = lane * PER + k;
+                v[k] = (c < n_act) ? row[c] : -3.0e38f;
+                mx = fmaxf(mx, v[k]);
+            }
+            mx = wave_max_g(mx);
+            float loc = 0.f;
+#pragma unroll
+            for (int k = 0; k < PER; ++k) {
+                const int c = lane * PER + k;
+                v[k] = (c < n_act) ? draw_exp(v[k] - mx) : 0.f;
+                loc += v[k];
+            }
+            float incl = loc;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const float t = __shfl_up(incl, off, 64);
+                if (lane >= off) incl += t;
+            }
+            const float total = __shfl(incl, 63, 64);
+            const float target = u_row[i] * total;
+            const unsigned long long over = __ballot(incl > target);
+            a = n_act - 1;
+            if (over != 0ull) {
+                // every lane walks its OWN PER values from its own exclusive prefix; the walk of the lane that holds the crossing is the answer
+                // (the same sums in the same order as walking that lane's values by broadcast, without ten dependent cross-lane reads)
+                const int first = __ffsll((long long)over) - 1;
+                float c = incl - loc;
+                int fk = -1;
+#pragma unroll
+                for (int k = 0; k < PER; ++k) {
+                    c += v[k];
+                    if (fk < 0 && c > target) fk = k;
+                }
+                fk = __shfl(fk, first, 64);
+                a = fk < 0 ? first * PER + PER - 1 : first * PER + fk;
+                if (a > n_act - 1) a = n_act - 1;
+            }
         }
         if (lane == 0) {
             if (COH) __hip_atomic_store(action + m, (long long)a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1355,14 +1370,14 @@ __device__ __forceinline__ void actor_head_tile(float *lds, const long long m0, 
     }
 }
 
-template <int RB>
+template <int RB, bool GREEDY = false>
 __global__ __launch_bounds__(kHdThr, 1) void actor_head_kernel(const float *__restrict__ h1, const float *__restrict__ w2t, const float *__restrict__ b2,
                                                                 const float *__restrict__ w3t, const float *__restrict__ b3p,
                                                                 const float *__restrict__ uni, long long n_rows, int n_act,
                                                                 float *__restrict__ h2_out, float *__restrict__ logits, long long ldl,
                                                                 long long *__restrict__ action) {
     __shared__ __attribute__((aligned(16))) float lds[HdPlan<RB>::LdsF];
-    actor_head_tile<RB, false>(lds, (long long)blockIdx.x * HdPlan<RB>::Rows, h1, w2t, b2, w3t, b3p, uni, n_rows, n_act, h2_out, logits, ldl, action);
+    actor_head_tile<RB, false, GREEDY>(lds, (long long)blockIdx.x * HdPlan<RB>::Rows, h1, w2t, b2, w3t, b3p, uni, n_rows, n_act, h2_out, logits, ldl, action);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1616,16 +1631,18 @@ static int cu_count_of_current_device() {
     return v;
 }
 
-extern "C" int uavagent_actor_head_f32(const float *h1, const float *w2t, const float *b2, const float *w3t_padded, const float *b3_padded,
-                                       const float *uniforms, int64_t n_rows, int32_t n_hidden, int32_t n_actions, float *h2_out,
-                                       float *logits_out, int64_t ld_logits, int64_t *actions_out, void *stream) {
-    if (!h1 || !w2t || !b2 || !w3t_padded || !b3_padded || !uniforms || !h2_out || !logits_out || !actions_out)
-        return fail3(UAVAGENT_E_INVALID, "actor_head: null pointer");
+// Checks and launch rule shared by the sampling head and the greedy head (`greedy`: the GREEDY instantiations, uniforms unused).
+static int actor_head_launch(const char *what, bool greedy, const float *h1, const float *w2t, const float *b2, const float *w3t_padded,
+                             const float *b3_padded, const float *uniforms, int64_t n_rows, int32_t n_hidden, int32_t n_actions, float *h2_out,
+                             float *logits_out, int64_t ld_logits, int64_t *actions_out, void *stream) {
+    const std::string w(what);
+    if (!h1 || !w2t || !b2 || !w3t_padded || !b3_padded || (!greedy && !uniforms) || !h2_out || !logits_out || !actions_out)
+        return fail3(UAVAGENT_E_INVALID, w + ": null pointer");
     if (n_hidden != kHdH || n_actions <= 576 || n_actions > kHdNP || ld_logits < kHdNP || (ld_logits & 3) || n_rows < 0)
-        return fail3(UAVAGENT_E_INVALID, "actor_head: built for 200 hidden units and 577..640 actions (the reference's 625 = 5^4; 10 policy columns "
-                                         "per lane, like uavagent_sample_actions at that width), ld_logits >= 640 and a multiple of 4");
+        return fail3(UAVAGENT_E_INVALID, w + ": built for 200 hidden units and 577..640 actions (the reference's 625 = 5^4; 10 policy columns "
+                                             "per lane, like uavagent_sample_actions at that width), ld_logits >= 640 and a multiple of 4");
     if (!aligned16(h1) || !aligned16(w2t) || !aligned16(w3t_padded) || !aligned16(h2_out) || !aligned16(logits_out))
-        return fail3(UAVAGENT_E_INVALID, "actor_head: matrices must be 16-byte aligned");
+        return fail3(UAVAGENT_E_INVALID, w + ": matrices must be 16-byte aligned");
     if (n_rows == 0) return UAVAGENT_OK;
     // 32-row workgroups while they give every CU one (a whole rollout batch of 8192 rows on 256 CUs); 16-row workgroups for fewer rows (half a
     // batch on its own stream): the time of a workgroup is its weight stream, so fewer, larger workgroups would only leave CUs idle
@@ -1633,16 +1650,29 @@ extern "C" int uavagent_actor_head_f32(const float *h1, const float *w2t, const 
     const int force_rb = force_env ? atoi(force_env) : 0;
     const int n_cu = cu_count_of_current_device();
     const bool small = force_rb ? (force_rb == 1) : (n_rows <= 24ll * n_cu);
-    if (small)
-        hipLaunchKernelGGL(actor_head_kernel<1>, dim3((unsigned)((n_rows + 15) / 16)), dim3(kHdThr), 0, (hipStream_t)stream, h1, w2t, b2, w3t_padded,
-                           b3_padded, uniforms, (long long)n_rows, (int)n_actions, h2_out, logits_out, (long long)ld_logits,
-                           reinterpret_cast<long long *>(actions_out));
-    else
-        hipLaunchKernelGGL(actor_head_kernel<2>, dim3((unsigned)((n_rows + 31) / 32)), dim3(kHdThr), 0, (hipStream_t)stream, h1, w2t, b2, w3t_padded,
-                           b3_padded, uniforms, (long long)n_rows, (int)n_actions, h2_out, logits_out, (long long)ld_logits,
-                           reinterpret_cast<long long *>(actions_out));
-    if (hipGetLastError() != hipSuccess) return fail3(UAVAGENT_E_HIP, "actor_head: launch failed");
+#define UAV_HEAD(RB_, GR_)                                                                                                                         \
+    hipLaunchKernelGGL((actor_head_kernel<RB_, GR_>), dim3((unsigned)((n_rows + 16 * RB_ - 1) / (16 * RB_))), dim3(kHdThr), 0, (hipStream_t)stream, \
+                       h1, w2t, b2, w3t_padded, b3_padded, uniforms, (long long)n_rows, (int)n_actions, h2_out, logits_out, (long long)ld_logits,   \
+                       reinterpret_cast<long long *>(actions_out))
+    if (greedy) { if (small) UAV_HEAD(1, true); else UAV_HEAD(2, true); }
+    else { if (small) UAV_HEAD(1, false); else UAV_HEAD(2, false); }
+#undef UAV_HEAD
+    if (hipGetLastError() != hipSuccess) return fail3(UAVAGENT_E_HIP, w + ": launch failed");
     return UAVAGENT_OK;
+}
+
+extern "C" int uavagent_actor_head_f32(const float *h1, const float *w2t, const float *b2, const float *w3t_padded, const float *b3_padded,
+                                       const float *uniforms, int64_t n_rows, int32_t n_hidden, int32_t n_actions, float *h2_out,
+                                       float *logits_out, int64_t ld_logits, int64_t *actions_out, void *stream) {
+    return actor_head_launch("actor_head", false, h1, w2t, b2, w3t_padded, b3_padded, uniforms, n_rows, n_hidden, n_actions, h2_out, logits_out,
+                             ld_logits, actions_out, stream);
+}
+
+extern "C" int uavagent_actor_head_greedy_f32(const float *h1, const float *w2t, const float *b2, const float *w3t_padded, const float *b3_padded,
+                                              int64_t n_rows, int32_t n_hidden, int32_t n_actions, float *h2_out, float *logits_out,
+                                              int64_t ld_logits, int64_t *actions_out, void *stream) {
+    return actor_head_launch("actor_head_greedy", true, h1, w2t, b2, w3t_padded, b3_padded, nullptr, n_rows, n_hidden, n_actions, h2_out,
+                             logits_out, ld_logits, actions_out, stream);
 }
 
 // ---- the gated head's error word: host-mapped, one per process (allocated by uavagent_gate_prepare, never inside a launch) ----

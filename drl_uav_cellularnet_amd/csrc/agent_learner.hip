@@ -124,6 +124,21 @@ __global__ __launch_bounds__(256) void sample_actions_kernel(const float *__rest
     if (lane == 0) action[r] = a;
 }
 
+// argmax_rows (the greedy policy of main_test.py:68 for logits that already exist): one wavefront per row, lane l reads columns l, l + 64,
+// ... (coalesced, ascending per lane) into greedy_take; greedy_wave picks the row's first maximum (agent_common.h states the rule).
+__global__ __launch_bounds__(256) void argmax_rows_kernel(const float *__restrict__ logits, long long ld, long long N, int A,
+                                                          long long *__restrict__ action) {
+    const int lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= N) return;
+    const float *row = logits + r * ld;
+    float bv = 0.f;
+    int bi = -1;
+    for (int c = lane; c < A; c += 64) greedy_take(bv, bi, row[c], c);
+    const int a = greedy_wave(bv, bi);
+    if (lane == 0) action[r] = a;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // a2c_loss_grad (main.py:64-74), rows = samples, grid-stride over rows, one wavefront per row at a time:
 //   p = softmax(logits);  td = v_target - v;  c_loss = td^2;  a_loss = -(beta * H + log(p[a] + 1e-5) * stop_gradient(td)),
@@ -679,6 +694,18 @@ extern "C" int uavagent_sample_actions(const float *logits, int64_t ld_logits, c
     }
 #undef UAVAGENT_SAMPLE
     return launch_ok("sample_actions");
+}
+
+extern "C" int uavagent_argmax_rows_f32(const float *logits, int64_t ld_logits, int64_t n_rows, int32_t n_actions, int64_t *actions_out,
+                                        void *stream) {
+    if (n_rows < 0 || n_actions < 1 || n_actions > 1024 || ld_logits < n_actions)
+        return fail2(UAVAGENT_E_INVALID, "argmax_rows: need 1 <= n_actions <= 1024 and ld_logits >= n_actions");
+    if (n_rows == 0) return UAVAGENT_OK;
+    if (!logits || !actions_out) return fail2(UAVAGENT_E_INVALID, "argmax_rows: null pointer");
+    if (n_rows > 4ll * 0x7FFFFFFFll) return fail2(UAVAGENT_E_INVALID, "argmax_rows: n_rows too large for one launch");
+    hipLaunchKernelGGL(argmax_rows_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, (long long)ld_logits,
+                       (long long)n_rows, (int)n_actions, reinterpret_cast<long long *>(actions_out));
+    return launch_ok("argmax_rows");
 }
 
 extern "C" size_t uavagent_loss_grad_workspace_bytes(int32_t n_actions) {

@@ -27,7 +27,8 @@ extern "C" {
 #define UAVAGENT_E_HIP (-3)
 #define UAVAGENT_E_DEVICE (-5)   /* a gated launch gave up on the device (uavagent_device_error) */
 
-int uavagent_abi_version(void);   /* 5 (5: + uavagent_actor_head_gated_f32, uavagent_gate_prepare, uavagent_device_error(_clear)) */
+int uavagent_abi_version(void);   /* 5 (5: + uavagent_actor_head_gated_f32, uavagent_gate_prepare, uavagent_device_error(_clear); ABI 5 later
+                                   *    gained uavagent_actor_head_greedy_f32 and uavagent_argmax_rows_f32: additive, the number stays) */
 const char *uavagent_last_error(void);
 
 /* out_a[m, :] = sum_k w_a[idx[m, k], :] + bias_a   (k ascending, fp32; bias added last, like embedding_bag(...) + b)
@@ -150,6 +151,21 @@ int uavagent_gemm_rows_f32(const float *a, int64_t lda, const float *w, int64_t 
 int uavagent_actor_head_f32(const float *h1, const float *w2t, const float *b2, const float *w3t_padded, const float *b3_padded,
                             const float *uniforms, int64_t n_rows, int32_t n_hidden, int32_t n_actions, float *h2_out, float *logits_out,
                             int64_t ld_logits, int64_t *actions_out, void *stream);
+
+/* The GREEDY policy of the evaluation loop (main_test.py:68,73: tf.argmax(a_prob)) for logits that exist: actions_out[m] = the first index
+ * a < n_actions whose logit no other exceeds -- strict >, so of equal logits the lowest index wins (np.argmax / tf.argmax); a NaN never
+ * wins; a row of NaNs only gives 0.  This is argmax(logits); it equals argmax(softmax(logits)) except where two DIFFERENT logits round to
+ * the same float32 probability (there the reference takes the lower index, this the larger logit).  logits f32 [n_rows, n_actions] with row
+ * stride ld_logits floats, actions_out int64 [n_rows]; one wavefront per row, n_actions <= 1024 like uavagent_sample_actions. */
+int uavagent_argmax_rows_f32(const float *logits, int64_t ld_logits, int64_t n_rows, int32_t n_actions, int64_t *actions_out, void *stream);
+
+/* uavagent_actor_head_f32 with that greedy choice in place of the draw (no uniforms): the same kernel body with the draw replaced at compile
+ * time, so h2_out and logits_out are bit-identical to the sampling head's on the same inputs, and shapes, tile heights, launch rule and the
+ * UAVAGENT_HEAD_RB override are its own.  actions_out[m] = uavagent_argmax_rows_f32 of logits_out's row m over [0, n_actions): the zero
+ * padding columns [n_actions, 640) are never candidates, even when every real logit is negative. */
+int uavagent_actor_head_greedy_f32(const float *h1, const float *w2t, const float *b2, const float *w3t_padded, const float *b3_padded,
+                                   int64_t n_rows, int32_t n_hidden, int32_t n_actions, float *h2_out, float *logits_out, int64_t ld_logits,
+                                   int64_t *actions_out, void *stream);
 
 /* The actor's head of a WHOLE rollout (n_steps x uavagent_actor_head_f32) as ONE persistent launch that runs beside the env library's
  * persistent rollout kernel (uavenv_rollout_gated, include/uavenv.h -- which states the protocol): per block b of 16 consecutive rows and

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define UAVENV_ABI_VERSION 8   /* 2: state blob = arrays of records (UavEnvStateLayout); 3: + uavenv_step_many, uavenv_step_seq;
+#define UAVENV_ABI_VERSION 9   /* 2: state blob = arrays of records (UavEnvStateLayout); 3: + uavenv_step_many, uavenv_step_seq;
                                 * 4: + uavenv_sinr_area_at, uavenv_step_many_packed / uavenv_unpack_outputs, uavenv_debug_variant_* (launch census), uavenv_debug_rotation_info,
                                 *      uavenv_step_many_prepare;
                                 * 5: + UAVENV_E_DEVICE, uavenv_device_error (one-launch rotation schedule with bounded hand-offs), uavenv_step_range,
@@ -32,7 +32,8 @@ extern "C" {
                                 *      under the one-launch schedule, removed with their 24 kernel instantiations per shape);
                                 * 7: + uavenv_rollout_gated / UavEnvGatedRollout (a whole rollout as one persistent launch beside a persistent policy kernel);
                                 * 8: + uavenv_gradient_actions (the SINR-gradient baseline's decision from a look-ahead step that commits nothing),
-                                *      uavenv_step_gradient */
+                                *      uavenv_step_gradient;
+                                * 9: + uavenv_eval_accumulate / UavEnvEvalAcc (a step's outputs folded into per-env totals and a serving-SINR histogram) */
 #define UAVENV_MAX_GROUPS 16
 #define UAVENV_MAX_BS 32
 
@@ -287,6 +288,26 @@ int uavenv_gradient_actions(uavenv_t *h, const int16_t *ue_xy_in_dev, const UavE
  * actions_out_dev [n_steps, N]; `out` in uavenv_step_many's layout (block t = what step t returned).  No host synchronisation,
  * capturable in a hipGraph, no allocation.  Bit-identical to the two-call loop by definition: it is that loop. */
 int uavenv_step_gradient(uavenv_t *h, int n_steps, int64_t *actions_out_dev, const UavEnvOut *out, void *stream);
+
+/* The evaluation loop's bookkeeping (main_test.py:46-113 keeps reward, outage and current_BS_sinr of every step; for 4096 envs x 2001 steps x
+ * 40 UEs the SINRs alone are 1.3 GB) as running totals on the device: ONE launch per step reads the step's outputs `out` (of the handle's
+ * shapes: what uavenv_step / uavenv_step_trace just wrote) and ADDS into caller-owned accumulators, which the caller zeroes.  One lane per env
+ * adds the scalars -- the total of an env is read and written by that lane only, so the float64 sums are the plain left-to-right sums over
+ * the steps, bit-reproducible; the histogram is built per workgroup in LDS (hence bins <= 1024) and flushed with integer atomics: counts,
+ * independent of the order.  No float atomics.  Any n_ue.  Required in `out`: reward_dev or reward_f64_dev, mean_sinr_dev or
+ * mean_sinr_f64_dev (the float64 member is used when present), n_out_dev, cur_sinr_dev.  UAVENV_E_INVALID before any launch for a null
+ * required member, bins outside [1, 1024] or a non-finite lo / inv_width. */
+typedef struct UavEnvEvalAcc {
+    double  *reward_sum_dev;     /* [N]    += reward_f64 if `out` has float64 outputs, else (double)reward                                 */
+    double  *mean_sinr_sum_dev;  /* [N]    += mean_sinr (same rule)                                                                       */
+    int64_t *n_out_sum_dev;      /* [N]    += n_out                                                                                       */
+    int32_t *steps_dev;          /* [N]    += 1                                                                                           */
+    int64_t *sinr_hist_dev;      /* [bins] += 1 per (env, UE): bin = floor(((double)cur_sinr - lo) * inv_width), clamped to [0, bins-1]   */
+    int64_t *sinr_nan_dev;       /* [1]    NaN values, counted here and in no bin                                                         */
+    double lo, inv_width;        /* default -50 dB and 1.0 ...                                                                            */
+    int32_t bins;                /* ... with 150 bins: the range of plot_sinr_map (mobile_env.py:252)                                     */
+} UavEnvEvalAcc;
+int uavenv_eval_accumulate(uavenv_t *h, const UavEnvOut *out, const UavEnvEvalAcc *acc, void *stream);
 
 /* Sticky device-side error of a handle: *code = 0, or the word a kernel left when it gave up (0x48414e44 "HAND": a wavefront of a
  * one-launch schedule waited longer than the spin budget for the wavefront that runs the first steps of the same envs -- never seen

@@ -2,13 +2,19 @@
 """BASELINE config 1: the evaluation loop of the reference's main_test.py (:46-113) on the HIP path.
 
   python tools/run_eval.py --out test/run1 [--trace ue_trace_10k.npy] [--actor Global_A_PARA.npz] [--steps 2000]
+  python tools/run_eval.py --out test/run4k --envs 4096 [--traces cells.npy] [--actor ...] [--steps 2000]      (batched, below)
 
 * The reference's trace file ue_trace_10k.npy is not in the mount (.MISSING_LARGE_BLOBS); README.md:32 says it was
   produced by saving the group model's integer UE cells.  --make-trace does exactly that with this repo's env
   ((T, 40, 2) int16, T = 10001 by default).
 * Policy: greedy argmax of the actor (main_test.py:68,73), weights from save_actor_npz (a fresh N(0,0.1) net if none).
 * Saves the arrays main_test.py saves: reward, decomposed_reward, sinr, time, outage_fraction, ue_location,
-  bs_location, action, and sinr_area at steps 0, 500, ... (GetSinrInArea, :85-89)."""
+  bs_location, action, and sinr_area at steps 0, 500, ... (GetSinrInArea, :85-89).
+* --envs N: the same greedy loop for N envs at once, device-resident (evaluate.GreedyEvaluator).  UE cells from --traces (int16
+  [T+1, N, U, 2], or [T+1, U, 2] for every env; --trace works too), else every env's own group mobility.  Saves reward and action
+  [T, N], the per-env totals reward_sum / mean_sinr_sum / n_out_sum / steps / outage_fraction, the serving-SINR histogram sinr_hist
+  with hist_edges and sinr_nan (instead of every step's sinr), and sinr_area of env 0 at steps 0, 500, ... as above.  Without
+  --envs nothing changes: same files, same N = 1 loop."""
 import argparse
 import os
 import sys
@@ -74,6 +80,40 @@ def run_test(trace, out_dir, actor_npz=None, max_step=2000, n_bs=4, n_ue=40, gri
     return {k: np.array(v) for k, v in buf.items()}
 
 
+def run_batched(n_envs, out_dir, trace=None, actor_npz=None, steps=2000, n_bs=4, n_ue=40, grid=100, seed=0x5EED, area_every=500, net="mlp"):
+    """main_test.py's loop for n_envs envs on the device: GreedyEvaluator.run + the SINR map of env 0 every area_every steps."""
+    from drl_uav_cellularnet_amd import BatchedMobiEnv
+    from drl_uav_cellularnet_amd.agent import ACNet, load_actor_npz
+    from drl_uav_cellularnet_amd.evaluate import GreedyEvaluator
+
+    os.makedirs(out_dir, exist_ok=True)
+    env = BatchedMobiEnv(n_envs, nBS=n_bs, nUE=n_ue, grid_n=grid, seed=seed)
+    if net == "cnn":
+        from drl_uav_cellularnet_amd.cnn_agent import CnnACNet
+
+        net = CnnACNet(n_bs, grid, env.action_space_dim)
+    else:
+        net = ACNet(env.observation_space_dim, env.action_space_dim)
+    if actor_npz:
+        load_actor_npz(net, actor_npz)
+    ev = GreedyEvaluator(env, net)
+    areas = []
+
+    def after_step(t):
+        if t % area_every == 0 or t == steps - 1:
+            areas.append(env.sinr_area()[0].cpu().numpy())                               # main_test.py:85-89, env 0
+
+    res = ev.run(steps, trace=trace, after_step=after_step)
+    torch.cuda.synchronize()
+    out = {"reward": res["reward"], "action": res["actions"], "sinr_area": np.array(areas)}
+    for k in ("reward_sum", "mean_sinr_sum", "n_out_sum", "steps", "outage_fraction", "sinr_hist", "sinr_nan", "hist_edges"):
+        out[k] = res[k]
+    out = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k), v)
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="test/eval")
@@ -83,10 +123,21 @@ if __name__ == "__main__":
     ap.add_argument("--actor", default=None)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--net", choices=("mlp", "cnn"), default="mlp", help="the network the actor file was trained with")
+    ap.add_argument("--envs", type=int, default=None, help="evaluate this many envs at once on the device (GreedyEvaluator)")
+    ap.add_argument("--traces", default=None, help="with --envs: int16 cells [T+1, N, U, 2] or [T+1, U, 2] (.npy); default: group mobility")
     a = ap.parse_args()
     if a.make_trace:
         np.save(a.make_trace, make_trace(a.trace_rows))
         print("wrote", a.make_trace)
+        sys.exit(0)
+    if a.envs is not None:
+        src = a.traces or a.trace
+        tr = np.load(src, allow_pickle=False).astype(np.int16) if src else None
+        t0 = time.time()
+        res = run_batched(a.envs, a.out, tr, a.actor, a.steps, net=a.net)
+        dt = time.time() - t0
+        print("eval: %d envs x %d steps in %.1f s (%.3g env-steps/s incl. set-up), mean reward %.4f, mean outage fraction %.4f -> %s" % (
+            a.envs, a.steps, dt, a.envs * a.steps / dt, float(res["reward"].mean()), float(res["outage_fraction"].mean()), a.out))
         sys.exit(0)
     tr = np.load(a.trace, allow_pickle=False) if a.trace else make_trace(a.steps + 2)
     t0 = time.time()
