@@ -593,6 +593,16 @@ __device__ __forceinline__ FinConst fin_const(const KParams &p) {
     return k;
 }
 
+// The reward of a step from the slot's SINR sum and its newly outaged walkers (mobile_env.py:163-189): env_finish's value, and the
+// value of every candidate action in the one-step search (uavenv_search_kernel.h) -- one function, so the two cannot drift apart.
+__device__ __forceinline__ double step_reward(const FinConst &K, double sum_cur, int n_outage) {
+    const double r0 = sum_cur * K.inv_U20;                // mobile_env.py:165  mean / 20
+    const double r1 = -((double)n_outage * K.inv_U);      // mobile_env.py:167  -1.0 * nOut / nUE
+    double reward = (0.0 + r0) + r1;                      // sum(r_dissect)
+    if (-1.0 > reward) reward = -1.0;                     // max(.., -1)  mobile_env.py:189
+    return reward;
+}
+
 // Per-env scalars and outputs after a step / reset: reward (mobile_env.py:163-189), done (:186-187).
 // `rec` is the env's record as loaded at kernel entry: fields a mode does not own keep their value (the aggregation counters in
 // the trace modes, depth and step count during warm-up), and the whole record goes back with one 32-byte store.
@@ -619,10 +629,7 @@ __device__ __forceinline__ void env_finish(const FinConst &K, const OutPtrs &o, 
     if (is_step(MODE)) {
         rec.fifo_depth = depth < 3 ? depth + 1 : depth;
         const double mean = sum_cur * K.inv_U;                // channel.py:216 (np.mean; <= 1 ulp from sum/U)
-        const double r0 = sum_cur * K.inv_U20;                // mobile_env.py:165  mean / 20
-        const double r1 = -((double)n_outage * K.inv_U);      // mobile_env.py:167  -1.0 * nOut / nUE
-        double reward = (0.0 + r0) + r1;                      // sum(r_dissect)
-        if (-1.0 > reward) reward = -1.0;                     // max(.., -1)  mobile_env.py:189
+        const double reward = step_reward(K, sum_cur, n_outage);
         step_n += 1;                                          // mobile_env.py:181
         rec.step_n = step_n;
         if (OUTS && UAV_OUT(o.step_n)) stx(o.step_n, e, step_n);
@@ -825,12 +832,23 @@ __device__ __forceinline__ void many_retire_loads() {
 // read, BS_move is skipped), computed exactly as above and then DROPPED: no store to the state; the step's outputs go to whichever members of
 // `pout` are non-null (tested at run time even when FAST, which here only selects the arithmetic variant the real step would run), and
 // the SINR-gradient rule (side_rule) turns cur_sinr into the joint action of `lk`.  LOOK = false is the code as it was.
-template <int BT, int MODE, bool PLC, bool FAST, bool PIN, bool MANY, int HO = 0, bool LOOK = false>
+// SEARCH (uavenv_search_actions, env_kernel_search in uavenv_search_kernel.h; implies LOOK): the same look-ahead up to the tick's draws, then
+// search_body() in place of the channel update: the reward of EVERY joint action from that tick, the first maximum to `sr`.  Nothing else is stored.
+struct SearchArgs;
+struct SearchLds;
+template <int BT, bool PLC, bool FAST, bool PRE>
+__device__ void search_body(const KParams &p, const HotConst &H, const LeanCoef &C, const FinConst &K, const SearchArgs &sa, SearchLds &L, int U, int EPW,
+                            int lane, int slot, int base, int ul, bool live, bool head, long long ew, int e_lo, int e_hi, long long e, uint32_t tick, int u,
+                            long long iu, int ix, int iy, const int (&bsx)[BT], const int (&bsy)[BT], const U4 &q0, const U4 &q1, int serving,
+                            unsigned long long prev_out, unsigned long long slot_mask);
+template <int BT, int MODE, bool PLC, bool FAST, bool PIN, bool MANY, int HO = 0, bool LOOK = false, bool SEARCH = false>
 __device__ __forceinline__ void env_packed_body(char *blob, const long long *actions, const int8_t *gid_of_u, long long N, int U, int EPW,
                                                 int Gr, int B_rt, int lane_magic, const KParams &p, int (*s_bs)[kMaxEpw][2 * kMaxBs],
                                                 const int wave, const long long ew, const int t0, const int nt, const int e_lo, const int e_hi,
-                                                const OutPtrs *po = nullptr, const LookArgs *lk = nullptr, LookLds *ll = nullptr) {
+                                                const OutPtrs *po = nullptr, const LookArgs *lk = nullptr, LookLds *ll = nullptr,
+                                                const SearchArgs *sr = nullptr, SearchLds *sl = nullptr) {
     static_assert(!LOOK || (is_step(MODE) && !MANY && !PIN && HO == 0), "the look-ahead is one plain step");
+    static_assert(!SEARCH || (LOOK && BT <= 8), "the search is a look-ahead with every UAV cell in registers");
     constexpr bool LDC = (HO & 1) != 0, STC = (HO & 2) != 0, ACC = (HO & 4) != 0;
     const OutPtrs &pout = po != nullptr ? *po : p.out;
     const int lane = threadIdx.x & 63;
@@ -1017,6 +1035,11 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
         if (MODE == MODE_WARMUP) continue;                // warm-up: mobility only
         if (has_mobility(MODE)) { ix = (int)x; iy = (int)y; }                            // .astype(int), mobile_env.py:154-155
 
+        if constexpr (SEARCH) {   // every joint action's reward from this tick's cells and draws; the state is left as it was loaded
+            search_body<BT, PLC, FAST, FAST && has_mobility(MODE)>(p, H, C, K, *sr, *sl, U, EPW, lane, slot, base, ul, live, head, ew, e_lo, e_hi, e, tick - 1u,
+                                                                   u, iu, ix, iy, bsx, bsy, q0, q1, serving, prev_out, slot_mask);
+            return;
+        }
         // ---- channel update (one per reset / step; Philox time = the tick just executed) ------------------
         {
             double pg[BT];

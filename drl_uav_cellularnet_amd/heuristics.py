@@ -4,7 +4,10 @@ every env operation (deepcopy, step_test) goes through the HIP path.
 
 For a batch the controller itself is a HIP kernel (BatchedMobiEnv.gradient_actions / step_gradient); here are its NumPy statement of
 the rule (side_rule) and the same decision built from a twin handle and the ordinary step (gradient_actions_reference), which is what
-the kernel is tested and timed against and what serves the shapes the kernel refuses (n_ue > 64)."""
+the kernel is tested and timed against and what serves the shapes the kernel refuses (n_ue > 64).
+
+The one-step search policy (BatchedMobiEnv.search_actions / step_search: the best of all joint actions per env) has the same pair
+here: search_rule and search_actions_reference."""
 import warnings
 from copy import deepcopy
 
@@ -97,3 +100,38 @@ def gradient_actions_reference(env, twin, side_means=False):
     w = env.N_ACT ** torch.arange(env.nBS - 1, -1, -1, device=env.device, dtype=torch.int64)
     actions = (digit * w).sum(-1)
     return (actions, means) if side_means else actions
+
+
+def search_rule(rewards):
+    """The one-step search policy's choice from a table of action values: rewards [N, A] -> int64 [N], per row the FIRST maximum
+    (the lowest action among equal rewards).  A NaN never wins; a row of NaNs gives 0."""
+    r = np.asarray(rewards, np.float64)
+    return np.where(np.isnan(r), -np.inf, r).argmax(axis=1).astype(np.int64)           # np.argmax returns the first maximum
+
+
+def search_actions_reference(env, twin):
+    """The search of BatchedMobiEnv.search_actions from the pieces the env has always had: ``twin`` (a second BatchedMobiEnv of the
+    same shape, seed and env_id_base, e.g. ``env.clone()``, kept by the caller) takes a copy of the state before EACH of the
+    N_ACT ** nBS joint actions and steps with it for every env at once; the rewards (``reward_f64`` when the twin has float64
+    outputs, else the float32 ``reward``) fill the table.  ``env`` is not modified.  Any shape, n_ue > 64 included.  Returns
+    (actions int64 [N], table float64 [N, A]) on the device: the yardstick for tests and timing."""
+    import torch
+
+    A = env.N_ACT ** env.nBS
+    buf = getattr(twin, "_search_state_buf", None)
+    if buf is None:
+        buf = twin._search_state_buf = torch.empty(env._lay.total_bytes, dtype=torch.uint8, device=env.device)
+        twin._search_act = torch.empty((env.n_envs,), dtype=torch.int64, device=env.device)
+    env.copy_state_to(buf)
+    table = torch.empty((env.n_envs, A), dtype=torch.float64, device=env.device)
+    key = "reward_f64" if "reward_f64" in twin.out else "reward"
+    for a in range(A):
+        twin.copy_state_from(buf)
+        twin._search_act.fill_(a)
+        twin.step(twin._search_act)
+        table[:, a] = twin.out[key]
+    nan_low = torch.where(torch.isnan(table), torch.full_like(table, float("-inf")), table)
+    best = nan_low.max(dim=1, keepdim=True).values
+    idx = torch.arange(A, device=env.device).expand_as(table)
+    actions = torch.where(nan_low == best, idx, torch.full_like(idx, A)).min(dim=1).values      # the lowest index that holds the maximum
+    return actions, table

@@ -289,6 +289,27 @@ int uavenv_gradient_actions(uavenv_t *h, const int16_t *ue_xy_in_dev, const UavE
  * capturable in a hipGraph, no allocation.  Bit-identical to the two-call loop by definition: it is that loop. */
 int uavenv_step_gradient(uavenv_t *h, int n_steps, int64_t *actions_out_dev, const UavEnvOut *out, void *stream);
 
+/* The one-step search policy (what Choose_Act_Gradient did with itertools.product before the side-mean rule replaced it, gradient.py:8,14,17,36):
+ * for every env, the reward of EACH of the n_act^n_bs joint actions on the step the env is about to take, and the first maximum.  One launch
+ * that commits nothing: the mobility tick (or the trace cells) and the tick's fading draws do not depend on the action, and BS_move leaves a UAV
+ * on one of five cells, so a decision is one tick, one set of draws, 5 B received powers per UE and n_act^n_bs recombinations.
+ * rewards_dev[e, a] is the float64 reward uavenv_step with action a would return for env e from the present state (bit-identical to
+ * reward_f64 of that step on a copy of the handle; rounded to float32 it is that step's `reward`); actions_out_dev[e] is the FIRST maximum of
+ * row e (the lowest action among equal rewards; a NaN never wins), best_reward_dev[e] its reward.  The state and the handle's outputs are not
+ * modified.  Additive exports: the ABI version stays as it is.
+ * ue_xy_in_dev: NULL = group mobility (the next tick), else [N,U,2] trace cells.  checked: non-zero = the arithmetic variant of a step that
+ * asks for float64 outputs (injected draws select it too); 0 = the variant BatchedMobiEnv.step runs.
+ * actions_out_dev [N] int64 (required); best_reward_dev [N] float64 or NULL; rewards_dev [N, n_act^n_bs] float64 or NULL.
+ * UAVENV_E_INVALID with a message, before any HIP call: a null handle or actions_out_dev, a multi-pass handle (n_ue > 64), n_act != 5,
+ * 5^n_bs > 15625 (n_bs > 6). */
+int uavenv_search_actions(uavenv_t *h, const int16_t *ue_xy_in_dev, const UavEnvInject *inj, int checked,
+                          int64_t *actions_out_dev /*[N]*/, double *best_reward_dev /*[N] or NULL*/,
+                          double *rewards_dev /*[N, n_act^n_bs] or NULL*/, void *stream);
+/* n_steps x [uavenv_search_actions; uavenv_step with those actions] issued by ONE host call (group mobility, on-device randomness), like
+ * uavenv_step_gradient: actions_out_dev [n_steps, N]; `out` in uavenv_step_many's layout.  No synchronisation, no allocation.  The search runs
+ * the variant the step will run: checked iff `out` carries float64 members.  Refuses as uavenv_search_actions does, and a negative n_steps. */
+int uavenv_step_search(uavenv_t *h, int n_steps, int64_t *actions_out_dev /*[T,N]*/, const UavEnvOut *out, void *stream);
+
 /* The evaluation loop's bookkeeping (main_test.py:46-113 keeps reward, outage and current_BS_sinr of every step; for 4096 envs x 2001 steps x
  * 40 UEs the SINRs alone are 1.3 GB) as running totals on the device: ONE launch per step reads the step's outputs `out` (of the handle's
  * shapes: what uavenv_step / uavenv_step_trace just wrote) and ADDS into caller-owned accumulators, which the caller zeroes.  One lane per env
