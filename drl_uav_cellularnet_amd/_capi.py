@@ -54,6 +54,28 @@ class UavEnvEvalAcc(C.Structure):           # include/uavenv.h
         ("lo", C.c_double), ("inv_width", C.c_double), ("bins", C.c_int32)]
 
 
+RATE_MAX_MCS = 16
+RATE_OUT_FIELDS = (("dl_sinr_db", "f8"), ("dl_rate", "f8"), ("dl_mcs", "i1"), ("ul_avg_gain", "f8"), ("ul_interference", "f8"), ("ul_sinr_db", "f8"),
+                   ("ul_channels", "f8"), ("ul_rate", "f8"), ("ul_mcs", "i1"), ("dl_rate_serving", "f4"), ("ul_rate_serving", "f4"),
+                   ("dl_rate_mean", "f8"), ("ul_rate_mean", "f8"), ("dl_rate_mean_sum", "f8"), ("ul_rate_mean_sum", "f8"), ("rate_steps", "i4"),
+                   ("ul_draws_out", "f8"))   # members of UavEnvRates in order, with their element types
+
+
+class UavEnvRateConfig(C.Structure):        # include/uavenv.h
+    _fields_ = [("p_ue_dbm", C.c_double), ("ul_channels", C.c_double), ("ass_per_bs", C.c_double * MAX_BS),
+                ("n_samples", C.c_int32), ("n_mcs", C.c_int32), ("dth", C.c_double), ("ul_datarate", C.c_double),
+                ("sinr_thresholds_db", C.c_double * (RATE_MAX_MCS + 1)), ("sinr_thresholds_watt", C.c_double * (RATE_MAX_MCS + 1)),
+                ("rate_mbps", C.c_double * RATE_MAX_MCS)]
+
+
+class UavEnvRateInject(C.Structure):
+    _fields_ = [(n, _P) for n in ("fading_dev", "ul_draws_dev")]
+
+
+class UavEnvRates(C.Structure):
+    _fields_ = [(n + "_dev", _P) for n, _ in RATE_OUT_FIELDS]
+
+
 ABI_VERSION = 9   # UAVENV_ABI_VERSION of include/uavenv.h this binding is written against (tests/test_capi_load.py compares the three)
 STATE_FIELDS = ("ue_pos", "ue_aux", "grp", "env", "bs_xy", "out_bits")   # arrays of records, include/uavenv.h
 
@@ -63,7 +85,7 @@ class UavEnvStateLayout(C.Structure):
 
 
 EXPORTS = ("uavenv_abi_version", "uavenv_last_error", "uavenv_default_config", "uavenv_create", "uavenv_destroy",
-           "uavenv_init", "uavenv_warmup", "uavenv_reset", "uavenv_reset_trace", "uavenv_step", "uavenv_step_range", "uavenv_rollout_gated", "uavenv_gradient_actions", "uavenv_step_gradient", "uavenv_search_actions", "uavenv_step_search", "uavenv_eval_accumulate", "uavenv_step_many", "uavenv_step_seq", "uavenv_step_trace",
+           "uavenv_init", "uavenv_warmup", "uavenv_reset", "uavenv_reset_trace", "uavenv_step", "uavenv_step_range", "uavenv_rollout_gated", "uavenv_gradient_actions", "uavenv_step_gradient", "uavenv_search_actions", "uavenv_step_search", "uavenv_eval_accumulate", "uavenv_default_rate_config", "uavenv_link_rates", "uavenv_step_many", "uavenv_step_seq", "uavenv_step_trace",
            "uavenv_obs_dense", "uavenv_obs_dense_update", "uavenv_sinr_area", "uavenv_sinr_area_at",
            "uavenv_debug_variant_count", "uavenv_debug_variant_info", "uavenv_debug_variant_reset", "uavenv_debug_rotation_info", "uavenv_step_many_prepare", "uavenv_device_error", "uavenv_launch_timing", "uavenv_launch_times_us", "uavenv_debug_schedule",
            "uavenv_state_layout", "uavenv_get_state", "uavenv_set_state", "uavenv_philox4x32_10", "uavenv_lean_math_eval")
@@ -109,6 +131,8 @@ def load():
     lib.uavenv_search_actions.argtypes = [_P, _P, C.POINTER(UavEnvInject), C.c_int, _P, _P, _P, _P]
     lib.uavenv_step_search.argtypes = [_P, C.c_int, _P, C.POINTER(UavEnvOut), _P]
     lib.uavenv_eval_accumulate.argtypes = [_P, C.POINTER(UavEnvOut), C.POINTER(UavEnvEvalAcc), _P]
+    lib.uavenv_default_rate_config.argtypes = [C.POINTER(UavEnvRateConfig)]
+    lib.uavenv_link_rates.argtypes = [_P, C.POINTER(UavEnvRateConfig), C.POINTER(UavEnvRateInject), C.POINTER(UavEnvRates), _P]
     lib.uavenv_step_range.argtypes = [_P, _P, C.c_int64, C.c_int64, C.POINTER(UavEnvInject), C.POINTER(UavEnvOut), _P]
     lib.uavenv_step_many.argtypes = [_P, _P, C.c_int, C.POINTER(UavEnvOut), _P]
     lib.uavenv_step_seq.argtypes = [_P, _P, C.c_int, C.POINTER(UavEnvOut), _P]

@@ -547,6 +547,80 @@ class BatchedMobiEnv:
         if rc:
             _capi.check(rc)
 
+    # ---- link rates (channel.py:178-209, 272-385) ---------------------------------------------------
+    RATE_WANT = ("dl_sinr_db", "dl_rate", "dl_mcs", "ul_avg_gain", "ul_interference", "ul_sinr_db", "ul_channels", "ul_rate", "ul_mcs",
+                 "dl_rate_serving", "ul_rate_serving", "dl_rate_mean", "ul_rate_mean")
+    _RATE_DTYPES = {"f8": torch.float64, "f4": torch.float32, "i1": torch.int8, "i4": torch.int32}
+
+    def _rate_shape(self, name, n_samples):
+        N, U, B = self.n_envs, self.nUE, self.nBS
+        if name in ("ul_avg_gain",):
+            return (N, B, B)
+        if name == "ul_interference":
+            return (N, B)
+        if name in ("dl_rate_serving", "ul_rate_serving"):
+            return (N, U)
+        if name in ("dl_rate_mean", "ul_rate_mean", "dl_rate_mean_sum", "ul_rate_mean_sum", "rate_steps"):
+            return (N,)
+        if name == "ul_draws_out":
+            return (N, B * (B - 1) // 2, n_samples, 3)
+        return (N, U, B)
+
+    def rate_accumulators(self):
+        """Zeroed accumulators for ``link_rates(accumulate=...)``: ``dl_rate_mean_sum`` / ``ul_rate_mean_sum`` float64 [N] and
+        ``rate_steps`` int32 [N].  Every call adds its per-env means and 1; the caller divides (and zeroes them for a new run)."""
+        N, dev = self.n_envs, self.device
+        return {"dl_rate_mean_sum": torch.zeros(N, dtype=torch.float64, device=dev), "ul_rate_mean_sum": torch.zeros(N, dtype=torch.float64, device=dev),
+                "rate_steps": torch.zeros(N, dtype=torch.int32, device=dev)}
+
+    def link_rates(self, config=None, fading=None, ul_draws=None, want=RATE_WANT, accumulate=None, draws_out=False, out=None):
+        """The reference's link-rate model for the LATEST channel update of every env (uavenv_link_rates): downlink SINR -> MCS rate per
+        (UE, UAV), the Monte-Carlo uplink interference of every UAV pair (``config.n_samples`` imaginary users each), uplink SINR, channels
+        needed and rate, the values at the serving UAV and their per-env means.  The env is NOT modified: no state, none of ``self.out``;
+        two calls without a step in between return the same numbers.  ``config``: a ``UavEnvRateConfig`` (rates.default_rate_config());
+        ``fading`` [N, U, B]: the draws of that channel update, ``ul_draws`` [N, P, n, 3]: {theta_u, r_u, fading} per pair and sample
+        (parity mode; default: the on-device streams).  ``want``: names of UavEnvRates members to return; ``accumulate``: the dict of
+        rate_accumulators(), added to in place; ``draws_out``: also return ``ul_draws_out``, the uplink draws the kernel used.
+        ``out``: a dict returned by an earlier call with the same arguments, to be overwritten (no allocation: capturable).
+        Returns a dict of device tensors.  The reference's uplink interference sums the UAVs of a HIGHER index only (rates.py)."""
+        N, U, B = self.n_envs, self.nUE, self.nBS
+        n = 1000 if config is None else int(config.n_samples)
+        names = list(want) + (["ul_draws_out"] if draws_out else [])
+        specs = dict(_capi.RATE_OUT_FIELDS)
+        for k in names:
+            if k not in specs or k in ("dl_rate_mean_sum", "ul_rate_mean_sum", "rate_steps"):
+                raise ValueError("link_rates: unknown output %r" % (k,))
+        if out is None:
+            out = {k: torch.empty(self._rate_shape(k, n), dtype=self._RATE_DTYPES[specs[k]], device=self.device) for k in names}
+        elif set(out) != set(names) or any(tuple(out[k].shape) != self._rate_shape(k, n) or out[k].dtype != self._RATE_DTYPES[specs[k]]
+                                           or not out[k].is_contiguous() or out[k].device != self.device for k in names):
+            raise ValueError("out must be a dict returned by link_rates for the same arguments")
+        st = _capi.UavEnvRates()
+        for k in names:
+            setattr(st, k + "_dev", out[k].data_ptr())
+        if accumulate is not None:
+            for k in ("dl_rate_mean_sum", "ul_rate_mean_sum", "rate_steps"):
+                t = accumulate[k]
+                if tuple(t.shape) != (N,) or t.dtype != self._RATE_DTYPES[specs[k]] or not t.is_contiguous() or t.device != self.device:
+                    raise ValueError("accumulate must be the dict rate_accumulators() returned")
+                setattr(st, k + "_dev", t.data_ptr())
+        inj = None
+        if fading is not None or ul_draws is not None:
+            ri = _capi.UavEnvRateInject()
+            keep = []
+            if fading is not None:
+                keep.append(self._dev64(fading, (N, U, B)))
+                ri.fading_dev = keep[-1].data_ptr()
+            if ul_draws is not None:
+                keep.append(self._dev64(ul_draws, (N, B * (B - 1) // 2, n, 3)))
+                ri.ul_draws_dev = keep[-1].data_ptr()
+            self._rate_keep = keep      # stream-ordered use: keep alive until the next call
+            inj = C.byref(ri)
+        rc = self._lib.uavenv_link_rates(self._h, C.byref(config) if config is not None else None, inj, C.byref(st), self._stream())
+        if rc:
+            _capi.check(rc)
+        return out
+
     def step_trace(self, actions, ue_xy, fading=None):
         """MobiEnvironment.step_test with mobility_model == 'read_trace' (mobile_env.py:196-233)."""
         a = self._actions(actions)

@@ -15,7 +15,8 @@ namespace uavk {
 
 enum DrawSite : uint32_t {  // Philox counter word 3
     DOM_FADING = 1, DOM_HEADING = 2 /* quad mode (B > 8) only; otherwise headings come from the spare words of DOM_FADING calls */, DOM_GROUP_A = 3, DOM_GROUP_B = 4,
-    DOM_INIT_UE_A = 5, DOM_INIT_UE_B = 6, DOM_INIT_G_A = 7, DOM_INIT_G_B = 8, DOM_INIT_G_C = 9, DOM_AREA = 10
+    DOM_INIT_UE_A = 5, DOM_INIT_UE_B = 6, DOM_INIT_G_A = 7, DOM_INIT_G_B = 8, DOM_INIT_G_C = 9, DOM_AREA = 10,
+    DOM_UL_POS = 11, DOM_UL_FADE = 12   /* uavenv_link_rates: the imaginary uplink users of a UAV pair (layout: uavenv_kernels.h, next to the per-UE draw block) */
 };
 
 struct U4 { uint32_t x, y, z, w; };

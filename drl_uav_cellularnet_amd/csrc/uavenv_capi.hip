@@ -255,6 +255,11 @@ extern "C" int uavenv_create(const UavEnvConfig *cfg, int64_t n_envs, int device
         return bail(UAVENV_E_HIP, "hipMemcpy bs_init", e);
     if ((e = hipMemcpy(h->act_pow_dev, act_pow, sizeof(act_pow), hipMemcpyHostToDevice)) != hipSuccess) return bail(UAVENV_E_HIP, "hipMemcpy act_pow", e);
     if ((e = hipMemcpy(h->gid_dev, gid.data(), n_gid, hipMemcpyHostToDevice)) != hipSuccess) return bail(UAVENV_E_HIP, "hipMemcpy gid table", e);
+    if (cfg->n_ue <= 64 && cfg->n_bs <= 8) {   // uavenv_link_rates (uavenv_rates.hip) never allocates: its [N, B, B] pair means live here
+        const size_t bytes = (size_t)n_envs * B * B * sizeof(double);
+        if ((e = hipMalloc((void **)&h->ul_gain_dev, bytes)) != hipSuccess) return bail(UAVENV_E_NOMEM, "hipMalloc uplink pair means", e);
+        if ((e = hipMemset(h->ul_gain_dev, 0, bytes)) != hipSuccess) return bail(UAVENV_E_HIP, "hipMemset uplink pair means", e);
+    }
     {   // one-launch schedules (rotation_plan): one hand-off word per env-wavefront, and the sticky error word in host-mapped memory
         const size_t n_flag = (size_t)n_envs + 64;           // (>= env-wavefronts for any envs-per-wavefront)
         if ((e = hipMalloc((void **)&h->sched_flag_dev, n_flag * sizeof(uint32_t))) != hipSuccess) return bail(UAVENV_E_NOMEM, "hipMalloc hand-off words", e);
@@ -324,6 +329,7 @@ extern "C" void uavenv_destroy(uavenv_t *h) {
     if (h->obs_prev_dev) (void)hipFree(h->obs_prev_dev);
     if (h->tev) { for (hipEvent_t e : *h->tev) (void)hipEventDestroy(e); delete h->tev; }
     if (h->sched_flag_dev) (void)hipFree(h->sched_flag_dev);
+    if (h->ul_gain_dev) (void)hipFree(h->ul_gain_dev);
     if (h->err_host) (void)hipHostFree(h->err_host);
     if (h->rot_plans) {
         for (auto &pl : *h->rot_plans) (void)hipFree(pl.dev);

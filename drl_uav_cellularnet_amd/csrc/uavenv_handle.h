@@ -1,7 +1,7 @@
 // Internal to libuavenv (not installed): the handle and the helpers shared by its translation units (uavenv_capi.hip: everything but
 // the gated rollout and the gradient policy; uavenv_gated.hip: uavenv_rollout_gated and its kernel instantiations; uavenv_gradient.hip:
 // uavenv_gradient_actions / uavenv_step_gradient and the look-ahead kernels; uavenv_search.hip: uavenv_search_actions / uavenv_step_search
-// and the search kernels; uavenv_eval.hip: uavenv_eval_accumulate -- files of their own so that none rebuilds the others).
+// and the search kernels; uavenv_eval.hip: uavenv_eval_accumulate; uavenv_rates.hip: uavenv_link_rates and its kernels -- files of their own so that none rebuilds the others).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,6 +43,7 @@ struct uavenv {
     std::vector<hipEvent_t> *tev;
     int timing, n_timed;
     int force_pin;  // UAVENV_FORCE_PIN read ONCE at create (experiments: tools/pin_sweep.sh): -1 unset, 0 / 1 forced
+    double *ul_gain_dev;  // [N, B, B] pair means of uavenv_link_rates when the caller does not ask for them (n_ue <= 64 and n_bs <= 8 only, else null)
     UavEnvStateLayout lay;
     uavk::KParams kp;  // constants + state pointers, per-call fields patched at launch
 };

@@ -284,6 +284,13 @@ __device__ __forceinline__ void philox_u2(const KParams &p, uint32_t env, uint32
 //   call c of walker u:  q_c = Philox(ctr = (env, tick, u*QB + c, DOM_FADING)),  QB = ceil(B/4)
 //   UAVs 4c, 4c+1: radius uniform q_c.x * 2^-32, angle fraction q_c.y * 2^-32;   UAVs 4c+2, 4c+3: q_c.z and q_c.w
 //   heading uniform = u53(h.x, h.y),  h = Philox(ctr = (env, tick, u, DOM_HEADING)).
+// Link rates (uavenv_link_rates, uavenv_rates_kernel.h) read this block again one update later -- the state's tick is then one past the
+// Philox time of its latest channel update, so they call with tick - 1 -- and add the imaginary uplink users of UAV pair p (pairs in
+// the reference's call order: bs ascending, then intf > bs), sample s of n = n_samples:
+//   position:  q = Philox(ctr = (env, tick - 1, p*n + s, DOM_UL_POS));   theta_u = u53(q.x, q.y),  r_u = u53(q.z, q.w)
+//   shadowing: q = Philox(ctr = (env, tick - 1, p*n + (s >> 7)*64 + (s & 63), DOM_UL_FADE)), the Box-Muller form above (radius uniform
+//              u53(q.x, q.y), angle fraction q.z * 2^-32): samples with bit 6 of s clear take the cosine branch, the others the sine branch
+//              -- s and s + 64 are consecutive samples of ONE lane (lane l sums samples l, l + 64, ...), so one call serves both.
 __host__ __device__ constexpr bool quad_draws(int B) { return B > 8; }
 __device__ __forceinline__ U4 philox_raw(const KParams &p, uint32_t env, uint32_t tick, uint32_t idx, uint32_t dom) {
     return philox4x32_10(p.env_id_base + env, tick, idx, dom, p.key0, p.key1);

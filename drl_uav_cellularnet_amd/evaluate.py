@@ -134,14 +134,16 @@ class GreedyEvaluator:
         return t[:n_steps + 1].to(self.dev).contiguous()
 
     @torch.no_grad()
-    def run(self, n_steps, trace=None, keep=("reward", "actions"), after_step=None):
+    def run(self, n_steps, trace=None, keep=("reward", "actions"), after_step=None, rates=False):
         """``n_steps`` greedy steps of every env.  Group mobility (``trace`` None): from the env's current state.  Trace mode: row 0 of
         ``trace`` goes to reset_trace and row t + 1 to step t, the indexing main_test.py ends up with.  The accumulators are zeroed
         first.  Returns a dict: ``actions`` int64 [T, N] / ``reward`` float32 [T, N] when named in ``keep`` (overwritten by the next run
         of the same length), the accumulator tensors (reward_sum, mean_sinr_sum, n_out_sum, steps, sinr_hist, sinr_nan),
         ``outage_fraction`` = n_out_sum / (steps * nUE) float64 [N] and ``hist_edges`` float64 [bins + 1].  Asynchronous.
         ``after_step(t)``: an optional host callback behind step t's launches (tools/run_eval.py takes its SINR maps there); what it
-        synchronises or allocates is its own affair."""
+        synchronises or allocates is its own affair.  ``rates``: one link_rates call per step into rate accumulators; the result gains
+        ``dl_rate_mean`` / ``ul_rate_mean`` float64 [N], the per-env mean serving rates (Mb/s per channel) averaged over the steps.
+        Without it the loop issues exactly the launches it always did."""
         env, T, N = self.env, int(n_steps), self.env.n_envs
         keep = tuple(keep)
         if set(keep) - {"reward", "actions"}:
@@ -162,6 +164,13 @@ class GreedyEvaluator:
         self._refresh_weights()
         self.acc.zero_()
         reward = env.out["reward"]
+        racc = None
+        if rates:
+            if getattr(self, "_racc", None) is None:
+                self._racc = env.rate_accumulators()
+            racc = self._racc
+            for v in racc.values():
+                v.zero_()
         # ---- the loop: no synchronisation, no allocation ----
         for t in range(T):
             a = act_buf[t]
@@ -173,6 +182,8 @@ class GreedyEvaluator:
             if keep_r:
                 rew_buf[t].copy_(reward)
             env.eval_accumulate(self.acc)
+            if racc is not None:
+                env.link_rates(want=(), accumulate=racc)
             if after_step is not None:
                 after_step(t)
         res = dict(self.acc.tensors())
@@ -182,4 +193,8 @@ class GreedyEvaluator:
             res["reward"] = rew_buf
         res["outage_fraction"] = self.acc.n_out_sum.to(torch.float64) / (self.acc.steps.to(torch.float64) * env.nUE)
         res["hist_edges"] = torch.as_tensor(self.acc.hist_edges())
+        if racc is not None:
+            steps = racc["rate_steps"].to(torch.float64)
+            res["dl_rate_mean"] = racc["dl_rate_mean_sum"] / steps
+            res["ul_rate_mean"] = racc["ul_rate_mean_sum"] / steps
         return res

@@ -330,6 +330,64 @@ typedef struct UavEnvEvalAcc {
 } UavEnvEvalAcc;
 int uavenv_eval_accumulate(uavenv_t *h, const UavEnvOut *out, const UavEnvEvalAcc *acc, void *stream);
 
+/* The link-rate model of LTEChannel (channel.py:178-209, 272-385) for the LATEST CHANNEL UPDATE of every env -- the reset, step or trace
+ * step the state comes from: UE cells, UAV cells and serving UAVs are read from the state, the shadowing draws of that update are rebuilt
+ * from their Philox counters (env, tick - 1, index, fading site) or injected.  Downlink: the SINR of every (UE, UAV) pair in the checked
+ * float64 arithmetic of the step, mapped to an MCS rate per channel (GetDLRatePerChannel).  Uplink: per UAV pair (bs, intf > bs) the mean
+ * channel gain at `bs` of n_samples imaginary users spread around `intf` (GetAverageULChannelGainFromInterfBS), the interference power
+ * per UAV (GetULInterference), then per (UE, UAV) the uplink SINR, the channels needed for ul_datarate and the rate (GetULRateChannels).
+ * The reference fills only the upper triangle of the average-gain matrix (channel.py:317-329: the symmetric copy is never reached), so
+ * UAV b is interfered by the UAVs of a HIGHER index only and the last UAV by nobody: restated as it is, ul_interference[N, B-1] == 0.
+ * Additive exports: the ABI version stays as it is.  Neither the state nor the handle's outputs are modified; no allocation, capturable;
+ * two calls without a step in between return the same numbers (the draws are a function of the state's tick). */
+#define UAVENV_RATE_MAX_MCS 16
+typedef struct UavEnvRateConfig {
+    double p_ue_dbm;                                  /* 23                      channel.py:34               */
+    double ul_channels;                               /* (1 - 0.5) * 120 = 60    channel.py:72               */
+    double ass_per_bs[UAVENV_MAX_BS];                 /* 1: users already associated with each UAV   :79     */
+    int32_t n_samples;                                /* 1000 imaginary users per UAV pair           :75     */
+    int32_t n_mcs;                                    /* 16 MCS levels                                       */
+    double dth;                                       /* 100: radius of their disc, in cells         :77     */
+    double ul_datarate;                               /* 1: requested uplink rate                    :186    */
+    double sinr_thresholds_db[UAVENV_RATE_MAX_MCS + 1];    /* -inf, -6.5 ... 17.6, +inf  (n_mcs + 1 used)   :65   */
+    double sinr_thresholds_watt[UAVENV_RATE_MAX_MCS + 1];  /* pow(10, s / 10.)                              :66   */
+    double rate_mbps[UAVENV_RATE_MAX_MCS];                 /* (12 * 14 / 1e-3) * efficiency * 1e-6 (n_mcs used) :67-68 */
+} UavEnvRateConfig;
+int uavenv_default_rate_config(UavEnvRateConfig *cfg);
+
+/* Injected draws (parity mode); a NULL struct or member selects the on-device streams. */
+typedef struct UavEnvRateInject {
+    const double *fading_dev;     /* [N,U,B]      the N(mean, sd) draws of the channel update whose rates are asked for (UavEnvInject::fading_dev of it) */
+    const double *ul_draws_dev;   /* [N,P,n,3]    P = B (B - 1) / 2 pairs in the reference's call order (bs ascending, then intf > bs), n = n_samples;
+                                   *              per sample { theta_u, r_u, fading }: unit uniforms (theta = 2 pi theta_u, r = dth r_u) and an N(mean, sd) draw */
+} UavEnvRateInject;
+
+/* Outputs, all optional (NULL = skipped), at least one set.  -1 in an MCS index = no level matched (or a NaN SINR): the downlink rate is then 0
+ * as in the reference's zero-initialised array; in the uplink the reference raises on min([]), here channels and rate are NaN. */
+typedef struct UavEnvRates {
+    double *dl_sinr_db_dev;        /* [N,U,B]  GetDLSinrAllDb                                  channel.py:259-269 */
+    double *dl_rate_dev;           /* [N,U,B]  GetDLRatePerChannel, Mb/s                       :272-280           */
+    int8_t *dl_mcs_dev;            /* [N,U,B]  the matched level l: thr[l] <= sinr < thr[l+1]                    */
+    double *ul_avg_gain_dev;       /* [N,B,B]  GetAverageULChannelGain: [bs][intf > bs], 0 elsewhere   :317-329   */
+    double *ul_interference_dev;   /* [N,B]    GetULInterference, W                            :331-339           */
+    double *ul_sinr_db_dev;        /* [N,U,B]  GetULRateChannels: 10 log10(sinr_ratio)         :366-368           */
+    double *ul_channels_dev;       /* [N,U,B]  channels needed = min(match)                    :376-381           */
+    double *ul_rate_dev;           /* [N,U,B]  ul_datarate / min(match)                        :382               */
+    int8_t *ul_mcs_dev;            /* [N,U,B]  the level whose ul_datarate / rate is min(match)                   */
+    float *dl_rate_serving_dev;    /* [N,U]    dl_rate at the serving UAV (after the handover) :202-205           */
+    float *ul_rate_serving_dev;    /* [N,U]    ul_rate at the serving UAV                      :206               */
+    double *dl_rate_mean_dev;      /* [N]      mean over the UEs, summed in UE order           :208               */
+    double *ul_rate_mean_dev;      /* [N]                                                      :209               */
+    double *dl_rate_mean_sum_dev;  /* [N]      += dl_rate_mean   accumulators: one lane per env adds, so a total is the plain sum over the    */
+    double *ul_rate_mean_sum_dev;  /* [N]      += ul_rate_mean   calls in issue order (no float atomics); the caller zeroes them              */
+    int32_t *rate_steps_dev;       /* [N]      += 1                                                               */
+    double *ul_draws_out_dev;      /* [N,P,n,3] test hook: the uplink draws the kernel used, in UavEnvRateInject's layout */
+} UavEnvRates;
+/* rate_cfg NULL = uavenv_default_rate_config.  UAVENV_E_INVALID with a message, before any HIP call: a null handle or `out`, no output set,
+ * n_ue > 64 or n_bs > 8 (the draw layout of the packed kernels), n_samples outside [1, 65536], n_mcs outside [1, 16], thresholds that are
+ * not ascending, a non-positive ul_channels or dth. */
+int uavenv_link_rates(uavenv_t *h, const UavEnvRateConfig *rate_cfg, const UavEnvRateInject *inj, const UavEnvRates *out, void *stream);
+
 /* Sticky device-side error of a handle: *code = 0, or the word a kernel left when it gave up (0x48414e44 "HAND": a wavefront of a
  * one-launch schedule waited longer than the spin budget for the wavefront that runs the first steps of the same envs -- never seen
  * outside the test hook, but a bounded wait is what turns a scheduling bug into an error code instead of a hung GPU).  The word lives

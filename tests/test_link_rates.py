@@ -1,0 +1,147 @@
+"""CPU: the link-rate model (channel.py:178-209, 272-385) -- the library's default constants against the reference's lists, the NumPy
+restatement (rates.link_rates_reference) against every output the reference produced (tests/golden/ref_rates_4x40_g100_seed11.npz),
+the upper-triangle behaviour of the uplink interference, and the argument checks of uavenv_link_rates, which answer before any HIP call.
+
+The two refusals that read the handle (n_ue > 64, n_bs > 8) need a handle, and a handle needs a device: tests/test_link_rates_gpu.py holds them.
+"""
+import ctypes
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+if GOLDEN not in sys.path:
+    sys.path.insert(0, GOLDEN)
+
+REL64 = 1e-9          # the project's float64 bound; a mean of 1000 positive terms moves by ~1000 * 2^-53 = 1.1e-13 between summation orders
+FLOAT_KEYS = ("gain", "dl_sinr_db", "dl_rate", "ul_avg_gain", "ul_interference", "ul_sinr_db", "ul_channels", "ul_rate", "dl_rate_mean", "ul_rate_mean")
+
+
+@pytest.fixture(scope="module")
+def fx():
+    with np.load(os.path.join(GOLDEN, "ref_rates_4x40_g100_seed11.npz"), allow_pickle=False) as z:
+        return {k: z[k] for k in z.files}
+
+
+@pytest.fixture(scope="module")
+def reference_outputs(fx):
+    """link_rates_reference on the four recorded steps with the regenerated draws: computed once, shared, left unchanged."""
+    from make_golden_rates import regenerate_rate_draws
+
+    from drl_uav_cellularnet_amd import _capi
+    from drl_uav_cellularnet_amd.rates import link_rates_reference
+
+    cfg = _capi.make_config(int(fx["n_bs"]), int(fx["n_ue"]), int(fx["grid"]))
+    fading, ul = regenerate_rate_draws(fx)
+    return [link_rates_reference(cfg, None, fx["ue_loc"][s], fx["bs_loc"][s], fx["serving"][s], fading[s], ul[s]) for s in range(fading.shape[0])]
+
+
+def test_default_rate_config_carries_the_reference_lists_bit_for_bit(fx):
+    from drl_uav_cellularnet_amd.rates import default_rate_config
+
+    rc = default_rate_config()
+    assert (rc.n_samples, rc.n_mcs) == (int(fx["n_samples"]), 16) == (1000, 16)
+    assert (rc.p_ue_dbm, rc.ul_channels, rc.dth, rc.ul_datarate) == (float(fx["p_ue_dbm"]), float(fx["ul_channels_init"]), float(fx["dth"]), 1.0) == (23.0, 60.0, 100.0, 1.0)
+    assert list(rc.ass_per_bs) == [1.0] * 32 and np.array_equal(fx["ass_per_bs"], np.ones(4))
+    for name, key in (("sinr_thresholds_db", "sinr_thresholds"), ("sinr_thresholds_watt", "sinr_thresholds_watt"), ("rate_mbps", "rate_thresholds")):
+        got = np.array(list(getattr(rc, name)), dtype=np.float64)
+        assert got.tobytes() == np.asarray(fx[key], dtype=np.float64).tobytes(), name
+    assert rc.sinr_thresholds_watt[0] == 0.0 and rc.sinr_thresholds_watt[16] == np.inf
+
+
+def test_reference_restatement_reproduces_every_fixture_output(fx, reference_outputs):
+    assert len(reference_outputs) == fx["action"].shape[0] == 4
+    for s, got in enumerate(reference_outputs):
+        for k in FLOAT_KEYS:
+            np.testing.assert_allclose(got[k], fx[k][s], rtol=REL64, atol=0, err_msg="%s step %d" % (k, s))
+        for k in ("dl_rate_serving", "ul_rate_serving"):
+            assert np.array_equal(got[k], fx[k][s].astype(np.float32)), (k, s)
+        # the MCS indices are not recorded by the reference; its rates name them: exact
+        rates = fx["rate_thresholds"]
+        assert np.array_equal(rates[got["dl_mcs"]], fx["dl_rate"][s]) and got["dl_mcs"].min() >= 0
+        assert np.array_equal(1.0 / rates[got["ul_mcs"]], fx["ul_channels"][s]) and got["ul_mcs"].min() >= 0
+        assert np.array_equal(got["dl_rate"], fx["dl_rate"][s]) and np.array_equal(got["ul_channels"], fx["ul_channels"][s])
+        assert np.array_equal(got["ul_rate"], fx["ul_rate"][s])
+
+
+def test_uplink_interference_is_the_upper_triangle_only(fx, reference_outputs):
+    B = int(fx["n_bs"])
+    for s, got in enumerate(reference_outputs):
+        for src in (got, {k: fx[k][s] for k in ("ul_avg_gain", "ul_interference")}):
+            assert src["ul_interference"][B - 1] == 0.0                       # the last UAV is interfered by nobody
+            assert np.all(np.tril(src["ul_avg_gain"]) == 0.0) and np.all(src["ul_avg_gain"][np.triu_indices(B, 1)] > 0.0)
+            assert np.all(src["ul_interference"][:B - 1] > 0.0)
+
+
+def test_regenerated_draws_have_the_documented_shape_and_ranges(fx):
+    from make_golden_rates import regenerate_rate_draws
+
+    fading, ul = regenerate_rate_draws(fx)
+    assert fading.shape == (4, 40, 4) and ul.shape == (4, 6, 1000, 3)
+    assert ul[..., :2].min() >= 0.0 and ul[..., :2].max() < 1.0                # unit uniforms
+    assert abs(ul[..., 2].std() - 2.0) < 0.05 and abs(fading.std() - 2.0) < 0.2
+
+
+def test_entry_points_are_declared_and_exported():
+    from drl_uav_cellularnet_amd import _capi
+
+    header = open(os.path.join(ROOT, "include", "uavenv.h")).read()
+    assert re.search(r"\bint uavenv_link_rates\(uavenv_t \*h, const UavEnvRateConfig \*rate_cfg, const UavEnvRateInject \*inj, const UavEnvRates \*out,", header)
+    assert re.search(r"\bint uavenv_default_rate_config\(UavEnvRateConfig \*cfg\)", header)
+    assert "uavenv_link_rates" in _capi.EXPORTS and "uavenv_default_rate_config" in _capi.EXPORTS
+    assert int(re.search(r"#define UAVENV_ABI_VERSION (\d+)", header).group(1)) == _capi.ABI_VERSION == 9      # additive: the version stays
+    lib = _capi.load()
+    assert hasattr(lib, "uavenv_link_rates") and hasattr(lib, "uavenv_default_rate_config")
+    # the binding's structs are the header's: members in order
+    body = re.search(r"typedef struct UavEnvRates \{(.*?)\} UavEnvRates;", header, re.S).group(1)
+    assert re.findall(r"\*(\w+)_dev;", body) == [n for n, _ in _capi.RATE_OUT_FIELDS]
+    body = re.search(r"typedef struct UavEnvRateConfig \{(.*?)\} UavEnvRateConfig;", header, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    assert re.findall(r"\b(\w+)(?:\[[^\]]*\])?\s*[;,]", body) == [n for n, _ in _capi.UavEnvRateConfig._fields_]
+    assert ctypes.sizeof(_capi.UavEnvRateConfig) == 8 * (2 + 32 + 1 + 2 + 17 + 17 + 16)
+
+
+def test_link_rates_checks_arguments_before_any_hip_call():
+    from drl_uav_cellularnet_amd import _capi
+    from drl_uav_cellularnet_amd.rates import default_rate_config
+
+    lib = _capi.load()
+    one = ctypes.c_void_p(16)                               # a non-null dummy handle: never dereferenced on these paths
+    out = _capi.UavEnvRates()
+    out.dl_rate_dev = 16
+
+    def refused(rc, *words):
+        assert lib.uavenv_link_rates(one, ctypes.byref(rc) if rc is not None else None, None, ctypes.byref(out), None) == -1
+        msg = lib.uavenv_last_error()
+        assert b"link_rates" in msg and all(w in msg for w in words), msg
+
+    assert lib.uavenv_link_rates(None, None, None, ctypes.byref(out), None) == -1
+    assert b"link_rates" in lib.uavenv_last_error() and b"null" in lib.uavenv_last_error()
+    assert lib.uavenv_link_rates(one, None, None, None, None) == -1
+    assert b"link_rates" in lib.uavenv_last_error() and b"null" in lib.uavenv_last_error()
+    assert lib.uavenv_default_rate_config(None) == -1 and b"default_rate_config" in lib.uavenv_last_error()
+    for n in (0, -1, 65537):
+        rc = default_rate_config(); rc.n_samples = n
+        refused(rc, b"n_samples", b"65536")
+    for m in (0, 17, -3):
+        rc = default_rate_config(); rc.n_mcs = m
+        refused(rc, b"n_mcs", b"16")
+    rc = default_rate_config(); rc.sinr_thresholds_db[5] = rc.sinr_thresholds_db[4]
+    refused(rc, b"ascending")
+    rc = default_rate_config(); rc.sinr_thresholds_watt[9] = rc.sinr_thresholds_watt[7]
+    refused(rc, b"ascending")
+    rc = default_rate_config(); rc.sinr_thresholds_db[3] = float("nan")
+    refused(rc, b"ascending")
+    for v in (0.0, -60.0, float("nan")):
+        rc = default_rate_config(); rc.ul_channels = v
+        refused(rc, b"ul_channels", b"positive")
+        rc = default_rate_config(); rc.dth = v
+        refused(rc, b"dth", b"positive")
+    # an `out` whose members are all null names no output: refused before the handle is read
+    empty = _capi.UavEnvRates()
+    assert lib.uavenv_link_rates(one, None, None, ctypes.byref(empty), None) == -1
+    assert b"no output" in lib.uavenv_last_error()

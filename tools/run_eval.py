@@ -14,7 +14,9 @@
   [T+1, N, U, 2], or [T+1, U, 2] for every env; --trace works too), else every env's own group mobility.  Saves reward and action
   [T, N], the per-env totals reward_sum / mean_sinr_sum / n_out_sum / steps / outage_fraction, the serving-SINR histogram sinr_hist
   with hist_edges and sinr_nan (instead of every step's sinr), and sinr_area of env 0 at steps 0, 500, ... as above.  Without
-  --envs nothing changes: same files, same N = 1 loop."""
+  --envs nothing changes: same files, same N = 1 loop.
+* --rates (with --envs): one link-rate report per step (BatchedMobiEnv.link_rates); also writes dl_rate.npy / ul_rate.npy, the per-env
+  mean serving rates in Mb/s per channel averaged over the steps.  Without the flag the files are what they were."""
 import argparse
 import os
 import sys
@@ -80,7 +82,7 @@ def run_test(trace, out_dir, actor_npz=None, max_step=2000, n_bs=4, n_ue=40, gri
     return {k: np.array(v) for k, v in buf.items()}
 
 
-def run_batched(n_envs, out_dir, trace=None, actor_npz=None, steps=2000, n_bs=4, n_ue=40, grid=100, seed=0x5EED, area_every=500, net="mlp"):
+def run_batched(n_envs, out_dir, trace=None, actor_npz=None, steps=2000, n_bs=4, n_ue=40, grid=100, seed=0x5EED, area_every=500, net="mlp", rates=False):
     """main_test.py's loop for n_envs envs on the device: GreedyEvaluator.run + the SINR map of env 0 every area_every steps."""
     from drl_uav_cellularnet_amd import BatchedMobiEnv
     from drl_uav_cellularnet_amd.agent import ACNet, load_actor_npz
@@ -103,11 +105,13 @@ def run_batched(n_envs, out_dir, trace=None, actor_npz=None, steps=2000, n_bs=4,
         if t % area_every == 0 or t == steps - 1:
             areas.append(env.sinr_area()[0].cpu().numpy())                               # main_test.py:85-89, env 0
 
-    res = ev.run(steps, trace=trace, after_step=after_step)
+    res = ev.run(steps, trace=trace, after_step=after_step, rates=rates)
     torch.cuda.synchronize()
     out = {"reward": res["reward"], "action": res["actions"], "sinr_area": np.array(areas)}
     for k in ("reward_sum", "mean_sinr_sum", "n_out_sum", "steps", "outage_fraction", "sinr_hist", "sinr_nan", "hist_edges"):
         out[k] = res[k]
+    if rates:
+        out["dl_rate"], out["ul_rate"] = res["dl_rate_mean"], res["ul_rate_mean"]
     out = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
     for k, v in out.items():
         np.save(os.path.join(out_dir, k), v)
@@ -125,6 +129,7 @@ if __name__ == "__main__":
     ap.add_argument("--net", choices=("mlp", "cnn"), default="mlp", help="the network the actor file was trained with")
     ap.add_argument("--envs", type=int, default=None, help="evaluate this many envs at once on the device (GreedyEvaluator)")
     ap.add_argument("--traces", default=None, help="with --envs: int16 cells [T+1, N, U, 2] or [T+1, U, 2] (.npy); default: group mobility")
+    ap.add_argument("--rates", action="store_true", help="with --envs: also report the link rates (dl_rate.npy / ul_rate.npy)")
     a = ap.parse_args()
     if a.make_trace:
         np.save(a.make_trace, make_trace(a.trace_rows))
@@ -134,7 +139,7 @@ if __name__ == "__main__":
         src = a.traces or a.trace
         tr = np.load(src, allow_pickle=False).astype(np.int16) if src else None
         t0 = time.time()
-        res = run_batched(a.envs, a.out, tr, a.actor, a.steps, net=a.net)
+        res = run_batched(a.envs, a.out, tr, a.actor, a.steps, net=a.net, rates=a.rates)
         dt = time.time() - t0
         print("eval: %d envs x %d steps in %.1f s (%.3g env-steps/s incl. set-up), mean reward %.4f, mean outage fraction %.4f -> %s" % (
             a.envs, a.steps, dt, a.envs * a.steps / dt, float(res["reward"].mean()), float(res["outage_fraction"].mean()), a.out))
