@@ -479,16 +479,19 @@ static int launch_env(uavenv_t *h, const KParams &p_in, hipStream_t s, long long
     // only when the env launch drains (rocprofv3 timeline, profiles/r04g_*): ranges run unpinned (90 VGPRs).
     if (n_range > 0) pin = false;
     if (h->force_pin >= 0) pin = fast && (h->force_pin == 1);   // experiments only (read once in uavenv_create)
+    // Multi-step launches: env_kernel_packed<..., MANY> takes the per-env SINR sum in two levels and exists for U a multiple of 4 up to 32
+    // (slot_sum_in_quads); every other U runs env_kernel_many_rounds, the same step loop with slot_sum's six rounds.  One census slot for both.
+    using pk_kernel_t = void (*)(char *, const long long *, const int8_t *, long long, int, int, int, int, int, int, int, int, const KParams);
+    const bool rounds = MANY && !uavk::slot_sum_in_quads(p.U);
+#define UAVENV_PK_KERNEL(BT_, PLC_, FAST_, PIN_, SCH_)                                                           \
+    (rounds ? (pk_kernel_t)env_kernel_many_rounds<BT_, PLC_, FAST_, PIN_, SCH_> : (pk_kernel_t)env_kernel_packed<BT_, M, PLC_, FAST_, PIN_, MANY, SCH_>)
 #define UAVENV_LAUNCH_PKS(BT_, PLC_, SCH_)                                                                       \
     do {                                                                                                         \
-        if (MANY && tev0 != nullptr) {   /* (multi-step launches with uavenv_launch_timing on: events on the dispatch itself) */ \
-            if (pin) hipExtLaunchKernelGGL((env_kernel_packed<BT_, M, PLC_, true, true, MANY, SCH_>), dim3(grid), blk, 0, s, tev0, tev1, 0, PK_ARGS);     \
-            else if (fast) hipExtLaunchKernelGGL((env_kernel_packed<BT_, M, PLC_, true, false, MANY, SCH_>), dim3(grid), blk, 0, s, tev0, tev1, 0, PK_ARGS); \
-            else hipExtLaunchKernelGGL((env_kernel_packed<BT_, M, PLC_, false, false, MANY, SCH_>), dim3(grid), blk, 0, s, tev0, tev1, 0, PK_ARGS);       \
-        } else                                                                                                   \
-        if (pin) hipLaunchKernelGGL((env_kernel_packed<BT_, M, PLC_, true, true, MANY, SCH_>), dim3(grid), blk, 0, s, PK_ARGS);     \
-        else if (fast) hipLaunchKernelGGL((env_kernel_packed<BT_, M, PLC_, true, false, MANY, SCH_>), dim3(grid), blk, 0, s, PK_ARGS); \
-        else hipLaunchKernelGGL((env_kernel_packed<BT_, M, PLC_, false, false, MANY, SCH_>), dim3(grid), blk, 0, s, PK_ARGS);       \
+        const pk_kernel_t kern = pin ? UAVENV_PK_KERNEL(BT_, PLC_, true, true, SCH_)                             \
+                                     : (fast ? UAVENV_PK_KERNEL(BT_, PLC_, true, false, SCH_) : UAVENV_PK_KERNEL(BT_, PLC_, false, false, SCH_)); \
+        /* (multi-step launches with uavenv_launch_timing on: events on the dispatch itself) */                  \
+        if (MANY && tev0 != nullptr) hipExtLaunchKernelGGL(kern, dim3(grid), blk, 0, s, tev0, tev1, 0, PK_ARGS); \
+        else hipLaunchKernelGGL(kern, dim3(grid), blk, 0, s, PK_ARGS);                                           \
         counted = census_count(FAM_PACKED, BT_, M, PLC_, pin ? VAR_PIN : (fast ? VAR_FAST : VAR_CHECKED), MANY_ + ((SCH_) ? 1 : 0)); \
     } while (0)
 #define UAVENV_LAUNCH_PK(BT_, PLC_)                                                                              \
@@ -525,6 +528,7 @@ static int launch_env(uavenv_t *h, const KParams &p_in, hipStream_t s, long long
 #undef UAVENV_LAUNCH
 #undef UAVENV_LAUNCH_PK
 #undef UAVENV_LAUNCH_PKS
+#undef UAVENV_PK_KERNEL
 #undef PK_ARGS
     HIP_TRY(hipGetLastError());
     if (!counted) return fail(UAVENV_E_INVALID, "launch census: no kernel launched, or an instantiation outside variant_selectable()");

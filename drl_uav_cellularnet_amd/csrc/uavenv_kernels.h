@@ -267,6 +267,45 @@ __device__ __forceinline__ double slot_sum(double v, int ul, int U) {
     return v;
 }
 
+// The same sum in two levels, for the multi-step kernels (a wavefront alone on its SIMD pays every one of slot_sum's six dependent
+// ds_bpermute round trips in full: DESIGN.md section 4d).  U a multiple of 4 and <= 32: slot bases are multiples of 4, so a quad of
+// lanes never straddles two slots, and the head lane's result of slot_sum is, bit for bit (tests/test_slot_sum_tree.py),
+//   Q_j = (v[4j] + v[4j+1]) + (v[4j+2] + v[4j+3])                                   -- rounds 1 and 2: two DPP quad_perm moves, no LDS
+//   c_j = Q_j + Q_{j+1} if j+1 < nq else Q_j;  d_j = c_j + c_{j+2} if j+2 < nq else c_j;  d_0 + d_4 if 4 < nq else d_0   (nq = U / 4)
+// with Q_1 .. Q_7 fetched by independent ds_bpermutes: ONE round trip (slot_quads), whose wait the caller may put after work that does
+// not need the sum (slot_quads_sum).  No guards: an absent quad (j >= nq) is fetched from a lane that holds -0.0, and every
+// addition is made.  -0.0 is the identity of IEEE addition in round-to-nearest for EVERY x (x + -0.0 = x, also for x = -0.0 and
+// x = +0.0; float64 denormals are not flushed), and -0.0 + -0.0 = -0.0, so an all-absent subtree is absent for its parent in turn.
+// (+0.0 would not do: -0.0 + +0.0 = +0.0 changes a partial sum of -0.0.)
+__host__ __device__ constexpr bool slot_sum_in_quads(int U) { return (U & 3) == 0 && U <= 32; }
+constexpr int kMaxQuads = 8;
+template <int CTRL>   // quad_perm [a,b,c,d] = a | b << 2 | c << 4 | d << 6.  (A 64-bit VALU op takes no quad_perm itself: two v_mov_b32)
+__device__ __forceinline__ double quad_perm_f64(double v) {
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
+    return __hiloint2double(hi, lo);
+}
+// All 64 lanes active; U a multiple of 4, 4 <= U <= 32.  q[0] = this lane's quad sum (Q_0 in the slot's first lane), q[j] = Q_j of the
+// lane's slot, or -0.0, for 1 <= j < 8: in flight when this returns.
+__device__ __forceinline__ void slot_quads(double v, int base, int ul, int U, double (&q)[kMaxQuads]) {
+    v += quad_perm_f64<0xF5>(v);   // [1,1,3,3]
+    v += quad_perm_f64<0xEE>(v);   // [2,3,2,3]
+    q[0] = v;
+    const double s = (ul & 3) ? -0.0 : v;          // lanes 4j: Q_j; the other lanes' sums are of no use: they hold the identity
+    const int lo = __double2loint(s), hi = __double2hiint(s);
+    int b4 = base << 2, last = 4 * U - 12;         // byte addresses (lane * 4): the slot's first lane; lane U - 3 of the slot, an identity
+    asm volatile("" : "+v"(b4), "+s"(last));       // (computed here, in the step: hoisted out of the step loop the seven addresses cost
+                                                   //  seven registers for the whole kernel)
+#pragma unroll
+    for (int j = 1; j < kMaxQuads; ++j) {
+        const int a = b4 + min(16 * j, last);      // lane base + 4j (present: 4j <= U - 4) or base + U - 3 (absent: 4j >= U)
+        q[j] = __hiloint2double(__builtin_amdgcn_ds_bpermute(a, hi), __builtin_amdgcn_ds_bpermute(a, lo));
+    }
+}
+__device__ __forceinline__ double slot_quads_sum(const double (&q)[kMaxQuads]) {   // valid in the slot's first lane
+    return ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
+}
+
 __device__ __forceinline__ void philox_u2(const KParams &p, uint32_t env, uint32_t tick, uint32_t idx, uint32_t dom,
                                           double &u0, double &u1) {
     const U4 r = philox4x32_10(p.env_id_base + env, tick, idx, dom, p.key0, p.key1);
@@ -848,7 +887,7 @@ __device__ void search_body(const KParams &p, const HotConst &H, const LeanCoef 
                             int lane, int slot, int base, int ul, bool live, bool head, long long ew, int e_lo, int e_hi, long long e, uint32_t tick, int u,
                             long long iu, int ix, int iy, const int (&bsx)[BT], const int (&bsy)[BT], const U4 &q0, const U4 &q1, int serving,
                             unsigned long long prev_out, unsigned long long slot_mask);
-template <int BT, int MODE, bool PLC, bool FAST, bool PIN, bool MANY, int HO = 0, bool LOOK = false, bool SEARCH = false>
+template <int BT, int MODE, bool PLC, bool FAST, bool PIN, bool MANY, int HO = 0, bool LOOK = false, bool SEARCH = false, bool QSUM = false>
 __device__ __forceinline__ void env_packed_body(char *blob, const long long *actions, const int8_t *gid_of_u, long long N, int U, int EPW,
                                                 int Gr, int B_rt, int lane_magic, const KParams &p, int (*s_bs)[kMaxEpw][2 * kMaxBs],
                                                 const int wave, const long long ew, const int t0, const int nt, const int e_lo, const int e_hi,
@@ -856,6 +895,7 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
                                                 const SearchArgs *sr = nullptr, SearchLds *sl = nullptr) {
     static_assert(!LOOK || (is_step(MODE) && !MANY && !PIN && HO == 0), "the look-ahead is one plain step");
     static_assert(!SEARCH || (LOOK && BT <= 8), "the search is a look-ahead with every UAV cell in registers");
+    static_assert(!QSUM || MANY, "the two-level per-env sum is the multi-step kernels'");
     constexpr bool LDC = (HO & 1) != 0, STC = (HO & 2) != 0, ACC = (HO & 4) != 0;
     const OutPtrs &pout = po != nullptr ? *po : p.out;
     const int lane = threadIdx.x & 63;
@@ -952,6 +992,11 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
     // storing its outputs, with walker / group / UAV state carried in registers.
     U4 q0 = {0u, 0u, 0u, 0u}, q1 = {0u, 0u, 0u, 0u};   // this walker's Philox calls 0 / 1 of the last tick (heading + fading)
     double sum_cur = 0.0, cur = 0.0;
+    // QSUM (MANY, slot_sum_in_quads(U)): the per-env sum in two levels.  Pinned (a wavefront alone on its SIMD, or two): the gathers go out
+    // before the step's output stores and the sum is taken after them; unpinned (three wavefronts share a SIMD: the others cover the trip):
+    // taken at once, the gathered quads held across the stores would cost the registers of the third wavefront.
+    constexpr bool QLATE = QSUM && PIN;
+    double sq[kMaxQuads];
     int n_outage = 0;
     unsigned long long ob = 0ull;
     OutPtrs om = p.out;                                // MANY: the current step's output blocks (dead code otherwise)
@@ -1066,7 +1111,8 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
             }
             ob = (__ballot(live && (cur <= H.out_thr)) & slot_mask) >> base;               // :116 / :170
             if (!is_reset(MODE)) n_outage = __popcll(ob & ~prev_out);                      // :171-174 newly outaged
-            sum_cur = slot_sum(live ? cur : 0.0, ul, U);
+            if (QSUM) { slot_quads(live ? cur : 0.0, base, ul, U, sq); if (!QLATE) sum_cur = slot_quads_sum(sq); }
+            else sum_cur = slot_sum(live ? cur : 0.0, ul, U);
         }
         if (MANY) {
             // ---- this step's outputs (block `it` of every output array), then the hand-over to the next step ------------
@@ -1087,6 +1133,7 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
                     }
                 }
             } else if (bown) { if (UAV_OUT(om.bs_xy)) { stx(om.bs_xy, 2u * ib32, bx); stx(om.bs_xy, 2u * ib32 + 1u, by); } }
+            if (QLATE) sum_cur = slot_quads_sum(sq);
             if (it + 1 < n_ticks) {
                 if (head) env_finish<MODE, FAST, false>(K, om, st, e32, erec, tick, agg, deagg, depth, step_n, sum_cur, n_outage);
                 out_next_step<FAST>(om, N, U, B);
@@ -1183,10 +1230,14 @@ __device__ __forceinline__ bool sched_hand_off_wait(const KParams &p, int ew) {
 // SCHED (MANY only): the launch runs a rotation schedule (p.sched).  A kernel of its own, not a branch of the plain multi-step kernel: with
 // the schedule's three body copies inside it the plain unpinned kernel went from 167 to 169-180 VGPRs, i.e. from three to two wavefronts
 // per SIMD, and a 65 536-env call from 46.7 to 52.5 us per step (same-box A/B against the round-3 tree, profiles/r04s_*).
-template <int BT, int MODE, bool PLC, bool FAST, bool PIN, bool MANY = false, bool SCHED = false>
-__global__ __launch_bounds__(64 * kWavesPerBlock) void env_kernel_packed(char *blob, const long long *actions,
-                                                                              const int8_t *gid_of_u, long long N, int U, int EPW,
-                                                                              int Gr, int B_rt, int lane_magic, int wave0, int e_lo, int e_hi, const KParams p) {
+// QSUM (MANY only): the per-env SINR sum in two levels (slot_quads): the launcher guarantees slot_sum_in_quads(U).  A kernel of its own for
+// the same reason: with both sums behind a wave-uniform branch in one step loop, each form's loop-invariant lane masks and addresses stay
+// live through the whole kernel (160 -> 173 VGPRs unpinned, 237 -> 241 pinned); compiled alone the two-level form needs fewer than the six
+// rounds did (156 / 229).  env_kernel_packed<..., MANY = true> is the two-level kernel, env_kernel_many_rounds the one for every other U.
+// (`p` by value, as the kernels take it: through a reference the single-step reset kernel compiled to one instruction less than before.)
+template <int BT, int MODE, bool PLC, bool FAST, bool PIN, bool MANY, bool SCHED, bool QSUM>
+__device__ __forceinline__ void env_packed_entry(char *blob, const long long *actions, const int8_t *gid_of_u, long long N, int U, int EPW,
+                                                 int Gr, int B_rt, int lane_magic, int wave0, int e_lo, int e_hi, const KParams p) {
     static_assert(!MANY || MODE == MODE_STEP, "multi-step launches exist for MobiEnvironment.step only");
     static_assert(!SCHED || MANY, "rotation schedules exist for multi-step launches only");
     // Leading scalars arrive in SGPRs at wave launch (hipcc -mllvm -amdgpu-kernarg-preload-count=16), so the global
@@ -1205,7 +1256,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void env_kernel_packed(char *b
         // (Inlined copies of the body rather than a rolled loop around one: with the rolled loop hipcc allocated 330 VGPRs for the
         // pinned kernel instead of 233 -- one wavefront per SIMD -- and doubled its SGPR spills.)
         if (!SCHED) {
-            env_packed_body<BT, MODE, PLC, FAST, PIN, MANY>(blob, actions, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, p, s_bs, wave, gw, 0, p.n_ticks, e_lo, e_hi);
+            env_packed_body<BT, MODE, PLC, FAST, PIN, MANY, 0, false, false, QSUM>(blob, actions, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, p, s_bs, wave, gw, 0, p.n_ticks,
+                                                                                   e_lo, e_hi);
             return;
         }
         const int4 *sched = p.sched;
@@ -1223,8 +1275,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void env_kernel_packed(char *b
             if (nt <= 0) return true;
             if (Q > 0) __builtin_amdgcn_wave_barrier();                       // (the previous piece's reads of the LDS row are done)
             if (Q == 2) { if (!sched_hand_off_wait(p, ew)) return false; }
-            env_packed_body<BT, MODE, PLC, FAST, PIN, MANY, (Q == 0 ? 2 : (Q == 2 ? 1 : 0))>(blob, actions, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, p, s_bs,
-                                                                                                  wave, ew, t0, nt, e_lo, e_hi);
+            env_packed_body<BT, MODE, PLC, FAST, PIN, MANY, (Q == 0 ? 2 : (Q == 2 ? 1 : 0)), false, false, QSUM>(blob, actions, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic,
+                                                                                                                      p, s_bs, wave, ew, t0, nt, e_lo, e_hi);
             if (Q == 0 && (bits & SCHED_PUBLISH)) sched_hand_off_publish(p, ew);
             return true;
         };
@@ -1232,6 +1284,19 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void env_kernel_packed(char *b
         if (!piece(std::integral_constant<int, 1>{})) return;
         if (!piece(std::integral_constant<int, 2>{})) return;
     }
+}
+template <int BT, int MODE, bool PLC, bool FAST, bool PIN, bool MANY = false, bool SCHED = false>
+__global__ __launch_bounds__(64 * kWavesPerBlock) void env_kernel_packed(char *blob, const long long *actions,
+                                                                              const int8_t *gid_of_u, long long N, int U, int EPW,
+                                                                              int Gr, int B_rt, int lane_magic, int wave0, int e_lo, int e_hi, const KParams p) {
+    env_packed_entry<BT, MODE, PLC, FAST, PIN, MANY, SCHED, MANY>(blob, actions, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, wave0, e_lo, e_hi, p);
+}
+// The multi-step kernels for a U that is no multiple of 4, or above 32: slot_sum's six rounds, as in the single-step kernels.
+template <int BT, bool PLC, bool FAST, bool PIN, bool SCHED>
+__global__ __launch_bounds__(64 * kWavesPerBlock) void env_kernel_many_rounds(char *blob, const long long *actions,
+                                                                                   const int8_t *gid_of_u, long long N, int U, int EPW,
+                                                                                   int Gr, int B_rt, int lane_magic, int wave0, int e_lo, int e_hi, const KParams p) {
+    env_packed_entry<BT, MODE_STEP, PLC, FAST, PIN, true, SCHED, false>(blob, actions, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, wave0, e_lo, e_hi, p);
 }
 
 // ================================================================================================
