@@ -85,7 +85,7 @@ class UavEnvStateLayout(C.Structure):
 
 
 EXPORTS = ("uavenv_abi_version", "uavenv_last_error", "uavenv_default_config", "uavenv_create", "uavenv_destroy",
-           "uavenv_init", "uavenv_warmup", "uavenv_reset", "uavenv_reset_trace", "uavenv_step", "uavenv_step_range", "uavenv_rollout_gated", "uavenv_gradient_actions", "uavenv_step_gradient", "uavenv_search_actions", "uavenv_step_search", "uavenv_eval_accumulate", "uavenv_default_rate_config", "uavenv_link_rates", "uavenv_step_many", "uavenv_step_seq", "uavenv_step_trace",
+           "uavenv_init", "uavenv_warmup", "uavenv_reset", "uavenv_reset_trace", "uavenv_step", "uavenv_step_range", "uavenv_rollout_gated", "uavenv_gradient_actions", "uavenv_step_gradient", "uavenv_search_actions", "uavenv_step_search", "uavenv_coordinate_actions", "uavenv_step_coordinate", "uavenv_eval_accumulate", "uavenv_default_rate_config", "uavenv_link_rates", "uavenv_step_many", "uavenv_step_seq", "uavenv_step_trace",
            "uavenv_obs_dense", "uavenv_obs_dense_update", "uavenv_sinr_area", "uavenv_sinr_area_at",
            "uavenv_debug_variant_count", "uavenv_debug_variant_info", "uavenv_debug_variant_reset", "uavenv_debug_rotation_info", "uavenv_step_many_prepare", "uavenv_device_error", "uavenv_launch_timing", "uavenv_launch_times_us", "uavenv_debug_schedule",
            "uavenv_state_layout", "uavenv_get_state", "uavenv_set_state", "uavenv_philox4x32_10", "uavenv_lean_math_eval")
@@ -130,6 +130,8 @@ def load():
     lib.uavenv_step_gradient.argtypes = [_P, C.c_int, _P, C.POINTER(UavEnvOut), _P]
     lib.uavenv_search_actions.argtypes = [_P, _P, C.POINTER(UavEnvInject), C.c_int, _P, _P, _P, _P]
     lib.uavenv_step_search.argtypes = [_P, C.c_int, _P, C.POINTER(UavEnvOut), _P]
+    lib.uavenv_coordinate_actions.argtypes = [_P, _P, C.POINTER(UavEnvInject), C.c_int, _P, _P, _P, _P]
+    lib.uavenv_step_coordinate.argtypes = [_P, C.c_int, _P, C.POINTER(UavEnvOut), _P]
     lib.uavenv_eval_accumulate.argtypes = [_P, C.POINTER(UavEnvOut), C.POINTER(UavEnvEvalAcc), _P]
     lib.uavenv_default_rate_config.argtypes = [C.POINTER(UavEnvRateConfig)]
     lib.uavenv_link_rates.argtypes = [_P, C.POINTER(UavEnvRateConfig), C.POINTER(UavEnvRateInject), C.POINTER(UavEnvRates), _P]

@@ -533,6 +533,61 @@ class BatchedMobiEnv:
                 v.copy_(out[k][T - 1])
         return actions_out, out
 
+    # ---- the per-UAV coordinate-search policy: each UAV's best cell in turn, 4 nBS + 1 step values per decision ----
+    def coordinate_actions(self, ue_xy=None, theta_u=None, group_u=None, fading=None, best_reward=False, rewards=False):
+        """Coordinate ascent over the UAVs of every env, in UAV order, on the step the env is about to take, in one launch
+        (uavenv_coordinate_actions): UAV 0 takes the best of its five cells with everybody else staying, UAV 1 its best given UAV
+        0's choice, and so on.  The env is NOT modified: no state, none of ``self.out``.  ``ue_xy`` [N, U, 2]: the trace cells of the
+        step (read_trace), else the next mobility tick.  The arithmetic is that of this env's own step (checked when the env has
+        float64 outputs or draws are injected, else fast).  Serves every shape up to 16 UAVs x 256 UEs (n_ue <= 64: nBS <= 8).
+        Returns int64 [N] joint actions; with ``best_reward`` also float64 [N], bit for bit the ``reward_f64`` step(actions) returns
+        and never below the reward of all UAVs staying; with ``rewards`` also the float64 [N, nBS, 5] table: ``table[e, i, d]`` is the
+        reward of UAV i taking digit d given the digits chosen before it (heuristics.coordinate_rule states the choice)."""
+        N, U = self.n_envs, self.nUE
+        xptr = None
+        if ue_xy is not None:
+            x = torch.as_tensor(ue_xy).to(device=self.device, dtype=torch.int16).contiguous()
+            if x.numel() != N * U * 2:
+                raise ValueError("ue_xy must be [N, U, 2]")
+            self._trace_keep = x
+            xptr = x.data_ptr()
+        inj = self._inject(theta_u, group_u, fading)
+        checked = 1 if ("reward_f64" in self.out or inj is not None) else 0
+        acts = torch.empty(N, dtype=torch.int64, device=self.device)
+        best = torch.empty(N, dtype=torch.float64, device=self.device) if best_reward else None
+        table = torch.empty((N, self.nBS, self.N_ACT), dtype=torch.float64, device=self.device) if rewards else None
+        rc = self._lib.uavenv_coordinate_actions(self._h, xptr, inj, checked, acts.data_ptr(), best.data_ptr() if best_reward else None,
+                                                 table.data_ptr() if rewards else None, self._stream())
+        if rc:
+            _capi.check(rc)
+        res = (acts,) + ((best,) if best_reward else ()) + ((table,) if rewards else ())
+        return res[0] if len(res) == 1 else res
+
+    def step_coordinate(self, n_steps, out=None, actions_out=None):
+        """``n_steps`` x [coordinate_actions(); step(those actions)] issued by one C call (uavenv_step_coordinate; group mobility,
+        on-device randomness).  Returns (actions int64 [T, N], dict of [T, ...] tensors as step_many returns); ``self.out`` holds the
+        last step's results.  ``out`` / ``actions_out``: the results of an earlier call with the same T, to be overwritten (no
+        allocation).  Bit-identical to the loop of the two calls."""
+        T = int(n_steps)
+        if actions_out is None:
+            actions_out = torch.empty((T, self.n_envs), dtype=torch.int64, device=self.device)
+        elif not (actions_out.dtype == torch.int64 and tuple(actions_out.shape) == (T, self.n_envs) and actions_out.is_contiguous()
+                  and actions_out.device == self.device):
+            raise ValueError("actions_out must be a contiguous int64 [T, n_envs] tensor on the env's device")
+        if out is None:
+            out = {k: torch.empty((T,) + tuple(v.shape), dtype=v.dtype, device=self.device) for k, v in self.out.items()}
+        elif set(out) != set(self.out) or any(out[k].shape != (T,) + tuple(v.shape) or not out[k].is_contiguous()
+                                              for k, v in self.out.items()):
+            raise ValueError("out must be a dict returned by step_coordinate / step_many for the same number of steps")
+        st = self.out_struct_for(out)
+        rc = self._lib.uavenv_step_coordinate(self._h, T, actions_out.data_ptr(), C.byref(st), self._stream())
+        if rc:
+            _capi.check(rc)
+        if T > 0:
+            for k, v in self.out.items():
+                v.copy_(out[k][T - 1])
+        return actions_out, out
+
     # ---- evaluation totals (main_test.py:46-113 for a whole batch) ------------------------------------
     def eval_accumulators(self, hist=(-50.0, 100.0, 150)):
         """Zeroed accumulators for eval_accumulate(): ``hist`` = (lo, hi, bins) of the serving-SINR histogram in dB (default: the

@@ -1,7 +1,7 @@
 // Internal to libuavenv (not installed): the handle and the helpers shared by its translation units (uavenv_capi.hip: everything but
 // the gated rollout and the gradient policy; uavenv_gated.hip: uavenv_rollout_gated and its kernel instantiations; uavenv_gradient.hip:
 // uavenv_gradient_actions / uavenv_step_gradient and the look-ahead kernels; uavenv_search.hip: uavenv_search_actions / uavenv_step_search
-// and the search kernels; uavenv_eval.hip: uavenv_eval_accumulate; uavenv_rates.hip: uavenv_link_rates and its kernels -- files of their own so that none rebuilds the others).
+// and the search kernels; uavenv_coordinate.hip: uavenv_coordinate_actions / uavenv_step_coordinate and their kernels; uavenv_eval.hip: uavenv_eval_accumulate; uavenv_rates.hip: uavenv_link_rates and its kernels -- files of their own so that none rebuilds the others).
 #pragma once
 #include <hip/hip_runtime.h>
 

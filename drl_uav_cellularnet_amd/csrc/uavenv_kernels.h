@@ -880,22 +880,30 @@ __device__ __forceinline__ void many_retire_loads() {
 // the SINR-gradient rule (side_rule) turns cur_sinr into the joint action of `lk`.  LOOK = false is the code as it was.
 // SEARCH (uavenv_search_actions, env_kernel_search in uavenv_search_kernel.h; implies LOOK): the same look-ahead up to the tick's draws, then
 // search_body() in place of the channel update: the reward of EVERY joint action from that tick, the first maximum to `sr`.  Nothing else is stored.
+// COORD (uavenv_coordinate_actions, env_kernel_coordinate_packed in uavenv_coordinate_kernel.h; implies SEARCH): the same look-ahead, then
+// coordinate_body() in place of search_body(): B rounds of one UAV's four moves instead of every joint action.
 struct SearchArgs;
 struct SearchLds;
+struct CoordArgs;
+template <int BT, bool PLC, bool FAST, bool PRE>
+__device__ void coordinate_body(const KParams &p, const HotConst &H, const LeanCoef &C, const FinConst &K, const CoordArgs &ca, int U, int base, int ul, bool live,
+                                bool head, long long e, uint32_t tick, int u, long long iu, int ix, int iy, const int (&bsx)[BT], const int (&bsy)[BT],
+                                const U4 &q0, const U4 &q1, int serving, unsigned long long prev_out, unsigned long long slot_mask);
 template <int BT, bool PLC, bool FAST, bool PRE>
 __device__ void search_body(const KParams &p, const HotConst &H, const LeanCoef &C, const FinConst &K, const SearchArgs &sa, SearchLds &L, int U, int EPW,
                             int lane, int slot, int base, int ul, bool live, bool head, long long ew, int e_lo, int e_hi, long long e, uint32_t tick, int u,
                             long long iu, int ix, int iy, const int (&bsx)[BT], const int (&bsy)[BT], const U4 &q0, const U4 &q1, int serving,
                             unsigned long long prev_out, unsigned long long slot_mask);
-template <int BT, int MODE, bool PLC, bool FAST, bool PIN, bool MANY, int HO = 0, bool LOOK = false, bool SEARCH = false, bool QSUM = false>
+template <int BT, int MODE, bool PLC, bool FAST, bool PIN, bool MANY, int HO = 0, bool LOOK = false, bool SEARCH = false, bool QSUM = false, bool COORD = false>
 __device__ __forceinline__ void env_packed_body(char *blob, const long long *actions, const int8_t *gid_of_u, long long N, int U, int EPW,
                                                 int Gr, int B_rt, int lane_magic, const KParams &p, int (*s_bs)[kMaxEpw][2 * kMaxBs],
                                                 const int wave, const long long ew, const int t0, const int nt, const int e_lo, const int e_hi,
                                                 const OutPtrs *po = nullptr, const LookArgs *lk = nullptr, LookLds *ll = nullptr,
-                                                const SearchArgs *sr = nullptr, SearchLds *sl = nullptr) {
+                                                const SearchArgs *sr = nullptr, SearchLds *sl = nullptr, const CoordArgs *cr = nullptr) {
     static_assert(!LOOK || (is_step(MODE) && !MANY && !PIN && HO == 0), "the look-ahead is one plain step");
     static_assert(!SEARCH || (LOOK && BT <= 8), "the search is a look-ahead with every UAV cell in registers");
     static_assert(!QSUM || MANY, "the two-level per-env sum is the multi-step kernels'");
+    static_assert(!COORD || SEARCH, "the coordinate policy takes the search's look-ahead");
     constexpr bool LDC = (HO & 1) != 0, STC = (HO & 2) != 0, ACC = (HO & 4) != 0;
     const OutPtrs &pout = po != nullptr ? *po : p.out;
     const int lane = threadIdx.x & 63;
@@ -1087,7 +1095,11 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
         if (MODE == MODE_WARMUP) continue;                // warm-up: mobility only
         if (has_mobility(MODE)) { ix = (int)x; iy = (int)y; }                            // .astype(int), mobile_env.py:154-155
 
-        if constexpr (SEARCH) {   // every joint action's reward from this tick's cells and draws; the state is left as it was loaded
+        if constexpr (COORD) {    // B rounds of one UAV's four moves from this tick's cells and draws; the state is left as it was loaded
+            coordinate_body<BT, PLC, FAST, FAST && has_mobility(MODE)>(p, H, C, K, *cr, U, base, ul, live, head, e, tick - 1u, u, iu, ix, iy, bsx, bsy, q0, q1,
+                                                                       serving, prev_out, slot_mask);
+            return;
+        } else if constexpr (SEARCH) {   // every joint action's reward from this tick's cells and draws; the state is left as it was loaded
             search_body<BT, PLC, FAST, FAST && has_mobility(MODE)>(p, H, C, K, *sr, *sl, U, EPW, lane, slot, base, ul, live, head, ew, e_lo, e_hi, e, tick - 1u,
                                                                    u, iu, ix, iy, bsx, bsy, q0, q1, serving, prev_out, slot_mask);
             return;

@@ -7,7 +7,8 @@ the rule (side_rule) and the same decision built from a twin handle and the ordi
 the kernel is tested and timed against and what serves the shapes the kernel refuses (n_ue > 64).
 
 The one-step search policy (BatchedMobiEnv.search_actions / step_search: the best of all joint actions per env) has the same pair
-here: search_rule and search_actions_reference."""
+here: search_rule and search_actions_reference; so has the per-UAV coordinate-search policy (coordinate_actions / step_coordinate:
+each UAV's best cell in turn): coordinate_rule and coordinate_actions_reference."""
 import warnings
 from copy import deepcopy
 
@@ -135,3 +136,57 @@ def search_actions_reference(env, twin):
     idx = torch.arange(A, device=env.device).expand_as(table)
     actions = torch.where(nan_low == best, idx, torch.full_like(idx, A)).min(dim=1).values      # the lowest index that holds the maximum
     return actions, table
+
+
+def coordinate_rule(rewards, n_act=5):
+    """The coordinate-search policy's choice from a table whose rows are already conditional on the earlier choices: rewards
+    [N, B, n_act] -> (digits int64 [N, B], joint actions int64 [N]).  Per row the first maximum in the order stay (digit n_act - 1),
+    0, 1, ..: a UAV moves only for a strictly higher reward than staying, the lowest digit wins among equal moves, a NaN never
+    wins and a row of NaNs gives stay.  Joint action = sum digit_b n_act^(B-1-b), UAV 0 the most significant digit."""
+    r = np.asarray(rewards, np.float64)
+    N, B, A = r.shape
+    order = np.array([A - 1] + list(range(A - 1)))
+    v = np.where(np.isnan(r), -np.inf, r)[:, :, order]
+    digits = order[v.argmax(axis=2)].astype(np.int64)                                   # np.argmax returns the first maximum
+    w = np.array([n_act ** (B - 1 - b) for b in range(B)], dtype=object)                # exact beyond 2^53 as well
+    actions = np.array([int((row.astype(object) * w).sum()) for row in digits], dtype=np.int64).reshape(N)
+    return digits, actions
+
+
+def coordinate_actions_reference(env, twin):
+    """The search of BatchedMobiEnv.coordinate_actions from the pieces the env has always had: ``twin`` (a second BatchedMobiEnv of
+    the same shape, seed and env_id_base, e.g. ``env.clone()``, kept by the caller) takes a copy of the state before each of the
+    4 nBS + 1 joint actions -- per env (c_0 .. c_{i-1}, d, 4 .. 4) -- and steps with it; the rewards (``reward_f64`` when the twin
+    has float64 outputs, else the float32 ``reward``) fill the table.  ``env`` is not modified.  Any shape.  Returns (actions int64
+    [N], table float64 [N, B, 5], best reward float64 [N]) on the device: the yardstick for tests and timing."""
+    import torch
+
+    B, A, N = env.nBS, env.N_ACT, env.n_envs
+    stay_d = A - 1
+    buf = getattr(twin, "_coord_state_buf", None)
+    if buf is None:
+        buf = twin._coord_state_buf = torch.empty(env._lay.total_bytes, dtype=torch.uint8, device=env.device)
+    env.copy_state_to(buf)
+    key = "reward_f64" if "reward_f64" in twin.out else "reward"
+    w = A ** torch.arange(B - 1, -1, -1, device=env.device, dtype=torch.int64)
+    digits = torch.full((N, B), stay_d, dtype=torch.int64, device=env.device)
+    table = torch.empty((N, B, A), dtype=torch.float64, device=env.device)
+
+    def value(dg):
+        twin.copy_state_from(buf)
+        twin.step((dg * w).sum(-1))
+        return twin.out[key].double().clone()
+
+    best = value(digits)                                                                # every UAV staying
+    for i in range(B):
+        table[:, i, stay_d] = best
+        choice = torch.full((N,), stay_d, dtype=torch.int64, device=env.device)
+        for d in range(A - 1):
+            digits[:, i] = d
+            r = value(digits)
+            table[:, i, d] = r
+            win = (r > best) | (torch.isnan(best) & ~torch.isnan(r))                    # strict: stay, then the lowest digit, wins a tie
+            best = torch.where(win, r, best)
+            choice = torch.where(win, torch.full_like(choice, d), choice)
+        digits[:, i] = choice
+    return (digits * w).sum(-1), table, best

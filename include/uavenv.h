@@ -310,6 +310,30 @@ int uavenv_search_actions(uavenv_t *h, const int16_t *ue_xy_in_dev, const UavEnv
  * the variant the step will run: checked iff `out` carries float64 members.  Refuses as uavenv_search_actions does, and a negative n_steps. */
 int uavenv_step_search(uavenv_t *h, int n_steps, int64_t *actions_out_dev /*[T,N]*/, const UavEnvOut *out, void *stream);
 
+/* The per-UAV coordinate-search policy: coordinate ascent over the UAVs of every env, in UAV order, on the step the env is about to take.  UAV 0
+ * takes the best of its five cells (stay, +-bs_step in x or y) with everybody else staying, UAV 1 its best given UAV 0's choice, and so on:
+ * 4 n_bs + 1 step values per decision instead of the search's 5^n_bs, so 16 UAVs are within reach.  One launch that commits nothing.
+ * With c_0 .. c_{i-1} the digits already chosen and stay = digit 4, rewards[e, i, d] is the float64 reward uavenv_step would return from the present
+ * state for the joint action (c_0, .., c_{i-1}, d, 4, .., 4), UAV 0 the most significant digit -- bit for bit its reward_f64, and rounded to float32
+ * its reward: BS_move takes the UAVs in index order and tests UAV i against the moved cells of j < i, so those are the cells UAV i sees in the
+ * final joint action.  c_i is the first maximum of row i taken in the order 4, 0, 1, 2, 3: a UAV moves only for a strictly higher reward than
+ * staying, the lowest digit wins among equal moves, a NaN never wins and a row of NaNs gives 4.  actions_out[e] = sum c_b 5^(n_bs-1-b);
+ * best_reward[e] = the reward of that joint action = the maximum of row n_bs-1 (and rewards[e, i, 4] = the maximum of row i-1): never below
+ * the reward of every UAV staying.
+ * ue_xy_in_dev, inj, checked: as for uavenv_search_actions -- the variant evaluated is the one launch_env would run for the real step (a
+ * multi-pass handle has one variant: its step's fast and checked kernels share every expression).  Neither the state nor the handle's outputs
+ * are modified; no allocation; capturable in a hipGraph.
+ * actions_out_dev [N] int64 (required); best_reward_dev [N] float64 or NULL; rewards_dev [N, n_bs, 5] float64 or NULL.
+ * UAVENV_E_INVALID with a message, before any HIP call: a null handle or actions_out_dev; n_act != 5; a packed handle (n_ue <= 64, n_ue >= n_bs and
+ * n_groups) with n_bs > 8; a multi-pass handle with n_bs > 16 or n_ue > 256. */
+int uavenv_coordinate_actions(uavenv_t *h, const int16_t *ue_xy_in_dev, const UavEnvInject *inj, int checked,
+                              int64_t *actions_out_dev /*[N]*/, double *best_reward_dev /*[N] or NULL*/,
+                              double *rewards_dev /*[N, n_bs, 5] or NULL*/, void *stream);
+/* n_steps x [uavenv_coordinate_actions; uavenv_step with those actions] issued by ONE host call (group mobility, on-device randomness), like
+ * uavenv_step_search: actions_out_dev [n_steps, N]; `out` in uavenv_step_many's layout.  No synchronisation, no allocation.  The policy runs the
+ * variant the step will run: checked iff `out` carries float64 members.  Refuses as uavenv_coordinate_actions does, and a negative n_steps. */
+int uavenv_step_coordinate(uavenv_t *h, int n_steps, int64_t *actions_out_dev /*[T,N]*/, const UavEnvOut *out, void *stream);
+
 /* The evaluation loop's bookkeeping (main_test.py:46-113 keeps reward, outage and current_BS_sinr of every step; for 4096 envs x 2001 steps x
  * 40 UEs the SINRs alone are 1.3 GB) as running totals on the device: ONE launch per step reads the step's outputs `out` (of the handle's
  * shapes: what uavenv_step / uavenv_step_trace just wrote) and ADDS into caller-owned accumulators, which the caller zeroes.  One lane per env
