@@ -76,7 +76,7 @@ class UavEnvRates(C.Structure):
     _fields_ = [(n + "_dev", _P) for n, _ in RATE_OUT_FIELDS]
 
 
-ABI_VERSION = 9   # UAVENV_ABI_VERSION of include/uavenv.h this binding is written against (tests/test_capi_load.py compares the three)
+ABI_VERSION = 10  # UAVENV_ABI_VERSION of include/uavenv.h this binding is written against (tests/test_capi_load.py compares the three)
 STATE_FIELDS = ("ue_pos", "ue_aux", "grp", "env", "bs_xy", "out_bits")   # arrays of records, include/uavenv.h
 
 
@@ -87,7 +87,8 @@ class UavEnvStateLayout(C.Structure):
 EXPORTS = ("uavenv_abi_version", "uavenv_last_error", "uavenv_default_config", "uavenv_create", "uavenv_destroy",
            "uavenv_init", "uavenv_warmup", "uavenv_reset", "uavenv_reset_trace", "uavenv_step", "uavenv_step_range", "uavenv_rollout_gated", "uavenv_gradient_actions", "uavenv_step_gradient", "uavenv_search_actions", "uavenv_step_search", "uavenv_coordinate_actions", "uavenv_step_coordinate", "uavenv_eval_accumulate", "uavenv_default_rate_config", "uavenv_link_rates", "uavenv_step_many", "uavenv_step_seq", "uavenv_step_trace",
            "uavenv_obs_dense", "uavenv_obs_dense_update", "uavenv_sinr_area", "uavenv_sinr_area_at",
-           "uavenv_debug_variant_count", "uavenv_debug_variant_info", "uavenv_debug_variant_reset", "uavenv_debug_rotation_info", "uavenv_step_many_prepare", "uavenv_device_error", "uavenv_launch_timing", "uavenv_launch_times_us", "uavenv_debug_schedule",
+           "uavenv_debug_variant_count", "uavenv_debug_variant_info", "uavenv_debug_variant_reset",
+           "uavenv_debug_side_variant_count", "uavenv_debug_side_variant_info", "uavenv_debug_side_variant_reset", "uavenv_debug_rotation_info", "uavenv_step_many_prepare", "uavenv_device_error", "uavenv_launch_timing", "uavenv_launch_times_us", "uavenv_debug_schedule",
            "uavenv_state_layout", "uavenv_get_state", "uavenv_set_state", "uavenv_philox4x32_10", "uavenv_lean_math_eval")
 
 _lib = None
@@ -146,6 +147,9 @@ def load():
     lib.uavenv_debug_variant_count.restype = C.c_int
     lib.uavenv_debug_variant_info.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
     lib.uavenv_debug_variant_reset.restype = None
+    lib.uavenv_debug_side_variant_count.restype = C.c_int
+    lib.uavenv_debug_side_variant_info.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
+    lib.uavenv_debug_side_variant_reset.restype = None
     lib.uavenv_debug_rotation_info.argtypes = [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
     lib.uavenv_step_many_prepare.argtypes = [_P, C.c_int]
     lib.uavenv_device_error.argtypes = [_P, C.POINTER(C.c_uint32)]
@@ -190,16 +194,26 @@ def make_config(n_bs, n_ue, grid, groups=None, bs_init=None, **over):
     return cfg
 
 
+def _census(count, info):
+    out = []
+    buf = C.create_string_buffer(160)
+    for i in range(count()):
+        sel, n = C.c_int(), C.c_longlong()
+        check(info(i, buf, len(buf), C.byref(sel), C.byref(n)))
+        out.append((buf.value.decode(), bool(sel.value), int(n.value)))
+    return out
+
+
 def launch_census():
     """[(name, selectable, launches)] for every kernel instantiation slot (uavenv_debug_variant_info): test hook."""
     lib = load()
-    out = []
-    buf = C.create_string_buffer(160)
-    for i in range(lib.uavenv_debug_variant_count()):
-        sel, n = C.c_int(), C.c_longlong()
-        check(lib.uavenv_debug_variant_info(i, buf, len(buf), C.byref(sel), C.byref(n)))
-        out.append((buf.value.decode(), bool(sel.value), int(n.value)))
-    return out
+    return _census(lib.uavenv_debug_variant_count, lib.uavenv_debug_variant_info)
+
+
+def side_launch_census():
+    """The same for the kernels launched outside the env step's dispatch (uavenv_debug_side_variant_info): test hook."""
+    lib = load()
+    return _census(lib.uavenv_debug_side_variant_count, lib.uavenv_debug_side_variant_info)
 
 
 def philox4x32_10(ctr, key):

@@ -427,6 +427,98 @@ extern "C" void uavenv_debug_variant_reset(void) {
     for (auto &c : g_census) c.store(0, std::memory_order_relaxed);
 }
 
+// ---- side census (test hook, uavenv_debug_side_variant_*) ---------------------------------------------------------------------------
+// The same rule for the kernels launched outside launch_env (uavenv_handle.h: SideFamily): a table of its own, one run of slots per
+// family, each family indexed by the template arguments its dispatch site selects.  tests/test_side_variants_gpu.py drives every
+// selectable slot against its reference and asserts that none was left out.
+namespace {
+struct SideDims { const char *kernel; int n_bt, n_mode, n_fast, n_kt, n_two; };       // (PLC: two values in every family)
+constexpr SideDims kSideDims[uavenv_internal::SIDE_FAMILIES] = {
+    {"env_kernel_look", 4, 2, 2, 1, 1},              // uavenv_gradient_actions
+    {"env_kernel_search", 2, 2, 2, 1, 1},            // uavenv_search_actions
+    {"env_kernel_coordinate_packed", 2, 2, 2, 1, 1}, // uavenv_coordinate_actions, packed handles
+    {"env_kernel_coordinate", 1, 2, 1, 1, 1},        // ... multi-pass handles
+    {"env_kernel_gated", 1, 1, 1, 3, 2},             // uavenv_rollout_gated
+    {"ul_gain_kernel", 1, 1, 1, 1, 1},               // uavenv_link_rates: pair means
+    {"rates_ue_kernel", 2, 1, 1, 1, 1},              // ... per-UE columns
+    {"sinr_area_kernel", 4, 1, 1, 1, 1},             // uavenv_sinr_area(_at)
+};
+constexpr int side_slots(int fam) {
+    return kSideDims[fam].n_bt * kSideDims[fam].n_mode * 2 * kSideDims[fam].n_fast * kSideDims[fam].n_kt * kSideDims[fam].n_two;
+}
+constexpr int side_base(int fam) { return fam == 0 ? 0 : side_base(fam - 1) + side_slots(fam - 1); }
+constexpr int kSideSlots = side_base(uavenv_internal::SIDE_FAMILIES - 1) + side_slots(uavenv_internal::SIDE_FAMILIES - 1);
+static_assert(kSideSlots == 32 + 16 + 16 + 4 + 12 + 2 + 4 + 8, "side census: one slot per instantiation the translation units name");
+std::atomic<long long> g_side_census[kSideSlots];
+constexpr int kt_index(int kt) { return kt == 24 ? 0 : kt == 44 ? 1 : 2; }
+// -1: the family has no such key
+int side_index(int fam, int bt, int mode, bool plc, bool fast, int kt, bool two) {
+    if (fam < 0 || fam >= uavenv_internal::SIDE_FAMILIES) return -1;
+    const SideDims &d = kSideDims[fam];
+    if (d.n_bt == 1 ? bt != 4 : (bt != 4 && bt != 8 && !(d.n_bt == 4 && (bt == 16 || bt == 32)))) return -1;
+    if (d.n_mode == 1 ? mode != MODE_STEP : (mode != MODE_STEP && mode != MODE_TRACE)) return -1;
+    if ((d.n_fast == 1 && fast) || (d.n_two == 1 && two)) return -1;
+    if (d.n_kt == 1 ? kt != 0 : (kt != 24 && kt != 44 && kt != 0)) return -1;
+    int i = bt_index(bt);
+    i = i * d.n_mode + (mode == MODE_TRACE ? 1 : 0);
+    i = i * 2 + (plc ? 1 : 0);
+    i = i * d.n_fast + (fast ? 1 : 0);
+    i = i * d.n_kt + (d.n_kt == 1 ? 0 : kt_index(kt));
+    i = i * d.n_two + (two ? 1 : 0);
+    return side_base(fam) + i;
+}
+void side_decode(int i, int &fam, int &bt, int &mode, bool &plc, bool &fast, int &kt, bool &two) {
+    fam = 0;
+    while (i >= side_slots(fam)) { i -= side_slots(fam); ++fam; }
+    const SideDims &d = kSideDims[fam];
+    static const int bts[4] = {4, 8, 16, 32}, kts[3] = {24, 44, 0};
+    two = (i % d.n_two) != 0; i /= d.n_two;
+    kt = d.n_kt == 1 ? 0 : kts[i % d.n_kt]; i /= d.n_kt;
+    fast = (i % d.n_fast) != 0; i /= d.n_fast;
+    plc = (i & 1) != 0; i >>= 1;
+    mode = (i % d.n_mode) ? MODE_TRACE : MODE_STEP; i /= d.n_mode;
+    bt = bts[i];
+}
+}  // namespace
+// The image of the entry points' selection and refusal logic (keep them in step: side_census_count() refuses a key this predicate
+// rejects).  Every key a family has is selectable except the fast kernels of a bound no served n_bs can equal: uavenv_gradient_actions
+// serves n_bs <= 27 (n_act == 5 and 5^n_bs within int64), so BT = 32 is checked only; uavenv_search_actions serves n_bs <= 6, so BT = 8
+// is checked only.  (uavenv_coordinate_actions serves packed handles up to n_bs == 8: both bounds have a fast kernel.)
+bool uavenv_internal::side_variant_selectable(int fam, int bt, int mode, bool plc, bool fast, int kt, bool two) {
+    if (side_index(fam, bt, mode, plc, fast, kt, two) < 0) return false;
+    return !fast || side_has_fast(fam, bt);
+}
+bool uavenv_internal::side_census_count(int fam, int bt, int mode, bool plc, bool fast, int kt, bool two) {
+    if (!side_variant_selectable(fam, bt, mode, plc, fast, kt, two)) return false;
+    g_side_census[side_index(fam, bt, mode, plc, fast, kt, two)].fetch_add(1, std::memory_order_relaxed);
+    return true;
+}
+extern "C" int uavenv_debug_side_variant_count(void) { return kSideSlots; }
+extern "C" int uavenv_debug_side_variant_info(int i, char *name, size_t name_len, int *selectable, long long *launches) {
+    if (i < 0 || i >= kSideSlots) return fail(UAVENV_E_INVALID, "debug_side_variant_info: index out of range");
+    int fam, bt, mode, kt; bool plc, fast, two;
+    side_decode(i, fam, bt, mode, plc, fast, kt, two);
+    const bool sel = uavenv_internal::side_variant_selectable(fam, bt, mode, plc, fast, kt, two);
+    if (name && name_len) {
+        const SideDims &d = kSideDims[fam];
+        std::string s = std::string(d.kernel) + "<";
+        if (d.n_bt > 1 || fam == uavenv_internal::SIDE_GATED) s += "BT=" + std::to_string(bt) + ", ";
+        if (d.n_mode > 1) s += mode == MODE_TRACE ? "TRACE, " : "STEP, ";
+        s += "PLC=" + std::to_string((int)plc);
+        if (d.n_fast > 1) s += ", FAST=" + std::to_string((int)fast);
+        if (d.n_kt > 1) s += ", KT=" + std::to_string(kt);
+        if (d.n_two > 1) s += ", TWO=" + std::to_string((int)two);
+        s += sel ? ">" : "> (no such kernel)";
+        std::snprintf(name, name_len, "%s", s.c_str());
+    }
+    if (selectable) *selectable = sel ? 1 : 0;
+    if (launches) *launches = g_side_census[i].load(std::memory_order_relaxed);
+    return UAVENV_OK;
+}
+extern "C" void uavenv_debug_side_variant_reset(void) {
+    for (auto &c : g_side_census) c.store(0, std::memory_order_relaxed);
+}
+
 
 // MANY_: 0 = one step / reset / tick batch per launch, 1 = uavenv_step_many
 template <int MODE, int MANY_ = 0>
@@ -896,7 +988,9 @@ extern "C" int uavenv_sinr_area_at(uavenv_t *h, const int32_t *bs_xy_dev, const 
     do {                                                                                                              \
         if (h->plc) hipLaunchKernelGGL((sinr_area_kernel<BT_, true>), grid, blk, 0, s, k, cells, fading_inj_dev, out_f32_dev, out_f64_dev);   \
         else hipLaunchKernelGGL((sinr_area_kernel<BT_, false>), grid, blk, 0, s, k, cells, fading_inj_dev, out_f32_dev, out_f64_dev);         \
+        counted = uavenv_internal::side_census_count(uavenv_internal::SIDE_AREA, BT_, MODE_STEP, h->plc, false, 0, false);                   \
     } while (0)
+    bool counted = false;
     switch (h->bt) {
         case 4: UAVENV_AREA(4); break;
         case 8: UAVENV_AREA(8); break;
@@ -905,6 +999,7 @@ extern "C" int uavenv_sinr_area_at(uavenv_t *h, const int32_t *bs_xy_dev, const 
     }
 #undef UAVENV_AREA
     HIP_TRY(hipGetLastError());
+    if (!counted) return fail(UAVENV_E_INVALID, "side census: an area-map instantiation outside side_variant_selectable()");
     return UAVENV_OK;
 }
 

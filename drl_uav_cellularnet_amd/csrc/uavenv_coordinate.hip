@@ -1,7 +1,7 @@
 // libuavenv: uavenv_coordinate_actions / uavenv_step_coordinate (include/uavenv.h) -- the per-UAV coordinate-search policy for a whole
 // batch: per env, in UAV order, each UAV's best cell given the choices before it (uavenv_coordinate_kernel.h), and its launch.  A
 // translation unit of its own, like uavenv_search.hip: its 20 kernel instantiations (16 packed, 4 multi-pass) build beside those of
-// uavenv_capi.hip and stay out of the launch census.
+// uavenv_capi.hip and are counted by the side census (uavenv_handle.h), not the launch census.
 #include "uavenv_handle.h"
 #include "uavenv_coordinate_kernel.h"
 
@@ -10,11 +10,14 @@ using uavenv_internal::fail;
 using uavenv_internal::poisoned;
 using uavenv_internal::fill_call;
 using uavenv_internal::out_block;
+using uavenv_internal::kCoordPackedMaxBs;
+using uavenv_internal::side_census_count;
+using uavenv_internal::SIDE_COORD_PACKED;
+using uavenv_internal::SIDE_COORD_MULTIPASS;
 
-constexpr int kCoordPackedMaxBs = 8;   // the packed body keeps every UAV's five powers in registers: the template bounds 4 and 8
-
+// (both launchers -> whether the side census took the instantiation that ran)
 template <int BT, int MODE>
-static void launch_coordinate_packed(const uavenv_t *h, const KParams &p, const CoordArgs &ca, bool fast, hipStream_t s) {
+static bool launch_coordinate_packed(const uavenv_t *h, const KParams &p, const CoordArgs &ca, bool fast, hipStream_t s) {
     const long long waves = (p.N + p.epw - 1) / p.epw;
     const dim3 grid((unsigned)((waves + kWavesPerBlock - 1) / kWavesPerBlock)), blk(64 * kWavesPerBlock);
 #define COORD_ARGS h->blob, p.gid_of_u, p.N, p.U, p.epw, p.Gr, p.B, (int)uavk::lane_div_magic((uint32_t)p.U), ca, p
@@ -26,14 +29,16 @@ static void launch_coordinate_packed(const uavenv_t *h, const KParams &p, const 
         else hipLaunchKernelGGL((env_kernel_coordinate_packed<BT, MODE, false, false>), grid, blk, 0, s, COORD_ARGS);
     }
 #undef COORD_ARGS
+    return side_census_count(SIDE_COORD_PACKED, BT, MODE, h->plc, fast, 0, false);
 }
 
 template <int MODE>
-static void launch_coordinate_multipass(const uavenv_t *h, const KParams &p, const CoordArgs &ca, hipStream_t s) {
+static bool launch_coordinate_multipass(const uavenv_t *h, const KParams &p, const CoordArgs &ca, hipStream_t s) {
     const dim3 grid((unsigned)p.N), blk(64);               // one env per wavefront, one wavefront per workgroup
     const size_t lds = coordinate_lds_bytes(p.U, p.B);     // <= 34 816 bytes (16 x 256)
     if (h->plc) hipLaunchKernelGGL((env_kernel_coordinate<MODE, true>), grid, blk, lds, s, ca, p);
     else hipLaunchKernelGGL((env_kernel_coordinate<MODE, false>), grid, blk, lds, s, ca, p);
+    return side_census_count(SIDE_COORD_MULTIPASS, 4, MODE, h->plc, false, 0, false);
 }
 
 // Everything a handle must be for the policy, tested before any HIP call.  `who`: the entry point named in the message.
@@ -63,23 +68,25 @@ extern "C" int uavenv_coordinate_actions(uavenv_t *h, const int16_t *ue_xy_in_de
     CoordArgs ca;
     ca.actions_out = (long long *)actions_out_dev; ca.best_reward = best_reward_dev; ca.rewards = rewards_dev;
     hipStream_t s = (hipStream_t)stream;
+    bool counted = false;
     if (h->packed) {
         // The arithmetic variant the real step would run (launch_env): fast = no injected draws, no float64 copies (`checked` says whether
         // the step the caller has in mind asks for them), B == the template bound.
         const bool fast = !checked && !p.inj_theta && !p.inj_group && !p.inj_fading && (p.B == h->bt);
 #define COORD_LAUNCH(BT_)                                                                      \
     do {                                                                                       \
-        if (ue_xy_in_dev) launch_coordinate_packed<BT_, MODE_TRACE>(h, p, ca, fast, s);        \
-        else launch_coordinate_packed<BT_, MODE_STEP>(h, p, ca, fast, s);                      \
+        if (ue_xy_in_dev) counted = launch_coordinate_packed<BT_, MODE_TRACE>(h, p, ca, fast, s); \
+        else counted = launch_coordinate_packed<BT_, MODE_STEP>(h, p, ca, fast, s);            \
     } while (0)
         if (h->bt == 4) COORD_LAUNCH(4);
         else COORD_LAUNCH(8);                    // n_bs <= 8: the template bound is 4 or 8
 #undef COORD_LAUNCH
     } else {                                     // one variant: the multi-pass step's fast and checked kernels share every expression
-        if (ue_xy_in_dev) launch_coordinate_multipass<MODE_TRACE>(h, p, ca, s);
-        else launch_coordinate_multipass<MODE_STEP>(h, p, ca, s);
+        if (ue_xy_in_dev) counted = launch_coordinate_multipass<MODE_TRACE>(h, p, ca, s);
+        else counted = launch_coordinate_multipass<MODE_STEP>(h, p, ca, s);
     }
     HIP_TRY(hipGetLastError());
+    if (!counted) return fail(UAVENV_E_INVALID, "coordinate_actions: side census: an instantiation outside side_variant_selectable()");
     return UAVENV_OK;
 }
 

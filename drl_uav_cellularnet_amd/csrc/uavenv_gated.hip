@@ -1,5 +1,6 @@
 // libuavenv: uavenv_rollout_gated (include/uavenv.h) -- the persistent gated rollout kernel of uavenv_kernels.h (env_kernel_gated) and its
-// launch.  A translation unit of its own: the kernel instantiations here and the ~190 of uavenv_capi.hip build independently.
+// launch.  A translation unit of its own: its 12 kernel instantiations and the ~190 of uavenv_capi.hip build independently; they are counted by the side
+// census (uavenv_handle.h), not the launch census.
 #include <algorithm>
 
 #include "uavenv_handle.h"
@@ -16,8 +17,9 @@ extern "C" int uavenv_rollout_gated(uavenv_t *h, const UavEnvGatedRollout *r, co
     if (r->n_steps < 1 || !r->actions_dev || !r->gate_actions_dev || !r->gate_obs_dev || !r->claim_dev || !r->enc_table_a_dev || !r->enc_out_a_dev)
         return fail(UAVENV_E_INVALID, "rollout_gated: n_steps >= 1, the action tape, both gate arrays, the claim word, table a and its output are required");
     if ((r->enc_table_c_dev != nullptr) != (r->enc_out_c_dev != nullptr)) return fail(UAVENV_E_INVALID, "rollout_gated: table c and its output come together");
-    if (!h->packed || h->bt != 4 || h->kp.B != 4 || h->N > 0x7FFFFFFFll)
-        return fail(UAVENV_E_INVALID, "rollout_gated: built for n_ue <= 64 and n_bs == 4");
+    // encode_env gives each of the n_ue + n_bs observation nodes one lane of one wavefront (as uavagent_first_layer_from_obs_f32)
+    if (!h->packed || h->bt != 4 || h->kp.B != 4 || h->kp.U + h->kp.B > 64 || h->N > 0x7FFFFFFFll)
+        return fail(UAVENV_E_INVALID, "rollout_gated: built for n_bs == 4 and n_ue + n_bs <= 64 (one lane per node)");
     if (r->enc_hidden < 4 || r->enc_hidden % 4 != 0 || r->enc_hidden > 256 || r->enc_rows < 1 ||
         (unsigned long long)r->enc_rows * (unsigned long long)r->enc_hidden * 4ull >= (1ull << 32))
         return fail(UAVENV_E_INVALID, "rollout_gated: hidden must be a multiple of 4 up to 256 and a table smaller than 4 GiB");
@@ -48,13 +50,16 @@ extern "C" int uavenv_rollout_gated(uavenv_t *h, const UavEnvGatedRollout *r, co
     do {                                                                                                                 \
         if (two) hipLaunchKernelGGL((env_kernel_gated<4, PLC_, KT_, true>), dim3(grid), blk, 0, s, GATED_ARGS);          \
         else hipLaunchKernelGGL((env_kernel_gated<4, PLC_, KT_, false>), dim3(grid), blk, 0, s, GATED_ARGS);             \
+        counted = uavenv_internal::side_census_count(uavenv_internal::SIDE_GATED, 4, MODE_STEP, PLC_, false, KT_, two);  \
     } while (0)
+    bool counted = false;
     // (the node count as a template parameter for the reference's two shapes, 4 UAVs + 20 / 40 UEs: the row loop unrolls around v_readlane)
     if (h->plc) { if (K == 24) GATED_LAUNCH(true, 24); else if (K == 44) GATED_LAUNCH(true, 44); else GATED_LAUNCH(true, 0); }
     else { if (K == 24) GATED_LAUNCH(false, 24); else if (K == 44) GATED_LAUNCH(false, 44); else GATED_LAUNCH(false, 0); }
 #undef GATED_LAUNCH
 #undef GATED_ARGS
     HIP_TRY(hipGetLastError());
+    if (!counted) return fail(UAVENV_E_INVALID, "rollout_gated: side census: an instantiation outside side_variant_selectable()");
     return UAVENV_OK;
 }
 

@@ -1,6 +1,7 @@
 // libuavenv: uavenv_gradient_actions / uavenv_step_gradient (include/uavenv.h) -- the reference's SINR-gradient baseline controller
 // (gradient.py) for a whole batch: the look-ahead kernel of uavenv_gradient_kernel.h and its launch.  A translation unit of its own, like
-// uavenv_gated.hip: its 32 kernel instantiations build beside the ~190 of uavenv_capi.hip and stay out of the launch census.
+// uavenv_gated.hip: its 28 kernel instantiations build beside the ~190 of uavenv_capi.hip and are counted by the side census (uavenv_handle.h), not the
+// launch census.
 #include "uavenv_handle.h"
 #include "uavenv_gradient_kernel.h"
 
@@ -9,20 +10,27 @@ using uavenv_internal::fail;
 using uavenv_internal::poisoned;
 using uavenv_internal::fill_call;
 using uavenv_internal::out_block;
+using uavenv_internal::side_census_count;
+using uavenv_internal::side_has_fast;
+using uavenv_internal::SIDE_LOOK;
 
+// -> whether the side census took the instantiation that ran
 template <int BT, int MODE>
-static void launch_look(const uavenv_t *h, const KParams &p, const LookArgs &lk, bool fast, hipStream_t s) {
+static bool launch_look(const uavenv_t *h, const KParams &p, const LookArgs &lk, bool fast, hipStream_t s) {
+    // n_act == 5 caps n_bs at 27 (uavenv_handle.h: kLookMaxBs), so no handle has n_bs == 32: that bound has no fast kernel
+    constexpr bool kFast = side_has_fast(SIDE_LOOK, BT);
     const long long waves = (p.N + p.epw - 1) / p.epw;
     const dim3 grid((unsigned)((waves + kWavesPerBlock - 1) / kWavesPerBlock)), blk(64 * kWavesPerBlock);
 #define LOOK_ARGS h->blob, p.gid_of_u, p.N, p.U, p.epw, p.Gr, p.B, (int)uavk::lane_div_magic((uint32_t)p.U), lk, p
     if (h->plc) {
-        if (fast) hipLaunchKernelGGL((env_kernel_look<BT, MODE, true, true>), grid, blk, 0, s, LOOK_ARGS);
+        if (kFast && fast) hipLaunchKernelGGL((env_kernel_look<BT, MODE, true, kFast>), grid, blk, 0, s, LOOK_ARGS);
         else hipLaunchKernelGGL((env_kernel_look<BT, MODE, true, false>), grid, blk, 0, s, LOOK_ARGS);
     } else {
-        if (fast) hipLaunchKernelGGL((env_kernel_look<BT, MODE, false, true>), grid, blk, 0, s, LOOK_ARGS);
+        if (kFast && fast) hipLaunchKernelGGL((env_kernel_look<BT, MODE, false, kFast>), grid, blk, 0, s, LOOK_ARGS);
         else hipLaunchKernelGGL((env_kernel_look<BT, MODE, false, false>), grid, blk, 0, s, LOOK_ARGS);
     }
 #undef LOOK_ARGS
+    return side_census_count(SIDE_LOOK, BT, MODE, h->plc, kFast && fast, 0, false);
 }
 
 extern "C" int uavenv_gradient_actions(uavenv_t *h, const int16_t *ue_xy_in_dev, const UavEnvInject *inj, int64_t *actions_out_dev,
@@ -47,9 +55,10 @@ extern "C" int uavenv_gradient_actions(uavenv_t *h, const int16_t *ue_xy_in_dev,
     hipStream_t s = (hipStream_t)stream;
 #define LOOK_LAUNCH(BT_)                                                                 \
     do {                                                                                 \
-        if (ue_xy_in_dev) launch_look<BT_, MODE_TRACE>(h, p, lk, fast, s);               \
-        else launch_look<BT_, MODE_STEP>(h, p, lk, fast, s);                             \
+        if (ue_xy_in_dev) counted = launch_look<BT_, MODE_TRACE>(h, p, lk, fast, s);     \
+        else counted = launch_look<BT_, MODE_STEP>(h, p, lk, fast, s);                   \
     } while (0)
+    bool counted = false;
     switch (h->bt) {
         case 4: LOOK_LAUNCH(4); break;
         case 8: LOOK_LAUNCH(8); break;
@@ -58,6 +67,7 @@ extern "C" int uavenv_gradient_actions(uavenv_t *h, const int16_t *ue_xy_in_dev,
     }
 #undef LOOK_LAUNCH
     HIP_TRY(hipGetLastError());
+    if (!counted) return fail(UAVENV_E_INVALID, "gradient_actions: side census: an instantiation outside side_variant_selectable()");
     return UAVENV_OK;
 }
 

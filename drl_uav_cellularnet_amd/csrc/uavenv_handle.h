@@ -55,6 +55,22 @@ int poisoned(const uavenv *h, const char *what);
 void fill_call(uavk::KParams &p, const UavEnvInject *inj, const UavEnvOut *out);
 bool call_is_fast(const uavk::KParams &p);
 UavEnvOut out_block(const UavEnvOut &o, long long t, long long N, long long U, long long B);   // block t of [T][...] outputs; null members stay null
+
+// ---- side census (test hook, uavenv_debug_side_variant_*; defined once in uavenv_capi.hip) -------------------------------------------
+// The kernels launched outside launch_env -- policies, gated rollout, link rates, area map -- are templates too.  One family per dispatch
+// site; the key is the template arguments that site selects (a family ignores the arguments it does not have).  A launch site calls
+// side_census_count() after launching; false = side_variant_selectable() rejects the key, which the site reports as an error, as launch_env
+// does for the launch census.  tests/test_side_variants_gpu.py launches every selectable key against its reference and reads the table.
+enum SideFamily { SIDE_LOOK = 0, SIDE_SEARCH, SIDE_COORD_PACKED, SIDE_COORD_MULTIPASS, SIDE_GATED, SIDE_UL_GAIN, SIDE_RATES_UE, SIDE_AREA, SIDE_FAMILIES };
+constexpr int kLookMaxBs = 27;         // uavenv_gradient_actions needs n_act == 5, and check_config refuses 5^n_bs beyond int64: 5^27 < 2^63 < 5^28
+constexpr int kSearchMaxBs = 6;        // 5^6 = 15625 joint actions; 5^7 would be 78125 step bodies per decision
+constexpr int kCoordPackedMaxBs = 8;   // the packed body keeps every UAV's five powers in registers: the template bounds 4 and 8
+// FAST kernels are compiled for n_bs == BT exactly: a bound no served n_bs can equal has no fast kernel (not built, not selectable).
+constexpr bool side_has_fast(int fam, int bt) {
+    return fam == SIDE_LOOK ? bt <= kLookMaxBs : fam == SIDE_SEARCH ? bt <= kSearchMaxBs : fam == SIDE_COORD_PACKED ? bt <= kCoordPackedMaxBs : false;
+}
+bool side_variant_selectable(int fam, int bt, int mode, bool plc, bool fast, int kt, bool two);
+bool side_census_count(int fam, int bt, int mode, bool plc, bool fast, int kt, bool two);
 }  // namespace uavenv_internal
 
 #define HIP_TRY(expr)                                                                              \

@@ -1,7 +1,7 @@
 // libuavenv: uavenv_default_rate_config / uavenv_link_rates (include/uavenv.h) -- the link-rate model of LTEChannel (channel.py:178-209,
 // 272-385) for the latest channel update of a whole batch: downlink MCS rates and Monte-Carlo uplink rates per env (uavenv_rates_kernel.h).
 // A translation unit of its own, like uavenv_search.hip and uavenv_eval.hip: its kernel instantiations build beside those of
-// uavenv_capi.hip and stay out of the launch census.
+// uavenv_capi.hip and are counted by the side census (uavenv_handle.h), not the launch census.
 #include "uavenv_handle.h"
 #include "uavenv_rates_kernel.h"
 
@@ -104,6 +104,8 @@ extern "C" int uavenv_link_rates(uavenv_t *h, const UavEnvRateConfig *rate_cfg, 
         if (h->plc) hipLaunchKernelGGL((ul_gain_kernel<true>), grid, blk, 0, s, r, p);
         else hipLaunchKernelGGL((ul_gain_kernel<false>), grid, blk, 0, s, r, p);
         HIP_TRY(hipGetLastError());
+        if (!uavenv_internal::side_census_count(uavenv_internal::SIDE_UL_GAIN, 4, MODE_STEP, h->plc, false, 0, false))
+            return fail(UAVENV_E_INVALID, "link_rates: side census: a pair-mean instantiation outside side_variant_selectable()");
     }
     if (per_ue) {
         // (a downlink-only call computes its uplink columns from whatever means the buffer holds and stores none of them)
@@ -114,11 +116,14 @@ extern "C" int uavenv_link_rates(uavenv_t *h, const UavEnvRateConfig *rate_cfg, 
     do {                                                                                          \
         if (h->plc) hipLaunchKernelGGL((rates_ue_kernel<BT_, true>), grid, blk, 0, s, r, p);      \
         else hipLaunchKernelGGL((rates_ue_kernel<BT_, false>), grid, blk, 0, s, r, p);            \
+        counted = uavenv_internal::side_census_count(uavenv_internal::SIDE_RATES_UE, BT_, MODE_STEP, h->plc, false, 0, false); \
     } while (0)
+        bool counted = false;
         if (ec.n_bs <= 4) RATES_LAUNCH(4);
         else RATES_LAUNCH(8);
 #undef RATES_LAUNCH
         HIP_TRY(hipGetLastError());
+        if (!counted) return fail(UAVENV_E_INVALID, "link_rates: side census: a per-UE instantiation outside side_variant_selectable()");
     }
     return UAVENV_OK;
 }

@@ -1,7 +1,7 @@
 // libuavenv: uavenv_search_actions / uavenv_step_search (include/uavenv.h) -- the one-step search policy for a whole batch: per env the
 // reward of every joint action from the present state and the first maximum (uavenv_search_kernel.h), and its launch.  A translation
-// unit of its own, like uavenv_gradient.hip: its 16 kernel instantiations build beside those of uavenv_capi.hip and stay out of the
-// launch census.
+// unit of its own, like uavenv_gradient.hip: its 12 kernel instantiations build beside those of uavenv_capi.hip and are counted by the
+// side census (uavenv_handle.h), not the launch census.
 #include "uavenv_handle.h"
 #include "uavenv_search_kernel.h"
 
@@ -10,22 +10,28 @@ using uavenv_internal::fail;
 using uavenv_internal::poisoned;
 using uavenv_internal::fill_call;
 using uavenv_internal::out_block;
+using uavenv_internal::kSearchMaxBs;
+using uavenv_internal::side_census_count;
+using uavenv_internal::side_has_fast;
+using uavenv_internal::SIDE_SEARCH;
 
-constexpr int kSearchMaxBs = 6;   // 5^6 = 15625 joint actions; 5^7 would be 78125 step bodies per decision
-
+// -> whether the side census took the instantiation that ran
 template <int BT, int MODE>
-static void launch_search(const uavenv_t *h, const KParams &p, const SearchArgs &sa, bool fast, hipStream_t s) {
+static bool launch_search(const uavenv_t *h, const KParams &p, const SearchArgs &sa, bool fast, hipStream_t s) {
+    // n_bs <= 6 (kSearchMaxBs), so no handle has n_bs == 8: that bound has no fast kernel
+    constexpr bool kFast = side_has_fast(SIDE_SEARCH, BT);
     const long long waves = (p.N + p.epw - 1) / p.epw;
     const dim3 grid((unsigned)((waves + kWavesPerBlock - 1) / kWavesPerBlock)), blk(64 * kWavesPerBlock);
 #define SEARCH_ARGS h->blob, p.gid_of_u, p.N, p.U, p.epw, p.Gr, p.B, (int)uavk::lane_div_magic((uint32_t)p.U), sa, p
     if (h->plc) {
-        if (fast) hipLaunchKernelGGL((env_kernel_search<BT, MODE, true, true>), grid, blk, 0, s, SEARCH_ARGS);
+        if (kFast && fast) hipLaunchKernelGGL((env_kernel_search<BT, MODE, true, kFast>), grid, blk, 0, s, SEARCH_ARGS);
         else hipLaunchKernelGGL((env_kernel_search<BT, MODE, true, false>), grid, blk, 0, s, SEARCH_ARGS);
     } else {
-        if (fast) hipLaunchKernelGGL((env_kernel_search<BT, MODE, false, true>), grid, blk, 0, s, SEARCH_ARGS);
+        if (kFast && fast) hipLaunchKernelGGL((env_kernel_search<BT, MODE, false, kFast>), grid, blk, 0, s, SEARCH_ARGS);
         else hipLaunchKernelGGL((env_kernel_search<BT, MODE, false, false>), grid, blk, 0, s, SEARCH_ARGS);
     }
 #undef SEARCH_ARGS
+    return side_census_count(SIDE_SEARCH, BT, MODE, h->plc, kFast && fast, 0, false);
 }
 
 // Everything a handle must be for the search, tested before any HIP call.  `who`: the entry point named in the message.
@@ -60,13 +66,15 @@ extern "C" int uavenv_search_actions(uavenv_t *h, const int16_t *ue_xy_in_dev, c
     hipStream_t s = (hipStream_t)stream;
 #define SEARCH_LAUNCH(BT_)                                                               \
     do {                                                                                 \
-        if (ue_xy_in_dev) launch_search<BT_, MODE_TRACE>(h, p, sa, fast, s);             \
-        else launch_search<BT_, MODE_STEP>(h, p, sa, fast, s);                           \
+        if (ue_xy_in_dev) counted = launch_search<BT_, MODE_TRACE>(h, p, sa, fast, s);   \
+        else counted = launch_search<BT_, MODE_STEP>(h, p, sa, fast, s);                 \
     } while (0)
+    bool counted = false;
     if (h->bt == 4) SEARCH_LAUNCH(4);
     else SEARCH_LAUNCH(8);                       // n_bs <= 6: the template bound is 4 or 8
 #undef SEARCH_LAUNCH
     HIP_TRY(hipGetLastError());
+    if (!counted) return fail(UAVENV_E_INVALID, "search_actions: side census: an instantiation outside side_variant_selectable()");
     return UAVENV_OK;
 }
 

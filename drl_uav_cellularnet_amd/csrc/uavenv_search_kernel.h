@@ -31,7 +31,8 @@ struct SearchLds {            // per wavefront
 };
 
 // The two halves of rx_power (uavenv_kernels.h), apart, so that the draws of a (walker, UAV pair) are made once for all five candidate cells.
-// Each is rx_power's own text -- same operands, same order -- and tests/test_search_policy_gpu.py holds the two together bit for bit.
+// Each is rx_power's own text -- same operands, same order.  The tests hold the two together bit for bit: tests/test_search_policy_gpu.py
+// in the cube form (PLC), tests/test_side_variants_gpu.py in both forms and on either side of the pl_dis radius.
 // (rx_power itself is not built from them: the split moved the register allocation of two multi-step kernels of uavenv_capi.hip.)
 // Shadowing draws f0, f1 of UAVs b2, b2 + 1: injected, or Box-Muller on one Philox call.  No quad mode: that is B > 8, the search has B <= 6.
 template <int BT, bool FAST, bool PRE>

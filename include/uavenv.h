@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define UAVENV_ABI_VERSION 9   /* 2: state blob = arrays of records (UavEnvStateLayout); 3: + uavenv_step_many, uavenv_step_seq;
+#define UAVENV_ABI_VERSION 10  /* 2: state blob = arrays of records (UavEnvStateLayout); 3: + uavenv_step_many, uavenv_step_seq;
                                 * 4: + uavenv_sinr_area_at, uavenv_step_many_packed / uavenv_unpack_outputs, uavenv_debug_variant_* (launch census), uavenv_debug_rotation_info,
                                 *      uavenv_step_many_prepare;
                                 * 5: + UAVENV_E_DEVICE, uavenv_device_error (one-launch rotation schedule with bounded hand-offs), uavenv_step_range,
@@ -33,7 +33,9 @@ extern "C" {
                                 * 7: + uavenv_rollout_gated / UavEnvGatedRollout (a whole rollout as one persistent launch beside a persistent policy kernel);
                                 * 8: + uavenv_gradient_actions (the SINR-gradient baseline's decision from a look-ahead step that commits nothing),
                                 *      uavenv_step_gradient;
-                                * 9: + uavenv_eval_accumulate / UavEnvEvalAcc (a step's outputs folded into per-env totals and a serving-SINR histogram) */
+                                * 9: + uavenv_eval_accumulate / UavEnvEvalAcc (a step's outputs folded into per-env totals and a serving-SINR histogram);
+                                * 10: + uavenv_debug_side_variant_* (side census: the kernels launched outside the env step's dispatch);
+                                *      uavenv_rollout_gated refuses n_ue + n_bs > 64 */
 #define UAVENV_MAX_GROUPS 16
 #define UAVENV_MAX_BS 32
 
@@ -201,6 +203,16 @@ int uavenv_debug_variant_count(void);
 int uavenv_debug_variant_info(int i, char *name, size_t name_len, int *selectable, long long *launches);
 void uavenv_debug_variant_reset(void);
 
+/* Side census (test hook): the same three calls, same semantics, for the template kernels launched outside the env step's dispatch --
+ * a table of its own, one family per dispatch site: the look-ahead of uavenv_gradient_actions, uavenv_search_actions,
+ * uavenv_coordinate_actions (packed / multi-pass), uavenv_rollout_gated, the two kernels of uavenv_link_rates and uavenv_sinr_area(_at).
+ * An entry's key is the template arguments its site selects (bound on n_bs, step / trace mode, path-loss form, checked / fast, node count,
+ * one / two tables).  tests/test_side_variants_gpu.py launches every selectable entry against its reference and asserts that none is
+ * left at zero. */
+int uavenv_debug_side_variant_count(void);
+int uavenv_debug_side_variant_info(int i, char *name, size_t name_len, int *selectable, long long *launches);
+void uavenv_debug_side_variant_reset(void);
+
 /* Optional: prepare a multi-step call of n_steps ahead of time.  The first uavenv_step_many call with a new n_steps may build and
  * upload a launch schedule (a few hundred microseconds of host time, synchronous); a caller that times the call (bench.py) or must not
  * stall in it builds the schedule here instead.  Idempotent; 0 when there is nothing to prepare for this handle / n_steps. */
@@ -254,7 +266,8 @@ int uavenv_debug_schedule(int64_t n_wavefronts, int64_t n_slots, int n_steps, in
  * is written after step t, for t + 1 < T.  idx_out_dev (optional) is [T + 1][N][B + U] int64: slot t + 1 = the row indices after step t.
  * reward_dev (optional) [T][N]: the reward of step t; every other output of `out` is overwritten each step as by uavenv_step, and `out`
  * must hold all nine standard outputs.  State, outputs and rewards are bit-identical to T calls of uavenv_step with the same actions.
- * n_ue <= 64 and n_bs == 4 (the reference's shape), on-device randomness only; UAVENV_E_INVALID otherwise. */
+ * n_bs == 4 (the reference's shape) and n_ue + n_bs <= 64 (one lane per node), on-device randomness only; UAVENV_E_INVALID otherwise,
+ * before any device call. */
 #define UAVENV_GATE_ROWS 16
 typedef struct UavEnvGatedRollout {
     int32_t n_steps;

@@ -124,6 +124,27 @@ def test_host_side_calls_without_gpu():
     assert b"default_config" in lib.uavenv_last_error()
 
 
+def test_side_census_table_without_gpu():
+    """The side census (uavenv_debug_side_variant_*) is host logic: its table answers without a device.  94 uniquely named slots, 86 of
+    them selectable; the eight others are the fast kernels of a bound no served n_bs can equal, which are not built."""
+    import ctypes as C
+
+    from drl_uav_cellularnet_amd import _capi
+
+    lib = _capi.load()
+    census = _capi.side_launch_census()
+    names = [name for name, _, _ in census]
+    assert len(census) == lib.uavenv_debug_side_variant_count() == 94 and len(set(names)) == 94
+    off = sorted(name for name, sel, _ in census if not sel)
+    assert len(off) == 8 and all("(no such kernel)" in n and "FAST=1" in n for n in off)
+    assert sum(n.startswith("env_kernel_look<BT=32") for n in off) == 4 and sum(n.startswith("env_kernel_search<BT=8") for n in off) == 4
+    for bad in (-1, 94):
+        assert lib.uavenv_debug_side_variant_info(bad, None, 0, None, None) == -1 and b"out of range" in lib.uavenv_last_error()
+    sel = C.c_int(-1)
+    assert lib.uavenv_debug_side_variant_info(0, None, 0, C.byref(sel), None) == 0 and sel.value == 1      # every output is optional
+    assert sum(1 for _, s_, _ in _capi.launch_census() if s_) == 188                                       # the launch census keeps its own
+
+
 def test_create_validates_before_touching_the_device():
     """uavenv_create() refuses, before any HIP call, what the kernels cannot handle: a batch whose arrays would pass 4 GiB
     (they are addressed as base + 32-bit byte offset) and UAV start cells outside [1, grid-1] (the reference's boundaries)."""

@@ -33,7 +33,7 @@ def test_libraries_build_and_export_the_new_symbols():
     assert {"uavagent_actor_head_greedy_f32", "uavagent_argmax_rows_f32"} <= set(_agent_capi.EXPORTS)
     header = open(os.path.join(ROOT, "include", "uavenv.h")).read()
     declared = int(re.search(r"#define\s+UAVENV_ABI_VERSION\s+(\d+)", header).group(1))
-    assert _capi.load().uavenv_abi_version() == declared == _capi.ABI_VERSION == 9
+    assert _capi.load().uavenv_abi_version() == declared == _capi.ABI_VERSION == 10
     assert _agent_capi.load().uavagent_abi_version() == _agent_capi.ABI_VERSION == 5        # additive exports: the number stays
 
 

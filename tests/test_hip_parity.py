@@ -136,6 +136,9 @@ PHILOX_SHAPES = [
     (3, 20, 64, 12, 24, {}),                   # B = 3 < BT = 4: checked variant (FAST needs B == BT)
     (4, 20, 100, 32, 40, {"pl_b": 37.6, "pl_a": 15.3}),  # generic path-loss exponent (PLC = false), packed
     (16, 200, 100, 4, 12, {"pl_b": 37.6}),     # generic path-loss exponent, multi-pass
+    # near-field radius of 5 cells (loss = 0 for d <= pl_dis, channel.py:232-233); a last trace step puts UEs inside, exactly on and outside it
+    (4, 20, 40, 7, 12, {"pl_dis": 25.0, "pl_b": 27.5}),   # packed, generic form
+    (4, 72, 40, 3, 8, {"pl_dis": 25.0}),       # multi-pass, cube form
     # n_act = 9: digits 5..8 are the double steps of BS_move (ue_mobility.py:238-253); mobile_env.py only ever uses N_ACT = 5
     (4, 20, 100, 33, 40, {"n_act": 9}),        # packed FAST kernel, all nine digits
     (4, 20, 16, 33, 80, {"n_act": 9}),         # 16 x 16 grid: walls and the min-distance rule fire on most steps
@@ -216,6 +219,17 @@ def test_hip_matches_oracle_on_philox_streams(shape):
         env.step(torch.as_tensor(act, device=env.device))
         oo = orc.step(act)
         compare("step %d" % t)
+    if "pl_dis" in over:
+        # The radius on purpose, not by chance: a trace step (every UAV staying) whose first UEs stand at chosen offsets from the UAVs.
+        # Asserted on the oracle's outputs alone: pairs strictly inside, exactly on (d^2 == pl_dis^2) and outside the radius.
+        from near_field import radius_counts, trace_cells
+
+        cells = trace_cells(rs, N, U, G, orc.s["bs_xy"])
+        stay = np.full(N, n_act ** B - 1, np.int64)
+        env.step_trace(torch.as_tensor(stay, device=env.device), cells)
+        oo = orc.step_trace(stay, cells)
+        radius_counts(oo["ue_xy"], oo["bs_xy"], "near-field trace step")
+        compare("near-field trace step")
     s = env.state_fields()
     for k in ("ue_x", "ue_y", "g_x", "g_y", "g_fl", "g_v", "g_cos", "g_sin"):
         np.testing.assert_allclose(s[k], orc.s[k], rtol=0, atol=1e-9, err_msg=k)

@@ -42,22 +42,35 @@ def _buffers(torch, env, T, hid):
 
 
 # (n_envs, n_ue, T, hidden, two tables): whole pairs of blocks; a ragged last block and a lone last block; 40 UEs (one env per wavefront,
-# 44 nodes); one table; a node count without an instantiation of its own (36: run-time loop); more pairs than a small grid would hold
+# 44 nodes); one table; a node count without an instantiation of its own (36: run-time loop); more pairs than a small grid would hold;
+# 60 UEs (64 nodes: every lane of the encoder's wavefront is a node, the most the entry point accepts)
 SHAPES = [(64, 20, 6, 200, True), (200, 20, 5, 200, True), (16 * 3 + 5, 20, 4, 200, True), (40, 40, 4, 200, True), (96, 20, 3, 64, False), (48, 32, 3, 200, True),
-          (8192, 20, 3, 200, True)]
+          (8192, 20, 3, 200, True), (37, 60, 3, 64, True)]
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "%denv_%due_T%d_h%d_%s" % (s[0], s[1], s[2], s[3], "two" if s[4] else "one"))
 def test_gated_rollout_with_open_gates_equals_steps_plus_first_layer(shape):
     torch = _torch()
-    from drl_uav_cellularnet_amd import _agent_capi as A
-
     n, n_ue, T, hid, two = shape
     env = _env(n, n_ue)
-    ref = env.clone()
-    wa, ba, wc, bc = _tables(torch, env, hid, 3)
     g = torch.Generator().manual_seed(11)
     act = torch.randint(0, env.action_space_dim, (T, n), generator=g, dtype=torch.int64).to(env.device)
+    ref = open_gates_equal_steps_plus_first_layer(torch, env, act, hid, two)
+    # and the API continues from there
+    a = torch.randint(0, env.action_space_dim, (n,), generator=g, dtype=torch.int64).to(env.device)
+    env.step(a); ref.step(a)
+    assert np.array_equal(env.get_state(), ref.get_state())
+
+
+def open_gates_equal_steps_plus_first_layer(torch, env, act, hid, two, after_step=None):
+    """The rollout of ``act`` [T, N] on ``env`` with every action gate open, against T steps of a clone + first_layer_from_obs, bit for
+    bit.  ``after_step(t, ref)`` sees the clone after each of its steps.  Returns the clone.  (tests/test_side_variants_gpu.py runs it
+    over the kernel's other instantiations.)"""
+    from drl_uav_cellularnet_amd import _agent_capi as A
+
+    T, n, n_ue = int(act.shape[0]), env.n_envs, env.nUE
+    ref = env.clone()
+    wa, ba, wc, bc = _tables(torch, env, hid, 3)
     b = _buffers(torch, env, T, hid)
     env.rollout_gated(act, b["gate_act"], b["gate_obs"], b["claim"][0:1], wa, ba, b["out_a"], wc if two else None, bc if two else None, b["out_c"] if two else None,
                       idx_out=b["idx"], reward_out=b["rew"])
@@ -77,16 +90,15 @@ def test_gated_rollout_with_open_gates_equals_steps_plus_first_layer(shape):
             if two:
                 assert torch.equal(b["out_c"][t + 1], ec), "table c, slot %d" % (t + 1)
         del r
+        if after_step is not None:
+            after_step(t, ref)
     for k, v in ref.out.items():
         if k != "reward":
             assert torch.equal(env.out[k], v), k
     assert np.array_equal(env.get_state(), ref.get_state())
     assert bool((b["gate_obs"] == (T if T > 1 else 0)).all())
     assert bool(torch.isnan(b["out_a"][0]).all()) and bool((b["idx"][0] == -7).all())      # slot 0 is the caller's
-    # and the API continues from there
-    a = torch.randint(0, env.action_space_dim, (n,), generator=g, dtype=torch.int64).to(env.device)
-    env.step(a); ref.step(a)
-    assert np.array_equal(env.get_state(), ref.get_state())
+    return ref
 
 
 def test_a_gate_that_never_opens_is_an_error_code_not_a_hang(monkeypatch):
@@ -127,6 +139,32 @@ def test_gated_rollout_refuses_what_it_was_not_built_for():
     env4 = _env(32, 20)
     with pytest.raises(ValueError):
         env4.rollout_gated(act, b["gate_act"][:1], b["gate_obs"], b["claim"][0:1], wa, None, b["out_a"])
+
+
+@pytest.mark.parametrize("n_ue", [61, 64])
+def test_gated_rollout_refuses_more_nodes_than_lanes(n_ue):
+    """n_ue + n_bs > 64: the encoder gives each observation node one lane of one wavefront (as uavagent_first_layer_from_obs_f32, which
+    refuses the same shapes).  Refused on the host, before any launch: the state is untouched and the handle steps on."""
+    torch = _torch()
+    from drl_uav_cellularnet_amd import UavEnvError
+
+    n, T, hid = 19, 2, 64
+    env = _env(n, n_ue)                                               # a packed handle with n_bs == 4: everything else is in order
+    ref = env.clone()
+    state = env.get_state()
+    wa, ba, wc, bc = _tables(torch, env, hid, 3)
+    act = torch.zeros((T, n), dtype=torch.int64, device=env.device)
+    b = _buffers(torch, env, T, hid)
+    with pytest.raises(UavEnvError, match=r"rollout_gated: .*n_ue \+ n_bs <= 64 \(one lane per node\)"):
+        env.rollout_gated(act, b["gate_act"], b["gate_obs"], b["claim"][0:1], wa, ba, b["out_a"], wc, bc, b["out_c"], idx_out=b["idx"], reward_out=b["rew"])
+    torch.cuda.synchronize()
+    assert np.array_equal(env.get_state(), state) and env.device_error() == 0
+    assert bool(torch.isnan(b["out_a"]).all()) and bool((b["idx"] == -7).all()) and bool((b["gate_obs"] == 0).all())    # nothing ran
+    a = torch.full((n,), 7, dtype=torch.int64, device=env.device)
+    env.step(a); ref.step(a)
+    assert np.array_equal(env.get_state(), ref.get_state())
+    for k, v in ref.out.items():
+        assert torch.equal(env.out[k], v), k
 
 
 def _head_weights(torch, seed):
