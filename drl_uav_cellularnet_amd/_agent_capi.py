@@ -18,7 +18,8 @@ EXPORTS = ("uavagent_abi_version", "uavagent_last_error", "uavagent_sparse_rows_
            "uavagent_rows_grad_workspace_bytes", "uavagent_rows_grad_f32", "uavagent_rows_grad_sort", "uavagent_rows_grad_sums_f32", "uavagent_nstep_returns_f32", "uavagent_rmsprop_tf1",
            "uavagent_gemm_rows_f32", "uavagent_gemm_rows_workspace_bytes", "uavagent_gemm_tn_workspace_bytes", "uavagent_gemm_tn_f32",
            "uavagent_debug_tn_plan_check", "uavagent_actor_head_f32", "uavagent_actor_head_gated_f32", "uavagent_gate_prepare",
-           "uavagent_device_error", "uavagent_device_error_clear", "uavagent_actor_head_greedy_f32", "uavagent_argmax_rows_f32")
+           "uavagent_device_error", "uavagent_device_error_clear", "uavagent_actor_head_greedy_f32", "uavagent_argmax_rows_f32",
+           "uavagent_choose_factored_f32", "uavagent_loss_grad_factored_workspace_bytes", "uavagent_a2c_loss_grad_factored")
 ABI_VERSION = 5
 
 _lib = None
@@ -59,7 +60,7 @@ class _ProfiledLib:
 
     def __getattr__(self, name):
         fn = getattr(self._lib, name)
-        if not name.endswith(("_f32", "_grad", "_bwd", "_tf1", "_sort", "_indices", "_actions")) or name.endswith("_bytes"):
+        if not name.endswith(("_f32", "_grad", "_bwd", "_tf1", "_sort", "_indices", "_actions", "_grad_factored")) or name.endswith("_bytes"):
             return fn
 
         def timed(*args):
@@ -121,6 +122,8 @@ def load():
         "uavagent_actor_head_gated_f32": [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _I64, _P, _P, _P, _P, C.c_uint32, _P],
         "uavagent_actor_head_greedy_f32": [_P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _I64, _P, _P],
         "uavagent_argmax_rows_f32": [_P, _I64, _I64, _I32, _P, _P],
+        "uavagent_choose_factored_f32": [_P, _I64, _P, _I64, _I32, _I32, _P, _P, _P, _P],
+        "uavagent_a2c_loss_grad_factored": [_P, _I64, _P, _P, _P, _I64, _I32, _I32, _F, _P, _P, _P, _P, _P],
         "uavagent_gate_prepare": [],
         "uavagent_device_error": [C.POINTER(C.c_uint32)],
         "uavagent_device_error_clear": [],
@@ -131,6 +134,8 @@ def load():
         fn.argtypes = args
     lib.uavagent_loss_grad_workspace_bytes.restype = C.c_size_t
     lib.uavagent_loss_grad_workspace_bytes.argtypes = [_I32]
+    lib.uavagent_loss_grad_factored_workspace_bytes.restype = C.c_size_t
+    lib.uavagent_loss_grad_factored_workspace_bytes.argtypes = [_I32, _I32]
     lib.uavagent_relu6_bwd_workspace_bytes.restype = C.c_size_t
     lib.uavagent_relu6_bwd_workspace_bytes.argtypes = [_I32]
     lib.uavagent_rows_grad_workspace_bytes.restype = C.c_size_t
@@ -469,6 +474,59 @@ def argmax_rows(logits, out=None):
         rc = load().uavagent_argmax_rows_f32(_ptr(logits), ld, N, A, _ptr(out), _stream(logits.device))
     _check(rc, "uavagent_argmax_rows_f32")
     return out
+
+
+def choose_factored(logits, uniforms, n_heads, n_act, out=None, digits_out=None, prob_out=None):
+    """One n_act-way choice per (row, head) of logits float32 [N, n_heads * n_act] (possibly a column slice of a wider buffer) and the
+    row's joint action (uavagent_choose_factored_f32): uniforms float32 [N, n_heads] = the inverse-CDF draw per head, None = the greedy
+    digit.  digits_out int8 [N, n_heads] and prob_out float32 [N, n_heads * n_act] (the per-head softmax) are optional.  Returns int64 [N]."""
+    ld = _row_stride(logits, "logits")
+    N, C_ = logits.shape
+    B, A_ = int(n_heads), int(n_act)
+    if C_ != B * A_:
+        raise UavAgentError("choose_factored: logits must have n_heads * n_act = %d columns, got %d" % (B * A_, C_))
+    if uniforms is not None:
+        _f32c(uniforms, "uniforms")
+        if uniforms.numel() != N * B:
+            raise UavAgentError("choose_factored: one uniform per (row, head)")
+    if out is None:
+        out = torch.empty((N,), dtype=torch.int64, device=logits.device)
+    elif out.dtype != torch.int64 or out.numel() != N or not out.is_contiguous():
+        raise UavAgentError("choose_factored: out must be a contiguous int64 [N] tensor")
+    if digits_out is not None and (digits_out.dtype != torch.int8 or digits_out.numel() != N * B or not digits_out.is_contiguous()):
+        raise UavAgentError("choose_factored: digits_out must be a contiguous int8 [N, n_heads] tensor")
+    if prob_out is not None:
+        _f32c(prob_out, "prob_out")
+        if prob_out.numel() != N * C_:
+            raise UavAgentError("choose_factored: prob_out must be [N, n_heads * n_act]")
+    _same_device("choose_factored", logits, uniforms, out, digits_out, prob_out)
+    with torch.cuda.device(logits.device):
+        rc = load().uavagent_choose_factored_f32(_ptr(logits), ld, _ptr(uniforms), N, B, A_, _ptr(out), _ptr(digits_out), _ptr(prob_out),
+                                                 _stream(logits.device))
+    _check(rc, "uavagent_choose_factored_f32")
+    return out
+
+
+def loss_grad_factored_workspace(n_heads, n_act, device):
+    n = load().uavagent_loss_grad_factored_workspace_bytes(int(n_heads), int(n_act))
+    if n == 0:
+        raise UavAgentError("uavagent_loss_grad_factored_workspace_bytes: need 1 <= n_heads <= 32 and 2 <= n_act <= 8")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def a2c_loss_grad_factored(logits, v, target, actions, n_heads, n_act, beta, dv_out, dbias_out, loss_out, ws):
+    """a2c_loss_grad for the factorised head: in place, logits [M, n_heads * n_act] <- d a_loss / d logits; actions are JOINT actions
+    int64 [M].  loss_out: float64 [3] = (a_loss, c_loss, sum dv)."""
+    ld = _row_stride(logits, "logits")
+    M, C_ = logits.shape
+    if C_ != int(n_heads) * int(n_act):
+        raise UavAgentError("a2c_loss_grad_factored: logits must have n_heads * n_act = %d columns, got %d" % (int(n_heads) * int(n_act), C_))
+    if actions.dtype != torch.int64 or actions.numel() != M or not actions.is_contiguous():
+        raise UavAgentError("a2c_loss_grad_factored: actions must be a contiguous int64 [M] tensor")
+    with torch.cuda.device(logits.device):
+        rc = load().uavagent_a2c_loss_grad_factored(_ptr(logits), ld, _ptr(v), _ptr(target), _ptr(actions), M, int(n_heads), int(n_act),
+                                                    float(beta), _ptr(dv_out), _ptr(dbias_out), _ptr(loss_out), _ptr(ws), _stream(logits.device))
+    _check(rc, "uavagent_a2c_loss_grad_factored")
 
 
 def gate_prepare():

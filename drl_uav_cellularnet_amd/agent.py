@@ -963,7 +963,7 @@ class A2CRunner:
         for s in range(0, M, self.update_chunk):
             e = min(M, s + self.update_chunk)
             a_prob, v = self._reference_forward(idx[s:e])
-            a_loss, c_loss = a2c_losses(a_prob, v, act[s:e], target[s:e], self.beta)
+            a_loss, c_loss = self._losses(a_prob, v, act[s:e], target[s:e])
             w = (e - s) / M                                   # mean over the whole batch = weighted mean of chunks
             ((a_loss + c_loss) * w).backward()                # disjoint parameter sets: same grads as two backward()s
             a_tot += float(a_loss.detach()) * w
@@ -980,6 +980,10 @@ class A2CRunner:
     def _reference_forward(self, idx):
         """(a_prob, v) with autograd, for update_reference."""
         return self.net(idx)
+
+    def _losses(self, a_prob, v, actions, v_target):
+        """(a_loss, c_loss) of a chunk, for update_reference (a runner with another policy head states its own)."""
+        return a2c_losses(a_prob, v, actions, v_target, self.beta)
 
     def train_rollout(self):
         stats = self.update(*self.collect())

@@ -23,7 +23,7 @@ ENV_EXTRA = {"uavenv_gated.hip": [os.path.join(PKG_DIR, "csrc", f) for f in ("ua
 DEPS = ENV_SRCS + ENV_HDRS + [h for hs in ENV_EXTRA.values() for h in hs]
 LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB = os.path.join(LIB_DIR, "libuavenv.so")
-AGENT_SRCS = [os.path.join(PKG_DIR, "csrc", f) for f in ("agent_kernels.hip", "agent_learner.hip", "agent_gemm.hip")]
+AGENT_SRCS = [os.path.join(PKG_DIR, "csrc", f) for f in ("agent_kernels.hip", "agent_learner.hip", "agent_gemm.hip", "agent_factored.hip")]
 AGENT_SRC = AGENT_SRCS[0]
 AGENT_DEPS = AGENT_SRCS + [os.path.join(PKG_DIR, "csrc", f) for f in ("agent_common.h", "rollout_gate.h")] + [os.path.join(ROOT, "include", "uavagent.h")]
 AGENT_LIB = os.path.join(LIB_DIR, "libuavagent.so")

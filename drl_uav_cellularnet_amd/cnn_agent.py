@@ -275,7 +275,28 @@ class CnnA2CRunner(A2CRunner):
         K.conv1_from_idx(self.idx_buf[t], self.B, self.G, net.a_conv1_k, net.a_conv1_b, r["c1"])
         _trunk_tail(net, "a", r["c1"], r["c2"], r["c3"], r["h"], r["ws"])
         A.gemm_rows(r["h"], self._wt["ap_t"], r["logits_pad"], w_transposed=True, bias=self._wt["ap_b"])
-        A.sample_actions(r["logits_pad"][:, :net.n_action], self.u_buf[t], out=self.act_buf[t])
+        self._draw(r["logits_pad"][:, :net.n_action], t)
+
+    # ---- what depends on the form of the policy head (factored.FactoredCnnA2CRunner states its own) ----------------------------------
+    def _draw(self, logits, t):
+        """Step t's actions from its logits (GPU), into act_buf[t]."""
+        from . import _agent_capi as A
+
+        A.sample_actions(logits, self.u_buf[t], out=self.act_buf[t])
+
+    def _draw_reference(self, t):
+        """Step t's actions on the CPU path: the plain PyTorch forward and draw."""
+        return sample_actions(self.net.actor_only(self.idx_buf[t]), uniforms=self.u_buf[t])
+
+    def _loss_workspace(self):
+        from . import _agent_capi as A
+
+        return A.loss_grad_workspace(self.net.n_action, self.dev)
+
+    def _loss_grad(self, logits, v, target, actions, dv, dbias, loss, ws):
+        from . import _agent_capi as A
+
+        A.a2c_loss_grad(logits, v, target, actions, self.beta, dv, dbias, loss, ws)
 
     @torch.no_grad()
     def collect(self):
@@ -290,7 +311,7 @@ class CnnA2CRunner(A2CRunner):
             if cuda:
                 self._policy_step(t)
             else:
-                self.act_buf[t] = sample_actions(self.net.actor_only(self.idx_buf[t]), uniforms=self.u_buf[t])
+                self.act_buf[t] = self._draw_reference(t)
             env.step(self.act_buf[t], reward_out=self.rew_buf[t])
             self._indices_into(self.idx_buf[t + 1])
         done = env.out["done"].bool()
@@ -310,7 +331,7 @@ class CnnA2CRunner(A2CRunner):
              "dflat": _act(chunk, G - 12, dev), "dc2": _act(chunk, G - 8, dev), "dc1": _act(chunk, G - 4, dev),
              "loss": torch.zeros(3, dtype=torch.float64, device=dev), "loss_sum": torch.zeros(3, dtype=torch.float64, device=dev),
              "t_ap_k": f(DENSE, na), "t_ap_b": f(na), "t_d2_b": f(DENSE), "t_v_k": f(DENSE),
-             "ws_loss": A.loss_grad_workspace(na, dev), "ws_relu": A.relu6_bwd_workspace(DENSE, dev), "ws": {}}
+             "ws_loss": self._loss_workspace(), "ws_relu": A.relu6_bwd_workspace(DENSE, dev), "ws": {}}
         for p in ("a", "c"):
             b[p] = {"c1": _act(chunk, G - 4, dev), "c2": _act(chunk, G - 8, dev), "c3": _act(chunk, G - 12, dev), "h": f(chunk, DENSE)}
         self._upd = b
@@ -380,7 +401,7 @@ class CnnA2CRunner(A2CRunner):
             A.gemm_rows(ta["h"][:mc], wt["ap_t"], lp, w_transposed=True, bias=wt["ap_b"])
             v, dv = b["v"][:mc], b["dv"][:mc]
             A.rowdot(tc["h"][:mc], net.c_v_k.reshape(-1), net.c_v_b, v)
-            A.a2c_loss_grad(lp[:, :na], v, target[s:e], act[s:e], self.beta, dv, b["t_ap_b"], b["loss"], b["ws_loss"])
+            self._loss_grad(lp[:, :na], v, target[s:e], act[s:e], dv, b["t_ap_b"], b["loss"], b["ws_loss"])
             b["loss_sum"].add_(b["loss"], alpha=w)
             lp.mul_(w)
             dv.mul_(w)

@@ -38,7 +38,8 @@ class GreedyEvaluator:
 
     Routing: an ACNet of the reference's widths (200 hidden units, 577..640 actions) takes the fused greedy head
     (uavagent_actor_head_greedy_f32); any other ACNet width and CnnACNet compute their logits as their rollout does and pick with
-    uavagent_argmax_rows_f32.  The MLP's first layer comes straight from the compact observation (uavagent_first_layer_from_obs_f32,
+    uavagent_argmax_rows_f32; a factored.FactoredCnnACNet takes the CNN route with the greedy digit per UAV
+    (uavagent_choose_factored_f32 without uniforms) in its place.  The MLP's first layer comes straight from the compact observation (uavagent_first_layer_from_obs_f32,
     actor table only), which bounds it to nBS + nUE <= 64 like the index-list gather.  ``hist`` = (lo, hi, bins) of the serving-SINR histogram in dB."""
 
     def __init__(self, env, net, hist=(-50.0, 100.0, 150)):
@@ -52,7 +53,12 @@ class GreedyEvaluator:
         self.acc = env.eval_accumulators(hist)
         N, U, B = env.n_envs, env.nUE, env.nBS
         NA = int(net.n_action)
-        if NA != env.action_space_dim:
+        self._factored = bool(getattr(net, "factored", False))     # factored.FactoredCnnACNet: n_action = heads x digits, not joint actions
+        if self._factored:
+            if net.n_heads != B or net.joint_actions != env.action_space_dim:
+                raise ValueError("the net has %d heads of %d actions, the env %d UAVs and %d joint actions" % (
+                    net.n_heads, net.n_act, B, env.action_space_dim))
+        elif NA != env.action_space_dim:
             raise ValueError("the net has %d actions, the env %d" % (NA, env.action_space_dim))
         f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.dev)
         self._ldl = (NA + 15) // 16 * 16
@@ -113,7 +119,10 @@ class GreedyEvaluator:
             K.conv1_from_idx(self._idx, env.nBS, env.grid_n, net.a_conv1_k, net.a_conv1_b, self._c[0])
             _trunk_tail(net, "a", self._c[0], self._c[1], self._c[2], self._h1, self._ws)
             A.gemm_rows(self._h1, self._apt, self._logits_pad, w_transposed=True, bias=self._apb)
-            A.argmax_rows(self._logits_pad[:, :NA], out=act)
+            if self._factored:
+                A.choose_factored(self._logits_pad[:, :NA], None, net.n_heads, net.n_act, out=act)
+            else:
+                A.argmax_rows(self._logits_pad[:, :NA], out=act)
             return
         A.first_layer_from_obs(obs, env.grid_n, net.a_w1, net.a_b1, None, None, self._h1, None)      # actor table only, relu6
         if self.kind == "mlp_fused":

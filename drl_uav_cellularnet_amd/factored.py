@@ -1,0 +1,175 @@
+"""Factorised per-UAV policy head for the CNN actor-critic: one n_act-way softmax per UAV instead of the reference's one softmax over the
+N_A = 5^nBS joint actions (main.py:143-156), which cannot be built beyond a handful of UAVs (1.5e11 logits at 16).  An extension beyond
+the reference, like the search policies; DESIGN.md section 17.
+
+  layout    A = n_act (5), B = n_heads = nBS.  Logits z [M, B*A]; head b = columns [b*A, (b+1)*A); p_b = softmax(z_b); the joint
+            probability is the product over the heads.
+  action    a = sum_b d_b * A^(B-1-b), UAV 0 the most significant digit: Decimal_to_Base_N (ue_mobility.py:310-336), the order every
+            policy of this package uses (heuristics.coordinate_rule).
+  draw      per head, the rule of agent.sample_actions: the first digit d with cumsum(p_b)[d] > u[row, b] * cumsum(p_b)[-1].
+  loss      main.py:64-74 with the product policy, the reference's + 1e-5 once per head:
+            logp = sum_b log(p_b[d_b] + 1e-5);  H = sum_b -sum_j p_bj log(p_bj + 1e-5);  a_loss = mean(-(beta * H + logp * td)).
+            With B = 1 this is agent.a2c_losses term for term.
+
+On the GPU the draw, the greedy choice and the loss gradient are libuavagent.so's (csrc/agent_factored.hip); everything else -- trunks,
+head GEMMs, RMSProp, rollout, checkpoint -- is cnn_agent's, unchanged.
+"""
+import torch
+
+from .agent import ENTROPY_BETA
+from .cnn_agent import CnnA2CRunner, CnnACNet, _logits_cuda, _trunks_cuda, _value_cuda
+
+N_ACT = 5     # mobile_env.py:21
+
+
+def joint_to_digits(actions, n_heads, n_act=N_ACT):
+    """Joint actions int64 [...] -> digits int64 [..., n_heads], d_b = (a // n_act^(n_heads-1-b)) mod n_act (integer arithmetic: exact for
+    every action below 2^63)."""
+    a = torch.as_tensor(actions, dtype=torch.int64)
+    out = []
+    for _ in range(int(n_heads)):
+        out.append(a % n_act)
+        a = a // n_act
+    return torch.stack(out[::-1], dim=-1)
+
+
+def digits_to_joint(digits, n_act=N_ACT):
+    """Digits [..., n_heads] -> joint actions int64 [...], Horner's rule in int64: exact up to n_act^n_heads - 1 <= 2^63 - 1 (5^27 - 1)."""
+    d = torch.as_tensor(digits).to(torch.int64)
+    a = torch.zeros(d.shape[:-1], dtype=torch.int64, device=d.device)
+    for b in range(d.shape[-1]):
+        a = a * n_act + d[..., b]
+    return a
+
+
+def _heads(head_prob):
+    if head_prob.dim() != 3:
+        raise ValueError("per-head probabilities must be [M, n_heads, n_act]")
+    return head_prob
+
+
+def sample_actions_factored(head_prob, uniforms, return_digits=False):
+    """One joint action per row of head_prob [M, B, A] with the uniforms [M, B]: agent.sample_actions per head (cdf = cumsum(p_b); the
+    first digit with cdf > u * cdf[-1], i.e. searchsorted(side='right'); clamped to A - 1), the digits composed by digits_to_joint."""
+    p = _heads(head_prob)
+    M, B, A = p.shape
+    cdf = p.cumsum(dim=2)
+    u = uniforms.reshape(M, B, 1).to(p.dtype) * cdf[:, :, -1:]
+    d = torch.searchsorted(cdf, u, right=True).squeeze(2).clamp_(max=A - 1)
+    a = digits_to_joint(d, A)
+    return (a, d) if return_digits else a
+
+
+def a2c_losses_factored(head_prob, v, actions, v_target, beta=ENTROPY_BETA):
+    """(a_loss, c_loss) of main.py:64-74 for the product policy.  head_prob [M, B, A], v and v_target [M, 1], actions = JOINT actions [M]."""
+    p = _heads(head_prob)
+    M, B, A = p.shape
+    d = joint_to_digits(actions.reshape(-1), B, A)                              # [M, B]
+    td = v_target - v                                                           # :64
+    c_loss = (td ** 2).mean()                                                   # :66
+    log_prob = torch.log(p.gather(2, d.unsqueeze(2)).squeeze(2) + 1e-5).sum(dim=1, keepdim=True)   # :69, one + 1e-5 per head
+    exp_v = log_prob * td.detach()                                              # :70
+    entropy = -(p * torch.log(p + 1e-5)).sum(dim=(1, 2)).reshape(M, 1)          # :71-72, the entropy of a product = the sum over heads
+    a_loss = (-(beta * entropy + exp_v)).mean()                                 # :73-74
+    return a_loss, c_loss
+
+
+def loss_grad_factored_reference(logits, v, v_target, actions, n_heads, n_act=N_ACT, beta=ENTROPY_BETA):
+    """The closed-form gradient uavagent_a2c_loss_grad_factored implements, in PyTorch (dtype of logits).  With p = softmax(z_b), e = 1e-5:
+        gp_j = beta (log(p_j + e) + p_j / (p_j + e)) - [j == d_b] td / (p_{d_b} + e);   d a_loss / d z_j = p_j (gp_j - sum_i p_i gp_i) / M
+    head by head (the heads are separate terms of the loss), d c_loss / d v = -2 td / M.
+    -> (dlogits [M, B*A], dv [M], dbias [B*A] = column sums of dlogits, (a_loss, c_loss, sum(dv)))."""
+    M, B, A = logits.shape[0], int(n_heads), int(n_act)
+    z = logits.reshape(M, B, A)
+    p = torch.softmax(z, dim=2)
+    n_joint = A ** B
+    d = joint_to_digits(actions.reshape(-1).clamp(0, n_joint - 1), B, A)        # the kernel's clamp: no action is used as an index
+    td = (v_target.reshape(M) - v.reshape(M)).to(z.dtype)
+    lp = torch.log(p + 1e-5)
+    gp = beta * (lp + p / (p + 1e-5))
+    hot = torch.zeros_like(p).scatter_(2, d.unsqueeze(2), 1.0)
+    gp = gp - hot * (td.reshape(M, 1, 1) / (p + 1e-5))
+    dot = (p * gp).sum(dim=2, keepdim=True)
+    dz = (p * (gp - dot) / M).reshape(M, B * A)
+    dv = -2.0 * td / M
+    h = -(p * lp).sum(dim=(1, 2))
+    logp = (lp * hot).sum(dim=(1, 2))
+    a_loss = (-(beta * h + logp * td)).mean()
+    return dz, dv, dz.sum(dim=0), (a_loss, (td ** 2).mean(), dv.sum())
+
+
+class FactoredCnnACNet(CnnACNet):
+    """CnnACNet(n_bs, grid_n, n_bs * n_act) whose policy output is read as n_bs heads of n_act logits.  Parameter keys and shapes are
+    CnnACNet's (the head is [100, n_bs * n_act]), so agent.save_actor_npz / load_actor_npz serve it; ``forward``, ``actor_only`` and
+    ``forward_reference`` return the per-head probabilities [M, n_bs * n_act] (every run of n_act sums to 1)."""
+
+    factored = True
+
+    def __init__(self, n_bs, grid_n, n_act=N_ACT, seed=6):
+        super().__init__(n_bs, grid_n, int(n_bs) * int(n_act), seed=seed)
+        self.n_heads, self.n_act = int(n_bs), int(n_act)
+        self.joint_actions = self.n_act ** self.n_heads
+
+    def _head_softmax(self, logits):
+        M = logits.shape[0]
+        return torch.softmax(logits.reshape(M, self.n_heads, self.n_act), dim=-1).reshape(M, self.n_action)
+
+    def forward_reference(self, dense_obs):
+        ha, hc = self._trunk_reference(dense_obs, "a"), self._trunk_reference(dense_obs, "c")
+        return self._head_softmax(ha @ self.a_ap_k + self.a_ap_b), hc @ self.c_v_k + self.c_v_b
+
+    def forward(self, idx):
+        if idx.is_cuda:
+            ha, hc = _trunks_cuda(self, idx, ("a", "c"))
+            return self._head_softmax(_logits_cuda(self, ha)), _value_cuda(self, hc)
+        return self.forward_reference(self._dense(idx))
+
+    def actor_only(self, idx):
+        if idx.is_cuda:
+            (ha,) = _trunks_cuda(self, idx, ("a",))
+            return self._head_softmax(_logits_cuda(self, ha))
+        ha = self._trunk_reference(self._dense(idx), "a")
+        return self._head_softmax(ha @ self.a_ap_k + self.a_ap_b)
+
+
+class FactoredCnnA2CRunner(CnnA2CRunner):
+    """CnnA2CRunner with the factorised head: one uniform per (step, env, UAV), the draw by uavagent_choose_factored_f32 (GPU) or
+    sample_actions_factored (CPU), act_buf holding JOINT actions as the env takes them, and the factored loss in both update forms.
+    Serves every shape the env and the CNN's conv1 gather serve (up to 16 UAVs, 256 nodes)."""
+
+    NET_KIND = "cnn-factored"
+
+    def __init__(self, env, net=None, rollout=50, *, seed=6, **kw):
+        if net is None:
+            net = FactoredCnnACNet(env.nBS, env.grid_n, env.N_ACT, seed=seed)
+        if not isinstance(net, FactoredCnnACNet):
+            raise TypeError("FactoredCnnA2CRunner trains a FactoredCnnACNet")
+        if net.n_heads != env.nBS or net.joint_actions != env.action_space_dim:
+            raise ValueError("the net has %d heads of %d actions, the env %d UAVs and %d joint actions" % (
+                net.n_heads, net.n_act, env.nBS, env.action_space_dim))
+        super().__init__(env, net=net, rollout=rollout, seed=seed, **kw)
+        self.u_buf = torch.empty((self.T, env.n_envs, net.n_heads), dtype=torch.float32, device=self.dev)
+
+    def _draw(self, logits, t):
+        from . import _agent_capi as A
+
+        A.choose_factored(logits, self.u_buf[t], self.net.n_heads, self.net.n_act, out=self.act_buf[t])
+
+    def _draw_reference(self, t):
+        net = self.net
+        prob = net.actor_only(self.idx_buf[t]).reshape(-1, net.n_heads, net.n_act)
+        return sample_actions_factored(prob, self.u_buf[t])
+
+    def _loss_workspace(self):
+        from . import _agent_capi as A
+
+        return A.loss_grad_factored_workspace(self.net.n_heads, self.net.n_act, self.dev)
+
+    def _loss_grad(self, logits, v, target, actions, dv, dbias, loss, ws):
+        from . import _agent_capi as A
+
+        A.a2c_loss_grad_factored(logits, v, target, actions, self.net.n_heads, self.net.n_act, self.beta, dv, dbias, loss, ws)
+
+    def _losses(self, a_prob, v, actions, v_target):
+        net = self.net
+        return a2c_losses_factored(a_prob.reshape(-1, net.n_heads, net.n_act), v, actions, v_target, self.beta)

@@ -198,6 +198,32 @@ int uavagent_debug_tn_plan_check(int32_t plan);
 int uavagent_gemm_tn_f32(const float *a, const float *b, int64_t m_rows, int32_t n_i, int32_t n_j, int64_t ldb, float *c, int64_t ldc,
                          float *dbias_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- The factorised policy head (csrc/agent_factored.hip; additive to ABI 5, the number stays).  An extension beyond the reference, whose
+ * one softmax over N_A = 5^nBS joint actions (main.py:143-156) cannot be built for 16 UAVs: one n_act-way softmax PER UAV instead.  logits f32
+ * [rows, n_heads * n_act] with row stride ld_logits floats, head b in columns [b * n_act, (b + 1) * n_act), p_b = softmax of that run; the joint
+ * probability is the product over the heads and the joint action  a = sum_b d_b * n_act^(n_heads - 1 - b)  (UAV 0 the most significant digit:
+ * Decimal_to_Base_N, ue_mobility.py:310-336).  1 <= n_heads <= 32, 2 <= n_act <= 8, n_act^n_heads <= 2^63 - 1 (5^27 fits, 5^28 does not),
+ * ld_logits >= n_heads * n_act; columns beyond n_heads * n_act of a row are neither read nor written.  Zero rows: no launch. ---- */
+
+/* One digit per (row, head) and the row's joint action.  uniforms f32 [n_rows, n_heads] in [0, 1): the inverse-CDF draw of
+ * uavagent_sample_actions per head (float32 softmax with the head's maximum subtracted; the first digit d with cumsum(p_b)[d] > u * cumsum(p_b)[-1],
+ * else n_act - 1); uniforms == NULL: the greedy digit, the rule of uavagent_argmax_rows_f32 per head.  actions_out int64 [n_rows] (required),
+ * composed with integer arithmetic only; digits_out int8 [n_rows, n_heads] or NULL; prob_out f32 [n_rows, n_heads * n_act] contiguous or NULL (the
+ * per-head softmax). */
+int uavagent_choose_factored_f32(const float *logits, int64_t ld_logits, const float *uniforms, int64_t n_rows, int32_t n_heads,
+                                 int32_t n_act, int64_t *actions_out, int8_t *digits_out, float *prob_out, void *stream);
+
+/* uavagent_a2c_loss_grad with the product policy: the reference's + 1e-5 inside its one log becomes one per head,
+ *   td = v_target - v;  c_loss = mean(td^2);  a_loss = mean(-(beta * sum_b H_b + td * sum_b log(p_b[d_b] + 1e-5))),  H_b = -sum_j p_bj log(p_bj + 1e-5),
+ * d_b = digit b of the row's action clamped to [0, n_act^n_heads - 1] (no action value is used as an index).  At n_heads = 1 this is
+ * uavagent_a2c_loss_grad's loss term for term.  IN / OUT as there: logits_inout -> d(a_loss)/d(logits); dv_out [m_rows]; dbias_out
+ * [n_heads * n_act] column sums; loss_out double[3] = {a_loss, c_loss, sum(dv)}.  Library expf / logf; the sums go through `workspace`
+ * (8-byte aligned, uavagent_loss_grad_factored_workspace_bytes bytes; 0 = shape not served) in a fixed order: bit-reproducible. */
+size_t uavagent_loss_grad_factored_workspace_bytes(int32_t n_heads, int32_t n_act);
+int uavagent_a2c_loss_grad_factored(float *logits_inout, int64_t ld_logits, const float *v, const float *v_target, const int64_t *actions,
+                                    int64_t m_rows, int32_t n_heads, int32_t n_act, float beta, float *dv_out, float *dbias_out,
+                                    double *loss_out, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,9 @@ collect() and an update, then the same rollout and update through the PyTorch re
 autograd) at the same size.  Prints one JSON line: env-steps/s, ms per rollout and per update, per-kernel ms with TFLOP/s from the
 FLOP formulas below, and their fraction of the 157 TFLOP/s float32 MFMA peak.
 
-  python tools/bench_cnn.py [--envs 8192] [--rollout 50] [--timed 2] [--no-reference]"""
+  python tools/bench_cnn.py [--envs 8192] [--rollout 50] [--timed 2] [--no-reference]
+  python tools/bench_cnn.py --factored --n-bs 16 --n-ue 200 --envs 1024      # one 5-way head per UAV (factored.FactoredCnnA2CRunner); the
+                                                                             # line is also written to profiles/cnn_factored_a2c_bench.json"""
 import argparse
 import json
 import os
@@ -24,6 +26,8 @@ def main():
     ap.add_argument("--n-ue", type=int, default=40)
     ap.add_argument("--update-chunk", type=int, default=4096)
     ap.add_argument("--no-reference", action="store_true")
+    ap.add_argument("--factored", action="store_true", help="the factorised head (one 5-way softmax per UAV) instead of the joint one")
+    ap.add_argument("--n-bs", type=int, default=4, help="UAVs; more than a handful need --factored (the joint head has 5^n_bs logits)")
     a = ap.parse_args()
     import torch
 
@@ -32,8 +36,13 @@ def main():
     from drl_uav_cellularnet_amd.cnn_agent import CnnA2CRunner
 
     G, N, T = 100, a.envs, a.rollout
-    env = BatchedMobiEnv(N, nBS=4, nUE=a.n_ue, grid_n=G, device="cuda:0")
-    runner = CnnA2CRunner(env, rollout=T, update_chunk=a.update_chunk)
+    env = BatchedMobiEnv(N, nBS=a.n_bs, nUE=a.n_ue, grid_n=G, device="cuda:0")
+    if a.factored:
+        from drl_uav_cellularnet_amd.factored import FactoredCnnA2CRunner
+
+        runner = FactoredCnnA2CRunner(env, rollout=T, update_chunk=a.update_chunk)
+    else:
+        runner = CnnA2CRunner(env, rollout=T, update_chunk=a.update_chunk)
     ev = lambda: torch.cuda.Event(enable_timing=True)
 
     def one(fn_collect, fn_update):
@@ -52,8 +61,14 @@ def main():
     upd_ms = sum(t[1] for t in times) / len(times)
     # per-kernel figures: one more rollout + update with every libuavcnn launch bracketed by events
     K.profile_begin()
+    if a.factored:                                                      # the head's own launches too: the two factored kernels' share
+        from drl_uav_cellularnet_amd import _agent_capi as A
+
+        A.profile_begin()
     runner.update_fused(*runner.collect())
     prof = K.profile_end()
+    if a.factored:
+        prof.update(A.profile_end())
     Ho = {"conv1": G - 4, "conv2": G - 8, "conv3": G - 12}
     M_roll, M_upd = N * T, N * T                                        # rows the rollout and the update push through each layer
     # FLOP per sample of each layer (G = 100: conv2 42.3 M, conv3 38.7 M, dense 15.5 M; dX conv3 42.3 M, conv2 46.1 M; dW conv3 38.7, conv2 42.3)
@@ -75,7 +90,7 @@ def main():
             tf = flops[k] / (ms * 1e-3) / 1e12
             row.update({"tflops": round(tf, 2), "of_f32_mfma_peak": round(tf * 1e12 / PEAK_F32_MFMA, 3)})
         kernels[k] = row
-    out = {"bench": "cnn_a2c", "envs": N, "rollout": T, "timed_rollouts": a.timed, "n_ue": a.n_ue, "grid": G,
+    out = {"bench": "cnn_factored_a2c" if a.factored else "cnn_a2c", "envs": N, "rollout": T, "timed_rollouts": a.timed, "n_bs": a.n_bs, "n_ue": a.n_ue, "grid": G,
            "update_chunk": a.update_chunk, "env_steps_per_s": round(N * T / ((roll_ms + upd_ms) * 1e-3), 1),
            "rollout_ms": round(roll_ms, 2), "update_ms": round(upd_ms, 2), "kernels_ms_one_rollout_plus_update": kernels}
     if not a.no_reference:
@@ -85,6 +100,9 @@ def main():
         out.update({"reference_rollout_ms": round(rt[0], 2), "reference_update_ms": round(rt[1], 2),
                     "reference_env_steps_per_s": round(N * T / ((rt[0] + rt[1]) * 1e-3), 1)})
     print(json.dumps(out), flush=True)
+    if a.factored:
+        with open(os.path.join(ROOT, "profiles", "cnn_factored_a2c_bench.json"), "w") as f:
+            f.write(json.dumps(out) + "\n")
 
 
 def _collect_reference(runner, torch):
@@ -97,8 +115,14 @@ def _collect_reference(runner, torch):
         runner.idx_buf[0].copy_(runner.idx_buf[T])
         for t in range(T):
             ha = net._trunk_reference(net._dense(runner.idx_buf[t]), "a")
-            prob = torch.softmax(ha @ net.a_ap_k + net.a_ap_b, dim=-1)
-            runner.act_buf[t] = sample_actions(prob, uniforms=runner.u_buf[t])
+            logits = ha @ net.a_ap_k + net.a_ap_b
+            if getattr(net, "factored", False):
+                from drl_uav_cellularnet_amd.factored import sample_actions_factored
+
+                prob = torch.softmax(logits.reshape(-1, net.n_heads, net.n_act), dim=-1)
+                runner.act_buf[t] = sample_actions_factored(prob, runner.u_buf[t])
+            else:
+                runner.act_buf[t] = sample_actions(torch.softmax(logits, dim=-1), uniforms=runner.u_buf[t])
             env.step(runner.act_buf[t], reward_out=runner.rew_buf[t])
             runner._indices_into(runner.idx_buf[t + 1])
         done = env.out["done"].bool()

@@ -47,7 +47,12 @@ def run_test(trace, out_dir, actor_npz=None, max_step=2000, n_bs=4, n_ue=40, gri
 
     os.makedirs(out_dir, exist_ok=True)
     test_env = MobiEnvironment(n_bs, n_ue, grid, "read_trace", trace, seed=seed)       # main_test.py:51
-    if net == "cnn":                                                                     # netType='CNN' (main.py:88-140)
+    factored = net == "cnn-factored"
+    if factored:                                                                         # one 5-way head per UAV (factored.py)
+        from drl_uav_cellularnet_amd.factored import FactoredCnnACNet, digits_to_joint
+
+        net = FactoredCnnACNet(n_bs, grid)
+    elif net == "cnn":                                                                   # netType='CNN' (main.py:88-140)
         from drl_uav_cellularnet_amd.cnn_agent import CnnACNet
 
         net = CnnACNet(n_bs, grid, test_env.action_space_dim)
@@ -64,7 +69,11 @@ def run_test(trace, out_dir, actor_npz=None, max_step=2000, n_bs=4, n_ue=40, gri
         t0 = time.time()
         with torch.no_grad():
             idx = obs_to_indices(test_env._env.observation(), grid, n_bs)                # the state, as its non-zero cells
-            action = int(torch.argmax(net.actor_only(idx), dim=1)[0])                    # :68,73 greedy
+            prob = net.actor_only(idx)
+            if factored:                                                                 # the greedy digit of every UAV
+                action = int(digits_to_joint(torch.argmax(prob.reshape(1, n_bs, -1), dim=2))[0])
+            else:
+                action = int(torch.argmax(prob, dim=1)[0])                               # :68,73 greedy
         buf["time"].append(time.time() - t0)
         _, r, done, info = test_env.step_test(np.array([action]), False)                 # :75
         buf["reward"].append(r)
@@ -90,7 +99,11 @@ def run_batched(n_envs, out_dir, trace=None, actor_npz=None, steps=2000, n_bs=4,
 
     os.makedirs(out_dir, exist_ok=True)
     env = BatchedMobiEnv(n_envs, nBS=n_bs, nUE=n_ue, grid_n=grid, seed=seed)
-    if net == "cnn":
+    if net == "cnn-factored":
+        from drl_uav_cellularnet_amd.factored import FactoredCnnACNet
+
+        net = FactoredCnnACNet(n_bs, grid)
+    elif net == "cnn":
         from drl_uav_cellularnet_amd.cnn_agent import CnnACNet
 
         net = CnnACNet(n_bs, grid, env.action_space_dim)
@@ -126,26 +139,28 @@ if __name__ == "__main__":
     ap.add_argument("--trace-rows", type=int, default=10001)
     ap.add_argument("--actor", default=None)
     ap.add_argument("--steps", type=int, default=2000)
-    ap.add_argument("--net", choices=("mlp", "cnn"), default="mlp", help="the network the actor file was trained with")
+    ap.add_argument("--net", choices=("mlp", "cnn", "cnn-factored"), default="mlp", help="the network the actor file was trained with")
+    ap.add_argument("--n-bs", type=int, default=4, help="UAVs (cnn-factored serves up to 16; the joint heads have 5^n_bs logits)")
+    ap.add_argument("--n-ue", type=int, default=40)
     ap.add_argument("--envs", type=int, default=None, help="evaluate this many envs at once on the device (GreedyEvaluator)")
     ap.add_argument("--traces", default=None, help="with --envs: int16 cells [T+1, N, U, 2] or [T+1, U, 2] (.npy); default: group mobility")
     ap.add_argument("--rates", action="store_true", help="with --envs: also report the link rates (dl_rate.npy / ul_rate.npy)")
     a = ap.parse_args()
     if a.make_trace:
-        np.save(a.make_trace, make_trace(a.trace_rows))
+        np.save(a.make_trace, make_trace(a.trace_rows, n_ue=a.n_ue))
         print("wrote", a.make_trace)
         sys.exit(0)
     if a.envs is not None:
         src = a.traces or a.trace
         tr = np.load(src, allow_pickle=False).astype(np.int16) if src else None
         t0 = time.time()
-        res = run_batched(a.envs, a.out, tr, a.actor, a.steps, net=a.net, rates=a.rates)
+        res = run_batched(a.envs, a.out, tr, a.actor, a.steps, n_bs=a.n_bs, n_ue=a.n_ue, net=a.net, rates=a.rates)
         dt = time.time() - t0
         print("eval: %d envs x %d steps in %.1f s (%.3g env-steps/s incl. set-up), mean reward %.4f, mean outage fraction %.4f -> %s" % (
             a.envs, a.steps, dt, a.envs * a.steps / dt, float(res["reward"].mean()), float(res["outage_fraction"].mean()), a.out))
         sys.exit(0)
-    tr = np.load(a.trace, allow_pickle=False) if a.trace else make_trace(a.steps + 2)
+    tr = np.load(a.trace, allow_pickle=False) if a.trace else make_trace(a.steps + 2, n_ue=a.n_ue)
     t0 = time.time()
-    res = run_test(tr, a.out, a.actor, a.steps, net=a.net)
+    res = run_test(tr, a.out, a.actor, a.steps, n_bs=a.n_bs, n_ue=a.n_ue, net=a.net)
     print("eval: %d step_test calls in %.1f s, mean reward %.4f, mean outage fraction %.4f -> %s" % (
         len(res["reward"]), time.time() - t0, float(res["reward"].mean()), float(res["outage_fraction"].mean()), a.out))

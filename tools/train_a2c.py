@@ -5,6 +5,7 @@ update per rollout; at the end the two files the reference writes: Global_return
 actor parameters (Global_A_PARA: here a named .npz, agent.save_actor_npz -- loadable by tools/run_eval.py without pickle).
 
   python tools/train_a2c.py --out train/run1 [--workers 8192] [--episodes 2] [--rollout 50] [--first-state zeros]
+  python tools/train_a2c.py --net cnn-factored --n-bs 16 --n-ue 200 --workers 1024      # one 5-way policy head per UAV (factored.py)
   python -m torch.distributed.run --nproc-per-node 8 tools/train_a2c.py ...     # one process per GPU, gradients all-reduced (RCCL)"""
 import argparse
 import json
@@ -62,8 +63,10 @@ def main():
                     "4096 workers on); per-step: the pipelined per-step launches (same results bit for bit)")
     ap.add_argument("--no-gemm-tuning", action="store_true", help="leave PyTorch's TunableOp off (library default; this tool turns the "
                     "shipped per-shape GEMM picks on: a resumed run is bit-identical only if it makes the same choice as the original)")
-    ap.add_argument("--net", choices=("mlp", "cnn"), default="mlp", help="the reference's netType: MLP (agent.ACNet) or CNN "
-                    "(cnn_agent.CnnACNet, one process only)")
+    ap.add_argument("--net", choices=("mlp", "cnn", "cnn-factored"), default="mlp", help="the reference's netType: MLP (agent.ACNet) or CNN "
+                    "(cnn_agent.CnnACNet, one process only); cnn-factored: the CNN with one 5-way head per UAV "
+                    "(factored.FactoredCnnACNet, one process only) -- the only one that exists beyond a handful of UAVs")
+    ap.add_argument("--n-bs", type=int, default=4, help="UAVs; the joint heads of mlp / cnn have 5^n_bs logits (625 at the reference's 4)")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -81,8 +84,12 @@ def main():
     from drl_uav_cellularnet_amd.sharding import shard_for_rank
 
     base, _ = shard_for_rank(rank, world, a.workers)
-    env = BatchedMobiEnv(a.workers, nBS=4, nUE=a.n_ue, grid_n=a.grid, device=dev, env_id_base=base)
-    if a.net == "cnn":
+    env = BatchedMobiEnv(a.workers, nBS=a.n_bs, nUE=a.n_ue, grid_n=a.grid, device=dev, env_id_base=base)
+    if a.net == "cnn-factored":
+        from drl_uav_cellularnet_amd.factored import FactoredCnnA2CRunner
+
+        runner = FactoredCnnA2CRunner(env, rollout=a.rollout, first_state=a.first_state)
+    elif a.net == "cnn":
         from drl_uav_cellularnet_amd.cnn_agent import CnnA2CRunner
 
         runner = CnnA2CRunner(env, rollout=a.rollout, first_state=a.first_state)
