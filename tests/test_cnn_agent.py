@@ -180,3 +180,32 @@ def test_cnn_library_exports_its_header_and_checks_arguments():
     assert lib.uavcnn_dense_dx_f32(one, one, odd, 8, 77440, 100, one, None) == -1 and b"misaligned" in err()
     assert lib.uavcnn_dense_wgrad_f32(one, one, 8, 0, 100, one, 0, None) == -1 and b"d outside" in err()
     assert lib.uavcnn_dense_wgrad_f32(one, one, 1 << 23, 77440, 100, one, 0, None) == -1 and b"m_rows" in err()
+
+
+def test_plan_shapes_select_their_branches():
+    """The shapes tests/test_cnn_plans_gpu.py runs (tests/cnn_plan_shapes.py) reach the branches they are there for, by the library's own
+    launch plans: counts derived from the host-only *_workspace_bytes functions, no plan formula restated here."""
+    import cnn_plan_shapes as P
+    from drl_uav_cellularnet_amd import _cnn_capi, build
+
+    build.build_cnn()
+    lib = _cnn_capi.load()
+    for M, D in P.DENSE_DEEP:
+        nbytes = lib.uavcnn_dense_fwd_workspace_bytes(M, D)
+        assert nbytes > 0 and nbytes % (400 * M) == 0
+        ns = nbytes // (400 * M)                                          # partials [ns][M][100] float32
+        assert 1 <= ns < -(-D // 64), (M, D, ns)                          # a slice holds more than one 64-chunk: the k0 loop runs again
+    M = P.CONV1_MULTI_M
+    for n_bs, _ in P.CONV1_MULTI_NBS_K:
+        per = 4 * (250 * (n_bs + 1) + 10)
+        nbytes = lib.uavcnn_conv1_wgrad_workspace_bytes(M, n_bs)
+        assert nbytes > 0 and nbytes % per == 0
+        nb = nbytes // per
+        assert 1 <= nb < M and M % nb != 0, (M, n_bs, nb)                 # several samples per workgroup, unevenly split
+    for S, M in P.CONV5_MULTI:
+        nbytes = lib.uavcnn_conv5_wgrad_workspace_bytes(M, S)
+        assert nbytes > 0 and nbytes % (4 * 2510) == 0
+        nb = nbytes // (4 * 2510)
+        assert 1 <= nb < M * (S - 4), (M, S, nb)                          # several (sample, row) pairs per workgroup
+    assert all(K > 64 for _, K in P.CONV1_MULTI_NBS_K)                    # nodes beyond wavefront 0
+    assert {n_bs + 1 for n_bs, _ in P.CONV1_MULTI_NBS_K} == {17, 2}       # the widest and the narrowest conv1 input
