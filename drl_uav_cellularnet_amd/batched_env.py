@@ -426,6 +426,56 @@ class BatchedMobiEnv:
         4096-env batch, uavenv_step_many_prepare): the first call with a new n_steps would otherwise build it, synchronously."""
         _capi.check(self._lib.uavenv_step_many_prepare(self._h, int(n_steps)))
 
+    # ---- what the look-ahead policies below share --------------------------------------------------------
+    def _stage_ue_xy(self, ue_xy):
+        """Device pointer of the trace cells ``ue_xy`` [N, U, 2] as int16 (kept alive until the next call), or None."""
+        if ue_xy is None:
+            return None
+        x = torch.as_tensor(ue_xy).to(device=self.device, dtype=torch.int16).contiguous()
+        if x.numel() != self.n_envs * self.nUE * 2:
+            raise ValueError("ue_xy must be [N, U, 2]")
+        self._trace_keep = x
+        return x.data_ptr()
+
+    def _lookahead_actions(self, fn, ue_xy, draws, best_reward, table_shape):
+        """search_actions / coordinate_actions: ``fn`` is the C entry, ``draws`` = (theta_u, group_u, fading), ``table_shape`` the per-env
+        shape of the reward table or None."""
+        N = self.n_envs
+        xptr = self._stage_ue_xy(ue_xy)
+        inj = self._inject(*draws)
+        checked = 1 if ("reward_f64" in self.out or inj is not None) else 0
+        acts = torch.empty(N, dtype=torch.int64, device=self.device)
+        best = torch.empty(N, dtype=torch.float64, device=self.device) if best_reward else None
+        table = torch.empty((N,) + table_shape, dtype=torch.float64, device=self.device) if table_shape else None
+        rc = fn(self._h, xptr, inj, checked, acts.data_ptr(), best.data_ptr() if best_reward else None,
+                table.data_ptr() if table_shape else None, self._stream())
+        if rc:
+            _capi.check(rc)
+        res = (acts,) + ((best,) if best_reward else ()) + ((table,) if table_shape else ())
+        return res[0] if len(res) == 1 else res
+
+    def _step_policy(self, fn, name, n_steps, out, actions_out):
+        """step_gradient / step_search / step_coordinate: ``fn`` is the C entry, ``name`` the public method."""
+        T = int(n_steps)
+        if actions_out is None:
+            actions_out = torch.empty((T, self.n_envs), dtype=torch.int64, device=self.device)
+        elif not (actions_out.dtype == torch.int64 and tuple(actions_out.shape) == (T, self.n_envs) and actions_out.is_contiguous()
+                  and actions_out.device == self.device):
+            raise ValueError("actions_out must be a contiguous int64 [T, n_envs] tensor on the env's device")
+        if out is None:
+            out = {k: torch.empty((T,) + tuple(v.shape), dtype=v.dtype, device=self.device) for k, v in self.out.items()}
+        elif set(out) != set(self.out) or any(out[k].shape != (T,) + tuple(v.shape) or not out[k].is_contiguous()
+                                              for k, v in self.out.items()):
+            raise ValueError("out must be a dict returned by %s / step_many for the same number of steps" % name)
+        st = self.out_struct_for(out)
+        rc = fn(self._h, T, actions_out.data_ptr(), C.byref(st), self._stream())
+        if rc:
+            _capi.check(rc)
+        if T > 0:
+            for k, v in self.out.items():
+                v.copy_(out[k][T - 1])
+        return actions_out, out
+
     # ---- the SINR-gradient baseline controller (gradient.py) -------------------------------------------
     def gradient_actions(self, ue_xy=None, theta_u=None, group_u=None, fading=None, side_means=False, look=False):
         """Choose_Act_Gradient (gradient.py:14-37) for every env in one launch (uavenv_gradient_actions): look one step ahead with
@@ -433,14 +483,8 @@ class BatchedMobiEnv:
         modified: no state, none of ``self.out``.  ``ue_xy`` [N, U, 2]: the trace cells of the step (read_trace), else the next
         mobility tick.  Returns int64 [N] joint actions; with ``side_means`` also float64 [N, B, 4] (NaN = empty side); with
         ``look`` also the look-ahead step's outputs, a dict of fresh tensors named like ``self.out``."""
-        N, U, B = self.n_envs, self.nUE, self.nBS
-        xptr = None
-        if ue_xy is not None:
-            x = torch.as_tensor(ue_xy).to(device=self.device, dtype=torch.int16).contiguous()
-            if x.numel() != N * U * 2:
-                raise ValueError("ue_xy must be [N, U, 2]")
-            self._trace_keep = x
-            xptr = x.data_ptr()
+        N, B = self.n_envs, self.nBS
+        xptr = self._stage_ue_xy(ue_xy)
         acts = torch.empty(N, dtype=torch.int64, device=self.device)
         means = torch.empty((N, B, 4), dtype=torch.float64, device=self.device) if side_means else None
         lo, lref = None, None
@@ -460,25 +504,7 @@ class BatchedMobiEnv:
         on-device randomness).  Returns (actions int64 [T, N], dict of [T, ...] tensors as step_many returns); ``self.out`` holds
         the last step's results.  ``out`` / ``actions_out``: the results of an earlier call with the same T, to be overwritten
         (no allocation: capturable in a graph).  Bit-identical to the loop of the two calls."""
-        T = int(n_steps)
-        if actions_out is None:
-            actions_out = torch.empty((T, self.n_envs), dtype=torch.int64, device=self.device)
-        elif not (actions_out.dtype == torch.int64 and tuple(actions_out.shape) == (T, self.n_envs) and actions_out.is_contiguous()
-                  and actions_out.device == self.device):
-            raise ValueError("actions_out must be a contiguous int64 [T, n_envs] tensor on the env's device")
-        if out is None:
-            out = {k: torch.empty((T,) + tuple(v.shape), dtype=v.dtype, device=self.device) for k, v in self.out.items()}
-        elif set(out) != set(self.out) or any(out[k].shape != (T,) + tuple(v.shape) or not out[k].is_contiguous()
-                                              for k, v in self.out.items()):
-            raise ValueError("out must be a dict returned by step_gradient / step_many for the same number of steps")
-        st = self.out_struct_for(out)
-        rc = self._lib.uavenv_step_gradient(self._h, T, actions_out.data_ptr(), C.byref(st), self._stream())
-        if rc:
-            _capi.check(rc)
-        if T > 0:
-            for k, v in self.out.items():
-                v.copy_(out[k][T - 1])
-        return actions_out, out
+        return self._step_policy(self._lib.uavenv_step_gradient, "step_gradient", n_steps, out, actions_out)
 
     # ---- the one-step search policy: the best of all joint actions per env -----------------------------
     def search_actions(self, ue_xy=None, theta_u=None, group_u=None, fading=None, best_reward=False, rewards=False):
@@ -488,50 +514,15 @@ class BatchedMobiEnv:
         own step: the checked variant when the env has float64 outputs or draws are injected, else the fast one.  Returns int64 [N]
         joint actions (the lowest action among equal rewards); with ``best_reward`` also float64 [N]; with ``rewards`` also the
         float64 [N, N_ACT ** nBS] table: ``table[e, a]`` is bit for bit the ``reward_f64`` step(a) would return for env e."""
-        N, U = self.n_envs, self.nUE
-        xptr = None
-        if ue_xy is not None:
-            x = torch.as_tensor(ue_xy).to(device=self.device, dtype=torch.int16).contiguous()
-            if x.numel() != N * U * 2:
-                raise ValueError("ue_xy must be [N, U, 2]")
-            self._trace_keep = x
-            xptr = x.data_ptr()
-        inj = self._inject(theta_u, group_u, fading)
-        checked = 1 if ("reward_f64" in self.out or inj is not None) else 0
-        acts = torch.empty(N, dtype=torch.int64, device=self.device)
-        best = torch.empty(N, dtype=torch.float64, device=self.device) if best_reward else None
-        table = torch.empty((N, self.action_space_dim), dtype=torch.float64, device=self.device) if rewards else None
-        rc = self._lib.uavenv_search_actions(self._h, xptr, inj, checked, acts.data_ptr(), best.data_ptr() if best_reward else None,
-                                             table.data_ptr() if rewards else None, self._stream())
-        if rc:
-            _capi.check(rc)
-        res = (acts,) + ((best,) if best_reward else ()) + ((table,) if rewards else ())
-        return res[0] if len(res) == 1 else res
+        return self._lookahead_actions(self._lib.uavenv_search_actions, ue_xy, (theta_u, group_u, fading), best_reward,
+                                       (self.action_space_dim,) if rewards else None)
 
     def step_search(self, n_steps, out=None, actions_out=None):
         """``n_steps`` x [search_actions(); step(those actions)] issued by one C call (uavenv_step_search; group mobility,
         on-device randomness): every env takes its one-step-optimal action each step.  Returns (actions int64 [T, N], dict of
         [T, ...] tensors as step_many returns); ``self.out`` holds the last step's results.  ``out`` / ``actions_out``: the results
         of an earlier call with the same T, to be overwritten (no allocation).  Bit-identical to the loop of the two calls."""
-        T = int(n_steps)
-        if actions_out is None:
-            actions_out = torch.empty((T, self.n_envs), dtype=torch.int64, device=self.device)
-        elif not (actions_out.dtype == torch.int64 and tuple(actions_out.shape) == (T, self.n_envs) and actions_out.is_contiguous()
-                  and actions_out.device == self.device):
-            raise ValueError("actions_out must be a contiguous int64 [T, n_envs] tensor on the env's device")
-        if out is None:
-            out = {k: torch.empty((T,) + tuple(v.shape), dtype=v.dtype, device=self.device) for k, v in self.out.items()}
-        elif set(out) != set(self.out) or any(out[k].shape != (T,) + tuple(v.shape) or not out[k].is_contiguous()
-                                              for k, v in self.out.items()):
-            raise ValueError("out must be a dict returned by step_search / step_many for the same number of steps")
-        st = self.out_struct_for(out)
-        rc = self._lib.uavenv_step_search(self._h, T, actions_out.data_ptr(), C.byref(st), self._stream())
-        if rc:
-            _capi.check(rc)
-        if T > 0:
-            for k, v in self.out.items():
-                v.copy_(out[k][T - 1])
-        return actions_out, out
+        return self._step_policy(self._lib.uavenv_step_search, "step_search", n_steps, out, actions_out)
 
     # ---- the per-UAV coordinate-search policy: each UAV's best cell in turn, 4 nBS + 1 step values per decision ----
     def coordinate_actions(self, ue_xy=None, theta_u=None, group_u=None, fading=None, best_reward=False, rewards=False):
@@ -543,50 +534,15 @@ class BatchedMobiEnv:
         Returns int64 [N] joint actions; with ``best_reward`` also float64 [N], bit for bit the ``reward_f64`` step(actions) returns
         and never below the reward of all UAVs staying; with ``rewards`` also the float64 [N, nBS, 5] table: ``table[e, i, d]`` is the
         reward of UAV i taking digit d given the digits chosen before it (heuristics.coordinate_rule states the choice)."""
-        N, U = self.n_envs, self.nUE
-        xptr = None
-        if ue_xy is not None:
-            x = torch.as_tensor(ue_xy).to(device=self.device, dtype=torch.int16).contiguous()
-            if x.numel() != N * U * 2:
-                raise ValueError("ue_xy must be [N, U, 2]")
-            self._trace_keep = x
-            xptr = x.data_ptr()
-        inj = self._inject(theta_u, group_u, fading)
-        checked = 1 if ("reward_f64" in self.out or inj is not None) else 0
-        acts = torch.empty(N, dtype=torch.int64, device=self.device)
-        best = torch.empty(N, dtype=torch.float64, device=self.device) if best_reward else None
-        table = torch.empty((N, self.nBS, self.N_ACT), dtype=torch.float64, device=self.device) if rewards else None
-        rc = self._lib.uavenv_coordinate_actions(self._h, xptr, inj, checked, acts.data_ptr(), best.data_ptr() if best_reward else None,
-                                                 table.data_ptr() if rewards else None, self._stream())
-        if rc:
-            _capi.check(rc)
-        res = (acts,) + ((best,) if best_reward else ()) + ((table,) if rewards else ())
-        return res[0] if len(res) == 1 else res
+        return self._lookahead_actions(self._lib.uavenv_coordinate_actions, ue_xy, (theta_u, group_u, fading), best_reward,
+                                       (self.nBS, self.N_ACT) if rewards else None)
 
     def step_coordinate(self, n_steps, out=None, actions_out=None):
         """``n_steps`` x [coordinate_actions(); step(those actions)] issued by one C call (uavenv_step_coordinate; group mobility,
         on-device randomness).  Returns (actions int64 [T, N], dict of [T, ...] tensors as step_many returns); ``self.out`` holds the
         last step's results.  ``out`` / ``actions_out``: the results of an earlier call with the same T, to be overwritten (no
         allocation).  Bit-identical to the loop of the two calls."""
-        T = int(n_steps)
-        if actions_out is None:
-            actions_out = torch.empty((T, self.n_envs), dtype=torch.int64, device=self.device)
-        elif not (actions_out.dtype == torch.int64 and tuple(actions_out.shape) == (T, self.n_envs) and actions_out.is_contiguous()
-                  and actions_out.device == self.device):
-            raise ValueError("actions_out must be a contiguous int64 [T, n_envs] tensor on the env's device")
-        if out is None:
-            out = {k: torch.empty((T,) + tuple(v.shape), dtype=v.dtype, device=self.device) for k, v in self.out.items()}
-        elif set(out) != set(self.out) or any(out[k].shape != (T,) + tuple(v.shape) or not out[k].is_contiguous()
-                                              for k, v in self.out.items()):
-            raise ValueError("out must be a dict returned by step_coordinate / step_many for the same number of steps")
-        st = self.out_struct_for(out)
-        rc = self._lib.uavenv_step_coordinate(self._h, T, actions_out.data_ptr(), C.byref(st), self._stream())
-        if rc:
-            _capi.check(rc)
-        if T > 0:
-            for k, v in self.out.items():
-                v.copy_(out[k][T - 1])
-        return actions_out, out
+        return self._step_policy(self._lib.uavenv_step_coordinate, "step_coordinate", n_steps, out, actions_out)
 
     # ---- evaluation totals (main_test.py:46-113 for a whole batch) ------------------------------------
     def eval_accumulators(self, hist=(-50.0, 100.0, 150)):

@@ -45,27 +45,10 @@ __device__ __forceinline__ void coordinate_body(const KParams &p, const HotConst
     // phase 2 (as search_body): pcK[b] = power of UAV b on the cell digit K proposes from its PRESENT cell -- UAV b has not moved before its
     // own round, so these are round b's candidates; pg[b] = on the cell it holds now.
     double pc0[BT], pc1[BT], pc2[BT], pc3[BT], pg[BT];
-#pragma unroll
-    for (int b2 = 0; b2 < BT; b2 += 2) {
-        double f0 = 0.0, f1 = 0.0;
-        if (b2 < B) search_fading_pair<BT, FAST, PRE>(p, H, C, e, tick, u, live, iu, B, b2, q0, q1, f0, f1);
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int b = b2 + k;
-            if (b < BT) {
-                pc0[b] = pc1[b] = pc2[b] = pc3[b] = pg[b] = 0.0;
-                if (b < B) {
-                    const double f = (k == 0) ? f0 : f1;
-                    pc0[b] = search_gain<PLC>(H, C, f, ix, iy, bsx[b] + bstep, bsy[b]);
-                    pc1[b] = search_gain<PLC>(H, C, f, ix, iy, bsx[b] - bstep, bsy[b]);
-                    pc2[b] = search_gain<PLC>(H, C, f, ix, iy, bsx[b], bsy[b] + bstep);
-                    pc3[b] = search_gain<PLC>(H, C, f, ix, iy, bsx[b], bsy[b] - bstep);
-                    pg[b] = search_gain<PLC>(H, C, f, ix, iy, bsx[b], bsy[b]);
-                }
-            }
-        }
-    }
-    auto value = [&](const double (&g)[BT]) -> double {      // the step's reward for the powers g; valid on the slot's first lane
+    candidate_powers<BT, PLC, FAST, PRE>(p, H, C, e, tick, u, live, iu, ix, iy, bsx, bsy, q0, q1, pc0, pc1, pc2, pc3, pg);
+    // The step's reward for the powers g; valid on the slot's first lane.  (search_body states the same four lines in its loop: one helper for
+    // both raises the VGPR count of one of the two families, whichever form it takes -- profiles/policy_fold_listings.txt.)
+    auto value = [&](const double (&g)[BT]) -> double {
         const double cur = sinr_db<BT, FAST>(p, H, C, g, serving);                             // serving UAV BEFORE any handover (channel.py:145-146)
         const unsigned long long ob = (__ballot(live && (cur <= H.out_thr)) & slot_mask) >> base;   // :170
         const int n_outage = __popcll(ob & ~prev_out);                                          // :171-174 newly outaged
@@ -125,6 +108,19 @@ __device__ __forceinline__ void coordinate_body(const KParams &p, const HotConst
     }
 }
 
+// env_packed_body's hook: the search's look-ahead, coordinate_body after the tick in place of search_body.
+struct CoordPolicy {
+    static constexpr bool kLookAhead = true, kAfterTick = true;
+    const CoordArgs &ca;
+    template <int BT, bool PLC, bool FAST, bool PRE>
+    __device__ __forceinline__ void after_tick(const KParams &p, const HotConst &H, const LeanCoef &C, const FinConst &K, int U, int, int, int, int base,
+                                               int ul, bool live, bool head, long long, int, int, long long e, uint32_t tick, int u, long long iu,
+                                               int ix, int iy, const int (&bsx)[BT], const int (&bsy)[BT], const U4 &q0, const U4 &q1, int serving,
+                                               unsigned long long prev_out, unsigned long long slot_mask) const {
+        coordinate_body<BT, PLC, FAST, PRE>(p, H, C, K, ca, U, base, ul, live, head, e, tick, u, iu, ix, iy, bsx, bsy, q0, q1, serving, prev_out, slot_mask);
+    }
+};
+
 template <int BT, int MODE, bool PLC, bool FAST>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void env_kernel_coordinate_packed(char *blob, const int8_t *gid_of_u, long long N, int U, int EPW, int Gr,
                                                                                          int B_rt, int lane_magic, const CoordArgs ca, const KParams p) {
@@ -132,8 +128,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void env_kernel_coordinate_pac
     __shared__ int s_bs[kWavesPerBlock][kMaxEpw][2 * kMaxBs];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long long gw = (long long)blockIdx.x * kWavesPerBlock + wave;
-    env_packed_body<BT, MODE, PLC, FAST, false, false, 0, true, true, false, true>(blob, nullptr, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, p, s_bs, wave, gw, 0,
-                                                                                   1, 0, (int)N, nullptr, nullptr, nullptr, nullptr, nullptr, &ca);
+    env_packed_body<BT, MODE, PLC, FAST, false, false, 0, false, CoordPolicy>(blob, nullptr, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, p, s_bs, wave, gw, 0, 1, 0,
+                                                                              (int)N, nullptr, CoordPolicy{ca});
 }
 
 // ---- multi-pass family: one env per wavefront, walkers in passes of 64 (env_kernel_multipass's layout) ------------------------------

@@ -1,12 +1,15 @@
 // Internal to libuavenv (not installed): the handle and the helpers shared by its translation units (uavenv_capi.hip: everything but
-// the gated rollout and the gradient policy; uavenv_gated.hip: uavenv_rollout_gated and its kernel instantiations; uavenv_gradient.hip:
+// the gated rollout and the policies; uavenv_gated.hip: uavenv_rollout_gated and its kernel instantiations; uavenv_gradient.hip:
 // uavenv_gradient_actions / uavenv_step_gradient and the look-ahead kernels; uavenv_search.hip: uavenv_search_actions / uavenv_step_search
 // and the search kernels; uavenv_coordinate.hip: uavenv_coordinate_actions / uavenv_step_coordinate and their kernels; uavenv_eval.hip: uavenv_eval_accumulate; uavenv_rates.hip: uavenv_link_rates and its kernels -- files of their own so that none rebuilds the others).
+// The three policy units share what stands at the end of this file: the call preamble (policy_call), the one launcher of a packed policy
+// kernel (launch_packed_policy; each unit names its kernels in a family type) and the decide-then-step loop (decide_then_step).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/uavenv.h"
@@ -92,3 +95,72 @@ struct DeviceGuard {
     }
 };
 
+// ---- the look-ahead policies (uavenv_gradient.hip, uavenv_search.hip, uavenv_coordinate.hip) -------------------------------------------
+namespace uavenv_internal {
+// Does a step with these outputs run the checked variant for their sake?  (float64 copies)
+inline bool wants_f64(const UavEnvOut *out) { return out && (out->cur_sinr_f64_dev || out->mean_sinr_f64_dev || out->reward_f64_dev); }
+
+// The preamble of a policy's decide call: `p` = the handle's parameters for one look-ahead step on the next tick or on trace cells.
+// `fast` = the arithmetic variant the real step would run (launch_env): no injected draws, no float64 copies (`checked` says whether the
+// step the caller has in mind asks for them), B == the template bound.
+inline int policy_call(const uavenv *h, const char *who, const int16_t *ue_xy_in_dev, const UavEnvInject *inj, const UavEnvOut *out, bool checked,
+                       uavk::KParams &p, bool &fast) {
+    if (int rc_dev = poisoned(h, who)) return rc_dev;
+    p = h->kp;
+    fill_call(p, inj, out);
+    p.actions = nullptr; p.trace_xy = ue_xy_in_dev; p.n_ticks = 1;
+    fast = !checked && !p.inj_theta && !p.inj_group && !p.inj_fading && (p.B == h->bt);
+    return UAVENV_OK;
+}
+
+// One launch of a packed policy kernel.  F, the family: kFam (its side-census family), kMaxBt (the largest template bound it instantiates),
+// Args (what the kernel takes before the parameters) and kernel<BT, MODE, PLC, FAST>.  A FAST kernel exists only where side_has_fast().
+template <class F, int BT>
+int launch_packed_policy_bt(const uavenv *h, const char *who, const uavk::KParams &p, const typename F::Args &a, bool fast, hipStream_t s) {
+    if constexpr (BT > F::kMaxBt) {
+        return fail(UAVENV_E_INVALID, std::string(who) + ": no kernel for this template bound");   // (the entry refused such a handle)
+    } else {
+        constexpr bool kFast = side_has_fast(F::kFam, BT);
+        fast = fast && kFast;
+        const int mode = p.trace_xy ? uavk::MODE_TRACE : uavk::MODE_STEP;
+        const long long waves = (p.N + p.epw - 1) / p.epw;
+        const dim3 grid((unsigned)((waves + uavk::kWavesPerBlock - 1) / uavk::kWavesPerBlock)), blk(64 * uavk::kWavesPerBlock);
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, blk, 0, s, h->blob, p.gid_of_u, p.N, p.U, p.epw, p.Gr, p.B, (int)uavk::lane_div_magic((uint32_t)p.U), a, p);
+        };
+        auto plc_fast = [&](auto mode_c) {
+            constexpr int MODE = decltype(mode_c)::value;
+            if (h->plc) { if (fast) go(F::template kernel<BT, MODE, true, kFast>); else go(F::template kernel<BT, MODE, true, false>); }
+            else { if (fast) go(F::template kernel<BT, MODE, false, kFast>); else go(F::template kernel<BT, MODE, false, false>); }
+        };
+        if (mode == uavk::MODE_TRACE) plc_fast(std::integral_constant<int, uavk::MODE_TRACE>{});
+        else plc_fast(std::integral_constant<int, uavk::MODE_STEP>{});
+        const bool counted = side_census_count(F::kFam, BT, mode, h->plc, fast, 0, false);
+        HIP_TRY(hipGetLastError());
+        if (!counted) return fail(UAVENV_E_INVALID, std::string(who) + ": side census: an instantiation outside side_variant_selectable()");
+        return UAVENV_OK;
+    }
+}
+template <class F>
+int launch_packed_policy(const uavenv *h, const char *who, const uavk::KParams &p, const typename F::Args &a, bool fast, hipStream_t s) {
+    switch (h->bt) {
+        case 4: return launch_packed_policy_bt<F, 4>(h, who, p, a, fast, s);
+        case 8: return launch_packed_policy_bt<F, 8>(h, who, p, a, fast, s);
+        case 16: return launch_packed_policy_bt<F, 16>(h, who, p, a, fast, s);
+        default: return launch_packed_policy_bt<F, 32>(h, who, p, a, fast, s);
+    }
+}
+
+// n_steps x [decide(actions of step t); uavenv_step with them]: two launches per step, one host call (as uavenv_step_seq).
+template <class Decide>
+int decide_then_step(uavenv *h, int n_steps, int64_t *actions_out_dev, const UavEnvOut *out, void *stream, Decide decide) {
+    for (int t = 0; t < n_steps; ++t) {
+        int64_t *a = actions_out_dev + (long long)t * h->N;
+        if (int rc = decide(a)) return rc;
+        UavEnvOut blk;
+        if (out) blk = out_block(*out, t, h->N, h->cfg.n_ue, h->cfg.n_bs);
+        if (int rc = uavenv_step(h, a, nullptr, out ? &blk : nullptr, stream)) return rc;
+    }
+    return UAVENV_OK;
+}
+}  // namespace uavenv_internal

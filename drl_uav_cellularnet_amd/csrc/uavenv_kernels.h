@@ -689,77 +689,6 @@ __device__ __forceinline__ void env_finish(const FinConst &K, const OutPtrs &o, 
     if (REC) stx_c<COH>(st.env, e, rec);
 }
 
-// Choose_Act_Gradient's rule (gradient.py:26-34) for the env of one slot, from the serving SINR of a look-ahead step: per UAV b the mean
-// of `cur` over the walkers with x > bx, x <= bx, y > by, y <= by (dir_grad, :27-31; an empty side is NaN), digit_b = np.nanargmin of the
-// four (the first minimum), joint action = sum digit_b n_act^(B-1-b) (:34).  Every walker covers one of x > bx / x <= bx, so a minimum exists.
-// Mapping: the walkers' (cur, cell) go through LDS once; then ONE LANE PER SIDE (side 4 b + k on lane 4 b + k of the slot, in passes of U
-// sides when 4 B > U) walks its env's U walkers in index order -- broadcast LDS reads, no cross-lane traffic -- and adds cur_j or +0.0.
-// The order of the additions depends on U alone, so a side sum is a function of the selected SET: two sides that select the same
-// walkers (all of them right of AND above a UAV) give bit-equal means and the tie goes to the lower digit, as in NumPy, where both
-// are the same np.mean of the same array.  All 4 B means, counts and divisions of an env run side by side in its lanes; the head lane
-// only picks the digits.  (First form: 4 B segmented shuffle reductions and 4 B divisions one after the other, 18.3 us against 13.3 us
-// for the step kernel itself at 4096 envs x 4 x 40)
-struct LookArgs {
-    long long *actions_out;   // [N]
-    double *side_means;       // [N,B,4] or null
-};
-struct LookLds {              // per wavefront
-    double cur[64];           // cur_sinr of the walker on each lane
-    short x[64], y[64];       // its cell (cells are int16 in the state)
-    double mean[256];         // [slot][4 B] side means: EPW * 4 B <= 4 * EPW * U <= 256
-};
-template <int BT>
-__device__ __forceinline__ void side_rule(const LookArgs &lk, LookLds &L, int B, int U, int n_act, int lane, int slot, int base, int ul, bool live,
-                                          bool head, uint32_t e32, int ix, int iy, double cur, const int (&bsx)[BT], const int (&bsy)[BT]) {
-    L.cur[lane] = cur;
-    L.x[lane] = (short)ix;
-    L.y[lane] = (short)iy;
-    __builtin_amdgcn_wave_barrier();
-    const int n_side = 4 * B;
-    const int rb = live ? base : 0;                       // (lanes past the last slot: any row inside the arrays; they store nothing)
-    const int mrow = live ? slot * n_side : 0;
-    for (int s0 = 0; s0 < n_side; s0 += U) {              // uniform
-        const int sd = s0 + ul;                           // this lane's side
-        const bool mine = live && sd < n_side;
-        const int b = sd >> 2, k = sd & 3;
-        int thr = 0;                                      // the UAV coordinate this side compares with
-#pragma unroll
-        for (int bb = 0; bb < BT; ++bb)
-            if (bb == b) thr = (k < 2) ? bsx[bb] : bsy[bb];
-        const short *coord = (k >= 2 ? L.y : L.x) + rb;   // the walker coordinate it compares
-        const bool le = (k & 1) != 0;
-        double sum = 0.0;
-        int cnt = 0;
-        for (int j = 0; j < U; ++j) {                     // walkers in index order: the fixed shape of every side sum
-            const double cj = L.cur[rb + j];
-            const bool in = ((int)coord[j] > thr) != le;
-            sum = fma(cj, in ? 1.0 : 0.0, sum);          // sum + cj or sum + 0, exactly (cf. sinr_db_px): one select, not two
-            cnt += in ? 1 : 0;
-        }
-        const double mean = cnt > 0 ? sum / (double)cnt : __builtin_nan("");   // IEEE division, as np.mean's
-        if (mine) {
-            L.mean[mrow + sd] = mean;
-            if (lk.side_means != nullptr) lk.side_means[(size_t)e32 * (size_t)n_side + (size_t)sd] = mean;
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (head) {
-        unsigned long long a = 0ull;
-        for (int b = 0; b < B; ++b) {
-            int digit = 0;
-            double lowest = 0.0;
-            bool have = false;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const double m = L.mean[mrow + 4 * b + k];
-                if (m == m && (!have || m < lowest)) { lowest = m; digit = k; have = true; }   // np.nanargmin: NaNs skipped, first minimum
-            }
-            a = a * (unsigned long long)n_act + (unsigned long long)digit;
-        }
-        lk.actions_out[e32] = (long long)a;
-    }
-}
-
 // Multi-step launches (uavenv_step_many): every output array holds one block per step, [T][...]; the pointers move on by one
 // block after each step (uniform 64-bit adds on the scalar unit).  A null (skipped) output stays null.
 template <bool FAST>
@@ -874,36 +803,24 @@ __device__ __forceinline__ void many_retire_loads() {
 // bit 1 = another wavefront continues this piece's job (state STORED coherently); 0 everywhere else.  Bit 2 (the gated rollout kernel,
 // env_kernel_gated): the ACTIONS are loaded coherently too -- another kernel wrote them while this one was running.
 // `po` (single-step launches): where the outputs go instead of p.out (the gated rollout kernel moves the reward pointer on per step).
-// LOOK (uavenv_gradient_actions, env_kernel_look in uavenv_gradient_kernel.h): the step with every UAV staying (digit 4 everywhere: no action is
-// read, BS_move is skipped), computed exactly as above and then DROPPED: no store to the state; the step's outputs go to whichever members of
-// `pout` are non-null (tested at run time even when FAST, which here only selects the arithmetic variant the real step would run), and
-// the SINR-gradient rule (side_rule) turns cur_sinr into the joint action of `lk`.  LOOK = false is the code as it was.
-// SEARCH (uavenv_search_actions, env_kernel_search in uavenv_search_kernel.h; implies LOOK): the same look-ahead up to the tick's draws, then
-// search_body() in place of the channel update: the reward of EVERY joint action from that tick, the first maximum to `sr`.  Nothing else is stored.
-// COORD (uavenv_coordinate_actions, env_kernel_coordinate_packed in uavenv_coordinate_kernel.h; implies SEARCH): the same look-ahead, then
-// coordinate_body() in place of search_body(): B rounds of one UAV's four moves instead of every joint action.
-struct SearchArgs;
-struct SearchLds;
-struct CoordArgs;
-template <int BT, bool PLC, bool FAST, bool PRE>
-__device__ void coordinate_body(const KParams &p, const HotConst &H, const LeanCoef &C, const FinConst &K, const CoordArgs &ca, int U, int base, int ul, bool live,
-                                bool head, long long e, uint32_t tick, int u, long long iu, int ix, int iy, const int (&bsx)[BT], const int (&bsy)[BT],
-                                const U4 &q0, const U4 &q1, int serving, unsigned long long prev_out, unsigned long long slot_mask);
-template <int BT, bool PLC, bool FAST, bool PRE>
-__device__ void search_body(const KParams &p, const HotConst &H, const LeanCoef &C, const FinConst &K, const SearchArgs &sa, SearchLds &L, int U, int EPW,
-                            int lane, int slot, int base, int ul, bool live, bool head, long long ew, int e_lo, int e_hi, long long e, uint32_t tick, int u,
-                            long long iu, int ix, int iy, const int (&bsx)[BT], const int (&bsy)[BT], const U4 &q0, const U4 &q1, int serving,
-                            unsigned long long prev_out, unsigned long long slot_mask);
-template <int BT, int MODE, bool PLC, bool FAST, bool PIN, bool MANY, int HO = 0, bool LOOK = false, bool SEARCH = false, bool QSUM = false, bool COORD = false>
+// POLICY (a look-ahead policy's kernel: uavenv_gradient_kernel.h, uavenv_search_kernel.h, uavenv_coordinate_kernel.h; NoPolicy = the step as it
+// is): a type with two constants and a hook, carrying its own arguments and LDS by reference.  kLookAhead: the step with every UAV staying
+// (digit 4 everywhere: no action is read, BS_move is skipped), computed exactly as above and then DROPPED: no store to the state.  kAfterTick:
+// the policy takes over from the tick's cells and draws, `pol.after_tick<BT, PLC, FAST, PRE>()` in place of the channel update; else after
+// the channel update: the step's outputs go to whichever members of `pout` are non-null (tested at run time even when FAST, which here
+// only selects the arithmetic variant the real step would run), then `pol.after_update<BT>()` with cur_sinr.
+struct NoPolicy {
+    static constexpr bool kLookAhead = false, kAfterTick = false;
+};
+template <int BT, int MODE, bool PLC, bool FAST, bool PIN, bool MANY, int HO = 0, bool QSUM = false, class POLICY = NoPolicy>
 __device__ __forceinline__ void env_packed_body(char *blob, const long long *actions, const int8_t *gid_of_u, long long N, int U, int EPW,
                                                 int Gr, int B_rt, int lane_magic, const KParams &p, int (*s_bs)[kMaxEpw][2 * kMaxBs],
                                                 const int wave, const long long ew, const int t0, const int nt, const int e_lo, const int e_hi,
-                                                const OutPtrs *po = nullptr, const LookArgs *lk = nullptr, LookLds *ll = nullptr,
-                                                const SearchArgs *sr = nullptr, SearchLds *sl = nullptr, const CoordArgs *cr = nullptr) {
+                                                const OutPtrs *po = nullptr, const POLICY &pol = POLICY()) {
+    constexpr bool LOOK = POLICY::kLookAhead;
     static_assert(!LOOK || (is_step(MODE) && !MANY && !PIN && HO == 0), "the look-ahead is one plain step");
-    static_assert(!SEARCH || (LOOK && BT <= 8), "the search is a look-ahead with every UAV cell in registers");
+    static_assert(!POLICY::kAfterTick || (LOOK && BT <= 8), "a policy that takes over after the tick is a look-ahead with every UAV cell in registers");
     static_assert(!QSUM || MANY, "the two-level per-env sum is the multi-step kernels'");
-    static_assert(!COORD || SEARCH, "the coordinate policy takes the search's look-ahead");
     constexpr bool LDC = (HO & 1) != 0, STC = (HO & 2) != 0, ACC = (HO & 4) != 0;
     const OutPtrs &pout = po != nullptr ? *po : p.out;
     const int lane = threadIdx.x & 63;
@@ -1095,13 +1012,9 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
         if (MODE == MODE_WARMUP) continue;                // warm-up: mobility only
         if (has_mobility(MODE)) { ix = (int)x; iy = (int)y; }                            // .astype(int), mobile_env.py:154-155
 
-        if constexpr (COORD) {    // B rounds of one UAV's four moves from this tick's cells and draws; the state is left as it was loaded
-            coordinate_body<BT, PLC, FAST, FAST && has_mobility(MODE)>(p, H, C, K, *cr, U, base, ul, live, head, e, tick - 1u, u, iu, ix, iy, bsx, bsy, q0, q1,
-                                                                       serving, prev_out, slot_mask);
-            return;
-        } else if constexpr (SEARCH) {   // every joint action's reward from this tick's cells and draws; the state is left as it was loaded
-            search_body<BT, PLC, FAST, FAST && has_mobility(MODE)>(p, H, C, K, *sr, *sl, U, EPW, lane, slot, base, ul, live, head, ew, e_lo, e_hi, e, tick - 1u,
-                                                                   u, iu, ix, iy, bsx, bsy, q0, q1, serving, prev_out, slot_mask);
+        if constexpr (POLICY::kAfterTick) {   // the policy's values from this tick's cells and draws; the state is left as it was loaded
+            pol.template after_tick<BT, PLC, FAST, FAST && has_mobility(MODE)>(p, H, C, K, U, EPW, lane, slot, base, ul, live, head, ew, e_lo, e_hi, e, tick - 1u,
+                                                                               u, iu, ix, iy, bsx, bsy, q0, q1, serving, prev_out, slot_mask);
             return;
         }
         // ---- channel update (one per reset / step; Philox time = the tick just executed) ------------------
@@ -1162,7 +1075,7 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
             if (ul == b) { bx = bsx[b]; by = bsy[b]; }                                   // the cell this lane writes back
     }
 
-    if (LOOK) {   // look-ahead: the requested outputs of the dropped step, then the rule; the state is left as it was loaded
+    if constexpr (LOOK && !POLICY::kAfterTick) {   // look-ahead: the requested outputs of the dropped step, then the policy; the state is left as it was loaded
         if (live) {
             if (pout.ue_xy != nullptr) { stx(pout.ue_xy, 2u * iu32, (int16_t)ix); stx(pout.ue_xy, 2u * iu32 + 1u, (int16_t)iy); }
             if (pout.serving != nullptr) stx(pout.serving, iu32, (int8_t)serving);
@@ -1171,7 +1084,7 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
         }
         if (bown && pout.bs_xy != nullptr) { stx(pout.bs_xy, 2u * ib32, bx); stx(pout.bs_xy, 2u * ib32 + 1u, by); }
         if (head) env_finish<MODE, false, false>(K, pout, st, e32, erec, tick, agg, deagg, depth, step_n, sum_cur, n_outage);
-        side_rule<BT>(*lk, *ll, B, U, p.n_act, lane, slot, base, ul, live, head, e32, ix, iy, cur, bsx, bsy);
+        pol.template after_update<BT>(B, U, p.n_act, lane, slot, base, ul, live, head, e32, ix, iy, cur, bsx, bsy);
         return;
     }
 
@@ -1268,8 +1181,7 @@ __device__ __forceinline__ void env_packed_entry(char *blob, const long long *ac
         // (Inlined copies of the body rather than a rolled loop around one: with the rolled loop hipcc allocated 330 VGPRs for the
         // pinned kernel instead of 233 -- one wavefront per SIMD -- and doubled its SGPR spills.)
         if (!SCHED) {
-            env_packed_body<BT, MODE, PLC, FAST, PIN, MANY, 0, false, false, QSUM>(blob, actions, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, p, s_bs, wave, gw, 0, p.n_ticks,
-                                                                                   e_lo, e_hi);
+            env_packed_body<BT, MODE, PLC, FAST, PIN, MANY, 0, QSUM>(blob, actions, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, p, s_bs, wave, gw, 0, p.n_ticks, e_lo, e_hi);
             return;
         }
         const int4 *sched = p.sched;
@@ -1287,8 +1199,8 @@ __device__ __forceinline__ void env_packed_entry(char *blob, const long long *ac
             if (nt <= 0) return true;
             if (Q > 0) __builtin_amdgcn_wave_barrier();                       // (the previous piece's reads of the LDS row are done)
             if (Q == 2) { if (!sched_hand_off_wait(p, ew)) return false; }
-            env_packed_body<BT, MODE, PLC, FAST, PIN, MANY, (Q == 0 ? 2 : (Q == 2 ? 1 : 0)), false, false, QSUM>(blob, actions, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic,
-                                                                                                                      p, s_bs, wave, ew, t0, nt, e_lo, e_hi);
+            env_packed_body<BT, MODE, PLC, FAST, PIN, MANY, (Q == 0 ? 2 : (Q == 2 ? 1 : 0)), QSUM>(blob, actions, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, p, s_bs, wave, ew,
+                                                                                                        t0, nt, e_lo, e_hi);
             if (Q == 0 && (bits & SCHED_PUBLISH)) sched_hand_off_publish(p, ew);
             return true;
         };

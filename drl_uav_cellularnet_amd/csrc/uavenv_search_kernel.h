@@ -4,7 +4,7 @@
 //
 // Why one launch can do it: neither the mobility tick nor the tick's fading draws depend on the action (the Philox counter is (env, tick,
 // index, site)), and BS_move leaves a UAV on one of five cells: its own, or +-bs_step in x or in y (a blocked or frozen move is "stay").
-//   phase 1  the look-ahead of env_kernel_look (env_packed_body with SEARCH): state loaded, next tick or trace cells, the tick's draws;
+//   phase 1  the look-ahead of env_kernel_look (env_packed_body with SearchPolicy): state loaded, next tick or trace cells, the tick's draws;
 //   phase 2  per lane (walker) the received power of every UAV on each of its five candidate cells, in the two halves of rx_power: the
 //            draws of a (walker, UAV pair) once (search_fading_pair), then search_gain per cell -- the very expression of the step, PLC
 //            and non-PLC forms and the d <= pl_dis branch included;
@@ -74,18 +74,16 @@ __device__ __forceinline__ double search_gain(const HotConst &H, const LeanCoef 
     return g;
 }
 
+// Phase 2 of the search and of the coordinate policy: candidate powers.  pcK[b] = received power of UAV b on the cell digit K proposes (0..3 =
+// +x, -x, +y, -y by bs_step, 4 = stay): rx_power's loop with five cells per UAV -- the pair's draws once (search_fading_pair), then
+// search_gain per cell.  Five arrays, not a [5][BT] table: every index is static from the start, so they are promoted to registers (a table
+// filled by a loop over K was unrolled only after the promotion pass had given up: 160 bytes of scratch at BT = 4).
 template <int BT, bool PLC, bool FAST, bool PRE>
-__device__ __forceinline__ void search_body(const KParams &p, const HotConst &H, const LeanCoef &C, const FinConst &K, const SearchArgs &sa, SearchLds &L,
-                                            int U, int EPW, int lane, int slot, int base, int ul, bool live, bool head, long long ew, int e_lo, int e_hi,
-                                            long long e, uint32_t tick, int u, long long iu, int ix, int iy, const int (&bsx)[BT], const int (&bsy)[BT],
-                                            const U4 &q0, const U4 &q1, int serving, unsigned long long prev_out, unsigned long long slot_mask) {
-    // ---- phase 2: candidate powers.  pcK[b] = received power of UAV b on the cell digit K proposes (0..3 = +x, -x, +y, -y by bs_step,
-    // 4 = stay): rx_power's loop with five cells per UAV -- the pair's draws once (search_fading_pair), then search_gain per cell.
-    // Five arrays, not a [5][BT] table: every index is static from the start, so they are promoted to registers (a table filled by a
-    // loop over K was unrolled only after the promotion pass had given up: 160 bytes of scratch at BT = 4).
+__device__ __forceinline__ void candidate_powers(const KParams &p, const HotConst &H, const LeanCoef &C, long long e, uint32_t tick, int u, bool live,
+                                                 long long iu, int ix, int iy, const int (&bsx)[BT], const int (&bsy)[BT], const U4 &q0, const U4 &q1,
+                                                 double (&pc0)[BT], double (&pc1)[BT], double (&pc2)[BT], double (&pc3)[BT], double (&pc4)[BT]) {
     const int B = uav_count<BT, FAST>(p.B);
     const int bstep = p.bs_step;
-    double pc0[BT], pc1[BT], pc2[BT], pc3[BT], pc4[BT];
 #pragma unroll
     for (int b2 = 0; b2 < BT; b2 += 2) {
         double f0 = 0.0, f1 = 0.0;
@@ -106,6 +104,15 @@ __device__ __forceinline__ void search_body(const KParams &p, const HotConst &H,
             }
         }
     }
+}
+
+template <int BT, bool PLC, bool FAST, bool PRE>
+__device__ __forceinline__ void search_body(const KParams &p, const HotConst &H, const LeanCoef &C, const FinConst &K, const SearchArgs &sa, SearchLds &L,
+                                            int U, int EPW, int lane, int slot, int base, int ul, bool live, bool head, long long ew, int e_lo, int e_hi,
+                                            long long e, uint32_t tick, int u, long long iu, int ix, int iy, const int (&bsx)[BT], const int (&bsy)[BT],
+                                            const U4 &q0, const U4 &q1, int serving, unsigned long long prev_out, unsigned long long slot_mask) {
+    double pc0[BT], pc1[BT], pc2[BT], pc3[BT], pc4[BT];                                      // phase 2
+    candidate_powers<BT, PLC, FAST, PRE>(p, H, C, e, tick, u, live, iu, ix, iy, bsx, bsy, q0, q1, pc0, pc1, pc2, pc3, pc4);
 
     // ---- phase 3: the action loop -------------------------------------------------------------------------------------------------
     const int A = sa.n_actions;
@@ -156,6 +163,21 @@ __device__ __forceinline__ void search_body(const KParams &p, const HotConst &H,
     }
 }
 
+// env_packed_body's hook: a look-ahead that takes over after the tick, in place of the channel update.
+struct SearchPolicy {
+    static constexpr bool kLookAhead = true, kAfterTick = true;
+    const SearchArgs &sa;
+    SearchLds &L;
+    template <int BT, bool PLC, bool FAST, bool PRE>
+    __device__ __forceinline__ void after_tick(const KParams &p, const HotConst &H, const LeanCoef &C, const FinConst &K, int U, int EPW, int lane, int slot,
+                                               int base, int ul, bool live, bool head, long long ew, int e_lo, int e_hi, long long e, uint32_t tick, int u,
+                                               long long iu, int ix, int iy, const int (&bsx)[BT], const int (&bsy)[BT], const U4 &q0, const U4 &q1, int serving,
+                                               unsigned long long prev_out, unsigned long long slot_mask) const {
+        search_body<BT, PLC, FAST, PRE>(p, H, C, K, sa, L, U, EPW, lane, slot, base, ul, live, head, ew, e_lo, e_hi, e, tick, u, iu, ix, iy, bsx, bsy, q0, q1,
+                                        serving, prev_out, slot_mask);
+    }
+};
+
 template <int BT, int MODE, bool PLC, bool FAST>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void env_kernel_search(char *blob, const int8_t *gid_of_u, long long N, int U, int EPW, int Gr, int B_rt,
                                                                               int lane_magic, const SearchArgs sa, const KParams p) {
@@ -164,8 +186,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void env_kernel_search(char *b
     __shared__ SearchLds s_search[kWavesPerBlock];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long long gw = (long long)blockIdx.x * kWavesPerBlock + wave;
-    env_packed_body<BT, MODE, PLC, FAST, false, false, 0, true, true>(blob, nullptr, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, p, s_bs, wave, gw, 0, 1, 0,
-                                                                      (int)N, nullptr, nullptr, nullptr, &sa, &s_search[wave]);
+    env_packed_body<BT, MODE, PLC, FAST, false, false, 0, false, SearchPolicy>(blob, nullptr, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, p, s_bs, wave, gw, 0, 1,
+                                                                               0, (int)N, nullptr, SearchPolicy{sa, s_search[wave]});
 }
 
 }  // namespace uavk
