@@ -387,6 +387,13 @@ class BatchedMobiEnv:
         _capi.check(self._lib.uavenv_launch_times_us(self._h, buf, 256, C.byref(n)))
         return [buf[i] for i in range(min(n.value, 256))]
 
+    def path_launches(self):
+        """Launches of the UAV path kernel on this handle so far (uavenv_debug_path_launches): one per step_many call that runs the FAST
+        step kernels with 4 or 8 UAVs, none for any other call.  Test hook."""
+        n = C.c_longlong(0)
+        _capi.check(self._lib.uavenv_debug_path_launches(self._h, C.byref(n)))
+        return int(n.value)
+
     def step_many(self, actions, out=None, refresh_out=True):
         """T consecutive step() calls in ONE launch (uavenv_step_many) for actions that do not depend on the observations in
         between: ``actions`` int64 [T, N] on this device.  Returns a dict of [T, ...] tensors (block t = what step t returned;

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "uavenv_handle.h"
+#include "uavenv_path_kernel.h"
 
 using namespace uavk;
 using uavenv_internal::fail;
@@ -862,8 +863,55 @@ extern "C" int uavenv_debug_rotation_info(uavenv_t *h, int n_steps, int *n_launc
     return UAVENV_OK;
 }
 
+// The producer of a FAST multi-step call with BT <= 8 (uavenv_path_kernel.h): the UAV cells of all n_steps steps into out.bs_xy and the cells
+// after the last step into the state, ONE launch per call -- not per piece of a schedule -- on the caller's stream, immediately before the
+// step kernel, which reads them.  The same predicate as launch_env's `fast`: every FAST multi-step launch reads the path, no checked one does.
+// With uavenv_launch_timing on its dispatch is timed like the step kernel's.  It is counted on the handle (uavenv_debug_path_launches), in
+// neither census: those list the instantiations of the env step's dispatch and of the side entry points.
+static bool call_reads_path(const uavenv_t *h, const KParams &p) {
+    return h->packed && call_is_fast(p) && (p.B == h->bt) && (h->bt <= uavk::kPathMaxBs);
+}
+static int launch_path(uavenv_t *h, const KParams &p, int n_steps, hipStream_t s) {
+    uavk::PathParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.actions = p.actions; q.st_bs_xy = p.bs_xy; q.out_bs_xy = p.out.bs_xy;
+    q.N = p.N; q.T = n_steps; q.B = p.B; q.n_act = p.n_act; q.bs_step = p.bs_step; q.G = p.G; q.min_bs_dist2 = p.min_bs_dist2;
+    q.div_magic = p.div_magic; q.div_shift = p.div_shift;
+    if (h->bt <= uavk::kPathQuadMaxBs) {
+        uint32_t pw = 1;
+        for (int b = p.B - 2; b >= 0; --b) {               // UAV b's digit is (a / n_act^(B-1-b)) % n_act; UAV B-1 divides by one, i.e. not at all
+            pw *= (uint32_t)p.n_act;
+            uavk::u32div_gen(pw, &q.pw_magic[b], &q.pw_shift[b]);
+        }
+    }
+    const int per = h->bt <= uavk::kPathQuadMaxBs ? 64 / uavk::kPathQuadMaxBs : 64;          // envs per wavefront
+    const dim3 grid((unsigned)((p.N + per - 1) / per)), blk(64);
+    hipEvent_t tev0 = nullptr, tev1 = nullptr;
+    if (h->timing && h->tev && h->n_timed < kTimedLaunches) {
+        tev0 = (*h->tev)[(size_t)h->n_timed * 2]; tev1 = (*h->tev)[(size_t)h->n_timed * 2 + 1];
+        h->n_timed += 1;
+    }
+    if (h->bt <= uavk::kPathQuadMaxBs) {
+        if (tev0 != nullptr) hipExtLaunchKernelGGL(uavk::uav_path_kernel<4>, grid, blk, 0, s, tev0, tev1, 0, q);
+        else hipLaunchKernelGGL(uavk::uav_path_kernel<4>, grid, blk, 0, s, q);
+    } else {
+        if (tev0 != nullptr) hipExtLaunchKernelGGL(uavk::uav_path_kernel<8>, grid, blk, 0, s, tev0, tev1, 0, q);
+        else hipLaunchKernelGGL(uavk::uav_path_kernel<8>, grid, blk, 0, s, q);
+    }
+    HIP_TRY(hipGetLastError());
+    h->path_launches += 1;
+    return UAVENV_OK;
+}
+
+extern "C" int uavenv_debug_path_launches(uavenv_t *h, long long *n) {
+    if (!h || !n) return fail(UAVENV_E_INVALID, "debug_path_launches: null argument");
+    *n = h->path_launches;
+    return UAVENV_OK;
+}
+
 template <int MANY_>
 static int launch_many(uavenv_t *h, KParams &p, int n_steps, hipStream_t s) {
+    if (call_reads_path(h, p)) { if (int rc = launch_path(h, p, n_steps, s)) return rc; }
     const int i = rotation_plan(h, n_steps, s);        // (first use of this n_steps outside a capture: builds + uploads the table, synchronously)
     if (i >= 0) {
         const uavenv::RotPlan pl = (*h->rot_plans)[(size_t)i];

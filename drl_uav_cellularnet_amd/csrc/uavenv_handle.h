@@ -45,6 +45,7 @@ struct uavenv {
     // the dispatch packet, no marker packets around it), a ring of kTimedLaunches pairs
     std::vector<hipEvent_t> *tev;
     int timing, n_timed;
+    long long path_launches;  // launches of uav_path_kernel on this handle (uavenv_debug_path_launches)
     int force_pin;  // UAVENV_FORCE_PIN read ONCE at create (experiments: tools/pin_sweep.sh): -1 unset, 0 / 1 forced
     double *ul_gain_dev;  // [N, B, B] pair means of uavenv_link_rates when the caller does not ask for them (n_ue <= 64 and n_bs <= 8 only, else null)
     UavEnvStateLayout lay;

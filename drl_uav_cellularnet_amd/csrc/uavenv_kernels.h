@@ -794,7 +794,9 @@ __device__ __forceinline__ void many_retire_loads() {
 // ================================================================================================
 // MANY (MODE_STEP only): p.n_ticks whole steps in ONE launch -- uavenv_step_many.  State is loaded once, lives in registers
 // across the steps and is stored once; step t reads actions[t][N] (the next step's action is prefetched while this step
-// computes) and writes block t of every output array.  Exactly the arithmetic of p.n_ticks single-step launches, so results
+// computes) and writes block t of every output array -- the FAST kernels with BT <= 8 read the UAV cells of step t instead, which
+// uav_path_kernel has left in block t of out.bs_xy before this kernel starts (PATH below; uavenv_path_kernel.h), and neither read an
+// action nor move a UAV.  Exactly the arithmetic of p.n_ticks single-step launches, so results
 // are bit-identical (tests/test_step_many_gpu.py); what disappears is the per-step launch, kernarg fetch, state load round
 // trip and state store, i.e. the fixed ~5.8 us a 4096-env launch spends outside its arithmetic.
 // The kernel proper: `ew` = the env-wavefront this wavefront hosts (envs ew*EPW .. ew*EPW+EPW-1), `t0` / `nt` = first step and
@@ -851,18 +853,21 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
 
     // ================= load phase: every global read of the launch, issued before any dependent work ======
     constexpr bool REG_MOVE = (BT <= 8);   // serial BS_move in registers; n_act^B <= 9^8 always fits 32 bits here
-    // Pinned multi-step launches whose lanes all hold all B == BT cells of their env: the HEAD lane stores a step's bs_xy block (8 B
-    // contiguous bytes) from bsx[] / bsy[], and the owner lanes select the cell they write back to the state once, after the last step --
-    // not in every step (B selects on SGPR-pair conditions that were spill reloads: 6 v_readlane + 8 v_cndmask per step at B = 4).
-    // Pinned only: the unpinned kernel got SLOWER with it (65 536 envs: 45.1-45.3 against 44.0-44.3 us per step).
-    constexpr bool HEAD_BS = MANY && FAST && REG_MOVE && PIN;
+    // FAST multi-step launches with every cell of an env in registers take no UAV move at all: uav_path_kernel (uavenv_path_kernel.h), launched
+    // before this kernel, has written the cells after step t into block t of out.bs_xy and the cells after the call's last step into the state.
+    // The step loop reads block t (prefetched a step ahead, where the action used to be) and stores no cells: no action load, no
+    // bs_move_serial, no bs_xy output store, no bs_xy state store.  The checked kernels, which may have no bs_xy output, move in the loop.
+    constexpr bool PATH = MANY && FAST && REG_MOVE;
+    static_assert(!PATH || BT == 4 || BT == 8, "the path's cells are read two to a global_load_dwordx4");
     int bx = 0, by = 0;                    // the UAV this lane OWNS (store phase)
     int bsx[BT], bsy[BT];                  // all UAV cells of this lane's env (rx_power reads them)
     long long act = 0, apw = 1;
 #pragma unroll
     for (int b = 0; b < BT; ++b) { bsx[b] = 0; bsy[b] = 0; }
     if (MODE != MODE_WARMUP) {
-        if (REG_MOVE) {
+        if (PATH) {
+            // (the cells of step t0 are loaded below, once the parameter struct with the output pointers is there)
+        } else if (REG_MOVE) {
             const int2 *cells = reinterpret_cast<const int2 *>(is_reset(MODE) ? p.bs_init : st.bs_xy);
             const uint32_t c0 = is_reset(MODE) ? 0u : e32 * (uint32_t)B;                 // mobile_env.py:119 on reset
 #pragma unroll
@@ -926,24 +931,36 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
     unsigned long long ob = 0ull;
     OutPtrs om = p.out;                                // MANY: the current step's output blocks (dead code otherwise)
     if (MANY) out_skip_steps<FAST>(om, t0, N, U, B);
+    if (PATH) {                                        // the cells of step t0: plain loads, also in a hand-off piece (an earlier KERNEL wrote them)
+#pragma unroll
+        for (int b = 0; b < BT; b += 2) {
+            const int4 q = ldx(reinterpret_cast<const int4 *>(om.bs_xy), e32 * (uint32_t)(BT / 2) + (uint32_t)(b / 2));
+            bsx[b] = q.x; bsy[b] = q.y; bsx[b + 1] = q.z; bsy[b + 1] = q.w;
+        }
+    }
     // MANY: no wait on a store inside the step loop (many_retire_loads).  The first step needs every load of the load phase anyway.
     if (MANY) many_retire_loads();
     const FinConst K = fin_const<MANY && PIN>(p);
     for (int it = 0; it < n_ticks; ++it) {
         long long act_next = 0;
-        if (MANY) {                                    // prefetch the next step's action: its round trip hides behind this step
+        int4 cells_next[PATH ? BT / 2 : 1];
+        if (PATH) {                                    // prefetch the next step's cells (after the last step: this step's again, unused)
+            const int4 *nxt = reinterpret_cast<const int4 *>(om.bs_xy + ((it + 1 < n_ticks) ? 2 * N * BT : 0));
+#pragma unroll
+            for (int b = 0; b < BT / 2; ++b) cells_next[b] = ldx(nxt, e32 * (uint32_t)(BT / 2) + (uint32_t)b);
+        } else if (MANY) {                             // prefetch the next step's action: its round trip hides behind this step
             const long long *nxt = actions + (long long)((it + 1 < n_ticks) ? it + 1 : it) * N;
             if (REG_MOVE || bown) act_next = ldx(nxt, e32);
         }
         // ---- UAV move: Decimal_to_Base_N + BS_move (ue_mobility.py:191-271,310-336) ---------------
         if (MODE != MODE_WARMUP) {
-            if (REG_MOVE) {
+            if (PATH) {
+                // (bsx / bsy hold this step's cells: the load phase, or the hand-over at the end of the previous step)
+            } else if (REG_MOVE) {
                 if (is_step(MODE) && !LOOK) bs_move_serial<BT, FAST>(p, (unsigned)act, bsx, bsy);
-                if (!HEAD_BS) {
 #pragma unroll
-                    for (int b = 0; b < BT; ++b)
-                        if (ul == b) { bx = bsx[b]; by = bsy[b]; }         // the cell this lane writes back
-                }
+                for (int b = 0; b < BT; ++b)
+                    if (ul == b) { bx = bsx[b]; by = bsy[b]; }             // the cell this lane writes back
             } else {
                 // cooperative form for B > 8: one UAV per lane, sequential rounds, UAV cells staged in LDS
                 if (is_step(MODE) && !LOOK) {
@@ -1042,22 +1059,17 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
         if (MANY) {
             // ---- this step's outputs (block `it` of every output array), then the hand-over to the next step ------------
             many_retire_loads();                                  // outstanding: the prefetch, a step body old, and the previous step's stores
-            act = act_next;                                       // (BS_move, the only reader of `act`, is done; after the last step: unused)
+            if (PATH) {
+#pragma unroll
+                for (int b = 0; b < BT; b += 2) { bsx[b] = cells_next[b / 2].x; bsy[b] = cells_next[b / 2].y; bsx[b + 1] = cells_next[b / 2].z; bsy[b + 1] = cells_next[b / 2].w; }
+            } else act = act_next;                                // (BS_move, the only reader of `act`, is done; after the last step: unused)
             if (live) {
                 if (UAV_OUT(om.ue_xy)) { stx(om.ue_xy, 2u * iu32, (int16_t)ix); stx(om.ue_xy, 2u * iu32 + 1u, (int16_t)iy); }
                 if (UAV_OUT(om.serving)) stx(om.serving, iu32, (int8_t)serving);
                 if (UAV_OUT(om.cur_sinr)) stx(om.cur_sinr, iu32, (float)cur);
                 if (UAV_OUT64(om.cur_sinr_f64)) stx(om.cur_sinr_f64, iu32, cur);
             }
-            if (HEAD_BS) {
-                if (head) {
-#pragma unroll
-                    for (int b = 0; b < BT; ++b) {
-                        const uint32_t c = 2u * (e32 * (uint32_t)BT + (uint32_t)b);
-                        stx(om.bs_xy, c, bsx[b]); stx(om.bs_xy, c + 1u, bsy[b]);
-                    }
-                }
-            } else if (bown) { if (UAV_OUT(om.bs_xy)) { stx(om.bs_xy, 2u * ib32, bx); stx(om.bs_xy, 2u * ib32 + 1u, by); } }
+            if (!PATH && bown) { if (UAV_OUT(om.bs_xy)) { stx(om.bs_xy, 2u * ib32, bx); stx(om.bs_xy, 2u * ib32 + 1u, by); } }
             if (QLATE) sum_cur = slot_quads_sum(sq);
             if (it + 1 < n_ticks) {
                 if (head) env_finish<MODE, FAST, false>(K, om, st, e32, erec, tick, agg, deagg, depth, step_n, sum_cur, n_outage);
@@ -1069,11 +1081,6 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
         }
     }
     if (MODE == MODE_WARMUP) { ix = (int)x; iy = (int)y; }                               // cells after the last warm-up tick
-    if (HEAD_BS) {
-#pragma unroll
-        for (int b = 0; b < BT; ++b)
-            if (ul == b) { bx = bsx[b]; by = bsy[b]; }                                   // the cell this lane writes back
-    }
 
     if constexpr (LOOK && !POLICY::kAfterTick) {   // look-ahead: the requested outputs of the dropped step, then the policy; the state is left as it was loaded
         if (live) {
@@ -1105,7 +1112,7 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
         const uint32_t gw = block_local<!PIN>(ig32);
         stx_c<STC>(st.grp, gw, GrpRec{ogx, ogy, ogfl, ogv, ogc, ogs});
     }
-    if (bown) {
+    if (bown && !PATH) {                                                                 // (PATH: uav_path_kernel has stored the call's last cells)
         const uint32_t bw = block_local<!PIN>(ib32);
         stx_c<STC>(st.bs_xy, 2u * bw, bx); stx_c<STC>(st.bs_xy, 2u * bw + 1u, by);
         if (!MANY) { if (UAV_OUT(pout.bs_xy)) { stx(pout.bs_xy, 2u * bw, bx); stx(pout.bs_xy, 2u * bw + 1u, by); } }

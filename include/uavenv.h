@@ -227,6 +227,11 @@ int uavenv_step_many_prepare(uavenv_t *h, int n_steps);
  * whose hand-offs are never signalled (the time-out path's test). */
 int uavenv_debug_rotation_info(uavenv_t *h, int n_steps, int *n_launches, long long *slots);
 
+/* Test hook: *n = launches of the UAV path kernel on this handle so far.  A uavenv_step_many call that runs the FAST step kernels with
+ * n_bs = 4 or 8 (all nine standard outputs, no float64 copies, one launch: n_ue <= 64) launches it once, before the step kernel: the cells
+ * of every step go to out->bs_xy_dev and the step kernel reads them there instead of moving the UAVs itself.  No other call launches it. */
+int uavenv_debug_path_launches(uavenv_t *h, long long *n);
+
 /* Duration of the multi-step launches themselves, for callers that time SHORT calls (bench.py's 20-step region lasts 0.1 ms: a pair of
  * HIP events recorded on the stream around the call are two marker packets that cost it 10 us).  uavenv_launch_timing(h, 1) makes every
  * following uavenv_step_many dispatch carry its own start / stop events (hipExtLaunchKernelGGL: the dispatch packet's
