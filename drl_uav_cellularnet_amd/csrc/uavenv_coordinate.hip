@@ -7,15 +7,7 @@
 #include "uavenv_coordinate_kernel.h"
 
 using namespace uavk;
-using uavenv_internal::fail;
-using uavenv_internal::policy_call;
-using uavenv_internal::launch_packed_policy;
-using uavenv_internal::decide_then_step;
-using uavenv_internal::wants_f64;
-using uavenv_internal::kCoordPackedMaxBs;
-using uavenv_internal::side_census_count;
-using uavenv_internal::SIDE_COORD_PACKED;
-using uavenv_internal::SIDE_COORD_MULTIPASS;
+using namespace uavenv_internal;
 
 // n_bs <= 8 (kCoordPackedMaxBs): the template bound is 4 or 8
 struct CoordPackedFamily {
@@ -30,9 +22,13 @@ template <int MODE>
 static bool launch_coordinate_multipass(const uavenv_t *h, const KParams &p, const CoordArgs &ca, hipStream_t s) {
     const dim3 grid((unsigned)p.N), blk(64);               // one env per wavefront, one wavefront per workgroup
     const size_t lds = coordinate_lds_bytes(p.U, p.B);     // <= 34 816 bytes (16 x 256)
-    if (h->plc) hipLaunchKernelGGL((env_kernel_coordinate<MODE, true>), grid, blk, lds, s, ca, p);
-    else hipLaunchKernelGGL((env_kernel_coordinate<MODE, false>), grid, blk, lds, s, ca, p);
-    return side_census_count(SIDE_COORD_MULTIPASS, 4, MODE, h->plc, false, 0, false);
+    bool counted = false;
+    with_bool(h->plc, [&](auto plc_c) {
+        constexpr bool PLC = decltype(plc_c)::value;
+        hipLaunchKernelGGL((env_kernel_coordinate<MODE, PLC>), grid, blk, lds, s, ca, p);
+        counted = side_census_count(SIDE_COORD_MULTIPASS, 4, MODE, PLC, false, 0, false);
+    });
+    return counted;
 }
 
 // Everything a handle must be for the policy, tested before any HIP call.  `who`: the entry point named in the message.

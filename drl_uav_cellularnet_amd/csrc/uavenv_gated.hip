@@ -7,10 +7,7 @@
 #include "uavenv_gated_kernel.h"
 
 using namespace uavk;
-using uavenv_internal::fail;
-using uavenv_internal::poisoned;
-using uavenv_internal::fill_call;
-using uavenv_internal::call_is_fast;
+using namespace uavenv_internal;
 
 extern "C" int uavenv_rollout_gated(uavenv_t *h, const UavEnvGatedRollout *r, const UavEnvOut *out, void *stream) {
     if (!h || !r || !out) return fail(UAVENV_E_INVALID, "rollout_gated: null handle, description or outputs");
@@ -45,19 +42,18 @@ extern "C" int uavenv_rollout_gated(uavenv_t *h, const UavEnvGatedRollout *r, co
     hipStream_t s = (hipStream_t)stream;
     const int K = p.U + p.B;
     const bool two = g.wc != nullptr;
-#define GATED_ARGS h->blob, p.gid_of_u, p.N, p.U, p.epw, p.Gr, p.B, (int)uavk::lane_div_magic((uint32_t)p.U), g, p
-#define GATED_LAUNCH(PLC_, KT_)                                                                                          \
-    do {                                                                                                                 \
-        if (two) hipLaunchKernelGGL((env_kernel_gated<4, PLC_, KT_, true>), dim3(grid), blk, 0, s, GATED_ARGS);          \
-        else hipLaunchKernelGGL((env_kernel_gated<4, PLC_, KT_, false>), dim3(grid), blk, 0, s, GATED_ARGS);             \
-        counted = uavenv_internal::side_census_count(uavenv_internal::SIDE_GATED, 4, MODE_STEP, PLC_, false, KT_, two);  \
-    } while (0)
     bool counted = false;
     // (the node count as a template parameter for the reference's two shapes, 4 UAVs + 20 / 40 UEs: the row loop unrolls around v_readlane)
-    if (h->plc) { if (K == 24) GATED_LAUNCH(true, 24); else if (K == 44) GATED_LAUNCH(true, 44); else GATED_LAUNCH(true, 0); }
-    else { if (K == 24) GATED_LAUNCH(false, 24); else if (K == 44) GATED_LAUNCH(false, 44); else GATED_LAUNCH(false, 0); }
-#undef GATED_LAUNCH
-#undef GATED_ARGS
+    auto with_kt = [&](auto f) {
+        if (K == 24) f(std::integral_constant<int, 24>{}); else if (K == 44) f(std::integral_constant<int, 44>{}); else f(std::integral_constant<int, 0>{});
+    };
+    with_bool(h->plc, [&](auto plc_c) { with_kt([&](auto kt_c) { with_bool(two, [&](auto two_c) {
+        constexpr bool PLC = decltype(plc_c)::value, TWO = decltype(two_c)::value;
+        constexpr int KT = decltype(kt_c)::value;
+        hipLaunchKernelGGL((env_kernel_gated<4, PLC, KT, TWO>), dim3(grid), blk, 0, s, h->blob, p.gid_of_u, p.N, p.U, p.epw, p.Gr, p.B,
+                           (int)uavk::lane_div_magic((uint32_t)p.U), g, p);
+        counted = side_census_count(SIDE_GATED, 4, MODE_STEP, PLC, false, KT, TWO);
+    }); }); });
     HIP_TRY(hipGetLastError());
     if (!counted) return fail(UAVENV_E_INVALID, "rollout_gated: side census: an instantiation outside side_variant_selectable()");
     return UAVENV_OK;

@@ -1,9 +1,13 @@
-// Internal to libuavenv (not installed): the handle and the helpers shared by its translation units (uavenv_capi.hip: everything but
-// the gated rollout and the policies; uavenv_gated.hip: uavenv_rollout_gated and its kernel instantiations; uavenv_gradient.hip:
-// uavenv_gradient_actions / uavenv_step_gradient and the look-ahead kernels; uavenv_search.hip: uavenv_search_actions / uavenv_step_search
-// and the search kernels; uavenv_coordinate.hip: uavenv_coordinate_actions / uavenv_step_coordinate and their kernels; uavenv_eval.hip: uavenv_eval_accumulate; uavenv_rates.hip: uavenv_link_rates and its kernels -- files of their own so that none rebuilds the others).
+// Internal to libuavenv (not installed): the handle and the helpers shared by its translation units (uavenv_host.hip: everything
+// that launches no kernel -- create / destroy, config checks, state get / set, launch timing, both censuses, the rotation-schedule builder;
+// uavenv_capi.hip: the env step's kernels and the entry points that launch them, observations, area map, lean math; uavenv_gated.hip:
+// uavenv_rollout_gated and its kernel instantiations; uavenv_gradient.hip: uavenv_gradient_actions / uavenv_step_gradient and the
+// look-ahead kernels; uavenv_search.hip: uavenv_search_actions / uavenv_step_search and the search kernels; uavenv_coordinate.hip:
+// uavenv_coordinate_actions / uavenv_step_coordinate and their kernels; uavenv_eval.hip: uavenv_eval_accumulate; uavenv_rates.hip:
+// uavenv_link_rates and its kernels -- files of their own so that none rebuilds the others).
 // The three policy units share what stands at the end of this file: the call preamble (policy_call), the one launcher of a packed policy
 // kernel (launch_packed_policy; each unit names its kernels in a family type) and the decide-then-step loop (decide_then_step).
+// Every launch site goes from run-time values to a template instantiation through with_bool / with_bt / with_variant below.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -59,8 +63,46 @@ int poisoned(const uavenv *h, const char *what);
 void fill_call(uavk::KParams &p, const UavEnvInject *inj, const UavEnvOut *out);
 bool call_is_fast(const uavk::KParams &p);
 UavEnvOut out_block(const UavEnvOut &o, long long t, long long N, long long U, long long B);   // block t of [T][...] outputs; null members stay null
+int rotation_plan(uavenv *h, int n_steps, hipStream_t stream);   // uavenv_host.hip: index into h->rot_plans of the schedule uavenv_step_many runs, or -1 (plain launch)
 
-// ---- side census (test hook, uavenv_debug_side_variant_*; defined once in uavenv_capi.hip) -------------------------------------------
+// ---- from run-time values to a template instantiation ----------------------------------------------------------------------------------
+// f is a generic lambda; it reads the constant as decltype(c)::value and leaves out, with `if constexpr`, the combinations that have no kernel.
+template <class F>
+void with_bool(bool b, F &&f) {
+    if (b) f(std::true_type{}); else f(std::false_type{});
+}
+// The template bound on n_bs (uavenv::bt).  false, f not called: the bound is above MAX_BT, the largest the caller has kernels for.
+template <int MAX_BT = 32, class F>
+bool with_bt(int bt, F &&f) {
+    auto at = [&](auto bt_c) {
+        if constexpr (decltype(bt_c)::value <= MAX_BT) f(bt_c);
+        return decltype(bt_c)::value <= MAX_BT;
+    };
+    switch (bt) {
+        case 4: return at(std::integral_constant<int, 4>{});
+        case 8: return at(std::integral_constant<int, 8>{});
+        case 16: return at(std::integral_constant<int, 16>{});
+        default: return at(std::integral_constant<int, 32>{});
+    }
+}
+// The arithmetic variant of an env step kernel: its template arguments FAST and PIN (PIN exists only with FAST).
+enum { VAR_CHECKED = 0, VAR_FAST = 1, VAR_PIN = 2 };
+constexpr bool var_fast(int var) { return var != VAR_CHECKED; }
+constexpr bool var_pin(int var) { return var == VAR_PIN; }
+template <class F>
+void with_variant(int var, F &&f) {
+    if (var == VAR_PIN) f(std::integral_constant<int, VAR_PIN>{});
+    else if (var == VAR_FAST) f(std::integral_constant<int, VAR_FAST>{});
+    else f(std::integral_constant<int, VAR_CHECKED>{});
+}
+
+// ---- launch census (test hook, uavenv_debug_variant_*; uavenv_host.hip) ----------------------------------------------------------------
+// launch_env (uavenv_capi.hip) calls census_count() with the constants that instantiated the kernel it launched; false = variant_selectable()
+// rejects the key.  many: 0 single step, 1 multi-step, 2 multi-step under a rotation schedule (SCHED kernels).
+enum { FAM_PACKED = 0, FAM_MULTIPASS = 1 };
+bool census_count(int fam, int bt, int mode, bool plc, int var, int many);
+
+// ---- side census (test hook, uavenv_debug_side_variant_*; defined once in uavenv_host.hip) -------------------------------------------
 // The kernels launched outside launch_env -- policies, gated rollout, link rates, area map -- are templates too.  One family per dispatch
 // site; the key is the template arguments that site selects (a family ignores the arguments it does not have).  A launch site calls
 // side_census_count() after launching; false = side_variant_selectable() rejects the key, which the site reports as an error, as launch_env
@@ -116,40 +158,23 @@ inline int policy_call(const uavenv *h, const char *who, const int16_t *ue_xy_in
 
 // One launch of a packed policy kernel.  F, the family: kFam (its side-census family), kMaxBt (the largest template bound it instantiates),
 // Args (what the kernel takes before the parameters) and kernel<BT, MODE, PLC, FAST>.  A FAST kernel exists only where side_has_fast().
-template <class F, int BT>
-int launch_packed_policy_bt(const uavenv *h, const char *who, const uavk::KParams &p, const typename F::Args &a, bool fast, hipStream_t s) {
-    if constexpr (BT > F::kMaxBt) {
-        return fail(UAVENV_E_INVALID, std::string(who) + ": no kernel for this template bound");   // (the entry refused such a handle)
-    } else {
-        constexpr bool kFast = side_has_fast(F::kFam, BT);
-        fast = fast && kFast;
-        const int mode = p.trace_xy ? uavk::MODE_TRACE : uavk::MODE_STEP;
-        const long long waves = (p.N + p.epw - 1) / p.epw;
-        const dim3 grid((unsigned)((waves + uavk::kWavesPerBlock - 1) / uavk::kWavesPerBlock)), blk(64 * uavk::kWavesPerBlock);
-        auto go = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, blk, 0, s, h->blob, p.gid_of_u, p.N, p.U, p.epw, p.Gr, p.B, (int)uavk::lane_div_magic((uint32_t)p.U), a, p);
-        };
-        auto plc_fast = [&](auto mode_c) {
-            constexpr int MODE = decltype(mode_c)::value;
-            if (h->plc) { if (fast) go(F::template kernel<BT, MODE, true, kFast>); else go(F::template kernel<BT, MODE, true, false>); }
-            else { if (fast) go(F::template kernel<BT, MODE, false, kFast>); else go(F::template kernel<BT, MODE, false, false>); }
-        };
-        if (mode == uavk::MODE_TRACE) plc_fast(std::integral_constant<int, uavk::MODE_TRACE>{});
-        else plc_fast(std::integral_constant<int, uavk::MODE_STEP>{});
-        const bool counted = side_census_count(F::kFam, BT, mode, h->plc, fast, 0, false);
-        HIP_TRY(hipGetLastError());
-        if (!counted) return fail(UAVENV_E_INVALID, std::string(who) + ": side census: an instantiation outside side_variant_selectable()");
-        return UAVENV_OK;
-    }
-}
 template <class F>
 int launch_packed_policy(const uavenv *h, const char *who, const uavk::KParams &p, const typename F::Args &a, bool fast, hipStream_t s) {
-    switch (h->bt) {
-        case 4: return launch_packed_policy_bt<F, 4>(h, who, p, a, fast, s);
-        case 8: return launch_packed_policy_bt<F, 8>(h, who, p, a, fast, s);
-        case 16: return launch_packed_policy_bt<F, 16>(h, who, p, a, fast, s);
-        default: return launch_packed_policy_bt<F, 32>(h, who, p, a, fast, s);
-    }
+    fast = fast && side_has_fast(F::kFam, h->bt);
+    const long long waves = (p.N + p.epw - 1) / p.epw;
+    const dim3 grid((unsigned)((waves + uavk::kWavesPerBlock - 1) / uavk::kWavesPerBlock)), blk(64 * uavk::kWavesPerBlock);
+    bool counted = false;
+    const bool bound = with_bt<F::kMaxBt>(h->bt, [&](auto bt_c) { with_bool(p.trace_xy != nullptr, [&](auto trace_c) { with_bool(h->plc, [&](auto plc_c) { with_bool(fast, [&](auto fast_c) {
+        constexpr int BT = decltype(bt_c)::value, MODE = decltype(trace_c)::value ? uavk::MODE_TRACE : uavk::MODE_STEP;
+        constexpr bool PLC = decltype(plc_c)::value, FAST = decltype(fast_c)::value && side_has_fast(F::kFam, BT);
+        hipLaunchKernelGGL((F::template kernel<BT, MODE, PLC, FAST>), grid, blk, 0, s, h->blob, p.gid_of_u, p.N, p.U, p.epw, p.Gr, p.B,
+                           (int)uavk::lane_div_magic((uint32_t)p.U), a, p);
+        counted = side_census_count(F::kFam, BT, MODE, PLC, FAST, 0, false);
+    }); }); }); });
+    if (!bound) return fail(UAVENV_E_INVALID, std::string(who) + ": no kernel for this template bound");   // (the entry refused such a handle)
+    HIP_TRY(hipGetLastError());
+    if (!counted) return fail(UAVENV_E_INVALID, std::string(who) + ": side census: an instantiation outside side_variant_selectable()");
+    return UAVENV_OK;
 }
 
 // n_steps x [decide(actions of step t); uavenv_step with them]: two launches per step, one host call (as uavenv_step_seq).

@@ -9,8 +9,7 @@
 #include <cstring>
 
 using namespace uavk;
-using uavenv_internal::fail;
-using uavenv_internal::poisoned;
+using namespace uavenv_internal;
 
 static_assert(UAVENV_RATE_MAX_MCS == kRateMaxMcs, "header / kernel bounds differ");
 
@@ -101,10 +100,14 @@ extern "C" int uavenv_link_rates(uavenv_t *h, const UavEnvRateConfig *rate_cfg, 
     } else if (need_ul) {
         const long long waves = h->N * r.P;
         const dim3 grid((unsigned)((waves + kWavesPerBlock - 1) / kWavesPerBlock));
-        if (h->plc) hipLaunchKernelGGL((ul_gain_kernel<true>), grid, blk, 0, s, r, p);
-        else hipLaunchKernelGGL((ul_gain_kernel<false>), grid, blk, 0, s, r, p);
+        bool counted = false;
+        with_bool(h->plc, [&](auto plc_c) {
+            constexpr bool PLC = decltype(plc_c)::value;
+            hipLaunchKernelGGL((ul_gain_kernel<PLC>), grid, blk, 0, s, r, p);
+            counted = side_census_count(SIDE_UL_GAIN, 4, MODE_STEP, PLC, false, 0, false);
+        });
         HIP_TRY(hipGetLastError());
-        if (!uavenv_internal::side_census_count(uavenv_internal::SIDE_UL_GAIN, 4, MODE_STEP, h->plc, false, 0, false))
+        if (!counted)
             return fail(UAVENV_E_INVALID, "link_rates: side census: a pair-mean instantiation outside side_variant_selectable()");
     }
     if (per_ue) {
@@ -112,16 +115,13 @@ extern "C" int uavenv_link_rates(uavenv_t *h, const UavEnvRateConfig *rate_cfg, 
         const long long epw = 64 / ec.n_ue;
         const long long waves = (h->N + epw - 1) / epw;
         const dim3 grid((unsigned)((waves + kWavesPerBlock - 1) / kWavesPerBlock));
-#define RATES_LAUNCH(BT_)                                                                         \
-    do {                                                                                          \
-        if (h->plc) hipLaunchKernelGGL((rates_ue_kernel<BT_, true>), grid, blk, 0, s, r, p);      \
-        else hipLaunchKernelGGL((rates_ue_kernel<BT_, false>), grid, blk, 0, s, r, p);            \
-        counted = uavenv_internal::side_census_count(uavenv_internal::SIDE_RATES_UE, BT_, MODE_STEP, h->plc, false, 0, false); \
-    } while (0)
         bool counted = false;
-        if (ec.n_bs <= 4) RATES_LAUNCH(4);
-        else RATES_LAUNCH(8);
-#undef RATES_LAUNCH
+        with_bt<kRateMaxBs>(h->bt, [&](auto bt_c) { with_bool(h->plc, [&](auto plc_c) {     // (n_bs <= 8, checked above: the bound is 4 or 8)
+            constexpr int BT = decltype(bt_c)::value;
+            constexpr bool PLC = decltype(plc_c)::value;
+            hipLaunchKernelGGL((rates_ue_kernel<BT, PLC>), grid, blk, 0, s, r, p);
+            counted = side_census_count(SIDE_RATES_UE, BT, MODE_STEP, PLC, false, 0, false);
+        }); });
         HIP_TRY(hipGetLastError());
         if (!counted) return fail(UAVENV_E_INVALID, "link_rates: side census: a per-UE instantiation outside side_variant_selectable()");
     }

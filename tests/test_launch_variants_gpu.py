@@ -154,7 +154,7 @@ def test_every_selectable_instantiation_was_launched_and_nothing_else():
 
     census = _capi.launch_census()
     selectable = [c for c in census if c[1]]
-    assert len(selectable) == 188, len(selectable)      # 144 packed (incl. 24 SCHED) + 40 multi-pass + 4 warm-up (csrc/uavenv_capi.hip: variant_selectable)
+    assert len(selectable) == 188, len(selectable)      # 144 packed (incl. 24 SCHED) + 40 multi-pass + 4 warm-up (csrc/uavenv_host.hip: variant_selectable)
     never = [name for name, sel, n in census if sel and n == 0]
     assert not never, "instantiations launch_env can select but no test of this module launched:\n  " + "\n  ".join(never)
     stray = [name for name, sel, n in census if not sel and n != 0]

@@ -1,4 +1,4 @@
-"""CPU: the rotation schedule of uavenv_step_many (csrc/uavenv_capi.hip: build_schedule) as pure host arithmetic, through
+"""CPU: the rotation schedule of uavenv_step_many (csrc/uavenv_host.hip: build_schedule) as pure host arithmetic, through
 the test hook uavenv_debug_schedule -- no device needed.  For many (env-wavefronts W, slots S, steps T): every step of every job exactly
 once and in order; at most three pieces per slot, in the column order publish / whole / wait; a job is one whole piece or two pieces on
 different slots; the publishing piece is the FIRST piece of its slot (so it never waits: every hand-off wait ends, whatever order the

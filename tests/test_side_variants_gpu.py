@@ -32,7 +32,7 @@ G = 40
 F32_RTOL = TG.F32_RTOL
 FORMS = {"cube": {}, "generic": {"pl_b": 27.5}, "cube-near": {"pl_dis": PL_DIS}, "generic-near": {"pl_b": 27.5, "pl_dis": PL_DIS}}
 PLAIN, NEAR = ("cube", "generic"), ("cube-near", "generic-near")
-# what side_variant_selectable() admits per family (csrc/uavenv_capi.hip); 86 of the table's 94 slots: the fast look-ahead at BT = 32 (4)
+# what side_variant_selectable() admits per family (csrc/uavenv_host.hip); 86 of the table's 94 slots: the fast look-ahead at BT = 32 (4)
 # and the fast search at BT = 8 (4) are not built, since no handle those entry points serve has n_bs == 32 resp. 8
 SELECTABLE = {"env_kernel_look": 28, "env_kernel_search": 12, "env_kernel_coordinate_packed": 16, "env_kernel_coordinate": 4,
               "env_kernel_gated": 12, "ul_gain_kernel": 2, "rates_ue_kernel": 4, "sinr_area_kernel": 8}

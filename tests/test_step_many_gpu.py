@@ -72,7 +72,7 @@ ROT_SHAPES = [(100, 4, 20, 7, 24), (100, 4, 20, 50, 26), (301, 4, 20, 33, 80), (
 @pytest.mark.parametrize("shape", ROT_SHAPES, ids=lambda s: "%denv_%dx%d_T%d_S%d" % s)
 def test_rotation_schedule_is_bit_identical_to_the_plain_launch(shape, monkeypatch):
     """A multi-step call on S < W < 2 S wavefronts runs as ONE launch of S persistent wavefronts, each working through up to three pieces
-    (env-wavefront, first step, steps) of a wrap-around schedule (csrc/uavenv_capi.hip: rotation_plan); the two wavefronts that share
+    (env-wavefront, first step, steps) of a wrap-around schedule (csrc/uavenv_host.hip: rotation_plan); the two wavefronts that share
     a split job hand its state over through memory + a flag.  Same steps, same order per env: every output of every step and the final state must equal the
     single plain launch.  UAVENV_ROTATE_SLOTS makes small batches plan as if the device had that few SIMDs; at BASELINE's 4096 envs
     the schedule is chosen automatically (tests/test_full_size_parity_gpu.py compares that run with the oracle)."""

@@ -25,7 +25,9 @@ def read(path):
             if l.startswith(".Lfunc_end"):
                 name = None
             else:
-                bodies[name].append(re.sub(r"\.L(BB|tmp|func_\w+?)\d+", r".L\1", l))    # (local label numbers follow the order of the functions)
+                l = re.sub(r"\.L(BB|tmp|func_\w+?)\d+", r".L\1", l)    # (local label numbers follow the order of the functions,
+                l = re.sub(r"\bBB\d+_(\d+)", r"BB_\1", l)                # also where a loop comment names a block: Header=BB4_8,
+                bodies[name].append(re.sub(r"\s+;", " ;", l))                # and the comment column moves with the label's width)
     meta, cur = {}, None
     for l in lines:
         m = re.match(r"^\s+(?:- )?\.(\w+):\s+(\S+)$", l)
