@@ -19,7 +19,9 @@ EXPORTS = ("uavagent_abi_version", "uavagent_last_error", "uavagent_sparse_rows_
            "uavagent_gemm_rows_f32", "uavagent_gemm_rows_workspace_bytes", "uavagent_gemm_tn_workspace_bytes", "uavagent_gemm_tn_f32",
            "uavagent_debug_tn_plan_check", "uavagent_actor_head_f32", "uavagent_actor_head_gated_f32", "uavagent_gate_prepare",
            "uavagent_device_error", "uavagent_device_error_clear", "uavagent_actor_head_greedy_f32", "uavagent_argmax_rows_f32",
-           "uavagent_choose_factored_f32", "uavagent_loss_grad_factored_workspace_bytes", "uavagent_a2c_loss_grad_factored")
+           "uavagent_choose_factored_f32", "uavagent_loss_grad_factored_workspace_bytes", "uavagent_a2c_loss_grad_factored",
+           "uavagent_first_layer_wide_f32", "uavagent_first_layer_wide_from_obs_f32", "uavagent_rows_grad_wide_sort",
+           "uavagent_rows_grad_wide_sums_f32")
 ABI_VERSION = 5
 
 _lib = None
@@ -47,6 +49,9 @@ _PROF_KEYS = {
     "uavagent_actor_head_f32": lambda a: "rows=%d" % a[6],
     "uavagent_actor_head_greedy_f32": lambda a: "rows=%d" % a[5],
     "uavagent_first_layer_from_obs_f32": lambda a: "rows=%d" % a[9],
+    "uavagent_first_layer_wide_from_obs_f32": lambda a: "rows=%d" % a[9],
+    "uavagent_first_layer_wide_f32": lambda a: "rows=%d,K=%d" % (a[7], a[8]),
+    "uavagent_rows_grad_wide_sums_f32": lambda a: "M=%d,K=%d" % (a[1], a[2]),
     "uavagent_sparse_rows_sum_f32": lambda a: "rows=%d" % a[7],
     "uavagent_rows_grad_sums_f32": lambda a: "M=%d,K=%d" % (a[1], a[2]),
     "uavagent_rows_grad_f32": lambda a: "M=%d,K=%d" % (a[2], a[3]),
@@ -125,9 +130,16 @@ def load():
         "uavagent_choose_factored_f32": [_P, _I64, _P, _I64, _I32, _I32, _P, _P, _P, _P],
         "uavagent_a2c_loss_grad_factored": [_P, _I64, _P, _P, _P, _I64, _I32, _I32, _F, _P, _P, _P, _P, _P],
         "uavagent_gate_prepare": [],
+    }
+    for wide, narrow in (("uavagent_first_layer_wide_f32", "uavagent_first_layer_f32"),
+                         ("uavagent_first_layer_wide_from_obs_f32", "uavagent_first_layer_from_obs_f32"),
+                         ("uavagent_rows_grad_wide_sort", "uavagent_rows_grad_sort"),
+                         ("uavagent_rows_grad_wide_sums_f32", "uavagent_rows_grad_sums_f32")):
+        sig[wide] = sig[narrow]                             # the 256-node forms take their 64-node siblings' arguments
+    sig.update({
         "uavagent_device_error": [C.POINTER(C.c_uint32)],
         "uavagent_device_error_clear": [],
-    }
+    })
     for name, args in sig.items():
         fn = getattr(lib, name)
         fn.restype = C.c_int
@@ -184,8 +196,21 @@ def _f32c(t, what):
         raise UavAgentError("%s must be a contiguous float32 CUDA tensor" % what)
 
 
+NARROW_NODES = 64     # one lane per node: the bound of sparse_rows_sum, first_layer_from_obs and rows_grad*
+WIDE_NODES = 256      # ... and of their *_wide forms (four passes of 64)
+
+
 def sparse_rows_sum(idx, w_a, b_a, w_c=None, b_c=None, relu6=False, out_a=None, out_c=None):
-    """Raw launch, no autograd: returns out_a or (out_a, out_c).  idx int64 [M, K]; w_* f32 [S, H]; b_* f32 [H] or None."""
+    """Raw launch, no autograd: returns out_a or (out_a, out_c).  idx int64 [M, K <= 64]; w_* f32 [S, H]; b_* f32 [H] or None."""
+    return _sparse_rows_sum("uavagent_first_layer_f32", idx, w_a, b_a, w_c, b_c, relu6, out_a, out_c)
+
+
+def sparse_rows_sum_wide(idx, w_a, b_a, w_c=None, b_c=None, relu6=False, out_a=None, out_c=None):
+    """sparse_rows_sum for K <= 256 (uavagent_first_layer_wide_f32): the same bits for K <= 64, a sequential float32 sum for any K."""
+    return _sparse_rows_sum("uavagent_first_layer_wide_f32", idx, w_a, b_a, w_c, b_c, relu6, out_a, out_c)
+
+
+def _sparse_rows_sum(entry, idx, w_a, b_a, w_c, b_c, relu6, out_a, out_c):
     lib = load()
     if not (idx.is_cuda and w_a.is_cuda):
         raise UavAgentError("sparse_rows_sum needs CUDA tensors")
@@ -210,15 +235,24 @@ def sparse_rows_sum(idx, w_a, b_a, w_c=None, b_c=None, relu6=False, out_a=None, 
         if o is not None and (o.shape != (M, H) or o.dtype != torch.float32 or not o.is_contiguous()):
             raise UavAgentError("outputs must be contiguous float32 [M, H]")
     with torch.cuda.device(idx.device):
-        rc = lib.uavagent_first_layer_f32(_ptr(w_a), _ptr(b_a), _ptr(out_a), _ptr(w_c), _ptr(b_c), _ptr(out_c), _ptr(idx),
-                                          M, K, H, S, 1 if relu6 else 0, _stream(idx.device))
-    _check(rc, "uavagent_first_layer_f32")
+        rc = getattr(lib, entry)(_ptr(w_a), _ptr(b_a), _ptr(out_a), _ptr(w_c), _ptr(b_c), _ptr(out_c), _ptr(idx),
+                                 M, K, H, S, 1 if relu6 else 0, _stream(idx.device))
+    _check(rc, entry)
     return out_a if w_c is None else (out_a, out_c)
 
 
 def first_layer_from_obs(obs, grid_n, w_a, b_a, w_c, b_c, out_a, out_c, idx_out=None, relu6=True):
     """obs_indices + sparse_rows_sum in one launch (the rollout loop): obs = env.observation(); the index list of every env is built in
-    the kernel, stored to idx_out [N, B + U] (or not, when None) and summed.  Same bits as the two separate launches."""
+    the kernel, stored to idx_out [N, B + U] (or not, when None) and summed.  Same bits as the two separate launches.  B + U <= 64."""
+    return _first_layer_from_obs("uavagent_first_layer_from_obs_f32", obs, grid_n, w_a, b_a, w_c, b_c, out_a, out_c, idx_out, relu6)
+
+
+def first_layer_from_obs_wide(obs, grid_n, w_a, b_a, w_c, b_c, out_a, out_c, idx_out=None, relu6=True):
+    """first_layer_from_obs for B + U <= 256 (uavagent_first_layer_wide_from_obs_f32): obs_indices + sparse_rows_sum_wide in one launch."""
+    return _first_layer_from_obs("uavagent_first_layer_wide_from_obs_f32", obs, grid_n, w_a, b_a, w_c, b_c, out_a, out_c, idx_out, relu6)
+
+
+def _first_layer_from_obs(entry, obs, grid_n, w_a, b_a, w_c, b_c, out_a, out_c, idx_out, relu6):
     ue, bs, srv = obs["ue_xy"], obs["bs_xy"], obs["serving"]
     if ue.dtype != torch.int16 or bs.dtype != torch.int32 or srv.dtype != torch.int8:
         raise UavAgentError("first_layer_from_obs needs the env's compact observation dtypes (int16 / int32 / int8)")
@@ -234,10 +268,9 @@ def first_layer_from_obs(obs, grid_n, w_a, b_a, w_c, b_c, out_a, out_c, idx_out=
     if idx_out is not None and (idx_out.shape != (N, B + U) or idx_out.dtype != torch.int64 or not idx_out.is_contiguous()):
         raise UavAgentError("idx_out must be contiguous int64 [N, B + U]")
     with torch.cuda.device(ue.device):
-        rc = load().uavagent_first_layer_from_obs_f32(_ptr(w_a), _ptr(b_a), _ptr(out_a), _ptr(w_c), _ptr(b_c), _ptr(out_c), _ptr(ue), _ptr(bs),
-                                                      _ptr(srv), N, U, B, int(grid_n), H, S, 1 if relu6 else 0, _ptr(idx_out),
-                                                      _stream(ue.device))
-    _check(rc, "uavagent_first_layer_from_obs_f32")
+        rc = getattr(load(), entry)(_ptr(w_a), _ptr(b_a), _ptr(out_a), _ptr(w_c), _ptr(b_c), _ptr(out_c), _ptr(ue), _ptr(bs),
+                                    _ptr(srv), N, U, B, int(grid_n), H, S, 1 if relu6 else 0, _ptr(idx_out), _stream(ue.device))
+    _check(rc, entry)
     return out_a if w_c is None else (out_a, out_c)
 
 
@@ -332,28 +365,44 @@ def rows_grad(idx, g, h, n_rows, dw0, dw1, ws):
     _check(rc, "uavagent_rows_grad_f32")
 
 
-def rows_grad_sort(idx, n_cols_total, n_rows, ws):
+def rows_grad_sort(idx, n_cols_total, n_rows, ws, _entry="uavagent_rows_grad_sort"):
     """First half of rows_grad: the stable sort of the (row, sample) pairs into ws (needs only idx; current stream)."""
     if idx.dtype != torch.int64 or idx.dim() != 2 or not idx.is_contiguous():
         raise UavAgentError("idx must be contiguous int64 [M, K]")
     M, K = idx.shape
     off = (-ws.data_ptr()) % 256
     with torch.cuda.device(idx.device):
-        rc = load().uavagent_rows_grad_sort(_ptr(idx), M, K, int(n_cols_total), int(n_rows), C.c_void_p(ws.data_ptr() + off), ws.numel() - off,
-                                            _stream(idx.device))
-    _check(rc, "uavagent_rows_grad_sort")
+        rc = getattr(load(), _entry)(_ptr(idx), M, K, int(n_cols_total), int(n_rows), C.c_void_p(ws.data_ptr() + off), ws.numel() - off,
+                                     _stream(idx.device))
+    _check(rc, _entry)
 
 
-def rows_grad_sums(idx_shape, g, h, n_rows, dw0, dw1, ws):
+def rows_grad_sums(idx_shape, g, h, n_rows, dw0, dw1, ws, _entry="uavagent_rows_grad_sums_f32"):
     """Second half: the segmented sums over the pairs rows_grad_sort left in ws (same idx; ordered behind the sort by the caller)."""
     _f32c(g, "g")
     M, K = idx_shape
     n_tables = g.shape[1] // h
     off = (-ws.data_ptr()) % 256
     with torch.cuda.device(g.device):
-        rc = load().uavagent_rows_grad_sums_f32(_ptr(g), M, K, int(h), n_tables, int(n_rows), _ptr(dw0), _ptr(dw1),
-                                                C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream(g.device))
-    _check(rc, "uavagent_rows_grad_sums_f32")
+        rc = getattr(load(), _entry)(_ptr(g), M, K, int(h), n_tables, int(n_rows), _ptr(dw0), _ptr(dw1),
+                                     C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream(g.device))
+    _check(rc, _entry)
+
+
+def rows_grad_sort_wide(idx, n_cols_total, n_rows, ws):
+    """rows_grad_sort for K <= 256 (uavagent_rows_grad_wide_sort); the workspace is rows_grad_workspace's."""
+    rows_grad_sort(idx, n_cols_total, n_rows, ws, _entry="uavagent_rows_grad_wide_sort")
+
+
+def rows_grad_sums_wide(idx_shape, g, h, n_rows, dw0, dw1, ws):
+    """rows_grad_sums for K <= 256 (uavagent_rows_grad_wide_sums_f32)."""
+    rows_grad_sums(idx_shape, g, h, n_rows, dw0, dw1, ws, _entry="uavagent_rows_grad_wide_sums_f32")
+
+
+def rows_grad_wide(idx, g, h, n_rows, dw0, dw1, ws):
+    """rows_grad for K <= 256: the wide sort and the wide sums, one after the other on the current stream."""
+    rows_grad_sort_wide(idx, g.shape[1], n_rows, ws)
+    rows_grad_sums_wide(tuple(idx.shape), g, h, n_rows, dw0, dw1, ws)
 
 
 def nstep_returns(rewards, bootstrap, gamma, out=None):
@@ -631,7 +680,8 @@ def _table_grad_aten(g, idx, n_rows):
 
 class _SparseRowsSum(torch.autograd.Function):
     """Differentiable first layer for the autograd (reference) path of the learner: forward = the HIP gather kernel, backward =
-    uavagent_rows_grad_f32 for both tables in one sorted pass + plain column sums for the biases."""
+    uavagent_rows_grad_f32 for both tables in one sorted pass + plain column sums for the biases.  More than 64 nodes per sample (up to
+    256) take the wide forms of both."""
 
     @staticmethod
     def forward(ctx, idx, w_a, b_a, w_c, b_c):
@@ -639,7 +689,7 @@ class _SparseRowsSum(torch.autograd.Function):
         ctx.n_rows = w_a.shape[0]
         ctx.h = w_a.shape[1]
         ctx.two = w_c is not None
-        out = sparse_rows_sum(idx, w_a, b_a, w_c, b_c)
+        out = (sparse_rows_sum if idx.shape[1] <= NARROW_NODES else sparse_rows_sum_wide)(idx, w_a, b_a, w_c, b_c)
         if ctx.two:
             return out
         return out, None
@@ -655,7 +705,7 @@ class _SparseRowsSum(torch.autograd.Function):
             gw_a = torch.empty((ctx.n_rows, ctx.h), dtype=torch.float32, device=g.device)
             gw_c = torch.empty_like(gw_a) if two else None
             ws = rows_grad_workspace(idx.shape[0], idx.shape[1], g.shape[1], ctx.n_rows, g.device)
-            rows_grad(idx.contiguous(), g, ctx.h, ctx.n_rows, gw_a, gw_c, ws)
+            (rows_grad if idx.shape[1] <= NARROW_NODES else rows_grad_wide)(idx.contiguous(), g, ctx.h, ctx.n_rows, gw_a, gw_c, ws)
         gb_a = g_a.sum(dim=0) if need[2] else None
         gb_c = g_c.sum(dim=0) if (two and need[4]) else None
         return None, gw_a, gb_a, gw_c, gb_c

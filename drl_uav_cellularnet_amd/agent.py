@@ -89,10 +89,14 @@ class ACNet(torch.nn.Module):
     def critic_params(self):
         return [self.c_w1, self.c_b1, self.c_w2, self.c_b2, self.c_w3, self.c_b3]
 
+    def _policy_prob(self, logits):
+        """The policy output from the head's logits: one softmax over the joint actions (factored.FactoredACNet: one per UAV)."""
+        return torch.softmax(logits, dim=-1)
+
     def _heads(self, ha, hc):
         ha = F.relu6(F.relu6(ha) @ self.a_w2 + self.a_b2)
         hc = F.relu6(F.relu6(hc) @ self.c_w2 + self.c_b2)
-        a_prob = torch.softmax(ha @ self.a_w3 + self.a_b3, dim=-1)
+        a_prob = self._policy_prob(ha @ self.a_w3 + self.a_b3)
         v = hc @ self.c_w3 + self.c_b3
         return a_prob, v
 
@@ -104,7 +108,7 @@ class ACNet(torch.nn.Module):
     def actor_only(self, idx):
         ha, _ = sparse_first_layer(idx, self.a_w1, self.a_b1)
         ha = F.relu6(F.relu6(ha) @ self.a_w2 + self.a_b2)
-        return torch.softmax(ha @ self.a_w3 + self.a_b3, dim=-1)
+        return self._policy_prob(ha @ self.a_w3 + self.a_b3)
 
     def critic_only(self, idx):
         hc, _ = sparse_first_layer(idx, self.c_w1, self.c_b1)
@@ -353,7 +357,7 @@ class A2CRunner:
         self.fused_head = bool(fused_head) and self.hip_gemms and 576 < self.net.n_action <= 640
         # fused_obs: steps 1 .. T-1 of a rollout build their index list inside the first layer's kernel (uavagent_first_layer_from_obs_f32)
         # instead of a separate obs_indices launch after every env step
-        self.fused_obs = bool(fused_obs) and env.nBS + env.nUE <= 64
+        self.fused_obs = bool(fused_obs) and env.nBS + env.nUE <= self.FUSED_OBS_MAX_NODES
         self._side = None
         # pipeline_halves (GPU, fused_head + fused_obs): the workers of a2c_single_thread.py:113-118 are independent of each other for a
         # whole rollout, so the batch is cut in two halves that ping-pong on two streams inside the rollout (and inside its captured
@@ -419,6 +423,7 @@ class A2CRunner:
         self._upd = None
 
     NET_KIND = "mlp"
+    FUSED_OBS_MAX_NODES = 64      # uavagent_first_layer_from_obs_f32: one lane per node (factored.FactoredA2CRunner: the wide form's 256)
 
     def _init_common(self, env, net, rollout, gamma, beta, lr_a, lr_c, seed, update_chunk, first_state, tune_gemms):
         """What every runner over a BatchedMobiEnv sets up (A2CRunner and cnn_agent.CnnA2CRunner): the net in FlatParams with its two
@@ -489,11 +494,38 @@ class A2CRunner:
         if t == 0 or not self.fused_obs:
             # both trunks in one gather (tried twice, round 2 and round 3: the critic's half on a second stream beside the actor's GEMMs is
             # SLOWER, 6.3-6.4 against 5.5 ms per rollout: two 800-byte gathers cost more than one of 1600)
-            A.sparse_rows_sum(self.idx_buf[t][lo:hi], net.a_w1, net.a_b1, net.c_w1, net.c_b1, relu6=True, out_a=fw["h1a"][t][lo:hi],
-                              out_c=fw["h1c"][t][lo:hi])
+            self._gather_kernels()[0](self.idx_buf[t][lo:hi], net.a_w1, net.a_b1, net.c_w1, net.c_b1, relu6=True, out_a=fw["h1a"][t][lo:hi],
+                                      out_c=fw["h1c"][t][lo:hi])
         else:
-            A.first_layer_from_obs({k: v[lo:hi] for k, v in self.env.observation().items()}, self.G, net.a_w1, net.a_b1, net.c_w1, net.c_b1,
-                                   fw["h1a"][t][lo:hi], fw["h1c"][t][lo:hi], idx_out=self.idx_buf[t][lo:hi])
+            self._gather_kernels()[1]({k: v[lo:hi] for k, v in self.env.observation().items()}, self.G, net.a_w1, net.a_b1, net.c_w1, net.c_b1,
+                                      fw["h1a"][t][lo:hi], fw["h1c"][t][lo:hi], idx_out=self.idx_buf[t][lo:hi])
+
+    # ---- what depends on the form of the policy head and on the number of nodes (factored.FactoredA2CRunner states its own) ----------
+    def _gather_kernels(self):
+        """(index-list gather, gather from the observation, table-gradient sort, table-gradient sums) of the first layer."""
+        from . import _agent_capi as A
+
+        return A.sparse_rows_sum, A.first_layer_from_obs, A.rows_grad_sort, A.rows_grad_sums
+
+    def _draw(self, logits, t, lo, hi):
+        """Actions of the rows [lo, hi) of step t from their logits (GPU), into act_buf[t]."""
+        from . import _agent_capi as A
+
+        A.sample_actions(logits, self.u_buf[t][lo:hi], out=self.act_buf[t][lo:hi])
+
+    def _draw_reference(self, t):
+        """Step t's actions on the CPU path: the plain PyTorch forward and draw."""
+        return sample_actions(self.net.actor_only(self.idx_buf[t]), uniforms=self.u_buf[t])
+
+    def _loss_workspace(self):
+        from . import _agent_capi as A
+
+        return A.loss_grad_workspace(self.net.n_action, self.dev)
+
+    def _loss_grad(self, logits, v, target, actions, dv, dbias, loss, ws):
+        from . import _agent_capi as A
+
+        A.a2c_loss_grad(logits, v, target, actions, self.beta, dv, dbias, loss, ws)
 
     def _policy(self, t, lo, hi):
         """The actor's layer 2, policy head and action draw for the rows [lo, hi) of step t (GPU)."""
@@ -501,17 +533,17 @@ class A2CRunner:
 
         net, fw, wt = self.net, self._fwd, self._wt
         h1a, h2a, logits = fw["h1a"][t][lo:hi], fw["h2a"][t][lo:hi], fw["logits"][t][lo:hi]
-        u, act = self.u_buf[t][lo:hi], self.act_buf[t][lo:hi]
         if self.fused_head:      # one launch, 32 rows per workgroup
-            A.actor_head(h1a, wt["a_w2t"], net.a_b2, wt["a_w3t"], wt["a_b3p"], u, net.n_action, h2a, self._logits_pad[t][lo:hi], act)
+            A.actor_head(h1a, wt["a_w2t"], net.a_b2, wt["a_w3t"], wt["a_b3p"], self.u_buf[t][lo:hi], net.n_action, h2a, self._logits_pad[t][lo:hi],
+                         self.act_buf[t][lo:hi])
         elif wt is not None:     # float32 MFMA kernels, bias / relu6 fused, 64-row workgroups (8192 rows fill the chip)
             A.gemm_rows(h1a, wt["a_w2t"], h2a, w_transposed=True, bias=net.a_b2, relu6=True)
             A.gemm_rows(h2a, wt["a_w3t"], self._logits_pad[t][lo:hi], w_transposed=True, bias=wt["a_b3p"])
-            A.sample_actions(logits, u, out=act)
+            self._draw(logits, t, lo, hi)
         else:
             torch.addmm(net.a_b2, h1a, net.a_w2, out=h2a).clamp_(0.0, 6.0)
             torch.addmm(net.a_b3, h2a, net.a_w3, out=logits)
-            A.sample_actions(logits, u, out=act)
+            self._draw(logits, t, lo, hi)
 
     def _rollout_steps(self):
         """The T-step loop: choose_action (main.py:165-169) -> env.step -> next observation.  No host synchronisation, no
@@ -528,8 +560,7 @@ class A2CRunner:
                 self._first_layer(t, 0, N)
                 self._policy(t, 0, N)
             else:
-                prob = self.net.actor_only(self.idx_buf[t])
-                self.act_buf[t] = sample_actions(prob, uniforms=self.u_buf[t])
+                self.act_buf[t] = self._draw_reference(t)
             env.step(self.act_buf[t], reward_out=self.rew_buf[t])
             if not (cuda and self.fused_obs) or t == T - 1:
                 self._indices_into(self.idx_buf[t + 1])
@@ -808,7 +839,7 @@ class A2CRunner:
         self._upd = {"M": M, "own": own, "h1a": fw["h1a"], "h1c": fw["h1c"], "h2a": fw["h2a"], "logits": logits_pad[:, :NA],
                      "logits_pad": logits_pad, "h2c": f(M, H), "dh": f(M, H),
                      "gcat": f(M, 2 * H), "v": f(M), "dv": f(M), "target": f(M), "loss": torch.zeros(3, dtype=torch.float64, device=dev),
-                     "ws_loss": A.loss_grad_workspace(NA, dev), "ws_relu": A.relu6_bwd_workspace(H, dev),
+                     "ws_loss": self._loss_workspace(), "ws_relu": A.relu6_bwd_workspace(H, dev),
                      "ws_rows": A.rows_grad_workspace(M, K, 2 * H, self.net.n_state, dev)}
         if self.hip_gemms:
             self._upd.update({"w3p": torch.zeros((H, ldl), dtype=torch.float32, device=dev),       # a_w3 in rows of ldl, zero tail
@@ -874,21 +905,22 @@ class A2CRunner:
         if self._side is None:
             self._side = torch.cuda.Stream(device=self.dev)
         side = self._side
+        rows_sum, _, rows_sort, rows_sums = self._gather_kernels()
         # The table gradient's sort needs only idx: on the side stream, beside the forward pass and the dX chain (one sort serves both
         # trunks' sums when they are exchanged separately).
         side.wait_stream(main)
         with torch.cuda.stream(side):
-            A.rows_grad_sort(idx, 2 * H, net.n_state, b["ws_rows"])
+            rows_sort(idx, 2 * H, net.n_state, b["ws_rows"])
         sorted_ev = torch.cuda.Event()
         sorted_ev.record(side)
 
         def table_grad(g, dw0, dw1):
             main.wait_event(sorted_ev)
-            A.rows_grad_sums((M, K), g, H, net.n_state, dw0, dw1, b["ws_rows"])
+            rows_sums((M, K), g, H, net.n_state, dw0, dw1, b["ws_rows"])
         # forward: the actor's activations and both first layers were computed by the rollout itself, with these very weights
         reuse = b["own"] and self._fwd_valid and idx_buf.data_ptr() == self.idx_buf.data_ptr()
         if not reuse:
-            A.sparse_rows_sum(idx, net.a_w1, net.a_b1, net.c_w1, net.c_b1, relu6=True, out_a=b["h1a"], out_c=b["h1c"])
+            rows_sum(idx, net.a_w1, net.a_b1, net.c_w1, net.c_b1, relu6=True, out_a=b["h1a"], out_c=b["h1c"])
             if hip:
                 self._refresh_transposed()
                 A.gemm_rows(b["h1a"], self._wt["a_w2t"], b["h2a"], w_transposed=True, bias=net.a_b2, relu6=True)
@@ -905,7 +937,7 @@ class A2CRunner:
             torch.addmm(net.c_b2, b["h1c"], net.c_w2, out=b["h2c"]).clamp_(0.0, 6.0)
         A.rowdot(b["h2c"], net.c_w3, net.c_b3, b["v"])
         # loss and its gradient w.r.t. logits / v (logits are overwritten); d a_b3, d c_b3
-        A.a2c_loss_grad(b["logits"], b["v"], target, act, self.beta, b["dv"], gv["a_b3"], b["loss"], b["ws_loss"])
+        self._loss_grad(b["logits"], b["v"], target, act, b["dv"], gv["a_b3"], b["loss"], b["ws_loss"])
         gv["c_b3"].copy_(b["loss"][2:3].to(torch.float32))
         two_buckets = "g_a" in b
         ae = fl.actor_end

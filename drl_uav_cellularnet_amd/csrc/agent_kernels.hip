@@ -25,34 +25,13 @@ int fail(int code, const std::string &msg) { g_err = msg; return code; }
 namespace {
 using uavagent_internal::fail;
 
-__device__ __forceinline__ void add4(float4 &s, const float4 &v) { s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
-// s += v * w with w in {0.0f, 1.0f} held in an SGPR: one v_fmac per component, like the add it replaces; v * 1 + s rounds exactly
-// like s + v, and v * 0 + s is s for the finite table entries (a skipped row still costs its read, of row 0, but adds nothing).
-__device__ __forceinline__ void fma4(float4 &s, const float4 &v, float w) {
-    s.x = __builtin_fmaf(v.x, w, s.x); s.y = __builtin_fmaf(v.y, w, s.y); s.z = __builtin_fmaf(v.z, w, s.z); s.w = __builtin_fmaf(v.w, w, s.w);
-}
-__device__ __forceinline__ float lane_weight(float w, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), k)); }
-
 // KT > 0: K known at compile time (24 = 4 UAV + 20 UE, 44 = 4 + 40), so the row loop unrolls by UNR with no remainder --
 // v_readlane is a convergent operation and hipcc will not unroll a loop around it when the trip count is a run-time value.
 // KT == 0: any K, one row (per table) in flight at a time.
 // RELU6: the layer's activation applied to the stored result, h = relu6(sum + b) (tf.nn.relu6, main.py:147-148,153): saves the
 // separate elementwise pass over [M, H] on both the acting and the update path.
-__device__ __forceinline__ float4 relu6_4(float4 v) {
-    v.x = fminf(fmaxf(v.x, 0.f), 6.f); v.y = fminf(fmaxf(v.y, 0.f), 6.f); v.z = fminf(fmaxf(v.z, 0.f), 6.f); v.w = fminf(fmaxf(v.w, 0.f), 6.f);
-    return v;
-}
-// OBS: the index list is not read but BUILT, from the env's compact observation of sample (= env) m -- agent.obs_to_indices /
-// obs_indices_kernel (agent_learner.hip) folded into the gather: node k < B is UAV k in plane 0, node k >= B is UE k - B in plane
-// 1 + its serving UAV (mobile_env.py:169-170), row = (plane * G + x) * G + y, -1 for a node off the grid; the list is also stored
-// (idx_out [M, K], the update's sample record) unless idx_out is null.  One launch less per rollout step.
-struct ObsSrc {
-    const int16_t *ue_xy;       // [M, U, 2]
-    const int32_t *bs_xy;       // [M, B, 2]
-    const int8_t *serving;      // [M, U]
-    long long *idx_out;         // [M, U + B] or null
-    int U, B, G;
-};
+// OBS: the index list is not read but BUILT from the env's compact observation (ObsSrc / obs_row_index, agent_common.h); the list is
+// also stored (idx_out [M, K], the update's sample record) unless idx_out is null.  One launch less per rollout step.
 template <bool TWO, int KT, int UNR, bool RELU6, bool OBS>
 __global__ __launch_bounds__(256) void sparse_rows_sum_kernel(const float *__restrict__ wa, const float *__restrict__ ba,
                                                               float *__restrict__ oa, const float *__restrict__ wc,
@@ -67,17 +46,7 @@ __global__ __launch_bounds__(256) void sparse_rows_sum_kernel(const float *__res
     long long mine = 0;
     if (OBS) {
         if (lane < K) {
-            int x, y, pl;
-            if (lane < src.B) {
-                const int2 c = reinterpret_cast<const int2 *>(src.bs_xy)[m * src.B + lane];
-                x = c.x; y = c.y; pl = 0;
-            } else {
-                const long long iu = m * src.U + (lane - src.B);
-                const short2 c = reinterpret_cast<const short2 *>(src.ue_xy)[iu];
-                x = c.x; y = c.y; pl = 1 + src.serving[iu];
-            }
-            const bool ok = x >= 0 && x < src.G && y >= 0 && y < src.G && pl >= 0 && pl <= src.B;
-            mine = ok ? ((long long)pl * src.G + x) * src.G + y : -1ll;
+            mine = obs_row_index(src, m, lane);
             if (src.idx_out != nullptr) src.idx_out[m * K + lane] = mine;
         }
     } else if (lane < K) mine = idx[m * K + lane];

@@ -800,10 +800,16 @@ extern "C" size_t uavagent_rows_grad_workspace_bytes(int64_t m_rows, int32_t k, 
 
 // The two halves of uavagent_rows_grad_f32 (ABI 4).  The sort needs only idx, which a learner has long before g exists: it can run
 // beside the backward pass (another stream), and serve several sums over the same samples (one per trunk).
-extern "C" int uavagent_rows_grad_sort(const int64_t *idx, int64_t m_rows, int32_t k, int32_t n_cols_total, int64_t n_rows, void *workspace,
-                                       size_t workspace_bytes, void *stream) {
-    if (m_rows < 1 || k < 1 || k > 64 || n_cols_total < 4 || n_cols_total > 512 || (n_cols_total & 3) || n_rows < 1)
-        return fail2(UAVAGENT_E_INVALID, "rows_grad: need m_rows >= 1, 1 <= k <= 64, h a multiple of 4 in [4, 256], 1 or 2 tables");
+namespace {
+// Nothing in the sort or in stages A and B depends on k beyond samp = pair / k: the 64-node exports and the wide ones (k <= 256, the
+// nodes of uavagent_first_layer_wide_f32) share these two functions and differ in the bound they pass.
+int bad_shape(int k_max) {
+    return fail2(UAVAGENT_E_INVALID, "rows_grad: need m_rows >= 1, 1 <= k <= " + std::to_string(k_max) + ", h a multiple of 4 in [4, 256], 1 or 2 tables");
+}
+
+int rows_grad_sort_impl(int k_max, const int64_t *idx, int64_t m_rows, int32_t k, int32_t n_cols_total, int64_t n_rows, void *workspace,
+                        size_t workspace_bytes, void *stream) {
+    if (m_rows < 1 || k < 1 || k > k_max || n_cols_total < 4 || n_cols_total > 512 || (n_cols_total & 3) || n_rows < 1) return bad_shape(k_max);
     if (!idx || !workspace) return fail2(UAVAGENT_E_INVALID, "rows_grad: null pointer");
     if (reinterpret_cast<uintptr_t>(workspace) & 255u) return fail2(UAVAGENT_E_INVALID, "rows_grad: g and the tables must be 16-byte aligned, the workspace 256-byte aligned");
     const long long n_pairs = (long long)m_rows * k;
@@ -824,10 +830,9 @@ extern "C" int uavagent_rows_grad_sort(const int64_t *idx, int64_t m_rows, int32
     return UAVAGENT_OK;
 }
 
-extern "C" int uavagent_rows_grad_sums_f32(const float *g, int64_t m_rows, int32_t k, int32_t h, int32_t n_tables, int64_t n_rows,
-                                           float *dw0_out, float *dw1_out, void *workspace, size_t workspace_bytes, void *stream) {
-    if (m_rows < 1 || k < 1 || k > 64 || h < 4 || h > 256 || (h & 3) || (n_tables != 1 && n_tables != 2) || n_rows < 1)
-        return fail2(UAVAGENT_E_INVALID, "rows_grad: need m_rows >= 1, 1 <= k <= 64, h a multiple of 4 in [4, 256], 1 or 2 tables");
+int rows_grad_sums_impl(int k_max, const float *g, int64_t m_rows, int32_t k, int32_t h, int32_t n_tables, int64_t n_rows, float *dw0_out,
+                        float *dw1_out, void *workspace, size_t workspace_bytes, void *stream) {
+    if (m_rows < 1 || k < 1 || k > k_max || h < 4 || h > 256 || (h & 3) || (n_tables != 1 && n_tables != 2) || n_rows < 1) return bad_shape(k_max);
     if (!g || !dw0_out || (n_tables == 2 && !dw1_out) || !workspace) return fail2(UAVAGENT_E_INVALID, "rows_grad: null pointer");
     if (!al16(g) || !al16(dw0_out) || !al16(dw1_out) || (reinterpret_cast<uintptr_t>(workspace) & 255u))
         return fail2(UAVAGENT_E_INVALID, "rows_grad: g and the tables must be 16-byte aligned, the workspace 256-byte aligned");
@@ -854,6 +859,24 @@ extern "C" int uavagent_rows_grad_sums_f32(const float *g, int64_t m_rows, int32
     hipLaunchKernelGGL(rows_sum_stage_b, dim3(blocks), dim3(256), 0, s, head, tail, chunks, carry, (int)(ncol / 4), (int)(h / 4), dw0_out,
                        n_tables == 2 ? dw1_out : dw0_out);
     return launch_ok("rows_grad stage B");
+}
+}  // namespace
+
+extern "C" int uavagent_rows_grad_sort(const int64_t *idx, int64_t m_rows, int32_t k, int32_t n_cols_total, int64_t n_rows, void *workspace,
+                                       size_t workspace_bytes, void *stream) {
+    return rows_grad_sort_impl(64, idx, m_rows, k, n_cols_total, n_rows, workspace, workspace_bytes, stream);
+}
+extern "C" int uavagent_rows_grad_sums_f32(const float *g, int64_t m_rows, int32_t k, int32_t h, int32_t n_tables, int64_t n_rows,
+                                           float *dw0_out, float *dw1_out, void *workspace, size_t workspace_bytes, void *stream) {
+    return rows_grad_sums_impl(64, g, m_rows, k, h, n_tables, n_rows, dw0_out, dw1_out, workspace, workspace_bytes, stream);
+}
+extern "C" int uavagent_rows_grad_wide_sort(const int64_t *idx, int64_t m_rows, int32_t k, int32_t n_cols_total, int64_t n_rows,
+                                            void *workspace, size_t workspace_bytes, void *stream) {
+    return rows_grad_sort_impl(256, idx, m_rows, k, n_cols_total, n_rows, workspace, workspace_bytes, stream);
+}
+extern "C" int uavagent_rows_grad_wide_sums_f32(const float *g, int64_t m_rows, int32_t k, int32_t h, int32_t n_tables, int64_t n_rows,
+                                                float *dw0_out, float *dw1_out, void *workspace, size_t workspace_bytes, void *stream) {
+    return rows_grad_sums_impl(256, g, m_rows, k, h, n_tables, n_rows, dw0_out, dw1_out, workspace, workspace_bytes, stream);
 }
 
 extern "C" int uavagent_rows_grad_f32(const int64_t *idx, const float *g, int64_t m_rows, int32_t k, int32_t h, int32_t n_tables,

@@ -40,7 +40,8 @@ class GreedyEvaluator:
     (uavagent_actor_head_greedy_f32); any other ACNet width and CnnACNet compute their logits as their rollout does and pick with
     uavagent_argmax_rows_f32; a factored.FactoredCnnACNet takes the CNN route with the greedy digit per UAV
     (uavagent_choose_factored_f32 without uniforms) in its place.  The MLP's first layer comes straight from the compact observation (uavagent_first_layer_from_obs_f32,
-    actor table only), which bounds it to nBS + nUE <= 64 like the index-list gather.  ``hist`` = (lo, hi, bins) of the serving-SINR histogram in dB."""
+    actor table only), which bounds it to nBS + nUE <= 64 like the index-list gather.  A factored.FactoredACNet takes the MLP route up to 256
+    nodes (the wide from-obs gather above 64), its two dense layers through uavagent_gemm_rows_f32 and the greedy digit per UAV.  ``hist`` = (lo, hi, bins) of the serving-SINR histogram in dB."""
 
     def __init__(self, env, net, hist=(-50.0, 100.0, 150)):
         from . import _agent_capi as A
@@ -68,12 +69,14 @@ class GreedyEvaluator:
         self._bufs = {}                                    # T -> (actions [T, N] or None, reward [T, N] or None)
         if isinstance(net, ACNet):
             H = int(net.a_w2.shape[0])
-            self.kind = "mlp_fused" if (H == 200 and 576 < NA <= 640) else "mlp"
-            if B + U > 64:      # (building an index list first would not help: uavagent_first_layer_f32 has the same bound)
+            self.kind = "mlp_factored" if self._factored else ("mlp_fused" if (H == 200 and 576 < NA <= 640) else "mlp")
+            if self._factored and B + U > A.WIDE_NODES:
+                raise ValueError("GreedyEvaluator: the wide first-layer gather holds nBS + nUE <= 256 nodes (got %d)" % (B + U))
+            if not self._factored and B + U > 64:      # (building an index list first would not help: uavagent_first_layer_f32 has the same bound)
                 raise ValueError("GreedyEvaluator: the MLP's first-layer gather holds one node per lane, nBS + nUE <= 64 (got %d); "
                                  "larger shapes need the CNN actor" % (B + U))
             self._h1, self._h2 = f(N, H), f(N, H)
-            if self.kind == "mlp_fused":
+            if self.kind in ("mlp_fused", "mlp_factored"):
                 self._w2t = f(H, H)
                 self._w3t = torch.zeros((self._ldl, H), dtype=torch.float32, device=self.dev)
                 self._b3p = torch.zeros(self._ldl, dtype=torch.float32, device=self.dev)
@@ -96,7 +99,7 @@ class GreedyEvaluator:
     def _refresh_weights(self):
         """The transposed / padded copies the kernels read, from the parameters as they are now."""
         net, NA = self.net, self.net.n_action
-        if self.kind == "mlp_fused":
+        if self.kind in ("mlp_fused", "mlp_factored"):
             self._w2t.copy_(net.a_w2.t())
             self._w3t[:NA].copy_(net.a_w3.t())
             self._b3p[:NA].copy_(net.a_b3)
@@ -124,8 +127,13 @@ class GreedyEvaluator:
             else:
                 A.argmax_rows(self._logits_pad[:, :NA], out=act)
             return
-        A.first_layer_from_obs(obs, env.grid_n, net.a_w1, net.a_b1, None, None, self._h1, None)      # actor table only, relu6
-        if self.kind == "mlp_fused":
+        from_obs = A.first_layer_from_obs if env.nBS + env.nUE <= A.NARROW_NODES else A.first_layer_from_obs_wide
+        from_obs(obs, env.grid_n, net.a_w1, net.a_b1, None, None, self._h1, None)                     # actor table only, relu6
+        if self.kind == "mlp_factored":
+            A.gemm_rows(self._h1, self._w2t, self._h2, w_transposed=True, bias=net.a_b2, relu6=True)
+            A.gemm_rows(self._h2, self._w3t, self._logits_pad, w_transposed=True, bias=self._b3p)
+            A.choose_factored(self._logits_pad[:, :NA], None, net.n_heads, net.n_act, out=act)
+        elif self.kind == "mlp_fused":
             A.actor_head_greedy(self._h1, self._w2t, net.a_b2, self._w3t, self._b3p, NA, self._h2, self._logits_pad, act)
         else:
             logits = self._logits_pad[:, :NA]

@@ -1,4 +1,4 @@
-"""Factorised per-UAV policy head for the CNN actor-critic: one n_act-way softmax per UAV instead of the reference's one softmax over the
+"""Factorised per-UAV policy head for the CNN and the MLP actor-critic: one n_act-way softmax per UAV instead of the reference's one softmax over the
 N_A = 5^nBS joint actions (main.py:143-156), which cannot be built beyond a handful of UAVs (1.5e11 logits at 16).  An extension beyond
 the reference, like the search policies; DESIGN.md section 17.
 
@@ -12,11 +12,13 @@ the reference, like the search policies; DESIGN.md section 17.
             With B = 1 this is agent.a2c_losses term for term.
 
 On the GPU the draw, the greedy choice and the loss gradient are libuavagent.so's (csrc/agent_factored.hip); everything else -- trunks,
-head GEMMs, RMSProp, rollout, checkpoint -- is cnn_agent's, unchanged.
+head GEMMs, RMSProp, rollout, checkpoint -- is cnn_agent's (FactoredCnn*) or agent's (FactoredACNet / FactoredA2CRunner), unchanged.  The MLP's
+first layer holds one table row per observation node: beyond 64 nodes (16 UAV + 200 UE = 216) it runs on the 256-node gather and table
+gradient of csrc/agent_wide.hip.
 """
 import torch
 
-from .agent import ENTROPY_BETA
+from .agent import ENTROPY_BETA, HIDDEN, A2CRunner, ACNet
 from .cnn_agent import CnnA2CRunner, CnnACNet, _logits_cuda, _trunks_cuda, _value_cuda
 
 N_ACT = 5     # mobile_env.py:21
@@ -173,3 +175,83 @@ class FactoredCnnA2CRunner(CnnA2CRunner):
     def _losses(self, a_prob, v, actions, v_target):
         net = self.net
         return a2c_losses_factored(a_prob.reshape(-1, net.n_heads, net.n_act), v, actions, v_target, self.beta)
+
+
+class FactoredACNet(ACNet):
+    """ACNet(n_state, n_bs * n_act) whose policy output is read as n_bs heads of n_act logits.  Parameter keys and shapes are ACNet's (the
+    head is [200, n_bs * n_act]), so agent.save_actor_npz / load_actor_npz serve it; ``forward``, ``actor_only`` and ``forward_dense`` return
+    the per-head probabilities [M, n_bs * n_act] (every run of n_act sums to 1)."""
+
+    factored = True
+
+    def __init__(self, n_state, n_bs, n_act=N_ACT, hidden=HIDDEN, seed=6):
+        super().__init__(n_state, int(n_bs) * int(n_act), hidden=hidden, seed=seed)
+        self.n_heads, self.n_act = int(n_bs), int(n_act)
+        self.joint_actions = self.n_act ** self.n_heads
+
+    def _policy_prob(self, logits):
+        M = logits.shape[0]
+        return torch.softmax(logits.reshape(M, self.n_heads, self.n_act), dim=-1).reshape(M, self.n_action)
+
+
+class FactoredA2CRunner(A2CRunner):
+    """A2CRunner with the factorised head: one uniform per (step, env, UAV), the draw by uavagent_choose_factored_f32 (GPU) or
+    sample_actions_factored (CPU), act_buf holding JOINT actions as the env takes them, the factored loss in both update forms.  Up to 256
+    observation nodes (16 UAV x 200 UE): above 64 the first layer -- from the index list, from the observation (``fused_obs``) and its table
+    gradient -- runs on libuavagent's wide kernels; at 64 nodes or fewer on the ones A2CRunner uses.  The rollout step is first layer ->
+    gemm_rows -> gemm_rows -> choose_factored -> env step, in the captured graph.  The fused actor head, the pipelined halves and the
+    persistent rollout are built around 577-640 logits and 4 UAVs: they stay off here."""
+
+    NET_KIND = "mlp-factored"
+    FUSED_OBS_MAX_NODES = 256     # uavagent_first_layer_wide_from_obs_f32
+
+    def __init__(self, env, net=None, rollout=50, *, seed=6, **kw):
+        if net is None:
+            net = FactoredACNet((env.nBS + 1) * env.grid_n * env.grid_n, env.nBS, env.N_ACT, seed=seed)
+        if not isinstance(net, FactoredACNet):
+            raise TypeError("FactoredA2CRunner trains a FactoredACNet")
+        if net.n_heads != env.nBS or net.joint_actions != env.action_space_dim:
+            raise ValueError("the net has %d heads of %d actions, the env %d UAVs and %d joint actions" % (
+                net.n_heads, net.n_act, env.nBS, env.action_space_dim))
+        for k in ("fused_head", "pipeline_halves", "persistent_rollout"):
+            if kw.get(k) not in (None, False):
+                raise ValueError("FactoredA2CRunner: %s serves the joint head of 4 UAVs only" % k)
+            kw[k] = False
+        super().__init__(env, net=net, rollout=rollout, seed=seed, **kw)
+        self.u_buf = torch.empty((self.T, env.n_envs, net.n_heads), dtype=torch.float32, device=self.dev)
+
+    def _gather_kernels(self):
+        from . import _agent_capi as A
+
+        if self.idx_buf.shape[2] <= A.NARROW_NODES:
+            return super()._gather_kernels()
+        return A.sparse_rows_sum_wide, A.first_layer_from_obs_wide, A.rows_grad_sort_wide, A.rows_grad_sums_wide
+
+    def _draw(self, logits, t, lo, hi):
+        from . import _agent_capi as A
+
+        A.choose_factored(logits, self.u_buf[t][lo:hi], self.net.n_heads, self.net.n_act, out=self.act_buf[t][lo:hi])
+
+    def _draw_reference(self, t):
+        net = self.net
+        prob = net.actor_only(self.idx_buf[t]).reshape(-1, net.n_heads, net.n_act)
+        return sample_actions_factored(prob, self.u_buf[t])
+
+    def _loss_workspace(self):
+        from . import _agent_capi as A
+
+        return A.loss_grad_factored_workspace(self.net.n_heads, self.net.n_act, self.dev)
+
+    def _loss_grad(self, logits, v, target, actions, dv, dbias, loss, ws):
+        from . import _agent_capi as A
+
+        A.a2c_loss_grad_factored(logits, v, target, actions, self.net.n_heads, self.net.n_act, self.beta, dv, dbias, loss, ws)
+
+    def _losses(self, a_prob, v, actions, v_target):
+        net = self.net
+        return a2c_losses_factored(a_prob.reshape(-1, net.n_heads, net.n_act), v, actions, v_target, self.beta)
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["net"] = self.NET_KIND
+        return sd

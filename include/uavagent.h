@@ -224,6 +224,29 @@ int uavagent_a2c_loss_grad_factored(float *logits_inout, int64_t ld_logits, cons
                                     int64_t m_rows, int32_t n_heads, int32_t n_act, float beta, float *dv_out, float *dbias_out,
                                     double *loss_out, void *workspace, void *stream);
 
+/* ---- The first layer for up to 256 observation nodes per sample (csrc/agent_wide.hip; additive to ABI 5, the number stays): 16 UAV + 200 UE
+ * = 216 nodes at the largest shape the env serves.  The 64-node entry points above keep their bound. ---- */
+
+/* uavagent_first_layer_f32 with 1 <= k <= 256: same arguments, alignment rules, "no row" convention (an index outside [0, n_rows) adds
+ * nothing and is never dereferenced) and empty-batch rule.  Arithmetic: per output column ONE float32 accumulator, rows added in ascending k,
+ * then the bias, then relu6 -- for k <= 64 the bits of uavagent_first_layer_f32, for any k those of a sequential float32 loop.  One wavefront
+ * per sample walks the nodes in passes of 64; k = 216 has an instantiation of its own (8 row reads per table in flight). */
+int uavagent_first_layer_wide_f32(const float *w_a, const float *bias_a, float *out_a, const float *w_c, const float *bias_c,
+                                  float *out_c, const int64_t *idx, int64_t m_rows, int32_t k, int32_t h, int64_t n_rows,
+                                  int32_t relu6, void *stream);
+/* uavagent_first_layer_from_obs_f32 with n_bs + n_ue <= 256: the bits of uavagent_obs_indices followed by uavagent_first_layer_wide_f32, and
+ * idx_out (optional) holds what uavagent_obs_indices writes. */
+int uavagent_first_layer_wide_from_obs_f32(const float *w_a, const float *bias_a, float *out_a, const float *w_c, const float *bias_c,
+                                           float *out_c, const int16_t *ue_xy, const int32_t *bs_xy, const int8_t *serving, int64_t n_envs,
+                                           int32_t n_ue, int32_t n_bs, int32_t grid, int32_t h, int64_t n_rows, int32_t relu6,
+                                           int64_t *idx_out, void *stream);
+/* uavagent_rows_grad_sort / uavagent_rows_grad_sums_f32 with 1 <= k <= 256 (one implementation, two bounds).  The workspace is
+ * uavagent_rows_grad_workspace_bytes', which has no bound on k; m_rows * k <= 2^31 - 1 pairs as there. */
+int uavagent_rows_grad_wide_sort(const int64_t *idx, int64_t m_rows, int32_t k, int32_t n_cols_total, int64_t n_rows, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+int uavagent_rows_grad_wide_sums_f32(const float *g, int64_t m_rows, int32_t k, int32_t h, int32_t n_tables, int64_t n_rows, float *dw0_out,
+                                     float *dw1_out, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,11 +47,11 @@ def run_test(trace, out_dir, actor_npz=None, max_step=2000, n_bs=4, n_ue=40, gri
 
     os.makedirs(out_dir, exist_ok=True)
     test_env = MobiEnvironment(n_bs, n_ue, grid, "read_trace", trace, seed=seed)       # main_test.py:51
-    factored = net == "cnn-factored"
+    factored = net in ("cnn-factored", "mlp-factored")
     if factored:                                                                         # one 5-way head per UAV (factored.py)
-        from drl_uav_cellularnet_amd.factored import FactoredCnnACNet, digits_to_joint
+        from drl_uav_cellularnet_amd.factored import FactoredACNet, FactoredCnnACNet, digits_to_joint
 
-        net = FactoredCnnACNet(n_bs, grid)
+        net = FactoredCnnACNet(n_bs, grid) if net == "cnn-factored" else FactoredACNet(test_env.observation_space_dim, n_bs)
     elif net == "cnn":                                                                   # netType='CNN' (main.py:88-140)
         from drl_uav_cellularnet_amd.cnn_agent import CnnACNet
 
@@ -103,6 +103,10 @@ def run_batched(n_envs, out_dir, trace=None, actor_npz=None, steps=2000, n_bs=4,
         from drl_uav_cellularnet_amd.factored import FactoredCnnACNet
 
         net = FactoredCnnACNet(n_bs, grid)
+    elif net == "mlp-factored":
+        from drl_uav_cellularnet_amd.factored import FactoredACNet
+
+        net = FactoredACNet(env.observation_space_dim, n_bs)
     elif net == "cnn":
         from drl_uav_cellularnet_amd.cnn_agent import CnnACNet
 
@@ -139,8 +143,8 @@ if __name__ == "__main__":
     ap.add_argument("--trace-rows", type=int, default=10001)
     ap.add_argument("--actor", default=None)
     ap.add_argument("--steps", type=int, default=2000)
-    ap.add_argument("--net", choices=("mlp", "cnn", "cnn-factored"), default="mlp", help="the network the actor file was trained with")
-    ap.add_argument("--n-bs", type=int, default=4, help="UAVs (cnn-factored serves up to 16; the joint heads have 5^n_bs logits)")
+    ap.add_argument("--net", choices=("mlp", "cnn", "cnn-factored", "mlp-factored"), default="mlp", help="the network the actor file was trained with")
+    ap.add_argument("--n-bs", type=int, default=4, help="UAVs (cnn-factored and mlp-factored serve up to 16; the joint heads have 5^n_bs logits)")
     ap.add_argument("--n-ue", type=int, default=40)
     ap.add_argument("--envs", type=int, default=None, help="evaluate this many envs at once on the device (GreedyEvaluator)")
     ap.add_argument("--traces", default=None, help="with --envs: int16 cells [T+1, N, U, 2] or [T+1, U, 2] (.npy); default: group mobility")

@@ -6,6 +6,7 @@ actor parameters (Global_A_PARA: here a named .npz, agent.save_actor_npz -- load
 
   python tools/train_a2c.py --out train/run1 [--workers 8192] [--episodes 2] [--rollout 50] [--first-state zeros]
   python tools/train_a2c.py --net cnn-factored --n-bs 16 --n-ue 200 --workers 1024      # one 5-way policy head per UAV (factored.py)
+  python tools/train_a2c.py --net mlp-factored --n-bs 16 --n-ue 200 --workers 1024      # the MLP with that head (256-node first layer)
   python -m torch.distributed.run --nproc-per-node 8 tools/train_a2c.py ...     # one process per GPU, gradients all-reduced (RCCL)"""
 import argparse
 import json
@@ -63,9 +64,9 @@ def main():
                     "4096 workers on); per-step: the pipelined per-step launches (same results bit for bit)")
     ap.add_argument("--no-gemm-tuning", action="store_true", help="leave PyTorch's TunableOp off (library default; this tool turns the "
                     "shipped per-shape GEMM picks on: a resumed run is bit-identical only if it makes the same choice as the original)")
-    ap.add_argument("--net", choices=("mlp", "cnn", "cnn-factored"), default="mlp", help="the reference's netType: MLP (agent.ACNet) or CNN "
-                    "(cnn_agent.CnnACNet, one process only); cnn-factored: the CNN with one 5-way head per UAV "
-                    "(factored.FactoredCnnACNet, one process only) -- the only one that exists beyond a handful of UAVs")
+    ap.add_argument("--net", choices=("mlp", "cnn", "cnn-factored", "mlp-factored"), default="mlp", help="the reference's netType: MLP (agent.ACNet) or CNN "
+                    "(cnn_agent.CnnACNet, one process only); cnn-factored / mlp-factored: the CNN / the MLP with one 5-way head per UAV "
+                    "(factored.FactoredCnnACNet, one process only; factored.FactoredACNet) -- the two that exist beyond a handful of UAVs")
     ap.add_argument("--n-bs", type=int, default=4, help="UAVs; the joint heads of mlp / cnn have 5^n_bs logits (625 at the reference's 4)")
     a = ap.parse_args()
     import numpy as np
@@ -89,6 +90,10 @@ def main():
         from drl_uav_cellularnet_amd.factored import FactoredCnnA2CRunner
 
         runner = FactoredCnnA2CRunner(env, rollout=a.rollout, first_state=a.first_state)
+    elif a.net == "mlp-factored":
+        from drl_uav_cellularnet_amd.factored import FactoredA2CRunner
+
+        runner = FactoredA2CRunner(env, rollout=a.rollout, first_state=a.first_state, tune_gemms=not a.no_gemm_tuning)
     elif a.net == "cnn":
         from drl_uav_cellularnet_amd.cnn_agent import CnnA2CRunner
 
