@@ -21,7 +21,8 @@ EXPORTS = ("uavagent_abi_version", "uavagent_last_error", "uavagent_sparse_rows_
            "uavagent_device_error", "uavagent_device_error_clear", "uavagent_actor_head_greedy_f32", "uavagent_argmax_rows_f32",
            "uavagent_choose_factored_f32", "uavagent_loss_grad_factored_workspace_bytes", "uavagent_a2c_loss_grad_factored",
            "uavagent_first_layer_wide_f32", "uavagent_first_layer_wide_from_obs_f32", "uavagent_rows_grad_wide_sort",
-           "uavagent_rows_grad_wide_sums_f32")
+           "uavagent_rows_grad_wide_sums_f32", "uavagent_imitation_loss_grad_workspace_bytes", "uavagent_imitation_loss_grad_factored",
+           "uavagent_soft_targets_f32")
 ABI_VERSION = 5
 
 _lib = None
@@ -129,6 +130,8 @@ def load():
         "uavagent_argmax_rows_f32": [_P, _I64, _I64, _I32, _P, _P],
         "uavagent_choose_factored_f32": [_P, _I64, _P, _I64, _I32, _I32, _P, _P, _P, _P],
         "uavagent_a2c_loss_grad_factored": [_P, _I64, _P, _P, _P, _I64, _I32, _I32, _F, _P, _P, _P, _P, _P],
+        "uavagent_imitation_loss_grad_factored": [_P, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _F, _P, _P, _P, _P, _P],
+        "uavagent_soft_targets_f32": [_P, _I64, C.c_double, _I64, _I32, _I32, _P, _P],
         "uavagent_gate_prepare": [],
     }
     for wide, narrow in (("uavagent_first_layer_wide_f32", "uavagent_first_layer_f32"),
@@ -148,6 +151,8 @@ def load():
     lib.uavagent_loss_grad_workspace_bytes.argtypes = [_I32]
     lib.uavagent_loss_grad_factored_workspace_bytes.restype = C.c_size_t
     lib.uavagent_loss_grad_factored_workspace_bytes.argtypes = [_I32, _I32]
+    lib.uavagent_imitation_loss_grad_workspace_bytes.restype = C.c_size_t
+    lib.uavagent_imitation_loss_grad_workspace_bytes.argtypes = [_I32, _I32]
     lib.uavagent_relu6_bwd_workspace_bytes.restype = C.c_size_t
     lib.uavagent_relu6_bwd_workspace_bytes.argtypes = [_I32]
     lib.uavagent_rows_grad_workspace_bytes.restype = C.c_size_t
@@ -576,6 +581,62 @@ def a2c_loss_grad_factored(logits, v, target, actions, n_heads, n_act, beta, dv_
         rc = load().uavagent_a2c_loss_grad_factored(_ptr(logits), ld, _ptr(v), _ptr(target), _ptr(actions), M, int(n_heads), int(n_act),
                                                     float(beta), _ptr(dv_out), _ptr(dbias_out), _ptr(loss_out), _ptr(ws), _stream(logits.device))
     _check(rc, "uavagent_a2c_loss_grad_factored")
+
+
+def imitation_loss_grad_workspace(n_heads, n_act, device):
+    n = load().uavagent_imitation_loss_grad_workspace_bytes(int(n_heads), int(n_act))
+    if n == 0:
+        raise UavAgentError("uavagent_imitation_loss_grad_workspace_bytes: need 1 <= n_heads <= 32 and 2 <= n_act <= 8")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def imitation_loss_grad_factored(logits, v, target, n_heads, n_act, beta, dv_out, dbias_out, loss_out, ws, labels=None, targets=None):
+    """The supervised form of a2c_loss_grad_factored: in place, logits [M, n_heads * n_act] <- d a_loss / d logits of the cross entropy
+    against EITHER labels (JOINT actions int64 [M]: q = one-hot of their digits) OR targets (float32 [M, n_heads * n_act], one distribution
+    per head).  loss_out: float64 [4] = (a_loss, c_loss, sum dv, agreement)."""
+    ld = _row_stride(logits, "logits")
+    M, C_ = logits.shape
+    if C_ != int(n_heads) * int(n_act):
+        raise UavAgentError("imitation_loss_grad_factored: logits must have n_heads * n_act = %d columns, got %d" % (int(n_heads) * int(n_act), C_))
+    if (labels is None) == (targets is None):
+        raise UavAgentError("imitation_loss_grad_factored: exactly one of labels and targets must be given")
+    if labels is not None and (labels.dtype != torch.int64 or labels.numel() != M or not labels.is_contiguous()):
+        raise UavAgentError("imitation_loss_grad_factored: labels must be a contiguous int64 [M] tensor")
+    if targets is not None:
+        _f32c(targets, "targets")
+        if targets.numel() != M * C_:
+            raise UavAgentError("imitation_loss_grad_factored: targets must be [M, n_heads * n_act]")
+    if loss_out.dtype != torch.float64 or loss_out.numel() < 4 or not loss_out.is_contiguous():
+        raise UavAgentError("imitation_loss_grad_factored: loss_out must be a contiguous float64 tensor of 4 elements")
+    _same_device("imitation_loss_grad_factored", logits, v, target, labels, targets, dv_out, dbias_out, loss_out, ws)
+    with torch.cuda.device(logits.device):
+        rc = load().uavagent_imitation_loss_grad_factored(_ptr(logits), ld, _ptr(v), _ptr(target), _ptr(labels), _ptr(targets), M, int(n_heads),
+                                                          int(n_act), float(beta), _ptr(dv_out), _ptr(dbias_out), _ptr(loss_out), _ptr(ws),
+                                                          _stream(logits.device))
+    _check(rc, "uavagent_imitation_loss_grad_factored")
+
+
+def soft_targets(table, n_heads, n_act, tau, out=None):
+    """q float32 [rows, n_heads * n_act] = per-head softmax((t - max t) / tau) of the float64 reward table [rows, n_heads * n_act] (rows may be
+    strided; BatchedMobiEnv.coordinate_actions(rewards=True) viewed as [N, nBS * 5]), in float64, rounded once (uavagent_soft_targets_f32)."""
+    B, A_ = int(n_heads), int(n_act)
+    if not float(tau) > 0 or float(tau) == float("inf"):
+        raise UavAgentError("soft_targets: tau must be finite and > 0")
+    if table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != B * A_ or table.stride(1) != 1:
+        raise UavAgentError("soft_targets: table must be a float64 [rows, n_heads * n_act = %d] tensor with contiguous rows" % (B * A_))
+    R = table.shape[0]
+    ld = table.stride(0) if R > 1 else B * A_
+    if out is None:
+        out = torch.empty((R, B * A_), dtype=torch.float32, device=table.device)
+    else:
+        _f32c(out, "out")
+        if out.numel() != R * B * A_:
+            raise UavAgentError("soft_targets: out must be [rows, n_heads * n_act]")
+    _same_device("soft_targets", table, out)
+    with torch.cuda.device(table.device):
+        rc = load().uavagent_soft_targets_f32(_ptr(table), ld, 1.0 / float(tau), R, B, A_, _ptr(out), _stream(table.device))
+    _check(rc, "uavagent_soft_targets_f32")
+    return out
 
 
 def gate_prepare():

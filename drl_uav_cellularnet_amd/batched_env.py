@@ -444,16 +444,30 @@ class BatchedMobiEnv:
         self._trace_keep = x
         return x.data_ptr()
 
-    def _lookahead_actions(self, fn, ue_xy, draws, best_reward, table_shape):
+    def _out_buffer(self, out, dtype, shape, what):
+        """``out`` when the caller gave a buffer (checked: dtype, element count, contiguous, this device), else a fresh tensor."""
+        if out is None:
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        n = 1
+        for k in shape:
+            n *= k
+        if out.dtype != dtype or out.numel() != n or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("%s must be a contiguous %s tensor of shape %s on the env's device" % (what, dtype, tuple(shape)))
+        return out
+
+    def _lookahead_actions(self, fn, ue_xy, draws, best_reward, table_shape, actions_out=None, table_out=None):
         """search_actions / coordinate_actions: ``fn`` is the C entry, ``draws`` = (theta_u, group_u, fading), ``table_shape`` the per-env
-        shape of the reward table or None."""
+        shape of the reward table or None; ``actions_out`` / ``table_out``: the caller's buffers for the actions and the table (then
+        nothing is allocated)."""
         N = self.n_envs
         xptr = self._stage_ue_xy(ue_xy)
         inj = self._inject(*draws)
         checked = 1 if ("reward_f64" in self.out or inj is not None) else 0
-        acts = torch.empty(N, dtype=torch.int64, device=self.device)
+        if table_out is not None and not table_shape:
+            raise ValueError("table_out needs rewards=True")
+        acts = self._out_buffer(actions_out, torch.int64, (N,), "actions_out")
         best = torch.empty(N, dtype=torch.float64, device=self.device) if best_reward else None
-        table = torch.empty((N,) + table_shape, dtype=torch.float64, device=self.device) if table_shape else None
+        table = self._out_buffer(table_out, torch.float64, (N,) + table_shape, "table_out") if table_shape else None
         rc = fn(self._h, xptr, inj, checked, acts.data_ptr(), best.data_ptr() if best_reward else None,
                 table.data_ptr() if table_shape else None, self._stream())
         if rc:
@@ -484,15 +498,16 @@ class BatchedMobiEnv:
         return actions_out, out
 
     # ---- the SINR-gradient baseline controller (gradient.py) -------------------------------------------
-    def gradient_actions(self, ue_xy=None, theta_u=None, group_u=None, fading=None, side_means=False, look=False):
+    def gradient_actions(self, ue_xy=None, theta_u=None, group_u=None, fading=None, side_means=False, look=False, actions_out=None):
         """Choose_Act_Gradient (gradient.py:14-37) for every env in one launch (uavenv_gradient_actions): look one step ahead with
         every UAV staying, then send each UAV towards the side whose UEs have the lowest mean serving SINR.  The env is NOT
         modified: no state, none of ``self.out``.  ``ue_xy`` [N, U, 2]: the trace cells of the step (read_trace), else the next
         mobility tick.  Returns int64 [N] joint actions; with ``side_means`` also float64 [N, B, 4] (NaN = empty side); with
-        ``look`` also the look-ahead step's outputs, a dict of fresh tensors named like ``self.out``."""
+        ``look`` also the look-ahead step's outputs, a dict of fresh tensors named like ``self.out``.  ``actions_out``: an int64 [N]
+        buffer for the actions (then the plain call allocates nothing)."""
         N, B = self.n_envs, self.nBS
         xptr = self._stage_ue_xy(ue_xy)
-        acts = torch.empty(N, dtype=torch.int64, device=self.device)
+        acts = self._out_buffer(actions_out, torch.int64, (N,), "actions_out")
         means = torch.empty((N, B, 4), dtype=torch.float64, device=self.device) if side_means else None
         lo, lref = None, None
         if look:
@@ -514,15 +529,17 @@ class BatchedMobiEnv:
         return self._step_policy(self._lib.uavenv_step_gradient, "step_gradient", n_steps, out, actions_out)
 
     # ---- the one-step search policy: the best of all joint actions per env -----------------------------
-    def search_actions(self, ue_xy=None, theta_u=None, group_u=None, fading=None, best_reward=False, rewards=False):
+    def search_actions(self, ue_xy=None, theta_u=None, group_u=None, fading=None, best_reward=False, rewards=False, actions_out=None,
+                       table_out=None):
         """For every env the reward of EACH of the N_ACT ** nBS joint actions on the step the env is about to take, and the first
         maximum, in one launch (uavenv_search_actions).  The env is NOT modified: no state, none of ``self.out``.  ``ue_xy``
         [N, U, 2]: the trace cells of the step (read_trace), else the next mobility tick.  The arithmetic is that of this env's
         own step: the checked variant when the env has float64 outputs or draws are injected, else the fast one.  Returns int64 [N]
         joint actions (the lowest action among equal rewards); with ``best_reward`` also float64 [N]; with ``rewards`` also the
-        float64 [N, N_ACT ** nBS] table: ``table[e, a]`` is bit for bit the ``reward_f64`` step(a) would return for env e."""
+        float64 [N, N_ACT ** nBS] table: ``table[e, a]`` is bit for bit the ``reward_f64`` step(a) would return for env e.
+        ``actions_out`` / ``table_out``: buffers for the actions and (with ``rewards``) the table, so that the call allocates nothing."""
         return self._lookahead_actions(self._lib.uavenv_search_actions, ue_xy, (theta_u, group_u, fading), best_reward,
-                                       (self.action_space_dim,) if rewards else None)
+                                       (self.action_space_dim,) if rewards else None, actions_out, table_out)
 
     def step_search(self, n_steps, out=None, actions_out=None):
         """``n_steps`` x [search_actions(); step(those actions)] issued by one C call (uavenv_step_search; group mobility,
@@ -532,7 +549,8 @@ class BatchedMobiEnv:
         return self._step_policy(self._lib.uavenv_step_search, "step_search", n_steps, out, actions_out)
 
     # ---- the per-UAV coordinate-search policy: each UAV's best cell in turn, 4 nBS + 1 step values per decision ----
-    def coordinate_actions(self, ue_xy=None, theta_u=None, group_u=None, fading=None, best_reward=False, rewards=False):
+    def coordinate_actions(self, ue_xy=None, theta_u=None, group_u=None, fading=None, best_reward=False, rewards=False, actions_out=None,
+                           table_out=None):
         """Coordinate ascent over the UAVs of every env, in UAV order, on the step the env is about to take, in one launch
         (uavenv_coordinate_actions): UAV 0 takes the best of its five cells with everybody else staying, UAV 1 its best given UAV
         0's choice, and so on.  The env is NOT modified: no state, none of ``self.out``.  ``ue_xy`` [N, U, 2]: the trace cells of the
@@ -540,9 +558,10 @@ class BatchedMobiEnv:
         float64 outputs or draws are injected, else fast).  Serves every shape up to 16 UAVs x 256 UEs (n_ue <= 64: nBS <= 8).
         Returns int64 [N] joint actions; with ``best_reward`` also float64 [N], bit for bit the ``reward_f64`` step(actions) returns
         and never below the reward of all UAVs staying; with ``rewards`` also the float64 [N, nBS, 5] table: ``table[e, i, d]`` is the
-        reward of UAV i taking digit d given the digits chosen before it (heuristics.coordinate_rule states the choice)."""
+        reward of UAV i taking digit d given the digits chosen before it (heuristics.coordinate_rule states the choice).
+        ``actions_out`` / ``table_out``: buffers for the actions and (with ``rewards``) the table, so that the call allocates nothing."""
         return self._lookahead_actions(self._lib.uavenv_coordinate_actions, ue_xy, (theta_u, group_u, fading), best_reward,
-                                       (self.nBS, self.N_ACT) if rewards else None)
+                                       (self.nBS, self.N_ACT) if rewards else None, actions_out, table_out)
 
     def step_coordinate(self, n_steps, out=None, actions_out=None):
         """``n_steps`` x [coordinate_actions(); step(those actions)] issued by one C call (uavenv_step_coordinate; group mobility,

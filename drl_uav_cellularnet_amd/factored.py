@@ -100,6 +100,75 @@ def loss_grad_factored_reference(logits, v, v_target, actions, n_heads, n_act=N_
     return dz, dv, dz.sum(dim=0), (a_loss, (td ** 2).mean(), dv.sum())
 
 
+# ---- imitation: the cross entropy against a target distribution per head in place of the chosen-action term ----------
+def onehot_targets(labels, n_heads, n_act=N_ACT, dtype=torch.float64):
+    """JOINT actions int64 [M] (clamped to [0, n_act^n_heads - 1], the kernel's clamp) -> q [M, n_heads, n_act], the one-hot of each digit."""
+    d = joint_to_digits(torch.as_tensor(labels).reshape(-1).clamp(0, int(n_act) ** int(n_heads) - 1), n_heads, n_act)
+    return torch.zeros(d.shape + (int(n_act),), dtype=dtype, device=d.device).scatter_(2, d.unsqueeze(2), 1.0)
+
+
+def soft_targets(table, tau):
+    """Reward table [..., n_act] (float64: coordinate_actions(rewards=True) is [N, nBS, 5]) -> q of the same shape,
+    q = softmax((t - max t) / tau) over the last axis, in float64: what uavagent_soft_targets_f32 rounds to float32."""
+    if not tau > 0 or tau == float("inf"):
+        raise ValueError("tau must be finite and > 0")
+    t = torch.as_tensor(table, dtype=torch.float64)
+    return torch.softmax((t - t.max(dim=-1, keepdim=True).values) * (1.0 / float(tau)), dim=-1)
+
+
+def greedy_digits(logits):
+    """The greedy digit per head of logits [M, B, A], the rule of uavagent_choose_factored_f32(uniforms = NULL): the first index whose value
+    no other exceeds (strict >), a NaN never wins, an all-NaN head gives 0."""
+    M, B, A = logits.shape
+    bv = torch.zeros((M, B), dtype=logits.dtype, device=logits.device)
+    bi = torch.full((M, B), -1, dtype=torch.int64, device=logits.device)
+    for j in range(A):
+        x = logits[:, :, j]
+        take = (x == x) & ((bi < 0) | (x > bv))
+        bv, bi = torch.where(take, x, bv), torch.where(take, torch.full_like(bi, j), bi)
+    return bi.clamp(min=0)
+
+
+def agreement(logits, q):
+    """The fraction of (row, head) pairs whose greedy digit is the first maximum of q [M, B, A] (a float)."""
+    return float((greedy_digits(logits.detach()) == greedy_digits(q)).double().mean())
+
+
+def imitation_losses_factored(head_prob, v, q, v_target, beta=ENTROPY_BETA):
+    """(a_loss, c_loss) of the supervised phase.  head_prob and q [M, B, A] (sum_j q_bj = 1), v and v_target [M, 1].  With e = 1e-5:
+        X_b = -sum_j q_bj log(p_bj + e);  H_b = -sum_j p_bj log(p_bj + e);  a_loss = mean_rows sum_b (X_b - beta H_b)
+    and the critic's loss of a2c_losses_factored: c_loss = mean((v_target - v)^2).  With q = onehot(d) the actor's loss is
+    a2c_losses_factored's at td = 1."""
+    p = _heads(head_prob)
+    td = v_target - v
+    c_loss = (td ** 2).mean()
+    lp = torch.log(p + 1e-5)
+    x = -(q.to(p.dtype) * lp).sum(dim=(1, 2))
+    h = -(p * lp).sum(dim=(1, 2))
+    return (x - beta * h).mean(), c_loss
+
+
+def imitation_loss_grad_factored_reference(logits, v, v_target, n_heads, n_act=N_ACT, beta=ENTROPY_BETA, labels=None, targets=None):
+    """The closed-form gradient uavagent_imitation_loss_grad_factored implements, in PyTorch (dtype of logits): loss_grad_factored_reference
+    with the chosen-action term generalised to a target distribution q per head -- labels (JOINT actions [M], q = their one-hot) or targets
+    [M, B * A]:   gp_j = beta (log(p_j + e) + p_j / (p_j + e)) - q_j / (p_j + e);   d a_loss / d z_j = p_j (gp_j - sum_i p_i gp_i) / M;
+    d c_loss / d v = -2 td / M.   -> (dlogits [M, B*A], dv [M], dbias [B*A], (a_loss, c_loss, sum(dv), agreement))."""
+    if (labels is None) == (targets is None):
+        raise ValueError("exactly one of labels and targets must be given")
+    M, B, A = logits.shape[0], int(n_heads), int(n_act)
+    z = logits.reshape(M, B, A)
+    q = onehot_targets(labels, B, A, z.dtype) if labels is not None else targets.reshape(M, B, A).to(z.dtype)
+    p = torch.softmax(z, dim=2)
+    td = (v_target.reshape(M) - v.reshape(M)).to(z.dtype)
+    lp = torch.log(p + 1e-5)
+    gp = beta * (lp + p / (p + 1e-5)) - q / (p + 1e-5)
+    dot = (p * gp).sum(dim=2, keepdim=True)
+    dz = (p * (gp - dot) / M).reshape(M, B * A)
+    dv = -2.0 * td / M
+    a_loss = (-(q * lp).sum(dim=(1, 2)) + beta * (p * lp).sum(dim=(1, 2))).mean()
+    return dz, dv, dz.sum(dim=0), (a_loss, (td ** 2).mean(), dv.sum(), agreement(z, q))
+
+
 class FactoredCnnACNet(CnnACNet):
     """CnnACNet(n_bs, grid_n, n_bs * n_act) whose policy output is read as n_bs heads of n_act logits.  Parameter keys and shapes are
     CnnACNet's (the head is [100, n_bs * n_act]), so agent.save_actor_npz / load_actor_npz serve it; ``forward``, ``actor_only`` and
@@ -219,6 +288,8 @@ class FactoredA2CRunner(A2CRunner):
             kw[k] = False
         super().__init__(env, net=net, rollout=rollout, seed=seed, **kw)
         self.u_buf = torch.empty((self.T, env.n_envs, net.n_heads), dtype=torch.float32, device=self.dev)
+        self._imit = None             # "hard" / "soft" while imitate_rollout's update runs: the loss hooks answer with the imitation form
+        self._imit_marks = None       # tools/bench_imitate.py: a list makes the imitation rollout record (phase, event) pairs into it
 
     def _gather_kernels(self):
         from . import _agent_capi as A
@@ -245,13 +316,144 @@ class FactoredA2CRunner(A2CRunner):
     def _loss_grad(self, logits, v, target, actions, dv, dbias, loss, ws):
         from . import _agent_capi as A
 
-        A.a2c_loss_grad_factored(logits, v, target, actions, self.net.n_heads, self.net.n_act, self.beta, dv, dbias, loss, ws)
+        net = self.net
+        if self._imit is None:
+            A.a2c_loss_grad_factored(logits, v, target, actions, net.n_heads, net.n_act, self.beta, dv, dbias, loss, ws)
+        else:      # ``actions`` are the teacher's labels; with soft targets q_buf takes their place
+            soft = self._imit == "soft"
+            A.imitation_loss_grad_factored(logits, v, target, net.n_heads, net.n_act, self.beta, dv, dbias, loss, self._upd["ws_imit"],
+                                           labels=None if soft else actions, targets=self.q_buf.view(-1, net.n_action) if soft else None)
 
     def _losses(self, a_prob, v, actions, v_target):
         net = self.net
-        return a2c_losses_factored(a_prob.reshape(-1, net.n_heads, net.n_act), v, actions, v_target, self.beta)
+        prob = a_prob.reshape(-1, net.n_heads, net.n_act)
+        if self._imit is None:
+            return a2c_losses_factored(prob, v, actions, v_target, self.beta)
+        # update_reference hands its chunks over in row order: the cursor finds the chunk's rows of q_buf
+        n, lo = prob.shape[0], self._imit_cursor
+        self._imit_cursor = lo + n
+        if self._imit == "soft":
+            q = self.q_buf.view(-1, net.n_heads, net.n_act)[lo:lo + n]
+        else:
+            q = onehot_targets(actions, net.n_heads, net.n_act, prob.dtype)
+        self._imit_agree += agreement(prob, q) * n             # (the softmax keeps the order of the logits: their greedy digits)
+        return imitation_losses_factored(prob, v, q, v_target, self.beta)
+
+    def _ensure_update_buffers(self, M, K):
+        from . import _agent_capi as A
+
+        b = super()._ensure_update_buffers(M, K)
+        if "ws_imit" not in b:      # the imitation kernel writes a fourth sum (the agreement) behind the A2C kernel's three
+            b["loss"] = torch.zeros(4, dtype=torch.float64, device=self.dev)
+            b["ws_imit"] = A.imitation_loss_grad_workspace(self.net.n_heads, self.net.n_act, self.dev)
+        return b
 
     def state_dict(self):
         sd = super().state_dict()
         sd["net"] = self.NET_KIND
         return sd
+
+    # ---- the imitation warm start.  Self-contained: what it needs of the runner is collect()'s pieces (_first_layer,
+    # _policy / _draw_reference, _end_rollout), update() and the two loss hooks above. -----------------------------------------------------
+    TEACHERS = ("coordinate", "search", "gradient")
+
+    def _imitation_buffers(self, soft):
+        N, T, net = self.env.n_envs, self.T, self.net
+        if getattr(self, "label_buf", None) is None:
+            self.label_buf = torch.empty((T, N), dtype=torch.int64, device=self.dev)       # the teacher's decision before step t
+            self.step_buf = torch.empty((T, N), dtype=torch.int64, device=self.dev)        # the action step t took
+            self.u_mix = torch.empty((T, N), dtype=torch.float32, device=self.dev)
+            self.q_buf = None
+        if soft and self.q_buf is None:
+            self.q_buf = torch.empty((T, N, net.n_action), dtype=torch.float32, device=self.dev)
+            self._table_buf = torch.empty((N, net.n_heads, net.n_act), dtype=torch.float64, device=self.dev)
+
+    def _mark(self, phase):
+        if self._imit_marks is not None:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            self._imit_marks.append((phase, e))
+
+    def _teach(self, teacher, t, tau):
+        """The teacher's decision for the state the env is in, into label_buf[t]; with ``tau`` also its soft targets into q_buf[t]."""
+        env, net = self.env, self.net
+        if callable(teacher):
+            self.label_buf[t].copy_(torch.as_tensor(teacher(env), dtype=torch.int64).reshape(-1))
+        elif tau is None:
+            getattr(env, teacher + "_actions")(actions_out=self.label_buf[t])
+        else:
+            env.coordinate_actions(rewards=True, actions_out=self.label_buf[t], table_out=self._table_buf)
+            self._mark("teacher")
+            if self.dev.type == "cuda":
+                from . import _agent_capi as A
+
+                A.soft_targets(self._table_buf.view(-1, net.n_action), net.n_heads, net.n_act, tau, out=self.q_buf[t])
+            else:
+                self.q_buf[t].copy_(soft_targets(self._table_buf, tau).reshape(-1, net.n_action))
+
+    @torch.no_grad()
+    def _imitate_collect(self, teacher, mix, tau):
+        """collect() with a teacher beside the learner: per step the learner's forward pass and draw (act_buf[t]), the teacher's decision for
+        the same state (label_buf[t], q_buf[t]), and the env stepped with the teacher's action where u_mix[t] < mix, else the learner's
+        (step_buf[t]).  Eager launches, no host synchronisation inside the loop."""
+        env, T, N = self.env, self.T, self.env.n_envs
+        self.u_buf.copy_(torch.rand(self.u_buf.shape, device=self.dev, dtype=torch.float32, generator=self.gen))
+        self.u_mix.copy_(torch.rand(self.u_mix.shape, device=self.dev, dtype=torch.float32, generator=self.gen))
+        from_teacher = self.u_mix < float(mix)
+        self._refresh_transposed()
+        self.idx_buf[0].copy_(self.idx_buf[T])
+        cuda = self.dev.type == "cuda"
+        self._mark("start")
+        for t in range(T):
+            if cuda:
+                self._first_layer(t, 0, N)
+                self._policy(t, 0, N)
+            else:
+                self.act_buf[t] = self._draw_reference(t)
+            self._mark("learner")
+            self._teach(teacher, t, tau)
+            self._mark("teacher" if tau is None else "soft_targets")
+            torch.where(from_teacher[t], self.label_buf[t], self.act_buf[t], out=self.step_buf[t])
+            env.step(self.step_buf[t], reward_out=self.rew_buf[t])
+            if not (cuda and self.fused_obs) or t == T - 1:
+                self._indices_into(self.idx_buf[t + 1])
+            self._mark("env_step")
+        done = env.out["done"].bool()
+        any_done = bool(done.any())                                                  # (host sync: the rollout's kernels have finished)
+        self._fwd_valid = self._fwd is not None
+        return self._end_rollout(done, any_done)
+
+    def imitate_rollout(self, teacher="coordinate", mix=0.5, tau=None):
+        """One rollout and one update of the supervised phase: the actor learns the teacher's decisions (cross entropy per UAV, the entropy
+        bonus kept) on the states of a trajectory that follows the teacher with probability ``mix`` per (step, env) and the learner's own
+        draw otherwise -- mix = 1: behaviour cloning on the teacher's trajectories, mix = 0: DAgger on the learner's own; the critic learns
+        the n-step returns of that trajectory as in train_rollout.  ``teacher``: "coordinate", "search" or "gradient" (the env's own
+        *_actions call; its refusals pass through) or a callable teacher(env) -> int64 [N] joint actions.  ``tau``: None = hard labels; a
+        temperature = soft targets softmax(table / tau) per UAV from the coordinate search's reward table ("coordinate" only).
+        Returns update()'s stats with ``agreement`` added: the fraction of (sample, UAV) pairs whose greedy digit is the teacher's."""
+        if not callable(teacher) and teacher not in self.TEACHERS:
+            raise ValueError("teacher must be one of %s or a callable teacher(env) -> int64 [n_envs]" % (self.TEACHERS,))
+        if tau is not None:
+            if teacher != "coordinate":
+                raise ValueError("soft targets (tau) need the teacher's reward table: teacher='coordinate' only")
+            if not float(tau) > 0 or float(tau) == float("inf"):
+                raise ValueError("tau must be finite and > 0")
+        if not 0.0 <= float(mix) <= 1.0:
+            raise ValueError("mix must be in [0, 1]")
+        self._imitation_buffers(tau is not None)
+        idx, _, rew, boot = self._imitate_collect(teacher, mix, tau)
+        return self.imitate_update(idx, rew, boot, soft=tau is not None)
+
+    def imitate_update(self, idx_buf, rew_buf, boot, soft=False, fused=None):
+        """update() in imitation mode on the batch the last imitation rollout left: the teacher's label_buf (``soft``: q_buf) takes the
+        place of act_buf, the loss hooks answer with the imitation form, everything else is the A2C update as it stands.  ``fused``:
+        None = update()'s choice, True / False = update_fused / update_reference.  Returns the stats with ``agreement`` added."""
+        if fused is None:
+            fused = self.fused_update and self.dev.type == "cuda"
+        self._imit, self._imit_cursor, self._imit_agree = ("soft" if soft else "hard"), 0, 0.0
+        try:
+            stats = (self.update_fused if fused else self.update_reference)(idx_buf, self.label_buf, rew_buf, boot)
+            stats["agreement"] = float(self._upd["loss"][3]) if fused else self._imit_agree / self.label_buf.numel()
+        finally:
+            self._imit = None
+        return stats

@@ -224,6 +224,28 @@ int uavagent_a2c_loss_grad_factored(float *logits_inout, int64_t ld_logits, cons
                                     int64_t m_rows, int32_t n_heads, int32_t n_act, float beta, float *dv_out, float *dbias_out,
                                     double *loss_out, void *workspace, void *stream);
 
+/* The supervised (imitation) form of the loss above: the chosen-action term becomes the cross entropy against a target
+ * distribution q_b per (row, head), sum_j q_bj = 1:  a_loss = mean_rows sum_b (X_b - beta H_b),  X_b = -sum_j q_bj log(p_bj + 1e-5),
+ * gp_j = beta (log(p_j + e) + p_j / (p_j + e)) - q_j / (p_j + e),  d a_loss / d z_j = p_j (gp_j - sum_i p_i gp_i) / M;  the critic's c_loss and
+ * dv are those of uavagent_a2c_loss_grad_factored.  EXACTLY ONE of the two target forms is non-null (both or neither: refused):
+ *   labels   int64 [m_rows]: JOINT actions, clamped to [0, n_act^n_heads - 1] and decoded by integer division (no value is used as an
+ *            index); q_b = onehot(d_b).  The gradient is then bit for bit uavagent_a2c_loss_grad_factored's with actions = labels where
+ *            v_target - v == 1.
+ *   targets  f32 [m_rows, n_heads * n_act] contiguous (uavagent_soft_targets_f32 writes such rows).
+ * Layout, bounds, refusals and outputs as above; loss_out double[4] = {a_loss, c_loss, sum(dv), agreement}: the fraction of (row, head) pairs
+ * whose greedy digit (the rule of uavagent_choose_factored_f32 with uniforms == NULL) is the first maximum of q_b.  `workspace`:
+ * uavagent_imitation_loss_grad_workspace_bytes bytes, 8-byte aligned.  Fixed grid, fixed order: bit-reproducible. */
+size_t uavagent_imitation_loss_grad_workspace_bytes(int32_t n_heads, int32_t n_act);
+int uavagent_imitation_loss_grad_factored(float *logits_inout, int64_t ld_logits, const float *v, const float *v_target, const int64_t *labels,
+                                          const float *targets, int64_t m_rows, int32_t n_heads, int32_t n_act, float beta, float *dv_out,
+                                          float *dbias_out, double *loss_out, void *workspace, void *stream);
+
+/* Soft targets from a reward table: table f64 [n_rows, n_heads * n_act] with row stride ld_table doubles (uavenv_coordinate_actions' table
+ * viewed as [N, nBS * 5]), q_out f32 [n_rows, n_heads * n_act] contiguous:  q_b = softmax_j(inv_tau * (t_bj - max_j t_bj)), in float64,
+ * rounded once.  inv_tau must be finite and > 0.  Table entries are expected to be finite; none is used as an index. */
+int uavagent_soft_targets_f32(const double *table, int64_t ld_table, double inv_tau, int64_t n_rows, int32_t n_heads, int32_t n_act,
+                              float *q_out, void *stream);
+
 /* ---- The first layer for up to 256 observation nodes per sample (csrc/agent_wide.hip; additive to ABI 5, the number stays): 16 UAV + 200 UE
  * = 216 nodes at the largest shape the env serves.  The 64-node entry points above keep their bound. ---- */
 

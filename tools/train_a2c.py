@@ -7,6 +7,8 @@ actor parameters (Global_A_PARA: here a named .npz, agent.save_actor_npz -- load
   python tools/train_a2c.py --out train/run1 [--workers 8192] [--episodes 2] [--rollout 50] [--first-state zeros]
   python tools/train_a2c.py --net cnn-factored --n-bs 16 --n-ue 200 --workers 1024      # one 5-way policy head per UAV (factored.py)
   python tools/train_a2c.py --net mlp-factored --n-bs 16 --n-ue 200 --workers 1024      # the MLP with that head (256-node first layer)
+  python tools/train_a2c.py --net mlp-factored --n-bs 16 --n-ue 200 --workers 1024 --imitate-episodes 2 --episodes 4
+                                                   # the first 2 episodes imitate the coordinate search (imitate_rollout), then A2C
   python -m torch.distributed.run --nproc-per-node 8 tools/train_a2c.py ...     # one process per GPU, gradients all-reduced (RCCL)"""
 import argparse
 import json
@@ -68,7 +70,22 @@ def main():
                     "(cnn_agent.CnnACNet, one process only); cnn-factored / mlp-factored: the CNN / the MLP with one 5-way head per UAV "
                     "(factored.FactoredCnnACNet, one process only; factored.FactoredACNet) -- the two that exist beyond a handful of UAVs")
     ap.add_argument("--n-bs", type=int, default=4, help="UAVs; the joint heads of mlp / cnn have 5^n_bs logits (625 at the reference's 4)")
+    ap.add_argument("--imitate-episodes", type=int, default=0, help="mlp-factored: the first K episodes are the supervised warm start "
+                    "(FactoredA2CRunner.imitate_rollout), the rest the A2C loop; the phase depends on the episode counter only, so --resume "
+                    "stays bit-identical")
+    ap.add_argument("--teacher", choices=("coordinate", "search", "gradient"), default="coordinate", help="the env policy imitated")
+    ap.add_argument("--imitate-mix", type=float, default=0.5, help="probability per (step, env) that the env follows the teacher's action "
+                    "instead of the learner's draw (1 = behaviour cloning, 0 = DAgger)")
+    ap.add_argument("--imitate-tau", type=float, default=None, help="temperature of soft targets from the coordinate search's reward table "
+                    "(default: hard labels)")
     a = ap.parse_args()
+    imitation_flags = a.imitate_episodes != 0 or a.teacher != "coordinate" or a.imitate_mix != 0.5 or a.imitate_tau is not None
+    if imitation_flags and a.net != "mlp-factored":
+        ap.error("--imitate-episodes / --teacher / --imitate-mix / --imitate-tau are for --net mlp-factored")
+    if a.imitate_episodes < 0 or not 0.0 <= a.imitate_mix <= 1.0:
+        ap.error("--imitate-episodes must be >= 0 and --imitate-mix in [0, 1]")
+    if a.imitate_tau is not None and (a.teacher != "coordinate" or not a.imitate_tau > 0):
+        ap.error("--imitate-tau must be > 0 and needs --teacher coordinate")
     import numpy as np
     import torch
 
@@ -110,14 +127,26 @@ def main():
         first_ep, returns = int(sd["episode"]) + 1, list(sd["returns"])
         check_ranks_agree(torch, world, dev, first_ep, runner)
     for ep in range(first_ep, a.episodes):
+        imitating = ep < a.imitate_episodes                                # a function of the episode counter alone
+        reward_sum, agree = 0.0, []
         for r in range(per_episode):
-            st = runner.train_rollout()
+            if imitating:
+                st = runner.imitate_rollout(teacher=a.teacher, mix=a.imitate_mix, tau=a.imitate_tau)
+                agree.append(st["agreement"])
+            else:
+                st = runner.train_rollout()
+            reward_sum += st["mean_reward"]
         returns.append(runner.running_r)                                   # GLOBAL_RUNNING_R, :169-172
         if rank == 0:
-            print(json.dumps({"episode": ep, "episode_return": runner.last_episode_return, "running_return": runner.running_r,
-                              "a_loss": st["a_loss"], "c_loss": st["c_loss"],
-                              "mean_reward": st["mean_reward"], "env_steps": (ep + 1) * per_episode * a.rollout * a.workers * world,
-                              "seconds": time.time() - t0}), flush=True)
+            line = {"episode": ep, "episode_return": runner.last_episode_return, "running_return": runner.running_r,
+                    "a_loss": st["a_loss"], "c_loss": st["c_loss"],
+                    "mean_reward": st["mean_reward"], "env_steps": (ep + 1) * per_episode * a.rollout * a.workers * world,
+                    "seconds": time.time() - t0}
+            if a.net == "mlp-factored":
+                line.update({"phase": "imitate" if imitating else "a2c", "episode_mean_reward_per_step": reward_sum / per_episode})
+                if imitating:
+                    line["agreement"] = agree                               # the teacher agreement of every rollout of the episode
+            print(json.dumps(line), flush=True)
         if a.checkpoint_every and (ep + 1) % a.checkpoint_every == 0:
             save_checkpoint(torch, world, ckpt, {"runner": runner.state_dict(), "episode": ep, "returns": returns})
     if rank == 0:
