@@ -16,6 +16,50 @@ __attribute__((visibility("hidden"))) int fail(int code, const std::string &msg)
 #ifdef __HIPCC__
 __device__ __forceinline__ float draw_exp(float x_minus_max) { return __builtin_amdgcn_exp2f(x_minus_max * 1.4426950408889634f); }
 
+// The DRAW's column (sample_actions_kernel and the actor head's fused draw: one rule, stated once).  Lane l holds the numerators v[0 .. PER) of
+// columns l * PER .., `loc` their sum in that order, `incl` the inclusive scan of loc over the lanes; target = u * incl[63].  The answer is the
+// first column whose running sum exceeds target, found in the first lane with incl > target: every lane walks its OWN values from incl - loc
+// (the same sums in the same order as walking that lane's values by broadcast, without PER dependent cross-lane reads) and the walk of lane
+// `first` counts.  incl - loc is not the scan's exclusive prefix and the walk rounds differently from the scan, so within an ulp of a lane
+// boundary the walk may start above target (it crosses on its first column whatever that holds) or end at or below it (no crossing).
+// A column with numerator 0 has probability 0 and is never the answer.  THE RULE: the first column of lane `first` with a non-zero numerator
+// and a running sum above target; without one, the last column at or below the lane's last whose numerator is non-zero (one exists:
+// incl[first] > target >= 0).  Adding a zero leaves the running sum as it is, so a crossing on a zero numerator can only be the walk's FIRST
+// column: the walk itself is the plain one, one test behind it marks that case (-2) beside "no crossing" (-1), and both are settled inside a
+// wave-uniform branch that a draw away from a lane boundary never enters.  tests/agent_numerics_cases.py restates this in numpy.
+template <int PER>
+__device__ __forceinline__ int draw_column(const float (&v)[PER], float loc, float incl, float target, int n_act) {
+    const unsigned long long over = __ballot(incl > target);
+    if (over == 0ull) return n_act - 1;                 // u * total rounding up to total: the last action (the reference clamps too)
+    const int first = __ffsll((long long)over) - 1;
+    float c = incl - loc;
+    int fk = -1;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        c += v[k];
+        if (fk < 0 && c > target) fk = k;
+    }
+    if (fk == 0 && v[0] == 0.f) fk = -2;
+    fk = __shfl(fk, first, 64);
+    int a = first * PER + fk;
+    if (fk < 0) {
+        int nk = -1, lk = -1;                           // this lane's first and last non-zero numerators
+#pragma unroll
+        for (int k = 0; k < PER; ++k)
+            if (v[k] != 0.f) { lk = k; if (nk < 0) nk = k; }
+        nk = fk == -2 ? __shfl(nk, first, 64) : -1;     // the walk started above target: every column of the lane is past the crossing
+        if (nk >= 0) {
+            a = first * PER + nk;
+        } else {
+            const unsigned long long has = __ballot(lk >= 0) & (~0ull >> (63 - first));      // lanes 0 .. first that hold a non-zero one
+            const int src = has != 0ull ? 63 - __clzll((long long)has) : 0;
+            lk = __shfl(lk, src, 64);
+            a = src * PER + (lk < 0 ? 0 : lk);
+        }
+    }
+    return a > n_act - 1 ? n_act - 1 : a;
+}
+
 // The GREEDY choice (uavagent_argmax_rows_f32 and the greedy head's fused pick: one rule, stated once): the first index whose value no other
 // exceeds.  A lane feeds its columns in ASCENDING order to greedy_take -- strict >, so of equal values the lower index stays; a NaN is never
 // taken -- and greedy_wave reduces the 64 (value, index) pairs (equal values: the lower index) to the row's answer in every lane.  bi < 0 =

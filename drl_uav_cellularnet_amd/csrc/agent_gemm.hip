@@ -1344,24 +1344,7 @@ __device__ __forceinline__ void actor_head_tile(float *lds, const long long m0, 
                 if (lane >= off) incl += t;
             }
             const float total = __shfl(incl, 63, 64);
-            const float target = u_row[i] * total;
-            const unsigned long long over = __ballot(incl > target);
-            a = n_act - 1;
-            if (over != 0ull) {
-                // every lane walks its OWN PER values from its own exclusive prefix; the walk of the lane that holds the crossing is the answer
-                // (the same sums in the same order as walking that lane's values by broadcast, without ten dependent cross-lane reads)
-                const int first = __ffsll((long long)over) - 1;
-                float c = incl - loc;
-                int fk = -1;
-#pragma unroll
-                for (int k = 0; k < PER; ++k) {
-                    c += v[k];
-                    if (fk < 0 && c > target) fk = k;
-                }
-                fk = __shfl(fk, first, 64);
-                a = fk < 0 ? first * PER + PER - 1 : first * PER + fk;
-                if (a > n_act - 1) a = n_act - 1;
-            }
+            a = draw_column<PER>(v, loc, incl, u_row[i] * total, n_act);      // agent_common.h states the rule
         }
         if (lane == 0) {
             if (COH) __hip_atomic_store(action + m, (long long)a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

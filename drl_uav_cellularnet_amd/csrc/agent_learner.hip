@@ -103,24 +103,7 @@ __global__ __launch_bounds__(256) void sample_actions_kernel(const float *__rest
             if (c < A) prob[r * A + c] = v[k] * inv;
         }
     }
-    const float target = uni[r] * total;
-    const unsigned long long over = __ballot(incl > target);
-    int a = A - 1;                                      // u * total rounding up to total: the last action (the reference clamps too)
-    if (over != 0ull) {
-        const int first = __ffsll((long long)over) - 1;
-        // every lane walks its OWN PER values from its own exclusive prefix; the walk of the lane that holds the crossing is the answer
-        // (the same sums in the same order as walking that lane's values by broadcast, without PER dependent cross-lane reads)
-        float c = incl - loc;
-        int fk = -1;
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            c += v[k];
-            if (fk < 0 && c > target) fk = k;
-        }
-        fk = __shfl(fk, first, 64);
-        a = fk < 0 ? first * PER + PER - 1 : first * PER + fk;
-        if (a > A - 1) a = A - 1;
-    }
+    const int a = draw_column<PER>(v, loc, incl, uni[r] * total, A);      // agent_common.h states the rule
     if (lane == 0) action[r] = a;
 }
 

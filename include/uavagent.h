@@ -67,7 +67,8 @@ int uavagent_first_layer_from_obs_f32(const float *w_a, const float *bias_a, flo
 /* choose_action (main.py:165-169): p = softmax(logits[n, :]); np.random.choice(n_actions, p=p) with the uniform u[n] supplied by
  * the caller: the first a with cumsum(p)[a] > u[n] * cumsum(p)[-1].  logits f32 [n_rows, n_actions] with row stride ld_logits floats
  * (ABI 3: the learner keeps its 625 logits in rows of 640), uniforms f32 [n_rows] in [0, 1), actions_out int64 [n_rows]; prob_out f32
- * [n_rows, n_actions] contiguous or NULL.  n_actions <= 1024. */
+ * [n_rows, n_actions] contiguous or NULL.  n_actions <= 1024.  The cumulative sums are float32 (a draw within 1e-6 of a boundary of the CDF
+ * may go to either side); an action whose softmax numerator is 0 in float32 is never the answer. */
 int uavagent_sample_actions(const float *logits, int64_t ld_logits, const float *uniforms, int64_t n_rows, int32_t n_actions,
                             int64_t *actions_out, float *prob_out, void *stream);
 

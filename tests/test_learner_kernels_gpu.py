@@ -461,6 +461,44 @@ def test_actor_head_kernel_equals_the_three_launches(n_rows, tile, monkeypatch):
         A.actor_head(h1, w2t, b2, w3t, b3p, u, 100, h2a, lga, acta)          # built for the reference's 625 actions (577..640)
 
 
+def test_actor_head_kernel_equals_the_three_launches_with_saturated_logits():
+    """The same identity with w3 scaled until every row's logits spread over more than 150 (most numerators of the draw exactly 0) and the
+    uniforms within 8 float32 steps of the lane boundaries of each row's CDF, where the draw's walk and scan round differently
+    (agent_common.h: draw_column): the head's fused draw and uavagent_sample_actions still agree bit for bit, and both obey the float64 CDF."""
+    torch = _torch()
+    from drl_uav_cellularnet_amd import _agent_capi as A
+    import agent_numerics_cases as K
+
+    n_rows, H, NA = 63 * 17, 200, 625                   # one (lane boundary, neighbour) pair per row; ragged against both tile heights
+    g = torch.Generator(device="cuda").manual_seed(5)
+    rnd = lambda *s: torch.rand(s, device="cuda", generator=g) * 2.0 - 1.0
+    h1 = (rnd(n_rows, H) * 4.0 + 2.0).clamp_(0.0, 6.0)
+    w2, b2, w3, b3 = rnd(H, H) * 0.2, rnd(H), rnd(H, NA) * 2.4, rnd(NA)
+    w2t = w2.t().contiguous()
+    w3t, b3p = torch.zeros((640, H), device="cuda"), torch.zeros(640, device="cuda")
+    w3t[:NA], b3p[:NA] = w3.t(), b3
+    h2a, lga, acta = torch.empty((n_rows, H), device="cuda"), torch.empty((n_rows, 640), device="cuda"), torch.full((n_rows,), -1, dtype=torch.int64, device="cuda")
+    h2b, lgb = torch.empty_like(h2a), torch.empty_like(lga)
+    A.gemm_rows(h1, w2t, h2b, w_transposed=True, bias=b2, relu6=True)
+    A.gemm_rows(h2b, w3t, lgb, w_transposed=True, bias=b3p)
+    x = lgb[:, :NA].cpu().numpy()
+    assert float((x.max(axis=1) - x.min(axis=1)).min()) > 150.0
+    _, cdf = K.cdf64(x)
+    r = np.arange(n_rows)
+    un = np.float32(cdf[r, np.minimum(10 * (r % 63) + 9, NA - 1)] / cdf[:, -1])
+    for step in range(-8, 9):                           # row r: the boundary of lane r % 63, moved by r // 63 - 8 float32 steps
+        sel = r // 63 - 8 == step
+        for _ in range(abs(step)):
+            un[sel] = np.nextafter(un[sel], np.float32(2.0 if step > 0 else -1.0))
+    un = np.clip(un, np.float32(0.0), np.float32(1.0 - 2.0 ** -24))
+    u = torch.as_tensor(un).cuda()
+    A.actor_head(h1, w2t, b2, w3t, b3p, u, NA, h2a, lga, acta)
+    actb = A.sample_actions(lgb[:, :NA], u)
+    assert torch.equal(h2a, h2b) and torch.equal(lga, lgb) and torch.equal(acta, actb)
+    assert int(K.draw_violations(x, acta.cpu().numpy(), un, need_live=False).sum()) == 0
+    assert float((x.max(axis=1) - x[r, acta.cpu().numpy()]).max()) <= 105.0      # exp(-105) < 2^-150: beyond that a float32 numerator is 0, never drawn
+
+
 # (M, I, J, ldb): J <= 208 runs plan 13, wider plan 20; ldb > J = a column slice of a padded buffer (the learner's logits: 625 of 640)
 TN_SHAPES = [(1, 200, 200, 200), (31, 200, 200, 200), (5000, 200, 200, 200), (40037, 200, 200, 200), (3000, 200, 625, 640), (2999, 200, 625, 625),
              (700, 200, 640, 640), (1500, 64, 100, 100), (900, 200, 321, 324), (1200, 8, 5, 5)]
