@@ -323,7 +323,7 @@ __global__ __launch_bounds__(256) void gemm_tn_reduce(const f32x4 *__restrict__ 
 //   EPI 0 none;  1: + bias[n], then relu6 when asked (tf.nn.relu6);  2: relu6 backwards, C = (0 < H[m, n] < 6) ? sum : 0 with H the
 //   layer's forward output (main.py:147-148,153).
 // Four kernels, chosen by uavagent_gemm_rows_f32:
-//   gemm_rows_glds_kernel   dy @ W^T / x @ (W^T)^T, aligned operands, K % 40 == 0: LDS-DMA ring (the learner's shapes: all of them)
+//   gemm_rows_glds_kernel   dy @ W^T / x @ (W^T)^T, aligned operands, K % 40 == 0: LDS-DMA ring (the MLP learner's 200 / 640; not K = 32, 100)
 //   gemm_rows_nt_kernel     the same product for any K % 4 == 0: register-staged, k-contiguous tiles, wide fragment reads
 //   gemm_rows_vec_kernel    x @ W with W [K, N] as stored (n-contiguous W tile [k][208], A tile [row][22]: stride 22 puts the 16 rows x
 //                           2 k of a fragment read on 32 different banks), aligned operands: 128 rows x <= 208 columns per workgroup,

@@ -137,7 +137,13 @@ int uavagent_rmsprop_tf1(float *w, float *ms, const float *g, int64_t n, float l
  *   a f32 [m_rows, k] (row stride lda), c f32 [m_rows, n] (row stride ldc).  16-byte aligned pointers with lda, ldw, ldc, ldh, k, n all
  *   multiples of 4 take the fast path (float4 staging, coalesced epilogue); anything else is loaded dword by dword.
  *   colsum_out f32 [n] or NULL: column sums of c as stored (the bias gradient of the layer below when c is a masked dx); fast path only,
- *   needs `workspace` (16-byte aligned, uavagent_gemm_rows_workspace_bytes(m_rows) bytes); fixed summation order, bit-reproducible. */
+ *   needs `workspace` (16-byte aligned, uavagent_gemm_rows_workspace_bytes(m_rows) bytes); fixed summation order, bit-reproducible.
+ *   NaN: a NaN in a[m, :] makes row m of c NaN, a NaN in row n of w^T (column n of w) makes column n of c NaN, and nothing else; the mask
+ *   epilogue stores NaN where 0 < h < 6 and 0 elsewhere; a column sum is NaN iff a stored element of its column is.  relu6 != 0 stores 0 for
+ *   a NaN sum, in every kernel: it is fminf(fmaxf(v, 0), 6), and fmaxf returns its other operand for a NaN.  torch's relu6 (F.relu6 / clamp, the torch
+ *   path of agent.py) returns NaN there -- a diverged layer shows as NaN on that path and as zeros behind this one.
+ *   Nothing outside a[m_rows, k], w, bias[n], relu6_mask_h[m_rows, n] is read for its value and nothing outside c[m_rows, n], colsum_out[n]
+ *   and the workspace's stated bytes is written, whatever lies between the rows (lda > k, ldw, ldh, ldc > n). */
 size_t uavagent_gemm_rows_workspace_bytes(int64_t m_rows);
 int uavagent_gemm_rows_f32(const float *a, int64_t lda, const float *w, int64_t ldw, int32_t w_transposed, int64_t m_rows, int32_t k,
                            int32_t n, const float *bias, int32_t relu6, const float *relu6_mask_h, int64_t ldh, float *c, int64_t ldc,
@@ -191,7 +197,12 @@ int uavagent_actor_head_gated_f32(const float *h1, const float *w2t, const float
  * the same layer: a column of ones rides along in the kernel).  a f32 [m_rows, n_i] CONTIGUOUS (n_i % 4 == 0, <= 200, 16-byte aligned),
  * b f32 [m_rows, n_j] (row stride ldb, n_j <= 640), c f32 [n_i, n_j] (row stride ldc).  The sum over m is split over the CUs; partial
  * sums go to `workspace` (16-byte aligned, uavagent_gemm_tn_workspace_bytes(m_rows, n_j) bytes) and a second pass adds them in a fixed
- * order: bit-reproducible, no float atomics. */
+ * order: bit-reproducible, no float atomics.
+ * One thing is read beyond b[m_rows, n_j]: when b is 16-byte aligned, ldb % 4 == 0 and ldb >= roundup4(n_j), rows of b are staged as float4
+ * and columns n_j .. roundup4(n_j) - 1 of every row (inside the row stride) are read; they must hold FINITE values (any: they meet zeros),
+ * as the learner's [m, 625] logits gradient in rows of 640 with a zero tail does.  A NaN or infinity there spreads over c.  Everything else
+ * between and around the rows may hold anything.  NaN: a NaN at a[m, i] makes row i of c NaN and leaves dbias_out finite; a NaN at b[m, j]
+ * makes column j of c and dbias_out[j] NaN. */
 size_t uavagent_gemm_tn_workspace_bytes(int64_t m_rows, int32_t n_j);
 /* Test hook (host only): the dW kernel deals the 13 x 13 (plan 13) or 13 x 20 (plan 20) output blocks of a tile out to 8 wavefronts of equal
  * shape; > 0 = MFMAs issued per k-step when every block has exactly one owner, negative on a hole or an overlap. */
