@@ -54,6 +54,11 @@ class UavEnvEvalAcc(C.Structure):           # include/uavenv.h
         ("lo", C.c_double), ("inv_width", C.c_double), ("bins", C.c_int32)]
 
 
+class UavEnvRewardConfig(C.Structure):      # include/uavenv.h
+    _fields_ = [("kind", C.c_int32), ("use_floor", C.c_int32)] + [(n, C.c_double) for n in (
+        "floor", "sinr_div", "sinr_cap", "cap_div", "sep_threshold", "sep_weight", "collide_threshold", "collide_penalty")]
+
+
 RATE_MAX_MCS = 16
 RATE_OUT_FIELDS = (("dl_sinr_db", "f8"), ("dl_rate", "f8"), ("dl_mcs", "i1"), ("ul_avg_gain", "f8"), ("ul_interference", "f8"), ("ul_sinr_db", "f8"),
                    ("ul_channels", "f8"), ("ul_rate", "f8"), ("ul_mcs", "i1"), ("dl_rate_serving", "f4"), ("ul_rate_serving", "f4"),
@@ -85,7 +90,7 @@ class UavEnvStateLayout(C.Structure):
 
 
 EXPORTS = ("uavenv_abi_version", "uavenv_last_error", "uavenv_default_config", "uavenv_create", "uavenv_destroy",
-           "uavenv_init", "uavenv_warmup", "uavenv_reset", "uavenv_reset_trace", "uavenv_step", "uavenv_step_range", "uavenv_rollout_gated", "uavenv_gradient_actions", "uavenv_step_gradient", "uavenv_search_actions", "uavenv_step_search", "uavenv_coordinate_actions", "uavenv_step_coordinate", "uavenv_eval_accumulate", "uavenv_default_rate_config", "uavenv_link_rates", "uavenv_step_many", "uavenv_step_seq", "uavenv_step_trace",
+           "uavenv_init", "uavenv_warmup", "uavenv_reset", "uavenv_reset_trace", "uavenv_step", "uavenv_step_range", "uavenv_rollout_gated", "uavenv_gradient_actions", "uavenv_step_gradient", "uavenv_search_actions", "uavenv_step_search", "uavenv_coordinate_actions", "uavenv_step_coordinate", "uavenv_eval_accumulate", "uavenv_default_rate_config", "uavenv_link_rates", "uavenv_default_reward_config", "uavenv_shape_reward", "uavenv_step_many", "uavenv_step_seq", "uavenv_step_trace",
            "uavenv_obs_dense", "uavenv_obs_dense_update", "uavenv_sinr_area", "uavenv_sinr_area_at",
            "uavenv_debug_variant_count", "uavenv_debug_variant_info", "uavenv_debug_variant_reset",
            "uavenv_debug_side_variant_count", "uavenv_debug_side_variant_info", "uavenv_debug_side_variant_reset", "uavenv_debug_rotation_info", "uavenv_debug_path_launches", "uavenv_step_many_prepare", "uavenv_device_error", "uavenv_launch_timing", "uavenv_launch_times_us", "uavenv_debug_schedule",
@@ -136,6 +141,8 @@ def load():
     lib.uavenv_eval_accumulate.argtypes = [_P, C.POINTER(UavEnvOut), C.POINTER(UavEnvEvalAcc), _P]
     lib.uavenv_default_rate_config.argtypes = [C.POINTER(UavEnvRateConfig)]
     lib.uavenv_link_rates.argtypes = [_P, C.POINTER(UavEnvRateConfig), C.POINTER(UavEnvRateInject), C.POINTER(UavEnvRates), _P]
+    lib.uavenv_default_reward_config.argtypes = [C.POINTER(UavEnvRewardConfig)]
+    lib.uavenv_shape_reward.argtypes = [_P, C.POINTER(UavEnvRewardConfig), C.POINTER(UavEnvOut), C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P]
     lib.uavenv_step_range.argtypes = [_P, _P, C.c_int64, C.c_int64, C.POINTER(UavEnvInject), C.POINTER(UavEnvOut), _P]
     lib.uavenv_step_many.argtypes = [_P, _P, C.c_int, C.POINTER(UavEnvOut), _P]
     lib.uavenv_step_seq.argtypes = [_P, _P, C.c_int, C.POINTER(UavEnvOut), _P]

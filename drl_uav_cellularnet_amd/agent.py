@@ -389,7 +389,8 @@ class A2CRunner:
         self._persist_same_stream = False            # test hook: both persistent kernels in ONE queue, i.e. never side by side
         self._gate_spin_us = 0                       # test hook: the policy kernel's wait budget; 0 = the library's 2 s
         if (persistent_rollout and self.dev.type == "cuda" and self.fused_head and self.fused_obs and env.nBS == 4 and env.nUE <= 64
-                and env.n_envs % 4 == 0 and "cur_sinr_f64" not in env.out and (persistent_rollout is True or env.n_envs >= 4096)):
+                and env.n_envs % 4 == 0 and "cur_sinr_f64" not in env.out and (persistent_rollout is True or env.n_envs >= 4096)
+                and getattr(env, "reward", None) is None):   # (the persistent env kernel computes the step's own reward only)
             self._persistent = True
         N, T = env.n_envs, self.T
         # Forward activations of the rollout, kept for the update: between collect() and update() the weights do not change, so
@@ -430,6 +431,9 @@ class A2CRunner:
         TF1 RMSProp views, the rollout buffers, the first state, the episode bookkeeping and the action-sampling generator."""
         self.env = env
         self.dev = env.device
+        # the env's reward spec (BatchedMobiEnv.set_reward) as it is now: it decides the form of the rollout, and a captured rollout
+        # graph holds its shaping launches with the spec by value, so collect() refuses an env whose spec has changed since
+        self.reward_spec = getattr(env, "reward", None)
         self.gemm_tuning = enable_gemm_tuning() if (tune_gemms and self.dev.type == "cuda") else False
         self.G, self.B = env.grid_n, env.nBS
         self.net = net.to(self.dev)
@@ -690,6 +694,7 @@ class A2CRunner:
         """One rollout: returns (idx [T,N,K], actions [T,N], rewards [T,N], bootstrap [N]) -- views of persistent buffers, valid
         until the next collect()."""
         env, T = self.env, self.T
+        self._check_reward_spec()
         self.u_buf.copy_(torch.rand(self.u_buf.shape, device=self.dev, dtype=torch.float32, generator=self.gen))
         self._refresh_transposed()
         if self.collect_launch == "graph" and self.dev.type == "cuda" and self._graph is None:
@@ -729,6 +734,13 @@ class A2CRunner:
             any_done = bool(done.any())
         self._fwd_valid = self._fwd is not None
         return self._end_rollout(done, any_done)
+
+    def _check_reward_spec(self):
+        """Raises if the env's reward spec is not the one this runner was built with (see ``reward_spec`` in _init_common)."""
+        now = getattr(self.env, "reward", None)
+        if now != self.reward_spec:
+            raise RuntimeError("%s: the env's reward is now %r, this runner was built with %r (its rollout form and captured graph hold the "
+                               "old one); build a new runner after set_reward()" % (type(self).__name__, now, self.reward_spec))
 
     def _end_rollout(self, done, any_done):
         """After the T steps: episode returns, the bootstrap value v(s_T) (0 where done), the masked reset of the finished envs.

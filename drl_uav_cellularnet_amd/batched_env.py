@@ -9,6 +9,7 @@ same constructor meaning (nBS, nUE, grid_n), same ``reset()`` / ``step(action)``
     obs = env.reset()                                          # compact obs: dict of device tensors
     obs, reward, done, info = env.step(actions)                # actions: int64 [N] in [0, 5**nBS)
     dense = env.dense_obs()                                    # (N, nBS+1, G, G) float32, reference layout
+    env.set_reward(rewards.initial().with_separation())        # every later step returns this reward (rewards.py)
 """
 import ctypes as C
 
@@ -17,6 +18,8 @@ import torch
 
 from . import _capi
 from ._capi import UavEnvError  # noqa: F401  (re-export)
+from .rewards import TERMS as _REWARD_TERMS
+from .rewards import RewardSpec
 
 _OUT_SPECS = {
     # name: (dtype, shape-builder)
@@ -90,7 +93,7 @@ class BatchedMobiEnv:
     WARMUP_TICKS = 200  # mobile_env.py:77-79
 
     def __init__(self, n_envs, nBS=4, nUE=20, grid_n=100, groups=None, bs_init=None, device=None, seed=0x5EED,
-                 env_id_base=0, f64_outputs=False, construct=True, _cfg=None, **config_overrides):
+                 env_id_base=0, f64_outputs=False, construct=True, _cfg=None, reward=None, **config_overrides):
         if not torch.cuda.is_available():
             raise UavEnvError("BatchedMobiEnv needs a ROCm GPU (gfx950); there is no CPU fallback")
         self._lib = _capi.load()
@@ -135,6 +138,11 @@ class BatchedMobiEnv:
         self._keep = None
         self._many_structs = {}          # step_many: id(out dict) -> (dict, byref(UavEnvOut), T, struct)
         self._constructed = False
+        self.reward = None               # the RewardSpec in force (set_reward), or None: the step's own reward
+        self._reward_ref = None          # byref(UavEnvRewardConfig) of it
+        self.reward_terms = None         # float64 [N, 4]: t0 .. t3 of the last shaped step; a tensor of its own, not in self.out
+        self._terms_many = {}            # T -> float64 [T, N, 4]: the terms of every block of the last multi-step call
+        self.set_reward(reward)
         if construct:
             self.construct()
 
@@ -152,6 +160,100 @@ class BatchedMobiEnv:
 
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
+
+    # ---- selectable rewards (rewards.py; uavenv_shape_reward) ----------------------------------------
+    def set_reward(self, spec):
+        """Choose the reward every later step returns: a ``rewards.RewardSpec``, or None for the step's own
+        max(meanSINR / 20 - nOut / nUE, -1).  With a spec, step / step_range / step_trace / step_seq (its last step) launch ONE more
+        kernel behind the step, and step_many / step_gradient / step_search / step_coordinate one over all their blocks
+        (uavenv_shape_reward): the reward tensor the call writes -- ``self.out["reward"]`` or the caller's ``reward_out``, and
+        ``self.out["reward_f64"]`` where the env has it -- then holds the spec's reward, and ``self.reward_terms`` float64 [N, 4] the
+        terms t0 .. t3 of the last step.  With None every call issues exactly the launches it issues without this feature.
+        The look-ahead policies (gradient_actions, search_actions, coordinate_actions and the decisions inside step_gradient /
+        step_search / step_coordinate) keep valuing the step's OWN reward: their ``rewards`` / ``best_reward`` tables do not know the
+        spec.  rollout_gated computes the step's own reward inside its persistent kernel and refuses to run while a spec is set.
+        A captured graph holds the spec it was captured with."""
+        if spec is None:
+            self.reward, self._reward_ref = None, None
+            return
+        if not isinstance(spec, RewardSpec):
+            raise TypeError("set_reward takes a rewards.RewardSpec or None")
+        self._reward_cfg = spec.to_config()
+        self.reward, self._reward_ref = spec, C.byref(self._reward_cfg)
+        if self.reward_terms is None:
+            self.reward_terms = torch.zeros((self.n_envs, _REWARD_TERMS), dtype=torch.float64, device=self.device)
+
+    def _shape(self, src_struct, n_steps, first_env, n_envs, terms):
+        """The shaping launch behind a step that wrote through ``src_struct`` (a UavEnvOut): its reward members are overwritten."""
+        rc = self._lib.uavenv_shape_reward(self._h, self._reward_ref, C.byref(src_struct), n_steps, first_env, n_envs, src_struct.reward_dev,
+                                           src_struct.reward_f64_dev, terms.data_ptr(), self._stream())
+        if rc:
+            _capi.check(rc)
+
+    def _shape_many(self, src_struct, T):
+        """One shaping launch over the T blocks a multi-step call wrote; ``reward_terms`` takes the last block's terms."""
+        if T <= 0:
+            return
+        terms = self._terms_many.get(T)
+        if terms is None:
+            if len(self._terms_many) > 4:
+                self._terms_many.clear()
+            terms = self._terms_many[T] = torch.zeros((T, self.n_envs, _REWARD_TERMS), dtype=torch.float64, device=self.device)
+        self._shape(src_struct, T, 0, self.n_envs, terms)
+        self.reward_terms.copy_(terms[T - 1])
+
+    def shape_reward(self, spec, src=None, out=None, terms=None, first_env=0, n_envs=None):
+        """The bare uavenv_shape_reward call on tensors of the caller; neither the env's state nor its spec is touched.  ``src``: a dict
+        of device tensors named like ``self.out`` (default: ``self.out``), each [N, ...] or [T, N, ...] as step_many returns them; only
+        ``mean_sinr`` / ``mean_sinr_f64``, ``n_out``, ``cur_sinr`` / ``cur_sinr_f64`` and ``bs_xy`` are read, and only those the spec
+        needs must be there.  ``out``: a dict with ``reward`` (float32) and / or ``reward_f64`` tensors of shape [N] / [T, N] to write --
+        they may be ``src``'s own; default: fresh ones of both.  ``terms``: a float64 [N, 4] / [T, N, 4] tensor, None for a fresh one,
+        False for none.  Only the envs [first_env, first_env + n_envs) are read and written.  Returns ``out`` with ``terms`` added."""
+        if not isinstance(spec, RewardSpec):
+            raise TypeError("shape_reward takes a rewards.RewardSpec")
+        N = self.n_envs
+        src = self.out if src is None else src
+        shapes = {k: shp(N, self.nUE, self.nBS) for k, (dt, shp) in _OUT_SPECS.items()}
+        T = None
+        st = _capi.UavEnvOut()
+        for k, v in src.items():
+            if k not in _OUT_SPECS:
+                raise ValueError("shape_reward: unknown src member %r" % (k,))
+            lead = tuple(v.shape)[:v.dim() - len(shapes[k])]
+            if (v.dtype != _OUT_SPECS[k][0] or v.device != self.device or not v.is_contiguous() or len(lead) > 1
+                    or tuple(v.shape)[len(lead):] != shapes[k] or (T is not None and lead != T)):
+                raise ValueError("shape_reward: src[%r] must be a contiguous %s tensor of shape [T,] %s on the env's device, T the same for all" % (
+                    k, _OUT_SPECS[k][0], list(shapes[k])))
+            T = lead
+            setattr(st, k + "_dev", v.data_ptr())
+        if T is None:
+            raise ValueError("shape_reward: src is empty")
+        n_steps = T[0] if T else 1
+        if out is None:
+            out = {"reward": torch.empty(T + (N,), dtype=torch.float32, device=self.device),
+                   "reward_f64": torch.empty(T + (N,), dtype=torch.float64, device=self.device)}
+        out = dict(out)
+        if terms is None:
+            terms = torch.empty(T + (N, _REWARD_TERMS), dtype=torch.float64, device=self.device)
+        ptr = {}
+        for k, dt, shape in (("reward", torch.float32, T + (N,)), ("reward_f64", torch.float64, T + (N,)), ("terms", torch.float64, T + (N, _REWARD_TERMS))):
+            t = terms if k == "terms" else out.get(k)
+            if t is None or t is False:
+                ptr[k] = None
+                continue
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.device:
+                raise ValueError("shape_reward: %s must be a contiguous %s tensor of shape %s on the env's device" % (k, dt, list(shape)))
+            ptr[k] = t.data_ptr()
+        if set(out) - {"reward", "reward_f64"}:
+            raise ValueError("shape_reward: out may hold 'reward' and 'reward_f64'")
+        cfg = spec.to_config()
+        rc = self._lib.uavenv_shape_reward(self._h, C.byref(cfg), C.byref(st), n_steps, int(first_env), int(N - first_env if n_envs is None else n_envs),
+                                           ptr["reward"], ptr["reward_f64"], ptr["terms"], self._stream())
+        if rc:
+            _capi.check(rc)
+        if terms is not False:
+            out["terms"] = terms
+        return out
 
     # ---- injected randomness (parity tests) --------------------------------------------------------
     def _dev64(self, a, shape):
@@ -252,6 +354,8 @@ class BatchedMobiEnv:
         rc = self._lib.uavenv_step(self._h, a.data_ptr(), inj, out_ref, self._stream())
         if rc:
             _capi.check(rc)
+        if self._reward_ref is not None:
+            self._shape(self._out_struct if reward_out is None else st, 1, 0, self.n_envs, self.reward_terms)
         o = self.out
         if reward_out is not None:
             return self.observation(), reward_out, o["done"], {"mean_sinr": o["mean_sinr"], "n_out": o["n_out"],
@@ -280,6 +384,8 @@ class BatchedMobiEnv:
         rc = self._lib.uavenv_step_range(self._h, a.data_ptr(), int(first_env), int(n_envs), None, out_ref, self._stream())
         if rc:
             _capi.check(rc)
+        if self._reward_ref is not None:
+            self._shape(self._out_struct if reward_out is None else st, 1, int(first_env), int(n_envs), self.reward_terms)
 
     GATE_ROWS = 16          # UAVENV_GATE_ROWS: envs per gate word of rollout_gated
 
@@ -290,6 +396,9 @@ class BatchedMobiEnv:
         launch runs), ``gate_actions`` / ``gate_obs`` int32 [ceil(N / 16)] step counters, ``claim`` int32 [1] (zero before the launch), tables float32 [n_rows, hidden], outputs
         float32 [T, N, hidden] (slot t + 1 written after step t), ``idx_out`` int64 [T + 1, N, B + U], ``reward_out`` float32 [T, N].
         Asynchronous; a partner that never arrives ends in device_error() != 0, not in a hang."""
+        if self.reward is not None:
+            raise UavEnvError("rollout_gated computes the step's own reward inside its persistent kernel and cannot apply the reward %r; "
+                              "use the per-step calls (or set_reward(None))" % (self.reward,))
         T, N = int(actions.shape[0]), self.n_envs
         nb = (N + self.GATE_ROWS - 1) // self.GATE_ROWS
 
@@ -344,6 +453,8 @@ class BatchedMobiEnv:
             stream = self._stream()                      # the capturing stream
             for t in range(int(a.shape[0])):
                 _capi.check(self._lib.uavenv_step(self._h, a[t].data_ptr(), None, self._out_ref, stream))
+                if self._reward_ref is not None:
+                    self._shape(self._out_struct, 1, 0, self.n_envs, self.reward_terms)
         g._uavenv_keep = (a, self)                       # the graph holds raw pointers into both
         return g
 
@@ -356,6 +467,8 @@ class BatchedMobiEnv:
                 and a.dim() == 2 and a.shape[1] == self.n_envs):
             raise ValueError("actions must be a contiguous int64 [T, n_envs] tensor on the env's device")
         _capi.check(self._lib.uavenv_step_seq(self._h, a.data_ptr(), int(a.shape[0]), self._out_ref, self._stream()))
+        if self._reward_ref is not None and int(a.shape[0]) > 0:      # self.out holds the last step's results: that step's reward is shaped
+            self._shape(self._out_struct, 1, 0, self.n_envs, self.reward_terms)
         o = self.out
         return self.observation(), o["reward"], o["done"], {"mean_sinr": o["mean_sinr"], "n_out": o["n_out"],
                                                              "step_n": o["step_n"], "cur_sinr": o["cur_sinr"]}
@@ -423,6 +536,8 @@ class BatchedMobiEnv:
         rc = self._lib.uavenv_step_many(self._h, a.data_ptr(), T, cached[1], self._stream())
         if rc:
             _capi.check(rc)
+        if self._reward_ref is not None:
+            self._shape_many(cached[3], T)
         if T > 0 and refresh_out:                        # (refresh_out=False: self.out goes stale until the next step()/reset())
             for k, v in self.out.items():
                 v.copy_(out[k][T - 1])
@@ -492,6 +607,8 @@ class BatchedMobiEnv:
         rc = fn(self._h, T, actions_out.data_ptr(), C.byref(st), self._stream())
         if rc:
             _capi.check(rc)
+        if self._reward_ref is not None:
+            self._shape_many(st, T)
         if T > 0:
             for k, v in self.out.items():
                 v.copy_(out[k][T - 1])
@@ -667,6 +784,8 @@ class BatchedMobiEnv:
         self._trace_keep = x
         _capi.check(self._lib.uavenv_step_trace(self._h, a.data_ptr(), x.data_ptr(), self._inject(None, None, fading),
                                                 self._out_ref, self._stream()))
+        if self._reward_ref is not None:
+            self._shape(self._out_struct, 1, 0, self.n_envs, self.reward_terms)
         o = self.out
         return self.observation(), o["reward"], o["done"], {"mean_sinr": o["mean_sinr"], "n_out": o["n_out"],
                                                              "step_n": o["step_n"], "cur_sinr": o["cur_sinr"]}
@@ -793,12 +912,16 @@ class BatchedMobiEnv:
         other = BatchedMobiEnv.__new__(BatchedMobiEnv)
         BatchedMobiEnv.__init__(other, self.n_envs, self.nBS, self.nUE, self.grid_n, device=self.device,
                                 seed=self.seed, env_id_base=self.env_id_base,
-                                f64_outputs="cur_sinr_f64" in self.out, construct=False, _cfg=self.cfg)
+                                f64_outputs="cur_sinr_f64" in self.out, construct=False, _cfg=self.cfg, reward=self.reward)
         tmp = torch.empty(self._lay.total_bytes, dtype=torch.uint8, device=self.device)
         _capi.check(self._lib.uavenv_get_state(self._h, tmp.data_ptr(), 1, self._stream()))
         _capi.check(other._lib.uavenv_set_state(other._h, tmp.data_ptr(), 1, self._stream()))
         for k, v in self.out.items():
             other.out[k].copy_(v)
+        if self.reward_terms is not None:
+            if other.reward_terms is None:
+                other.reward_terms = torch.zeros_like(self.reward_terms)
+            other.reward_terms.copy_(self.reward_terms)
         other._constructed = self._constructed
         torch.cuda.current_stream(self.device).synchronize()
         return other

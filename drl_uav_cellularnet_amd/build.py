@@ -12,7 +12,7 @@ import sys
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG_DIR)
 SRC = os.path.join(PKG_DIR, "csrc", "uavenv_capi.hip")
-ENV_SRCS = [SRC] + [os.path.join(PKG_DIR, "csrc", f) for f in ("uavenv_host.hip", "uavenv_gated.hip", "uavenv_gradient.hip", "uavenv_eval.hip", "uavenv_search.hip", "uavenv_rates.hip", "uavenv_coordinate.hip")]     # one object per translation unit: a change to one does not rebuild the others
+ENV_SRCS = [SRC] + [os.path.join(PKG_DIR, "csrc", f) for f in ("uavenv_host.hip", "uavenv_gated.hip", "uavenv_gradient.hip", "uavenv_eval.hip", "uavenv_search.hip", "uavenv_rates.hip", "uavenv_coordinate.hip", "uavenv_reward.hip")]     # one object per translation unit: a change to one does not rebuild the others
 ENV_HDRS = [os.path.join(PKG_DIR, "csrc", f) for f in ("uavenv_kernels.h", "uavenv_handle.h", "philox.h", "lean_math.h", "intdiv.h",
                                                         "state_layout.h")] + [os.path.join(ROOT, "include", "uavenv.h")]
 ENV_EXTRA = {"uavenv_capi.hip": [os.path.join(PKG_DIR, "csrc", "uavenv_path_kernel.h")],

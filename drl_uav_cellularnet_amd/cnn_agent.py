@@ -303,6 +303,7 @@ class CnnA2CRunner(A2CRunner):
         """One rollout: per step conv1 from idx[t] -> conv2 -> conv3 -> dense -> policy head -> action draw -> env.step -> idx[t + 1].
         Returns (idx [T,N,K], actions [T,N], rewards [T,N], bootstrap [N]) -- views valid until the next collect()."""
         env, T = self.env, self.T
+        self._check_reward_spec()
         self.u_buf.copy_(torch.rand(self.u_buf.shape, device=self.dev, dtype=torch.float32, generator=self.gen))
         self._refresh_transposed()
         self.idx_buf[0].copy_(self.idx_buf[T])

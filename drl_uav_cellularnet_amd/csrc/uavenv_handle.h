@@ -4,7 +4,7 @@
 // uavenv_rollout_gated and its kernel instantiations; uavenv_gradient.hip: uavenv_gradient_actions / uavenv_step_gradient and the
 // look-ahead kernels; uavenv_search.hip: uavenv_search_actions / uavenv_step_search and the search kernels; uavenv_coordinate.hip:
 // uavenv_coordinate_actions / uavenv_step_coordinate and their kernels; uavenv_eval.hip: uavenv_eval_accumulate; uavenv_rates.hip:
-// uavenv_link_rates and its kernels -- files of their own so that none rebuilds the others).
+// uavenv_link_rates and its kernels; uavenv_reward.hip: uavenv_shape_reward -- files of their own so that none rebuilds the others).
 // The three policy units share what stands at the end of this file: the call preamble (policy_call), the one launcher of a packed policy
 // kernel (launch_packed_policy; each unit names its kernels in a family type) and the decide-then-step loop (decide_then_step).
 // Every launch site goes from run-time values to a template instantiation through with_bool / with_bt / with_variant below.

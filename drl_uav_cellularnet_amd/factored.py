@@ -397,6 +397,7 @@ class FactoredA2CRunner(A2CRunner):
         the same state (label_buf[t], q_buf[t]), and the env stepped with the teacher's action where u_mix[t] < mix, else the learner's
         (step_buf[t]).  Eager launches, no host synchronisation inside the loop."""
         env, T, N = self.env, self.T, self.env.n_envs
+        self._check_reward_spec()
         self.u_buf.copy_(torch.rand(self.u_buf.shape, device=self.dev, dtype=torch.float32, generator=self.gen))
         self.u_mix.copy_(torch.rand(self.u_mix.shape, device=self.dev, dtype=torch.float32, generator=self.gen))
         from_teacher = self.u_mix < float(mix)

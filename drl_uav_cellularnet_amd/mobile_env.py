@@ -13,6 +13,10 @@ Differences, all deliberate and documented in DESIGN.md:
  * mobility models no reference driver selects are not provided: ``in_coverage`` raises NotImplementedError,
    ``random_waypoint`` is not defined in the reference either (mobile_env.py:73 -> NameError there);
  * rendering (``render`` / ``plot_sinr_map``) is outside the hot path.
+
+Extension: ``reward=`` a ``rewards.RewardSpec`` -- one of the reference's reward functions (reward_functions.py), optionally with the UAV
+separation and collision terms mobile_env.py:172-184 carries commented out.  ``step`` / ``step_test`` then return that reward, and
+``r_dissect`` holds its four terms [t0, t1, t2, t3] (rewards.py); ``done`` is not changed by a collision.
 """
 import copy
 import sys
@@ -61,7 +65,7 @@ class _ChannelView:
 
 class MobiEnvironment:
     def __init__(self, nBS, nUE, grid_n=200, mobility_model="group", test_mobi_file_name="", device=None,
-                 seed=0x5EED, _env=None, _draw_hook=None):
+                 seed=0x5EED, _env=None, _draw_hook=None, reward=None):
         self.nBS, self.nUE = int(nBS), int(nUE)
         self.bs_h = H_BS
         self.grid_n = int(grid_n)
@@ -85,7 +89,7 @@ class MobiEnvironment:
                 raise ValueError("trace must be (T, >=nUE, 2|3) integer cells (mobile_env.py:85-88)")
         self._env = _env if _env is not None else BatchedMobiEnv(
             1, nBS=self.nBS, nUE=self.nUE, grid_n=self.grid_n, device=device, seed=seed, f64_outputs=True,
-            construct=False)
+            construct=False, reward=reward)
         cfg = self._env.cfg
         self.initBsLoc = np.array([[cfg.bs_init_xy[b][0], cfg.bs_init_xy[b][1], self.bs_h] for b in range(self.nBS)],
                                   dtype=np.int64)                     # mobile_env.py:58
@@ -195,7 +199,9 @@ class MobiEnvironment:
         mean_sinr = float(o["mean_sinr_f64"][0])
         n_out = int(o["n_out"][0])
         r_dissect = [mean_sinr / 20, -1.0 * n_out / self.nUE]          # mobile_env.py:163-167
-        reward = float(o["reward_f64"][0])                             # max(sum(r_dissect), -1)  (:189)
+        if self._env.reward is not None:                               # the spec's terms (the stream has been synchronised by _pull)
+            r_dissect = [float(v) for v in self._env.reward_terms[0].cpu().numpy()]
+        reward = float(o["reward_f64"][0])                             # max(sum(r_dissect), -1)  (:189), or the spec's reward
         done = bool(o["done"][0])
         self.association_map = np.array(self.state[1:])
         return r_dissect, reward, done, n_out

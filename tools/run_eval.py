@@ -41,12 +41,12 @@ def make_trace(n_rows=10001, n_ue=40, grid=100, seed=0x7ACE):
     return rows
 
 
-def run_test(trace, out_dir, actor_npz=None, max_step=2000, n_bs=4, n_ue=40, grid=100, seed=0x5EED, area_every=500, net="mlp"):
+def run_test(trace, out_dir, actor_npz=None, max_step=2000, n_bs=4, n_ue=40, grid=100, seed=0x5EED, area_every=500, net="mlp", reward=None):
     from drl_uav_cellularnet_amd import MobiEnvironment
     from drl_uav_cellularnet_amd.agent import ACNet, load_actor_npz, obs_to_indices
 
     os.makedirs(out_dir, exist_ok=True)
-    test_env = MobiEnvironment(n_bs, n_ue, grid, "read_trace", trace, seed=seed)       # main_test.py:51
+    test_env = MobiEnvironment(n_bs, n_ue, grid, "read_trace", trace, seed=seed, reward=reward)       # main_test.py:51
     factored = net in ("cnn-factored", "mlp-factored")
     if factored:                                                                         # one 5-way head per UAV (factored.py)
         from drl_uav_cellularnet_amd.factored import FactoredACNet, FactoredCnnACNet, digits_to_joint
@@ -91,14 +91,14 @@ def run_test(trace, out_dir, actor_npz=None, max_step=2000, n_bs=4, n_ue=40, gri
     return {k: np.array(v) for k, v in buf.items()}
 
 
-def run_batched(n_envs, out_dir, trace=None, actor_npz=None, steps=2000, n_bs=4, n_ue=40, grid=100, seed=0x5EED, area_every=500, net="mlp", rates=False):
+def run_batched(n_envs, out_dir, trace=None, actor_npz=None, steps=2000, n_bs=4, n_ue=40, grid=100, seed=0x5EED, area_every=500, net="mlp", rates=False, reward=None):
     """main_test.py's loop for n_envs envs on the device: GreedyEvaluator.run + the SINR map of env 0 every area_every steps."""
     from drl_uav_cellularnet_amd import BatchedMobiEnv
     from drl_uav_cellularnet_amd.agent import ACNet, load_actor_npz
     from drl_uav_cellularnet_amd.evaluate import GreedyEvaluator
 
     os.makedirs(out_dir, exist_ok=True)
-    env = BatchedMobiEnv(n_envs, nBS=n_bs, nUE=n_ue, grid_n=grid, seed=seed)
+    env = BatchedMobiEnv(n_envs, nBS=n_bs, nUE=n_ue, grid_n=grid, seed=seed, reward=reward)
     if net == "cnn-factored":
         from drl_uav_cellularnet_amd.factored import FactoredCnnACNet
 
@@ -149,7 +149,14 @@ if __name__ == "__main__":
     ap.add_argument("--envs", type=int, default=None, help="evaluate this many envs at once on the device (GreedyEvaluator)")
     ap.add_argument("--traces", default=None, help="with --envs: int16 cells [T+1, N, U, 2] or [T+1, U, 2] (.npy); default: group mobility")
     ap.add_argument("--rates", action="store_true", help="with --envs: also report the link rates (dl_rate.npy / ul_rate.npy)")
+    from drl_uav_cellularnet_amd import rewards
+
+    rewards.add_reward_arguments(ap)                                                     # the reward reported (the greedy policy does not depend on it)
     a = ap.parse_args()
+    try:
+        reward = rewards.spec_from_arguments(a)
+    except ValueError as ex:
+        ap.error(str(ex))
     if a.make_trace:
         np.save(a.make_trace, make_trace(a.trace_rows, n_ue=a.n_ue))
         print("wrote", a.make_trace)
@@ -158,13 +165,13 @@ if __name__ == "__main__":
         src = a.traces or a.trace
         tr = np.load(src, allow_pickle=False).astype(np.int16) if src else None
         t0 = time.time()
-        res = run_batched(a.envs, a.out, tr, a.actor, a.steps, n_bs=a.n_bs, n_ue=a.n_ue, net=a.net, rates=a.rates)
+        res = run_batched(a.envs, a.out, tr, a.actor, a.steps, n_bs=a.n_bs, n_ue=a.n_ue, net=a.net, rates=a.rates, reward=reward)
         dt = time.time() - t0
         print("eval: %d envs x %d steps in %.1f s (%.3g env-steps/s incl. set-up), mean reward %.4f, mean outage fraction %.4f -> %s" % (
             a.envs, a.steps, dt, a.envs * a.steps / dt, float(res["reward"].mean()), float(res["outage_fraction"].mean()), a.out))
         sys.exit(0)
     tr = np.load(a.trace, allow_pickle=False) if a.trace else make_trace(a.steps + 2, n_ue=a.n_ue)
     t0 = time.time()
-    res = run_test(tr, a.out, a.actor, a.steps, n_bs=a.n_bs, n_ue=a.n_ue, net=a.net)
+    res = run_test(tr, a.out, a.actor, a.steps, n_bs=a.n_bs, n_ue=a.n_ue, net=a.net, reward=reward)
     print("eval: %d step_test calls in %.1f s, mean reward %.4f, mean outage fraction %.4f -> %s" % (
         len(res["reward"]), time.time() - t0, float(res["reward"].mean()), float(res["outage_fraction"].mean()), a.out))

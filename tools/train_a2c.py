@@ -78,7 +78,14 @@ def main():
                     "instead of the learner's draw (1 = behaviour cloning, 0 = DAgger)")
     ap.add_argument("--imitate-tau", type=float, default=None, help="temperature of soft targets from the coordinate search's reward table "
                     "(default: hard labels)")
+    from drl_uav_cellularnet_amd import rewards
+
+    rewards.add_reward_arguments(ap)                                       # --reward / --sinr-cap / --sep-threshold / --sep-weight / --collide-threshold
     a = ap.parse_args()
+    try:
+        reward = rewards.spec_from_arguments(a)
+    except ValueError as ex:
+        ap.error(str(ex))
     imitation_flags = a.imitate_episodes != 0 or a.teacher != "coordinate" or a.imitate_mix != 0.5 or a.imitate_tau is not None
     if imitation_flags and a.net != "mlp-factored":
         ap.error("--imitate-episodes / --teacher / --imitate-mix / --imitate-tau are for --net mlp-factored")
@@ -102,7 +109,7 @@ def main():
     from drl_uav_cellularnet_amd.sharding import shard_for_rank
 
     base, _ = shard_for_rank(rank, world, a.workers)
-    env = BatchedMobiEnv(a.workers, nBS=a.n_bs, nUE=a.n_ue, grid_n=a.grid, device=dev, env_id_base=base)
+    env = BatchedMobiEnv(a.workers, nBS=a.n_bs, nUE=a.n_ue, grid_n=a.grid, device=dev, env_id_base=base, reward=reward)
     if a.net == "cnn-factored":
         from drl_uav_cellularnet_amd.factored import FactoredCnnA2CRunner
 
@@ -123,6 +130,10 @@ def main():
     ckpt = os.path.join(a.out, "checkpoint_rank%d.pt" % rank)
     if a.resume:
         sd = torch.load(ckpt, weights_only=True)                           # (a file this tool wrote: tensors and plain scalars only)
+        trained_with = sd.get("reward")                                    # (a checkpoint from before rewards could be chosen has none)
+        trained_with = None if trained_with is None else rewards.RewardSpec.from_dict(trained_with)
+        if trained_with != reward:
+            sys.exit("train_a2c: the checkpoint was trained with the reward %r, this run asks for %r: refusing to resume" % (trained_with, reward))
         runner.load_state_dict(sd["runner"])
         first_ep, returns = int(sd["episode"]) + 1, list(sd["returns"])
         check_ranks_agree(torch, world, dev, first_ep, runner)
@@ -148,7 +159,8 @@ def main():
                     line["agreement"] = agree                               # the teacher agreement of every rollout of the episode
             print(json.dumps(line), flush=True)
         if a.checkpoint_every and (ep + 1) % a.checkpoint_every == 0:
-            save_checkpoint(torch, world, ckpt, {"runner": runner.state_dict(), "episode": ep, "returns": returns})
+            save_checkpoint(torch, world, ckpt, {"runner": runner.state_dict(), "reward": None if reward is None else reward.as_dict(),
+                                                     "episode": ep, "returns": returns})
     if rank == 0:
         os.makedirs(a.out, exist_ok=True)
         np.save(os.path.join(a.out, "Global_return"), np.array([x for x in returns if x is not None], dtype=np.float64))   # :135
