@@ -90,7 +90,7 @@ class UavEnvStateLayout(C.Structure):
 
 
 EXPORTS = ("uavenv_abi_version", "uavenv_last_error", "uavenv_default_config", "uavenv_create", "uavenv_destroy",
-           "uavenv_init", "uavenv_warmup", "uavenv_reset", "uavenv_reset_trace", "uavenv_step", "uavenv_step_range", "uavenv_rollout_gated", "uavenv_gradient_actions", "uavenv_step_gradient", "uavenv_search_actions", "uavenv_step_search", "uavenv_coordinate_actions", "uavenv_step_coordinate", "uavenv_eval_accumulate", "uavenv_default_rate_config", "uavenv_link_rates", "uavenv_default_reward_config", "uavenv_shape_reward", "uavenv_step_many", "uavenv_step_seq", "uavenv_step_trace",
+           "uavenv_init", "uavenv_warmup", "uavenv_reset", "uavenv_reset_trace", "uavenv_step", "uavenv_step_range", "uavenv_rollout_gated", "uavenv_gradient_actions", "uavenv_step_gradient", "uavenv_search_actions", "uavenv_step_search", "uavenv_coordinate_actions", "uavenv_step_coordinate", "uavenv_eval_accumulate", "uavenv_default_rate_config", "uavenv_link_rates", "uavenv_default_reward_config", "uavenv_shape_reward", "uavenv_coordinate_actions_shaped", "uavenv_search_actions_shaped", "uavenv_step_coordinate_shaped", "uavenv_step_search_shaped", "uavenv_debug_shaped_variant_count", "uavenv_debug_shaped_variant_info", "uavenv_debug_shaped_variant_reset", "uavenv_step_many", "uavenv_step_seq", "uavenv_step_trace",
            "uavenv_obs_dense", "uavenv_obs_dense_update", "uavenv_sinr_area", "uavenv_sinr_area_at",
            "uavenv_debug_variant_count", "uavenv_debug_variant_info", "uavenv_debug_variant_reset",
            "uavenv_debug_side_variant_count", "uavenv_debug_side_variant_info", "uavenv_debug_side_variant_reset", "uavenv_debug_rotation_info", "uavenv_debug_path_launches", "uavenv_step_many_prepare", "uavenv_device_error", "uavenv_launch_timing", "uavenv_launch_times_us", "uavenv_debug_schedule",
@@ -143,6 +143,14 @@ def load():
     lib.uavenv_link_rates.argtypes = [_P, C.POINTER(UavEnvRateConfig), C.POINTER(UavEnvRateInject), C.POINTER(UavEnvRates), _P]
     lib.uavenv_default_reward_config.argtypes = [C.POINTER(UavEnvRewardConfig)]
     lib.uavenv_shape_reward.argtypes = [_P, C.POINTER(UavEnvRewardConfig), C.POINTER(UavEnvOut), C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P]
+    _RC = C.POINTER(UavEnvRewardConfig)
+    lib.uavenv_coordinate_actions_shaped.argtypes = [_P, _RC, _P, C.POINTER(UavEnvInject), C.c_int, _P, _P, _P, _P]
+    lib.uavenv_search_actions_shaped.argtypes = [_P, _RC, _P, C.POINTER(UavEnvInject), C.c_int, _P, _P, _P, _P]
+    lib.uavenv_step_coordinate_shaped.argtypes = [_P, _RC, C.c_int, _P, C.POINTER(UavEnvOut), _P]
+    lib.uavenv_step_search_shaped.argtypes = [_P, _RC, C.c_int, _P, C.POINTER(UavEnvOut), _P]
+    lib.uavenv_debug_shaped_variant_count.restype = C.c_int
+    lib.uavenv_debug_shaped_variant_info.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
+    lib.uavenv_debug_shaped_variant_reset.restype = None
     lib.uavenv_step_range.argtypes = [_P, _P, C.c_int64, C.c_int64, C.POINTER(UavEnvInject), C.POINTER(UavEnvOut), _P]
     lib.uavenv_step_many.argtypes = [_P, _P, C.c_int, C.POINTER(UavEnvOut), _P]
     lib.uavenv_step_seq.argtypes = [_P, _P, C.c_int, C.POINTER(UavEnvOut), _P]
@@ -222,6 +230,12 @@ def side_launch_census():
     """The same for the kernels launched outside the env step's dispatch (uavenv_debug_side_variant_info): test hook."""
     lib = load()
     return _census(lib.uavenv_debug_side_variant_count, lib.uavenv_debug_side_variant_info)
+
+
+def shaped_launch_census():
+    """The same for the reward-aware look-ahead kernels (uavenv_debug_shaped_variant_info): test hook."""
+    lib = load()
+    return _census(lib.uavenv_debug_shaped_variant_count, lib.uavenv_debug_shaped_variant_info)
 
 
 def philox4x32_10(ctr, key):

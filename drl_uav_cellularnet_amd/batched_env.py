@@ -170,8 +170,9 @@ class BatchedMobiEnv:
         ``self.out["reward_f64"]`` where the env has it -- then holds the spec's reward, and ``self.reward_terms`` float64 [N, 4] the
         terms t0 .. t3 of the last step.  With None every call issues exactly the launches it issues without this feature.
         The look-ahead policies (gradient_actions, search_actions, coordinate_actions and the decisions inside step_gradient /
-        step_search / step_coordinate) keep valuing the step's OWN reward: their ``rewards`` / ``best_reward`` tables do not know the
-        spec.  rollout_gated computes the step's own reward inside its persistent kernel and refuses to run while a spec is set.
+        step_search / step_coordinate) value the step's OWN reward unless asked otherwise: search_actions, coordinate_actions,
+        step_search and step_coordinate take ``shaped=True`` and then value every candidate under the spec (gradient_actions uses no
+        reward).  rollout_gated computes the step's own reward inside its persistent kernel and refuses to run while a spec is set.
         A captured graph holds the spec it was captured with."""
         if spec is None:
             self.reward, self._reward_ref = None, None
@@ -570,6 +571,15 @@ class BatchedMobiEnv:
             raise ValueError("%s must be a contiguous %s tensor of shape %s on the env's device" % (what, dtype, tuple(shape)))
         return out
 
+    def _shaped_entry(self, fn, fn_shaped, shaped, name):
+        """The C entry of a reward-valuing policy call: ``fn``, or with ``shaped`` ``fn_shaped`` bound to the env's spec."""
+        if not shaped:
+            return fn
+        if self._reward_ref is None:
+            raise ValueError("%s(shaped=True) values candidates under the env's reward spec, and none is set (set_reward)" % name)
+        ref = self._reward_ref
+        return lambda h, *args: fn_shaped(h, ref, *args)
+
     def _lookahead_actions(self, fn, ue_xy, draws, best_reward, table_shape, actions_out=None, table_out=None):
         """search_actions / coordinate_actions: ``fn`` is the C entry, ``draws`` = (theta_u, group_u, fading), ``table_shape`` the per-env
         shape of the reward table or None; ``actions_out`` / ``table_out``: the caller's buffers for the actions and the table (then
@@ -647,27 +657,35 @@ class BatchedMobiEnv:
 
     # ---- the one-step search policy: the best of all joint actions per env -----------------------------
     def search_actions(self, ue_xy=None, theta_u=None, group_u=None, fading=None, best_reward=False, rewards=False, actions_out=None,
-                       table_out=None):
+                       table_out=None, shaped=False):
         """For every env the reward of EACH of the N_ACT ** nBS joint actions on the step the env is about to take, and the first
         maximum, in one launch (uavenv_search_actions).  The env is NOT modified: no state, none of ``self.out``.  ``ue_xy``
         [N, U, 2]: the trace cells of the step (read_trace), else the next mobility tick.  The arithmetic is that of this env's
         own step: the checked variant when the env has float64 outputs or draws are injected, else the fast one.  Returns int64 [N]
         joint actions (the lowest action among equal rewards); with ``best_reward`` also float64 [N]; with ``rewards`` also the
         float64 [N, N_ACT ** nBS] table: ``table[e, a]`` is bit for bit the ``reward_f64`` step(a) would return for env e.
-        ``actions_out`` / ``table_out``: buffers for the actions and (with ``rewards``) the table, so that the call allocates nothing."""
-        return self._lookahead_actions(self._lib.uavenv_search_actions, ue_xy, (theta_u, group_u, fading), best_reward,
+        ``actions_out`` / ``table_out``: buffers for the actions and (with ``rewards``) the table, so that the call allocates nothing.
+        ``shaped=True`` (uavenv_search_actions_shaped): every joint action is valued under the env's reward spec (set_reward; ValueError
+        without one) -- ``table[e, a]`` is then what step(a) followed by the shaping launch would write: bit for bit its ``reward_f64`` on
+        an env with float64 outputs, and rounded to float32 exactly its ``reward`` otherwise (``sinr_capped``: to the rounding of two
+        summation orders)."""
+        fn = self._shaped_entry(self._lib.uavenv_search_actions, self._lib.uavenv_search_actions_shaped, shaped, "search_actions")
+        return self._lookahead_actions(fn, ue_xy, (theta_u, group_u, fading), best_reward,
                                        (self.action_space_dim,) if rewards else None, actions_out, table_out)
 
-    def step_search(self, n_steps, out=None, actions_out=None):
+    def step_search(self, n_steps, out=None, actions_out=None, shaped=False):
         """``n_steps`` x [search_actions(); step(those actions)] issued by one C call (uavenv_step_search; group mobility,
         on-device randomness): every env takes its one-step-optimal action each step.  Returns (actions int64 [T, N], dict of
         [T, ...] tensors as step_many returns); ``self.out`` holds the last step's results.  ``out`` / ``actions_out``: the results
-        of an earlier call with the same T, to be overwritten (no allocation).  Bit-identical to the loop of the two calls."""
-        return self._step_policy(self._lib.uavenv_step_search, "step_search", n_steps, out, actions_out)
+        of an earlier call with the same T, to be overwritten (no allocation).  Bit-identical to the loop of the two calls.
+        ``shaped=True`` (uavenv_step_search_shaped): the decisions are those of search_actions(shaped=True); the rewards returned are
+        shaped after the steps, as with ``shaped=False``."""
+        fn = self._shaped_entry(self._lib.uavenv_step_search, self._lib.uavenv_step_search_shaped, shaped, "step_search")
+        return self._step_policy(fn, "step_search", n_steps, out, actions_out)
 
     # ---- the per-UAV coordinate-search policy: each UAV's best cell in turn, 4 nBS + 1 step values per decision ----
     def coordinate_actions(self, ue_xy=None, theta_u=None, group_u=None, fading=None, best_reward=False, rewards=False, actions_out=None,
-                           table_out=None):
+                           table_out=None, shaped=False):
         """Coordinate ascent over the UAVs of every env, in UAV order, on the step the env is about to take, in one launch
         (uavenv_coordinate_actions): UAV 0 takes the best of its five cells with everybody else staying, UAV 1 its best given UAV
         0's choice, and so on.  The env is NOT modified: no state, none of ``self.out``.  ``ue_xy`` [N, U, 2]: the trace cells of the
@@ -676,16 +694,21 @@ class BatchedMobiEnv:
         Returns int64 [N] joint actions; with ``best_reward`` also float64 [N], bit for bit the ``reward_f64`` step(actions) returns
         and never below the reward of all UAVs staying; with ``rewards`` also the float64 [N, nBS, 5] table: ``table[e, i, d]`` is the
         reward of UAV i taking digit d given the digits chosen before it (heuristics.coordinate_rule states the choice).
-        ``actions_out`` / ``table_out``: buffers for the actions and (with ``rewards``) the table, so that the call allocates nothing."""
-        return self._lookahead_actions(self._lib.uavenv_coordinate_actions, ue_xy, (theta_u, group_u, fading), best_reward,
+        ``actions_out`` / ``table_out``: buffers for the actions and (with ``rewards``) the table, so that the call allocates nothing.
+        ``shaped=True`` (uavenv_coordinate_actions_shaped): every candidate is valued under the env's reward spec (set_reward; ValueError
+        without one); ``best_reward`` and the table then hold shaped values, as search_actions describes."""
+        fn = self._shaped_entry(self._lib.uavenv_coordinate_actions, self._lib.uavenv_coordinate_actions_shaped, shaped, "coordinate_actions")
+        return self._lookahead_actions(fn, ue_xy, (theta_u, group_u, fading), best_reward,
                                        (self.nBS, self.N_ACT) if rewards else None, actions_out, table_out)
 
-    def step_coordinate(self, n_steps, out=None, actions_out=None):
+    def step_coordinate(self, n_steps, out=None, actions_out=None, shaped=False):
         """``n_steps`` x [coordinate_actions(); step(those actions)] issued by one C call (uavenv_step_coordinate; group mobility,
         on-device randomness).  Returns (actions int64 [T, N], dict of [T, ...] tensors as step_many returns); ``self.out`` holds the
         last step's results.  ``out`` / ``actions_out``: the results of an earlier call with the same T, to be overwritten (no
-        allocation).  Bit-identical to the loop of the two calls."""
-        return self._step_policy(self._lib.uavenv_step_coordinate, "step_coordinate", n_steps, out, actions_out)
+        allocation).  Bit-identical to the loop of the two calls.  ``shaped=True`` (uavenv_step_coordinate_shaped): the decisions are
+        those of coordinate_actions(shaped=True); the rewards returned are shaped after the steps, as with ``shaped=False``."""
+        fn = self._shaped_entry(self._lib.uavenv_step_coordinate, self._lib.uavenv_step_coordinate_shaped, shaped, "step_coordinate")
+        return self._step_policy(fn, "step_coordinate", n_steps, out, actions_out)
 
     # ---- evaluation totals (main_test.py:46-113 for a whole batch) ------------------------------------
     def eval_accumulators(self, hist=(-50.0, 100.0, 150)):

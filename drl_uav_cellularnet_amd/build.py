@@ -12,14 +12,16 @@ import sys
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG_DIR)
 SRC = os.path.join(PKG_DIR, "csrc", "uavenv_capi.hip")
-ENV_SRCS = [SRC] + [os.path.join(PKG_DIR, "csrc", f) for f in ("uavenv_host.hip", "uavenv_gated.hip", "uavenv_gradient.hip", "uavenv_eval.hip", "uavenv_search.hip", "uavenv_rates.hip", "uavenv_coordinate.hip", "uavenv_reward.hip")]     # one object per translation unit: a change to one does not rebuild the others
+ENV_SRCS = [SRC] + [os.path.join(PKG_DIR, "csrc", f) for f in ("uavenv_host.hip", "uavenv_gated.hip", "uavenv_gradient.hip", "uavenv_eval.hip", "uavenv_search.hip", "uavenv_rates.hip", "uavenv_coordinate.hip", "uavenv_reward.hip", "uavenv_shaped.hip")]     # one object per translation unit: a change to one does not rebuild the others
 ENV_HDRS = [os.path.join(PKG_DIR, "csrc", f) for f in ("uavenv_kernels.h", "uavenv_handle.h", "philox.h", "lean_math.h", "intdiv.h",
                                                         "state_layout.h")] + [os.path.join(ROOT, "include", "uavenv.h")]
+_SHAPED_H = os.path.join(PKG_DIR, "csrc", "uavenv_shaped.h")      # the shape axis of the search and coordinate bodies
 ENV_EXTRA = {"uavenv_capi.hip": [os.path.join(PKG_DIR, "csrc", "uavenv_path_kernel.h")],
              "uavenv_gated.hip": [os.path.join(PKG_DIR, "csrc", f) for f in ("uavenv_gated_kernel.h", "rollout_gate.h")],
              "uavenv_gradient.hip": [os.path.join(PKG_DIR, "csrc", "uavenv_gradient_kernel.h")],
-             "uavenv_search.hip": [os.path.join(PKG_DIR, "csrc", "uavenv_search_kernel.h")],
-             "uavenv_coordinate.hip": [os.path.join(PKG_DIR, "csrc", f) for f in ("uavenv_coordinate_kernel.h", "uavenv_search_kernel.h")],
+             "uavenv_search.hip": [os.path.join(PKG_DIR, "csrc", "uavenv_search_kernel.h"), _SHAPED_H],
+             "uavenv_coordinate.hip": [os.path.join(PKG_DIR, "csrc", f) for f in ("uavenv_coordinate_kernel.h", "uavenv_search_kernel.h")] + [_SHAPED_H],
+             "uavenv_shaped.hip": [os.path.join(PKG_DIR, "csrc", f) for f in ("uavenv_shaped_kernel.h", "uavenv_coordinate_kernel.h", "uavenv_search_kernel.h")] + [_SHAPED_H],
              "uavenv_rates.hip": [os.path.join(PKG_DIR, "csrc", "uavenv_rates_kernel.h")]}      # headers of one translation unit only
 DEPS = ENV_SRCS + ENV_HDRS + [h for hs in ENV_EXTRA.values() for h in hs]
 LIB_DIR = os.path.join(PKG_DIR, "lib")

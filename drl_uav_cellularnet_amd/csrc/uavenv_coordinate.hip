@@ -32,7 +32,7 @@ static bool launch_coordinate_multipass(const uavenv_t *h, const KParams &p, con
 }
 
 // Everything a handle must be for the policy, tested before any HIP call.  `who`: the entry point named in the message.
-static int coordinate_refuses(const uavenv_t *h, const char *who) {
+int uavenv_internal::coordinate_refuses(const uavenv_t *h, const char *who) {
     const std::string w(who);
     if (h->cfg.n_act != 5)
         return fail(UAVENV_E_INVALID, w + ": the five candidate cells of a UAV (stay, +-bs_step in x or y) are those of n_act == 5 (ue_mobility.py:221-235)");

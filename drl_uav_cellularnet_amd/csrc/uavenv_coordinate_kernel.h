@@ -18,6 +18,7 @@
 namespace uavk {
 
 struct CoordArgs {
+    static constexpr bool kOn = false;   // (the shape axis of the multi-pass kernel: ShapedCoordArgs below)
     long long *actions_out;   // [N]        sum c_b 5^(B-1-b)
     double *best_reward;      // [N]        the reward of that joint action, or null
     double *rewards;          // [N, B, 5]  row i: UAV i's five digits given the rows before it, or null
@@ -35,11 +36,12 @@ __device__ __forceinline__ int coordinate_choice(const double (&r)[4], double &b
 // ---- packed family: search_body's phases 1 and 2, phase 3 as B rounds of four candidates ------------------------------------------
 // Every lane holds its env's cells and its walker's powers in registers, as in the search; the head lane's choice goes to the lanes of
 // its slot by one shuffle per round (the sums are valid on the head lane only).
-template <int BT, bool PLC, bool FAST, bool PRE>
+// SH (uavenv_shaped.h): NoShape = the step's own reward; PairTable<BT> = the value under a UavEnvRewardConfig (uavenv_coordinate_actions_shaped).
+template <int BT, bool PLC, bool FAST, bool PRE, class SH = NoShape>
 __device__ __forceinline__ void coordinate_body(const KParams &p, const HotConst &H, const LeanCoef &C, const FinConst &K, const CoordArgs &ca, int U,
                                                 int base, int ul, bool live, bool head, long long e, uint32_t tick, int u, long long iu, int ix, int iy,
                                                 const int (&bsx)[BT], const int (&bsy)[BT], const U4 &q0, const U4 &q1, int serving,
-                                                unsigned long long prev_out, unsigned long long slot_mask) {
+                                                unsigned long long prev_out, unsigned long long slot_mask, const SH &sh = SH()) {
     const int B = uav_count<BT, FAST>(p.B);
     const int bstep = p.bs_step;
     // phase 2 (as search_body): pcK[b] = power of UAV b on the cell digit K proposes from its PRESENT cell -- UAV b has not moved before its
@@ -48,11 +50,21 @@ __device__ __forceinline__ void coordinate_body(const KParams &p, const HotConst
     candidate_powers<BT, PLC, FAST, PRE>(p, H, C, e, tick, u, live, iu, ix, iy, bsx, bsy, q0, q1, pc0, pc1, pc2, pc3, pg);
     // The step's reward for the powers g; valid on the slot's first lane.  (search_body states the same four lines in its loop: one helper for
     // both raises the VGPR count of one of the two families, whichever form it takes -- profiles/policy_fold_listings.txt.)
+    [[maybe_unused]] int kd[BT];                             // shaped: the digit every UAV stands on in the candidate being valued
+#pragma unroll
+    for (int b = 0; b < BT; ++b) kd[b] = 4;
     auto value = [&](const double (&g)[BT]) -> double {
         const double cur = sinr_db<BT, FAST>(p, H, C, g, serving);                             // serving UAV BEFORE any handover (channel.py:145-146)
         const unsigned long long ob = (__ballot(live && (cur <= H.out_thr)) & slot_mask) >> base;   // :170
         const int n_outage = __popcll(ob & ~prev_out);                                          // :171-174 newly outaged
-        return step_reward(K, slot_sum(live ? cur : 0.0, ul, U), n_outage);
+        if constexpr (SH::kOn) {
+            double S;
+            bool hit;
+            sh.pairs(kd, S, hit);
+            return shaped_reward(sh.a, U, K.inv_U, slot_sum(live ? shaped_addend(sh.a, cur) : 0.0, ul, U), n_outage, S, hit);
+        } else {
+            return step_reward(K, slot_sum(live ? cur : 0.0, ul, U), n_outage);
+        }
     };
 
     // phase 3: the rounds
@@ -83,6 +95,7 @@ __device__ __forceinline__ void coordinate_body(const KParams &p, const HotConst
                 const int moved = (kx != 0) ? cx[i] + kx * bstep : cy[i] + ky * bstep;
                 const bool go = free_i && ((uint32_t)(moved - 2) < (uint32_t)(p.G - 2));        // bs_move_serial's `inside`: 1 < moved < G
                 pg[i] = d == 0 ? pc0[i] : (d == 1 ? pc1[i] : (d == 2 ? pc2[i] : pc3[i]));
+                if constexpr (SH::kOn) kd[i] = d;
                 const double v = value(pg);
                 r[d] = go ? v : stay;                        // a refused move is "stay"
             }
@@ -94,6 +107,7 @@ __device__ __forceinline__ void coordinate_body(const KParams &p, const HotConst
                 row[0] = r[0]; row[1] = r[1]; row[2] = r[2]; row[3] = r[3]; row[4] = stay;
             }
             c = __shfl(c, base, 64);                         // the head lane's choice, for every lane of its env
+            if constexpr (SH::kOn) kd[i] = c;
             const uint32_t sh = 3u * (uint32_t)c;
             cx[i] += ((int)((kDigitLutX >> sh) & 7u) - 2) * bstep;      // c is 4 or an accepted move
             cy[i] += ((int)((kDigitLutY >> sh) & 7u) - 2) * bstep;
@@ -159,9 +173,22 @@ __device__ __forceinline__ double coord_metres(int cell, double gw) {
 }
 constexpr int kCoordMaxBs = 16, kCoordMaxUe = 256;
 __host__ __device__ constexpr size_t coordinate_lds_bytes(int U, int B) { return (size_t)U * B * sizeof(double) + (size_t)U * sizeof(int2); }
+// Shaped (SH = WaveShape, uavenv_coordinate_actions_shaped): behind pw and wi, M[B][B] = the separation terms of the cells as the rounds have
+// moved them (symmetric, +0.0 on the diagonal) and R[4][B] = row i of the round's four candidates: 2.5 KB more at B = 16, 29 760 bytes at
+// 16 x 200, so five envs still share a CU's 160 KiB.  Lane r < B keeps the collision bits of row r (hrow).  Round i: lane j takes the root and
+// the division of pair (i, j) for the (up to) four cells -- the B - 1 pairs that change -- then lane l adds the B x B terms of candidate l & 3
+// in Get_loc_penalty's order, row and column i read from R: four chains side by side, one addition each per step.
+// The multi-pass body is instantiated on the type of its arguments: CoordArgs (env_kernel_coordinate, the kernel as it was) or ShapedCoordArgs
+// (env_kernel_coordinate_shaped).
+struct ShapedCoordArgs : CoordArgs {
+    static constexpr bool kOn = true;
+    ShapeArgs a;
+};
+__host__ __device__ constexpr size_t coordinate_shaped_lds_bytes(int U, int B) { return coordinate_lds_bytes(U, B) + (size_t)(B * B + 4 * B) * sizeof(double); }
 
-template <int MODE, bool PLC>
-__global__ __launch_bounds__(64) void env_kernel_coordinate(const CoordArgs ca, const KParams p) {
+template <int MODE, bool PLC, class SH>
+__device__ __forceinline__ void coordinate_multipass_body(const SH &ca, const KParams &p) {
+    [[maybe_unused]] const SH &sh = ca;
     static_assert(MODE == MODE_STEP || MODE == MODE_TRACE, "the policy looks one step ahead: group mobility or trace cells");
     extern __shared__ double coord_lds[];
     const StatePtrs st = state_from_params(p);
@@ -180,6 +207,9 @@ __global__ __launch_bounds__(64) void env_kernel_coordinate(const CoordArgs ca, 
     const int IT = tail_items(U, B);
     double *const pw = coord_lds;                          // [B][U]
     int2 *const wi = reinterpret_cast<int2 *>(coord_lds + (size_t)B * U);   // [U] {ix | iy << 16, serving | stored outage bit << 8}
+    [[maybe_unused]] double *const pm = coord_lds + (size_t)B * U + U;      // shaped: M [B][B]
+    [[maybe_unused]] double *const pr = pm + B * B;                         // shaped: R [4][B]
+    [[maybe_unused]] unsigned hrow = 0u;                                    // shaped, lane r < B: bit j = pair (r, j) is inside the collision threshold
 
     const EnvRec erec = st.env[e];
     const uint32_t tick = erec.tick;                       // the Philox time of the step's draws
@@ -254,6 +284,17 @@ __global__ __launch_bounds__(64) void env_kernel_coordinate(const CoordArgs ca, 
             }
         }
     }
+    if constexpr (SH::kOn) {                               // M and hrow of the present cells: lane r fills row r
+        for (int j = 0; j < B; ++j) {
+            double pv;
+            bool hit;
+            shaped_pair(sh.a.cfg, (double)U, cx - __shfl(cx, j, 64), cy - __shfl(cy, j, 64), pv, hit);
+            if (lane < B) {
+                pm[lane * B + j] = (j == lane) ? 0.0 : pv;
+                if (hit && j != lane) hrow |= 1u << j;
+            }
+        }
+    }
     __syncthreads();
 
     // ---- phase 3: round -1 values "every UAV stays"; round i = UAV i's four moves given the rounds before it ----------------------
@@ -277,6 +318,41 @@ __global__ __launch_bounds__(64) void env_kernel_coordinate(const CoordArgs ca, 
         }
         double sum[4] = {0.0, 0.0, 0.0, 0.0};
         int nout[4] = {0, 0, 0, 0};
+        [[maybe_unused]] double S[4] = {0.0, 0.0, 0.0, 0.0};
+        [[maybe_unused]] unsigned long long hb[4] = {0ull, 0ull, 0ull, 0ull};   // candidate d: the UAVs inside the collision threshold of UAV i
+        [[maybe_unused]] bool hit_rest = false;                                  // a pair without UAV i is inside it
+        if constexpr (SH::kOn) {
+            if (mv != 0u) {
+                if (i >= 0) {
+#pragma unroll
+                    for (int d = 0; d < 4; ++d) {
+                        if (mv & (1u << d)) {              // uniform
+                            double pv;
+                            bool hit;
+                            shaped_pair(sh.a.cfg, (double)U, ncx[d] - cx, ncy[d] - cy, pv, hit);
+                            if (lane < B) pr[d * B + lane] = (lane == i) ? 0.0 : pv;
+                            hb[d] = __ballot(lane < B && lane != i && hit);
+                        }
+                    }
+                    __syncthreads();
+                }
+                const int dd = lane & 3;
+                double Sl = 0.0;
+                for (int r = 0; r < B; ++r) {              // ue_mobility.py:361-370: i major, j minor
+                    double v[kCoordMaxBs];                 // a row's reads go out together; the additions then wait for one round trip, not B
+#pragma unroll
+                    for (int c = 0; c < kCoordMaxBs; ++c) {
+                        const double *src = (r == i) ? pr + dd * B + c : ((c == i) ? pr + dd * B + r : pm + r * B + c);
+                        v[c] = (c < B) ? *(c < B ? src : pm) : 0.0;    // +0.0 beyond B: no bit of S changes
+                    }
+#pragma unroll
+                    for (int c = 0; c < kCoordMaxBs; ++c) Sl = Sl + v[c];
+                }
+#pragma unroll
+                for (int d = 0; d < 4; ++d) S[d] = __shfl(Sl, d, 64);
+                hit_rest = __ballot(lane < B && lane != i && (hrow & ~(i >= 0 ? 1u << i : 0u)) != 0u) != 0ull;
+            }
+        }
         if (mv != 0u) {
             for (int pass = 0; pass < n_pass; ++pass) {
                 const bool item = (IT != 0) && (pass == n_full);
@@ -324,15 +400,23 @@ __global__ __launch_bounds__(64) void env_kernel_coordinate(const CoordArgs ca, 
                         const double psd = (i == serving) ? g[d] : ps;
                         const double cur = H.db_per_ln * lm_logc(lm_div(psd, H.noise + o[d]), C);   // channel.py:259-268
                         nout[d] += __popcll(__ballot(owner && (cur <= H.out_thr) && !was_out));      // :170-174 newly outaged
-                        sum[d] += wave_sum(owner ? cur : 0.0);
+                        if constexpr (SH::kOn) sum[d] += wave_sum(owner ? shaped_addend(sh.a, cur) : 0.0);
+                        else sum[d] += wave_sum(owner ? cur : 0.0);
                     }
                 }
             }
         }
-        if (i < 0) { stay = step_reward(K, sum[0], nout[0]); continue; }
         double r[4];
+        if constexpr (SH::kOn) {
+            if (i < 0) { stay = shaped_reward(sh.a, U, K.inv_U, sum[0], nout[0], S[0], hit_rest); continue; }
 #pragma unroll
-        for (int d = 0; d < 4; ++d) r[d] = (mv & (1u << d)) ? step_reward(K, sum[d], nout[d]) : stay;   // a refused move is "stay"
+            for (int d = 0; d < 4; ++d)
+                r[d] = (mv & (1u << d)) ? shaped_reward(sh.a, U, K.inv_U, sum[d], nout[d], S[d], hit_rest || hb[d] != 0ull) : stay;
+        } else {
+            if (i < 0) { stay = step_reward(K, sum[0], nout[0]); continue; }
+#pragma unroll
+            for (int d = 0; d < 4; ++d) r[d] = (mv & (1u << d)) ? step_reward(K, sum[d], nout[d]) : stay;   // a refused move is "stay"
+        }
         double best = stay;
         const int c = __builtin_amdgcn_readfirstlane(coordinate_choice(r, best));
         if (lane == 0 && ca.rewards != nullptr) {
@@ -344,6 +428,15 @@ __global__ __launch_bounds__(64) void env_kernel_coordinate(const CoordArgs ca, 
             const int wy = c == 0 ? ncy[0] : (c == 1 ? ncy[1] : (c == 2 ? ncy[2] : ncy[3]));
             if (lane == i) { cx = wx; cy = wy; }
             __syncthreads();                               // the round's reads of column i are done
+            if constexpr (SH::kOn) {                       // row and column i of M, and the collision bits, become the winner's
+                const unsigned long long hw = c == 0 ? hb[0] : (c == 1 ? hb[1] : (c == 2 ? hb[2] : hb[3]));
+                if (lane < B) {
+                    const double pv = pr[c * B + lane];
+                    pm[i * B + lane] = pv;
+                    pm[lane * B + i] = pv;
+                    hrow = (lane == i) ? (unsigned)hw : ((hrow & ~(1u << i)) | ((unsigned)((hw >> lane) & 1ull) << i));
+                }
+            }
             for (int pass = 0; pass < n_pass; ++pass) {
                 const int u = pass * 64 + lane;
                 const bool act = u < U;
@@ -363,6 +456,15 @@ __global__ __launch_bounds__(64) void env_kernel_coordinate(const CoordArgs ca, 
         ca.actions_out[e] = (long long)a;
         if (ca.best_reward != nullptr) ca.best_reward[e] = stay;
     }
+}
+
+template <int MODE, bool PLC>
+__global__ __launch_bounds__(64) void env_kernel_coordinate(const CoordArgs ca, const KParams p) {
+    coordinate_multipass_body<MODE, PLC, CoordArgs>(ca, p);
+}
+template <int MODE, bool PLC>
+__global__ __launch_bounds__(64) void env_kernel_coordinate_shaped(const ShapedCoordArgs ca, const KParams p) {
+    coordinate_multipass_body<MODE, PLC, ShapedCoordArgs>(ca, p);
 }
 
 }  // namespace uavk

@@ -4,7 +4,8 @@
 // uavenv_rollout_gated and its kernel instantiations; uavenv_gradient.hip: uavenv_gradient_actions / uavenv_step_gradient and the
 // look-ahead kernels; uavenv_search.hip: uavenv_search_actions / uavenv_step_search and the search kernels; uavenv_coordinate.hip:
 // uavenv_coordinate_actions / uavenv_step_coordinate and their kernels; uavenv_eval.hip: uavenv_eval_accumulate; uavenv_rates.hip:
-// uavenv_link_rates and its kernels; uavenv_reward.hip: uavenv_shape_reward -- files of their own so that none rebuilds the others).
+// uavenv_link_rates and its kernels; uavenv_reward.hip: uavenv_shape_reward; uavenv_shaped.hip: the reward-aware look-aheads
+// uavenv_*_actions_shaped / uavenv_step_*_shaped, their kernels and their census -- files of their own so that none rebuilds the others).
 // The three policy units share what stands at the end of this file: the call preamble (policy_call), the one launcher of a packed policy
 // kernel (launch_packed_policy; each unit names its kernels in a family type) and the decide-then-step loop (decide_then_step).
 // Every launch site goes from run-time values to a template instantiation through with_bool / with_bt / with_variant below.
@@ -117,6 +118,11 @@ constexpr bool side_has_fast(int fam, int bt) {
 }
 bool side_variant_selectable(int fam, int bt, int mode, bool plc, bool fast, int kt, bool two);
 bool side_census_count(int fam, int bt, int mode, bool plc, bool fast, int kt, bool two);
+// What the reward-valuing policies and the entry points that take a UavEnvRewardConfig refuse, before any HIP call (uavenv_coordinate.hip,
+// uavenv_search.hip, uavenv_reward.hip); shared with the shaped entry points of uavenv_shaped.hip.  `who`: the entry point named in the message.
+int coordinate_refuses(const uavenv *h, const char *who);
+int search_refuses(const uavenv *h, const char *who);
+int reward_config_refuses(const UavEnvRewardConfig *cfg, const char *who);
 }  // namespace uavenv_internal
 
 #define HIP_TRY(expr)                                                                              \

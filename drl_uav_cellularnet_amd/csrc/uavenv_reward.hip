@@ -136,15 +136,22 @@ extern "C" int uavenv_default_reward_config(UavEnvRewardConfig *cfg) {
     return UAVENV_OK;
 }
 
+// What every entry point that takes a UavEnvRewardConfig refuses about it, before any HIP call.  `who`: the entry point named in the message.
+int uavenv_internal::reward_config_refuses(const UavEnvRewardConfig *cfg, const char *who) {
+    const std::string w(who);
+    if (cfg->kind < REW_INITIAL || cfg->kind > REW_SINR_CAPPED) return fail(UAVENV_E_INVALID, w + ": kind must be 0 (initial), 1 (perfect), 2 (outage) or 3 (sinr_capped)");
+    for (double v : {cfg->floor, cfg->sinr_div, cfg->sinr_cap, cfg->cap_div, cfg->sep_threshold, cfg->sep_weight, cfg->collide_threshold, cfg->collide_penalty})
+        if (!std::isfinite(v)) return fail(UAVENV_E_INVALID, w + ": every parameter of UavEnvRewardConfig must be finite");
+    if (cfg->kind == REW_SINR_CAPPED && cfg->cap_div == 0.0) return fail(UAVENV_E_INVALID, w + ": sinr_capped needs cap_div != 0");
+    if (cfg->kind == REW_INITIAL && cfg->sinr_div == 0.0) return fail(UAVENV_E_INVALID, w + ": initial needs sinr_div != 0");
+    return UAVENV_OK;
+}
+
 extern "C" int uavenv_shape_reward(uavenv_t *h, const UavEnvRewardConfig *cfg, const UavEnvOut *src, int n_steps, int64_t first_env, int64_t n_envs,
                                    float *reward_dev, double *reward_f64_dev, double *terms_dev, void *stream) {
     if (!h || !cfg || !src) return fail(UAVENV_E_INVALID, "shape_reward: null handle, cfg or src");
     if (!reward_dev && !reward_f64_dev && !terms_dev) return fail(UAVENV_E_INVALID, "shape_reward: no output (reward_dev, reward_f64_dev and terms_dev are all null)");
-    if (cfg->kind < REW_INITIAL || cfg->kind > REW_SINR_CAPPED) return fail(UAVENV_E_INVALID, "shape_reward: kind must be 0 (initial), 1 (perfect), 2 (outage) or 3 (sinr_capped)");
-    for (double v : {cfg->floor, cfg->sinr_div, cfg->sinr_cap, cfg->cap_div, cfg->sep_threshold, cfg->sep_weight, cfg->collide_threshold, cfg->collide_penalty})
-        if (!std::isfinite(v)) return fail(UAVENV_E_INVALID, "shape_reward: every parameter of UavEnvRewardConfig must be finite");
-    if (cfg->kind == REW_SINR_CAPPED && cfg->cap_div == 0.0) return fail(UAVENV_E_INVALID, "shape_reward: sinr_capped needs cap_div != 0");
-    if (cfg->kind == REW_INITIAL && cfg->sinr_div == 0.0) return fail(UAVENV_E_INVALID, "shape_reward: initial needs sinr_div != 0");
+    if (int rc = uavenv_internal::reward_config_refuses(cfg, "shape_reward")) return rc;
     if (n_steps < 1 || n_steps > 65535) return fail(UAVENV_E_INVALID, "shape_reward: n_steps must lie in [1, 65535]");
     const bool uav_terms = cfg->sep_threshold > 0.0 || cfg->collide_threshold >= 0.0;
     if ((!src->mean_sinr_dev && !src->mean_sinr_f64_dev) || !src->n_out_dev) return fail(UAVENV_E_INVALID, "shape_reward: src needs mean_sinr (float32 or float64) and n_out");

@@ -13,6 +13,7 @@ using uavenv_internal::decide_then_step;
 using uavenv_internal::wants_f64;
 using uavenv_internal::kSearchMaxBs;
 using uavenv_internal::SIDE_SEARCH;
+using uavenv_internal::search_refuses;
 
 // n_bs <= 6 (kSearchMaxBs): the template bound is 4 or 8, and no handle has n_bs == 8: that bound has no fast kernel
 struct SearchFamily {
@@ -23,7 +24,7 @@ struct SearchFamily {
 };
 
 // Everything a handle must be for the search, tested before any HIP call.  `who`: the entry point named in the message.
-static int search_refuses(const uavenv_t *h, const char *who) {
+int uavenv_internal::search_refuses(const uavenv_t *h, const char *who) {
     const std::string w(who);
     if (!h->packed || h->cfg.n_ue > 64 || h->N > 0x7FFFFFFFll)
         return fail(UAVENV_E_INVALID, w + ": built for the packed kernels (n_ue <= 64, n_ue >= n_bs and n_groups); a multi-pass handle is searched "

@@ -15,6 +15,7 @@
 // Layout: that of the packed kernels -- one wavefront per EPW envs, one lane per walker, UAV cells in registers (B <= 6 here, so BT <= 8).
 #pragma once
 #include "uavenv_kernels.h"
+#include "uavenv_shaped.h"
 
 namespace uavk {
 
@@ -106,11 +107,13 @@ __device__ __forceinline__ void candidate_powers(const KParams &p, const HotCons
     }
 }
 
-template <int BT, bool PLC, bool FAST, bool PRE>
+// SH (uavenv_shaped.h): NoShape = the step's own reward; PairTable<BT> = the value under a UavEnvRewardConfig (uavenv_search_actions_shaped).
+template <int BT, bool PLC, bool FAST, bool PRE, class SH = NoShape>
 __device__ __forceinline__ void search_body(const KParams &p, const HotConst &H, const LeanCoef &C, const FinConst &K, const SearchArgs &sa, SearchLds &L,
                                             int U, int EPW, int lane, int slot, int base, int ul, bool live, bool head, long long ew, int e_lo, int e_hi,
                                             long long e, uint32_t tick, int u, long long iu, int ix, int iy, const int (&bsx)[BT], const int (&bsy)[BT],
-                                            const U4 &q0, const U4 &q1, int serving, unsigned long long prev_out, unsigned long long slot_mask) {
+                                            const U4 &q0, const U4 &q1, int serving, unsigned long long prev_out, unsigned long long slot_mask,
+                                            const SH &sh = SH()) {
     double pc0[BT], pc1[BT], pc2[BT], pc3[BT], pc4[BT];                                      // phase 2
     candidate_powers<BT, PLC, FAST, PRE>(p, H, C, e, tick, u, live, iu, ix, iy, bsx, bsy, q0, q1, pc0, pc1, pc2, pc3, pc4);
 
@@ -138,8 +141,22 @@ __device__ __forceinline__ void search_body(const KParams &p, const HotConst &H,
         const double cur = sinr_db<BT, FAST>(p, H, C, pg, serving);                         // serving UAV BEFORE any handover (channel.py:145-146)
         const unsigned long long ob = (__ballot(live && (cur <= H.out_thr)) & slot_mask) >> base;   // :170
         const int n_outage = __popcll(ob & ~prev_out);                                      // :171-174 newly outaged
-        const double sum_cur = slot_sum(live ? cur : 0.0, ul, U);
-        const double reward = step_reward(K, sum_cur, n_outage);                            // valid on the slot's first lane
+        const double sum_cur = slot_sum(live ? sum_addend(sh, cur) : 0.0, ul, U);
+        double reward;                                                                      // valid on the slot's first lane
+        if constexpr (SH::kOn) {
+            int k[BT];                                   // the digit every UAV landed on (a refused move: 4)
+#pragma unroll
+            for (int b = 0; b < BT; ++b) {
+                const int kx = nx[b] - bsx[b], ky = ny[b] - bsy[b];
+                k[b] = (kx > 0) ? 0 : ((kx < 0) ? 1 : ((ky > 0) ? 2 : ((ky < 0) ? 3 : 4)));
+            }
+            double S;
+            bool hit;
+            sh.pairs(k, S, hit);
+            reward = shaped_reward(sh.a, U, K.inv_U, sum_cur, n_outage, S, hit);
+        } else {
+            reward = step_reward(K, sum_cur, n_outage);
+        }
         if (reward > best) { best = reward; best_a = a; }
         if (table) {
             // The [N, A] table: the head lanes park their rewards in LDS; every kSearchChunk actions the wavefront stores each env's run

@@ -374,15 +374,17 @@ class FactoredA2CRunner(A2CRunner):
             e.record()
             self._imit_marks.append((phase, e))
 
-    def _teach(self, teacher, t, tau):
-        """The teacher's decision for the state the env is in, into label_buf[t]; with ``tau`` also its soft targets into q_buf[t]."""
+    def _teach(self, teacher, t, tau, shaped=False):
+        """The teacher's decision for the state the env is in, into label_buf[t]; with ``tau`` also its soft targets into q_buf[t].
+        ``shaped``: the teacher values its candidates under the env's reward spec."""
         env, net = self.env, self.net
+        kw = {"shaped": True} if shaped else {}
         if callable(teacher):
             self.label_buf[t].copy_(torch.as_tensor(teacher(env), dtype=torch.int64).reshape(-1))
         elif tau is None:
-            getattr(env, teacher + "_actions")(actions_out=self.label_buf[t])
+            getattr(env, teacher + "_actions")(actions_out=self.label_buf[t], **kw)
         else:
-            env.coordinate_actions(rewards=True, actions_out=self.label_buf[t], table_out=self._table_buf)
+            env.coordinate_actions(rewards=True, actions_out=self.label_buf[t], table_out=self._table_buf, **kw)
             self._mark("teacher")
             if self.dev.type == "cuda":
                 from . import _agent_capi as A
@@ -392,7 +394,7 @@ class FactoredA2CRunner(A2CRunner):
                 self.q_buf[t].copy_(soft_targets(self._table_buf, tau).reshape(-1, net.n_action))
 
     @torch.no_grad()
-    def _imitate_collect(self, teacher, mix, tau):
+    def _imitate_collect(self, teacher, mix, tau, shaped=False):
         """collect() with a teacher beside the learner: per step the learner's forward pass and draw (act_buf[t]), the teacher's decision for
         the same state (label_buf[t], q_buf[t]), and the env stepped with the teacher's action where u_mix[t] < mix, else the learner's
         (step_buf[t]).  Eager launches, no host synchronisation inside the loop."""
@@ -412,7 +414,7 @@ class FactoredA2CRunner(A2CRunner):
             else:
                 self.act_buf[t] = self._draw_reference(t)
             self._mark("learner")
-            self._teach(teacher, t, tau)
+            self._teach(teacher, t, tau, shaped)
             self._mark("teacher" if tau is None else "soft_targets")
             torch.where(from_teacher[t], self.label_buf[t], self.act_buf[t], out=self.step_buf[t])
             env.step(self.step_buf[t], reward_out=self.rew_buf[t])
@@ -424,16 +426,24 @@ class FactoredA2CRunner(A2CRunner):
         self._fwd_valid = self._fwd is not None
         return self._end_rollout(done, any_done)
 
-    def imitate_rollout(self, teacher="coordinate", mix=0.5, tau=None):
+    def imitate_rollout(self, teacher="coordinate", mix=0.5, tau=None, shaped_teacher=False):
         """One rollout and one update of the supervised phase: the actor learns the teacher's decisions (cross entropy per UAV, the entropy
         bonus kept) on the states of a trajectory that follows the teacher with probability ``mix`` per (step, env) and the learner's own
         draw otherwise -- mix = 1: behaviour cloning on the teacher's trajectories, mix = 0: DAgger on the learner's own; the critic learns
         the n-step returns of that trajectory as in train_rollout.  ``teacher``: "coordinate", "search" or "gradient" (the env's own
         *_actions call; its refusals pass through) or a callable teacher(env) -> int64 [N] joint actions.  ``tau``: None = hard labels; a
         temperature = soft targets softmax(table / tau) per UAV from the coordinate search's reward table ("coordinate" only).
+        ``shaped_teacher``: the "coordinate" / "search" teacher values its candidates under the env's reward spec (``shaped=True`` of the
+        env's call; the soft targets then come from the shaped table) -- refused without a spec, for "gradient" (it uses no reward) and for
+        a callable.
         Returns update()'s stats with ``agreement`` added: the fraction of (sample, UAV) pairs whose greedy digit is the teacher's."""
         if not callable(teacher) and teacher not in self.TEACHERS:
             raise ValueError("teacher must be one of %s or a callable teacher(env) -> int64 [n_envs]" % (self.TEACHERS,))
+        if shaped_teacher:
+            if callable(teacher) or teacher not in ("coordinate", "search"):
+                raise ValueError("shaped_teacher needs a teacher that values a reward: 'coordinate' or 'search'")
+            if getattr(self.env, "reward", None) is None:
+                raise ValueError("shaped_teacher needs a reward spec on the env (set_reward)")
         if tau is not None:
             if teacher != "coordinate":
                 raise ValueError("soft targets (tau) need the teacher's reward table: teacher='coordinate' only")
@@ -442,7 +452,7 @@ class FactoredA2CRunner(A2CRunner):
         if not 0.0 <= float(mix) <= 1.0:
             raise ValueError("mix must be in [0, 1]")
         self._imitation_buffers(tau is not None)
-        idx, _, rew, boot = self._imitate_collect(teacher, mix, tau)
+        idx, _, rew, boot = self._imitate_collect(teacher, mix, tau, bool(shaped_teacher))
         return self.imitate_update(idx, rew, boot, soft=tau is not None)
 
     def imitate_update(self, idx_buf, rew_buf, boot, soft=False, fused=None):

@@ -8,7 +8,12 @@ the kernel is tested and timed against and what serves the shapes the kernel ref
 
 The one-step search policy (BatchedMobiEnv.search_actions / step_search: the best of all joint actions per env) has the same pair
 here: search_rule and search_actions_reference; so has the per-UAV coordinate-search policy (coordinate_actions / step_coordinate:
-each UAV's best cell in turn): coordinate_rule and coordinate_actions_reference."""
+each UAV's best cell in turn): coordinate_rule and coordinate_actions_reference.
+
+Reward-aware look-ahead (``shaped=True`` of search_actions / coordinate_actions): the two *_actions_reference functions read the twin's
+``reward`` / ``reward_f64``, which the twin's post-step kernel has shaped when the twin carries a reward spec -- so with such a twin
+(``env.clone()`` of an env with a spec) they return SHAPED tables and are the yardstick of the shaped kernels as they stand.
+shaped_candidate_value states in NumPy what a shaped kernel computes for one candidate from the quantities it holds."""
 import warnings
 from copy import deepcopy
 
@@ -101,6 +106,31 @@ def gradient_actions_reference(env, twin, side_means=False):
     w = env.N_ACT ** torch.arange(env.nBS - 1, -1, -1, device=env.device, dtype=torch.int64)
     actions = (digit * w).sum(-1)
     return (actions, means) if side_means else actions
+
+
+def shaped_candidate_value(spec, sum_cur, n_out, cur, cells, n_ue, checked=True):
+    """The value a shaped look-ahead gives one candidate joint action (include/uavenv.h, "Reward-aware look-ahead"): ``sum_cur`` the
+    per-env sum of the serving SINRs, ``n_out`` the newly outaged walkers, ``cur`` [U] the serving SINRs before any handover, ``cells``
+    [B, 2] where BS_move leaves the UAVs.  rewards.reward_reference on mean = sum_cur * (1 / U) -- the product the step's mean_sinr is,
+    not sum_cur / U -- with, when not ``checked``, mean and cur rounded through float32 first (what the post-step kernel reads behind a
+    step with float32 outputs).  -> (value float64, terms float64 [4])."""
+    from . import rewards
+
+    mean = np.float64(sum_cur) * (np.float64(1.0) / np.float64(n_ue))
+    cur = None if cur is None else np.asarray(cur, np.float64)
+    if not checked:
+        mean = np.float64(np.float32(mean))
+        cur = None if cur is None else cur.astype(np.float32).astype(np.float64)
+    return rewards.reward_reference(spec, mean, n_out, cur, cells, n_ue)
+
+
+def frozen_uavs(bs_xy, min_bs_dist):
+    """UAVs BS_move will not move again: those with another UAV within ``min_bs_dist`` cells (ue_mobility.py:256-266; a UAV's own moves
+    cannot end it, its pre-move cell is what is tested).  bs_xy [..., B, 2] integer cells -> bool [..., B]."""
+    bs = np.asarray(bs_xy, np.int64)
+    d2 = ((bs[..., :, None, :] - bs[..., None, :, :]) ** 2).sum(-1)
+    B = bs.shape[-2]
+    return ((d2 <= int(min_bs_dist) ** 2) & ~np.eye(B, dtype=bool)).any(-1)
 
 
 def search_rule(rewards):

@@ -405,6 +405,39 @@ int uavenv_default_reward_config(UavEnvRewardConfig *cfg);
 int uavenv_shape_reward(uavenv_t *h, const UavEnvRewardConfig *cfg, const UavEnvOut *src, int n_steps, int64_t first_env, int64_t n_envs,
                         float *reward_dev, double *reward_f64_dev, double *terms_dev /* [n_steps, N, 4] or NULL */, void *stream);
 
+/* Reward-aware look-ahead: the two reward-valuing policies with every candidate valued under `cfg` instead of the step's own reward.  Each call
+ * takes the arguments of its unshaped namesake plus the config, refuses what the namesake refuses, and validates `cfg` exactly as
+ * uavenv_shape_reward does, before any HIP call.  Additive exports: the ABI version stays as it is.
+ * The value of a candidate joint action is the reward formula above applied to what the look-ahead holds for it: mean = sum * (1 / U) of
+ * the candidate's serving SINRs (the product the step's mean_sinr is), n_out = its newly outaged walkers, cur = every walker's serving SINR
+ * before any handover, bs = the cells BS_move would leave the UAVs on.
+ *   checked != 0 (a handle with float64 outputs): mean and cur are used as float64; a table entry is, bit for bit, the reward_f64 that
+ *     uavenv_step with that action followed by uavenv_shape_reward writes on a copy of the handle.
+ *   checked == 0: mean (and cur, for kind 3) are rounded through float first -- what uavenv_shape_reward reads behind a step with float32
+ *     outputs -- so a table entry rounded to float32 is exactly that step's shaped float32 reward.
+ * Kinds 0 .. 2 and t2 / t3 are bit-exact (S in Get_loc_penalty's order; +0.0 is added for pairs out of range).  Kind 3: the sum of the
+ * capped SINRs is taken in the look-ahead's own order (the packed kernels' slot sum; per pass a wave sum, the passes in order) in place of
+ * the SINR sum, so t0 differs from uavenv_shape_reward's by the rounding of two summation orders.
+ * A move BS_move refuses is "stay" and takes stay's value unevaluated.  The choice rules are the namesakes': first maximum in the order
+ * 4, 0, 1, 2, 3 per UAV (coordinate), the lowest action (search); a NaN never wins.
+ * uavenv_step_*_shaped change how the decisions are valued and nothing else: `out` receives the step's OWN reward (shape it afterwards with
+ * uavenv_shape_reward).  All four: no synchronisation, no allocation, capturable; the *_actions calls leave state and outputs untouched.
+ * The launches count into a census of their own (uavenv_debug_shaped_variant_*: the three calls of the side census, same contract); the
+ * side census and the launch census do not see them. */
+int uavenv_coordinate_actions_shaped(uavenv_t *h, const UavEnvRewardConfig *cfg, const int16_t *ue_xy_in_dev, const UavEnvInject *inj, int checked,
+                                     int64_t *actions_out_dev /*[N]*/, double *best_reward_dev /*[N] or NULL*/, double *rewards_dev /*[N,B,5] or NULL*/,
+                                     void *stream);
+int uavenv_search_actions_shaped(uavenv_t *h, const UavEnvRewardConfig *cfg, const int16_t *ue_xy_in_dev, const UavEnvInject *inj, int checked,
+                                 int64_t *actions_out_dev /*[N]*/, double *best_reward_dev /*[N] or NULL*/, double *rewards_dev /*[N,A] or NULL*/,
+                                 void *stream);
+int uavenv_step_coordinate_shaped(uavenv_t *h, const UavEnvRewardConfig *cfg, int n_steps, int64_t *actions_out_dev /*[T,N]*/, const UavEnvOut *out,
+                                  void *stream);
+int uavenv_step_search_shaped(uavenv_t *h, const UavEnvRewardConfig *cfg, int n_steps, int64_t *actions_out_dev /*[T,N]*/, const UavEnvOut *out,
+                                  void *stream);
+int uavenv_debug_shaped_variant_count(void);
+int uavenv_debug_shaped_variant_info(int i, char *name, size_t name_len, int *selectable, long long *launches);
+void uavenv_debug_shaped_variant_reset(void);
+
 /* The link-rate model of LTEChannel (channel.py:178-209, 272-385) for the LATEST CHANNEL UPDATE of every env -- the reset, step or trace
  * step the state comes from: UE cells, UAV cells and serving UAVs are read from the state, the shadowing draws of that update are rebuilt
  * from their Philox counters (env, tick - 1, index, fading site) or injected.  Downlink: the SINR of every (UE, UAV) pair in the checked

@@ -29,31 +29,42 @@ def main():
     ap.add_argument("--chunk", type=int, default=100, help="policy steps per host call")
     ap.add_argument("--seed", type=int, default=0x5EED)
     ap.add_argument("--no-gain", action="store_true", help="do not record best_reward - reward(all-stay)")
+    ap.add_argument("--shaped", action="store_true", help="the decisions value the chosen reward (search_actions(shaped=True)); needs a reward flag")
+    from drl_uav_cellularnet_amd import rewards
+
+    rewards.add_reward_arguments(ap)                     # --reward / --sinr-cap / --sep-threshold / --sep-weight / --collide-threshold
     ap.add_argument("--out", default="search")
     a = ap.parse_args()
+    try:
+        spec = rewards.spec_from_arguments(a)
+    except ValueError as ex:
+        ap.error(str(ex))
+    if a.shaped and spec is None:
+        ap.error("--shaped needs a reward (--reward / --sep-threshold / --collide-threshold)")
+    kw = {"shaped": True} if a.shaped else {}
     import numpy as np
     import torch
 
     from drl_uav_cellularnet_amd import BatchedMobiEnv
 
-    env = BatchedMobiEnv(a.envs, nBS=a.n_bs, nUE=a.n_ue, grid_n=a.grid, seed=a.seed, device="cuda:0")
+    env = BatchedMobiEnv(a.envs, nBS=a.n_bs, nUE=a.n_ue, grid_n=a.grid, seed=a.seed, device="cuda:0", reward=spec)
     stay = env.N_ACT ** env.nBS - 1                              # digit 4 for every UAV
     bufs = {}
 
     def run(n):
         """n policy steps; the [n, ...] outputs (buffers reused per chunk length)."""
         if n not in bufs:
-            bufs[n] = env.step_search(n)
+            bufs[n] = env.step_search(n, **kw)
             return bufs[n][1]
         acts, out = bufs[n]
-        return env.step_search(n, out=out, actions_out=acts)[1]
+        return env.step_search(n, out=out, actions_out=acts, **kw)[1]
 
     def run_with_gain(n, gain):
         """The same n steps decided by search_actions with its table; gain[t] = best_reward - reward(all-stay)."""
         rew = torch.empty((n, a.envs), dtype=torch.float32, device=env.device)
         snr = torch.empty((n, a.envs), dtype=torch.float32, device=env.device)
         for t in range(n):
-            acts, best, table = env.search_actions(best_reward=True, rewards=True)
+            acts, best, table = env.search_actions(best_reward=True, rewards=True, **kw)
             gain[t] = best - table[:, stay]
             env.step(acts)
             rew[t] = env.out["reward"]
@@ -90,6 +101,12 @@ def main():
     np.save(os.path.join(a.out, "time.npy"), np.array(times))
     if gain is not None:
         np.save(os.path.join(a.out, "gain_over_stay.npy"), gain)
+    from drl_uav_cellularnet_amd import heuristics
+
+    frozen = heuristics.frozen_uavs(env.out["bs_xy"].cpu().numpy(), int(env.cfg.min_bs_dist))
+    print("reward %s (decisions %s): mean return per env %.4f; %d of %d UAVs frozen at the end of the run (another UAV within %d cells), %.2f per env"
+          % ("the step's own" if spec is None else repr(spec), "shaped" if a.shaped else "unshaped", float(reward.sum(axis=0).mean()), int(frozen.sum()),
+             frozen.size, int(env.cfg.min_bs_dist), float(frozen.sum(axis=-1).mean())))
     print("%d steps x %d envs: mean reward %.4f, mean SINR %.2f dB, %.3e env-steps/s (recorded chunks)%s"
           % (a.steps, a.envs, float(reward.mean()), float(sinr.mean()), a.steps * a.envs / sum(times),
              "" if gain is None else ", mean gain over all-stay %.4f" % float(gain.mean())))

@@ -51,6 +51,27 @@ def check_ranks_agree(torch, world, dev, episode, runner):
         sys.exit(4)
 
 
+def teacher_shaped_error(teacher_shaped, teacher, reward):
+    """What is wrong with --teacher-shaped beside the other flags, or None."""
+    if not teacher_shaped:
+        return None
+    if reward is None:
+        return "--teacher-shaped needs a reward (--reward / --sep-threshold / --collide-threshold): there is nothing to value the candidates under"
+    if teacher not in ("coordinate", "search"):
+        return "--teacher-shaped needs --teacher coordinate or search: the gradient policy uses no reward"
+    return None
+
+
+def teacher_shaped_refusal(checkpoint, teacher_shaped):
+    """Why --resume must not continue ``checkpoint`` (the dict save_checkpoint wrote) with this --teacher-shaped, or None.  A checkpoint
+    from before the flag existed was trained with an unshaped teacher."""
+    trained = bool(checkpoint.get("teacher_shaped", False))
+    if trained != bool(teacher_shaped):
+        return "train_a2c: the checkpoint was trained with --teacher-shaped %s, this run asks for %s: refusing to resume" % (
+            "on" if trained else "off", "on" if teacher_shaped else "off")
+    return None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="train/run")
@@ -78,6 +99,8 @@ def main():
                     "instead of the learner's draw (1 = behaviour cloning, 0 = DAgger)")
     ap.add_argument("--imitate-tau", type=float, default=None, help="temperature of soft targets from the coordinate search's reward table "
                     "(default: hard labels)")
+    ap.add_argument("--teacher-shaped", action="store_true", help="the teacher values its candidates under the chosen reward "
+                    "(imitate_rollout(shaped_teacher=True)): needs a reward flag and --teacher coordinate or search")
     from drl_uav_cellularnet_amd import rewards
 
     rewards.add_reward_arguments(ap)                                       # --reward / --sinr-cap / --sep-threshold / --sep-weight / --collide-threshold
@@ -86,9 +109,12 @@ def main():
         reward = rewards.spec_from_arguments(a)
     except ValueError as ex:
         ap.error(str(ex))
-    imitation_flags = a.imitate_episodes != 0 or a.teacher != "coordinate" or a.imitate_mix != 0.5 or a.imitate_tau is not None
+    imitation_flags = a.imitate_episodes != 0 or a.teacher != "coordinate" or a.imitate_mix != 0.5 or a.imitate_tau is not None or a.teacher_shaped
     if imitation_flags and a.net != "mlp-factored":
-        ap.error("--imitate-episodes / --teacher / --imitate-mix / --imitate-tau are for --net mlp-factored")
+        ap.error("--imitate-episodes / --teacher / --imitate-mix / --imitate-tau / --teacher-shaped are for --net mlp-factored")
+    msg = teacher_shaped_error(a.teacher_shaped, a.teacher, reward)
+    if msg:
+        ap.error(msg)
     if a.imitate_episodes < 0 or not 0.0 <= a.imitate_mix <= 1.0:
         ap.error("--imitate-episodes must be >= 0 and --imitate-mix in [0, 1]")
     if a.imitate_tau is not None and (a.teacher != "coordinate" or not a.imitate_tau > 0):
@@ -134,6 +160,9 @@ def main():
         trained_with = None if trained_with is None else rewards.RewardSpec.from_dict(trained_with)
         if trained_with != reward:
             sys.exit("train_a2c: the checkpoint was trained with the reward %r, this run asks for %r: refusing to resume" % (trained_with, reward))
+        msg = teacher_shaped_refusal(sd, a.teacher_shaped)
+        if msg:
+            sys.exit(msg)
         runner.load_state_dict(sd["runner"])
         first_ep, returns = int(sd["episode"]) + 1, list(sd["returns"])
         check_ranks_agree(torch, world, dev, first_ep, runner)
@@ -142,7 +171,7 @@ def main():
         reward_sum, agree = 0.0, []
         for r in range(per_episode):
             if imitating:
-                st = runner.imitate_rollout(teacher=a.teacher, mix=a.imitate_mix, tau=a.imitate_tau)
+                st = runner.imitate_rollout(teacher=a.teacher, mix=a.imitate_mix, tau=a.imitate_tau, shaped_teacher=a.teacher_shaped)
                 agree.append(st["agreement"])
             else:
                 st = runner.train_rollout()
@@ -160,6 +189,7 @@ def main():
             print(json.dumps(line), flush=True)
         if a.checkpoint_every and (ep + 1) % a.checkpoint_every == 0:
             save_checkpoint(torch, world, ckpt, {"runner": runner.state_dict(), "reward": None if reward is None else reward.as_dict(),
+                                                     "teacher_shaped": bool(a.teacher_shaped),
                                                      "episode": ep, "returns": returns})
     if rank == 0:
         os.makedirs(a.out, exist_ok=True)
