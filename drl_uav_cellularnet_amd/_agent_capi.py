@@ -22,7 +22,8 @@ EXPORTS = ("uavagent_abi_version", "uavagent_last_error", "uavagent_sparse_rows_
            "uavagent_choose_factored_f32", "uavagent_loss_grad_factored_workspace_bytes", "uavagent_a2c_loss_grad_factored",
            "uavagent_first_layer_wide_f32", "uavagent_first_layer_wide_from_obs_f32", "uavagent_rows_grad_wide_sort",
            "uavagent_rows_grad_wide_sums_f32", "uavagent_imitation_loss_grad_workspace_bytes", "uavagent_imitation_loss_grad_factored",
-           "uavagent_soft_targets_f32")
+           "uavagent_soft_targets_f32", "uavagent_gae_f32", "uavagent_logp_factored_f32", "uavagent_ppo_loss_grad_factored_workspace_bytes",
+           "uavagent_ppo_loss_grad_factored")
 ABI_VERSION = 5
 
 _lib = None
@@ -132,6 +133,9 @@ def load():
         "uavagent_a2c_loss_grad_factored": [_P, _I64, _P, _P, _P, _I64, _I32, _I32, _F, _P, _P, _P, _P, _P],
         "uavagent_imitation_loss_grad_factored": [_P, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _F, _P, _P, _P, _P, _P],
         "uavagent_soft_targets_f32": [_P, _I64, C.c_double, _I64, _I32, _I32, _P, _P],
+        "uavagent_gae_f32": [_P, _P, _P, _I64, _I32, _F, _F, _P, _P, _P],
+        "uavagent_logp_factored_f32": [_P, _I64, _P, _I64, _I32, _I32, _P, _P],
+        "uavagent_ppo_loss_grad_factored": [_P, _I64, _P, _P, _P, _P, _P, _I64, _I32, _I32, _F, _F, _P, _P, _P, _P, _P],
         "uavagent_gate_prepare": [],
     }
     for wide, narrow in (("uavagent_first_layer_wide_f32", "uavagent_first_layer_f32"),
@@ -153,6 +157,8 @@ def load():
     lib.uavagent_loss_grad_factored_workspace_bytes.argtypes = [_I32, _I32]
     lib.uavagent_imitation_loss_grad_workspace_bytes.restype = C.c_size_t
     lib.uavagent_imitation_loss_grad_workspace_bytes.argtypes = [_I32, _I32]
+    lib.uavagent_ppo_loss_grad_factored_workspace_bytes.restype = C.c_size_t
+    lib.uavagent_ppo_loss_grad_factored_workspace_bytes.argtypes = [_I32, _I32]
     lib.uavagent_relu6_bwd_workspace_bytes.restype = C.c_size_t
     lib.uavagent_relu6_bwd_workspace_bytes.argtypes = [_I32]
     lib.uavagent_rows_grad_workspace_bytes.restype = C.c_size_t
@@ -581,6 +587,82 @@ def a2c_loss_grad_factored(logits, v, target, actions, n_heads, n_act, beta, dv_
         rc = load().uavagent_a2c_loss_grad_factored(_ptr(logits), ld, _ptr(v), _ptr(target), _ptr(actions), M, int(n_heads), int(n_act),
                                                     float(beta), _ptr(dv_out), _ptr(dbias_out), _ptr(loss_out), _ptr(ws), _stream(logits.device))
     _check(rc, "uavagent_a2c_loss_grad_factored")
+
+
+def gae(rewards, values, bootstrap, gamma, lam, adv_out=None, ret_out=None):
+    """GAE(lambda) in one launch (uavagent_gae_f32; factored.gae_reference states it): rewards and values float32 [T, N], bootstrap [N]
+    (0 where the episode ended).  Returns (adv, ret), float32 [T, N]."""
+    _f32c(rewards, "rewards")
+    _f32c(values, "values")
+    _f32c(bootstrap, "bootstrap")
+    T, N = rewards.shape
+    if tuple(values.shape) != (T, N) or bootstrap.numel() != N:
+        raise UavAgentError("gae: values must be [T, N] like rewards and bootstrap [N]")
+    adv_out = torch.empty_like(rewards) if adv_out is None else adv_out
+    ret_out = torch.empty_like(rewards) if ret_out is None else ret_out
+    for o, what in ((adv_out, "adv_out"), (ret_out, "ret_out")):
+        _f32c(o, what)
+        if o.numel() != T * N:
+            raise UavAgentError("gae: %s must hold [T, N] floats" % what)
+    _same_device("gae", rewards, values, bootstrap, adv_out, ret_out)
+    with torch.cuda.device(rewards.device):
+        rc = load().uavagent_gae_f32(_ptr(rewards), _ptr(values), _ptr(bootstrap), N, T, float(gamma), float(lam), _ptr(adv_out), _ptr(ret_out),
+                                     _stream(rewards.device))
+    _check(rc, "uavagent_gae_f32")
+    return adv_out, ret_out
+
+
+def _factored_rows(what, logits, actions, n_heads, n_act):
+    ld = _row_stride(logits, "logits")
+    M, C_ = logits.shape
+    if C_ != int(n_heads) * int(n_act):
+        raise UavAgentError("%s: logits must have n_heads * n_act = %d columns, got %d" % (what, int(n_heads) * int(n_act), C_))
+    if actions.dtype != torch.int64 or actions.numel() != M or not actions.is_contiguous():
+        raise UavAgentError("%s: actions must be a contiguous int64 [M] tensor" % what)
+    return ld, M
+
+
+def logp_factored(logits, actions, n_heads, n_act, out=None):
+    """log pi(a | s) = sum_b log(p_b[d_b] + 1e-5) per row (uavagent_logp_factored_f32): logits float32 [M, n_heads * n_act] (possibly a column
+    slice of a wider buffer), actions = JOINT actions int64 [M].  Returns float32 [M]."""
+    ld, M = _factored_rows("logp_factored", logits, actions, n_heads, n_act)
+    if out is None:
+        out = torch.empty((M,), dtype=torch.float32, device=logits.device)
+    else:
+        _f32c(out, "out")
+        if out.numel() != M:
+            raise UavAgentError("logp_factored: out must hold M floats")
+    _same_device("logp_factored", logits, actions, out)
+    with torch.cuda.device(logits.device):
+        rc = load().uavagent_logp_factored_f32(_ptr(logits), ld, _ptr(actions), M, int(n_heads), int(n_act), _ptr(out), _stream(logits.device))
+    _check(rc, "uavagent_logp_factored_f32")
+    return out
+
+
+def ppo_loss_grad_workspace(n_heads, n_act, device):
+    n = load().uavagent_ppo_loss_grad_factored_workspace_bytes(int(n_heads), int(n_act))
+    if n == 0:
+        raise UavAgentError("uavagent_ppo_loss_grad_factored_workspace_bytes: need 1 <= n_heads <= 32 and 2 <= n_act <= 8")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def ppo_loss_grad_factored(logits, v, ret, adv, logp_old, actions, n_heads, n_act, beta, clip, dv_out, dbias_out, loss_out, ws):
+    """The PPO form of a2c_loss_grad_factored: in place, logits [M, n_heads * n_act] <- d a_loss / d logits of the clipped surrogate with the
+    entropy bonus; v, ret, adv, logp_old float32 [M]; actions = JOINT actions int64 [M].  loss_out: float64 [5] = (a_loss, c_loss, sum dv,
+    clip_fraction, mean(logp_old - logp))."""
+    ld, M = _factored_rows("ppo_loss_grad_factored", logits, actions, n_heads, n_act)
+    for t, what in ((v, "v"), (ret, "ret"), (adv, "adv"), (logp_old, "logp_old")):
+        _f32c(t, what)
+        if t.numel() != M:
+            raise UavAgentError("ppo_loss_grad_factored: %s must hold M floats" % what)
+    if loss_out.dtype != torch.float64 or loss_out.numel() < 5 or not loss_out.is_contiguous():
+        raise UavAgentError("ppo_loss_grad_factored: loss_out must be a contiguous float64 tensor of 5 elements")
+    _same_device("ppo_loss_grad_factored", logits, v, ret, adv, logp_old, actions, dv_out, dbias_out, loss_out, ws)
+    with torch.cuda.device(logits.device):
+        rc = load().uavagent_ppo_loss_grad_factored(_ptr(logits), ld, _ptr(v), _ptr(ret), _ptr(adv), _ptr(logp_old), _ptr(actions), M,
+                                                    int(n_heads), int(n_act), float(beta), float(clip), _ptr(dv_out), _ptr(dbias_out),
+                                                    _ptr(loss_out), _ptr(ws), _stream(logits.device))
+    _check(rc, "uavagent_ppo_loss_grad_factored")
 
 
 def imitation_loss_grad_workspace(n_heads, n_act, device):

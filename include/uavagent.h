@@ -281,6 +281,36 @@ int uavagent_rows_grad_wide_sort(const int64_t *idx, int64_t m_rows, int32_t k, 
 int uavagent_rows_grad_wide_sums_f32(const float *g, int64_t m_rows, int32_t k, int32_t h, int32_t n_tables, int64_t n_rows, float *dw0_out,
                                      float *dw1_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- PPO for the factorised head (csrc/agent_ppo.hip; additive to ABI 5, the number stays).  Layout, digit decode,
+ * clamp of the actions, bounds and refusals are those of the factorised head above. ---- */
+
+/* GAE(lambda): delta[t] = r[t] + gamma * v[t+1] - v[t], v[T] := bootstrap; adv[t] = delta[t] + gamma*lam*adv[t+1]; ret[t] = adv[t] + v[t].
+ * rewards / values / adv_out / ret_out f32 [n_steps, n_envs], bootstrap f32 [n_envs] (0 where the episode ended, as for nstep_returns).
+ * gamma and lam in [0, 1].  Float32, two roundings per product-sum (no FMA contraction).  Zero envs or zero steps: no launch. */
+int uavagent_gae_f32(const float *rewards, const float *values, const float *bootstrap, int64_t n_envs, int32_t n_steps, float gamma,
+                     float lam, float *adv_out, float *ret_out, void *stream);
+
+/* logp[r] = sum_b log(p_b[d_b] + 1e-5), heads added in the order b = 0 .. n_heads-1; layout, digit decode and clamping of
+ * uavagent_a2c_loss_grad_factored (the reference's + 1e-5 kept, so that beta and the chosen-action term mean what they mean there).
+ * logp_out f32 [n_rows]: the terms are float32, their sum is taken in float64 and rounded once.  The per-head softmax is the one uavagent_ppo_loss_grad_factored evaluates: on the same logits and actions the two
+ * hold the same bits, and uavagent_ppo_loss_grad_factored counts a logp that rounds to the float32 logp_old it is given as equal to it
+ * (rho == 1 exactly on unchanged logits); every other difference logp - logp_old is taken in float64. */
+int uavagent_logp_factored_f32(const float *logits, int64_t ld_logits, const int64_t *actions, int64_t n_rows, int32_t n_heads,
+                               int32_t n_act, float *logp_out, void *stream);
+
+/* The clipped surrogate of PPO with the product policy.  Per row, logp as above:  rho = exp(logp - logp_old);  the row is clipped when
+ * (adv > 0 and rho > 1 + clip) or (adv < 0 and rho < 1 - clip);  s = clipped ? clamp(rho, 1 - clip, 1 + clip) * adv : rho * adv;
+ *   a_loss = mean(-s - beta * sum_b H_b)  (H_b as in uavagent_a2c_loss_grad_factored);  c_loss = mean((ret - v)^2);  dv = -2 (ret - v) / M;
+ * the gradient is that kernel's with its td replaced by w = clipped ? 0 : rho * adv in the chosen-action term -- with logp_old == logp,
+ * v == 0 and ret == adv its dlogits, dbias and dv bit for bit at v_target = adv.  v / ret / adv / logp_old f32 [m_rows], actions int64 [m_rows],
+ * clip in (0, 1).  IN / OUT as there; loss_out double[5] = {a_loss, c_loss, sum(dv), clip_fraction, mean(logp_old - logp)}.  `workspace`:
+ * uavagent_ppo_loss_grad_factored_workspace_bytes bytes (0 = shape not served), 8-byte aligned.  Fixed grid, fixed order: bit-reproducible. */
+size_t uavagent_ppo_loss_grad_factored_workspace_bytes(int32_t n_heads, int32_t n_act);
+int uavagent_ppo_loss_grad_factored(float *logits_inout, int64_t ld_logits, const float *v, const float *ret, const float *adv,
+                                    const float *logp_old, const int64_t *actions, int64_t m_rows, int32_t n_heads, int32_t n_act,
+                                    float beta, float clip, float *dv_out, float *dbias_out, double *loss_out /* [5] */,
+                                    void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,8 @@ actor parameters (Global_A_PARA: here a named .npz, agent.save_actor_npz -- load
   python tools/train_a2c.py --net mlp-factored --n-bs 16 --n-ue 200 --workers 1024      # the MLP with that head (256-node first layer)
   python tools/train_a2c.py --net mlp-factored --n-bs 16 --n-ue 200 --workers 1024 --imitate-episodes 2 --episodes 4
                                                    # the first 2 episodes imitate the coordinate search (imitate_rollout), then A2C
+  python tools/train_a2c.py --net mlp-factored --n-bs 16 --n-ue 200 --workers 1024 --algo ppo --ppo-epochs 4 --ppo-clip 0.2 --gae-lambda 0.95
+                                                   # PPO in place of A2C: GAE advantages, 4 clipped-surrogate epochs per rollout (ppo_rollout)
   python -m torch.distributed.run --nproc-per-node 8 tools/train_a2c.py ...     # one process per GPU, gradients all-reduced (RCCL)"""
 import argparse
 import json
@@ -72,6 +74,14 @@ def teacher_shaped_refusal(checkpoint, teacher_shaped):
     return None
 
 
+def algo_refusal(checkpoint, algo):
+    """Why --resume must not continue ``checkpoint`` with this --algo, or None.  A checkpoint from before the flag was trained with a2c."""
+    trained = checkpoint.get("algo", "a2c")
+    if trained != algo:
+        return "train_a2c: the checkpoint was trained with --algo %s, this run asks for %s: refusing to resume" % (trained, algo)
+    return None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="train/run")
@@ -101,6 +111,12 @@ def main():
                     "(default: hard labels)")
     ap.add_argument("--teacher-shaped", action="store_true", help="the teacher values its candidates under the chosen reward "
                     "(imitate_rollout(shaped_teacher=True)): needs a reward flag and --teacher coordinate or search")
+    ap.add_argument("--algo", choices=("a2c", "ppo"), default="a2c", help="mlp-factored: the update after the imitation episodes -- a2c "
+                    "(train_rollout: n-step returns, one gradient step per rollout) or ppo (FactoredA2CRunner.ppo_rollout: GAE advantages, "
+                    "several clipped-surrogate epochs per rollout)")
+    ap.add_argument("--ppo-epochs", type=int, default=4, help="--algo ppo: full-batch epochs per rollout")
+    ap.add_argument("--ppo-clip", type=float, default=0.2, help="--algo ppo: the probability ratio is clipped to 1 +- this")
+    ap.add_argument("--gae-lambda", type=float, default=0.95, help="--algo ppo: lambda of the advantage estimate")
     from drl_uav_cellularnet_amd import rewards
 
     rewards.add_reward_arguments(ap)                                       # --reward / --sinr-cap / --sep-threshold / --sep-weight / --collide-threshold
@@ -119,6 +135,11 @@ def main():
         ap.error("--imitate-episodes must be >= 0 and --imitate-mix in [0, 1]")
     if a.imitate_tau is not None and (a.teacher != "coordinate" or not a.imitate_tau > 0):
         ap.error("--imitate-tau must be > 0 and needs --teacher coordinate")
+    ppo_flags = a.algo != "a2c" or a.ppo_epochs != 4 or a.ppo_clip != 0.2 or a.gae_lambda != 0.95
+    if ppo_flags and a.net != "mlp-factored":
+        ap.error("--algo / --ppo-epochs / --ppo-clip / --gae-lambda are for --net mlp-factored")
+    if a.ppo_epochs < 1 or not 0.0 < a.ppo_clip < 1.0 or not 0.0 <= a.gae_lambda <= 1.0:
+        ap.error("--ppo-epochs must be >= 1, --ppo-clip in (0, 1) and --gae-lambda in [0, 1]")
     import numpy as np
     import torch
 
@@ -163,16 +184,23 @@ def main():
         msg = teacher_shaped_refusal(sd, a.teacher_shaped)
         if msg:
             sys.exit(msg)
+        msg = algo_refusal(sd, a.algo)
+        if msg:
+            sys.exit(msg)
         runner.load_state_dict(sd["runner"])
         first_ep, returns = int(sd["episode"]) + 1, list(sd["returns"])
         check_ranks_agree(torch, world, dev, first_ep, runner)
     for ep in range(first_ep, a.episodes):
         imitating = ep < a.imitate_episodes                                # a function of the episode counter alone
-        reward_sum, agree = 0.0, []
+        reward_sum, agree, clip_frac, kl = 0.0, [], [], []
         for r in range(per_episode):
             if imitating:
                 st = runner.imitate_rollout(teacher=a.teacher, mix=a.imitate_mix, tau=a.imitate_tau, shaped_teacher=a.teacher_shaped)
                 agree.append(st["agreement"])
+            elif a.algo == "ppo":
+                st = runner.ppo_rollout(epochs=a.ppo_epochs, clip=a.ppo_clip, lam=a.gae_lambda)
+                clip_frac.append(st["clip_fraction"])
+                kl.append(st["approx_kl"])
             else:
                 st = runner.train_rollout()
             reward_sum += st["mean_reward"]
@@ -183,13 +211,16 @@ def main():
                     "mean_reward": st["mean_reward"], "env_steps": (ep + 1) * per_episode * a.rollout * a.workers * world,
                     "seconds": time.time() - t0}
             if a.net == "mlp-factored":
-                line.update({"phase": "imitate" if imitating else "a2c", "episode_mean_reward_per_step": reward_sum / per_episode})
+                line.update({"phase": "imitate" if imitating else a.algo, "episode_mean_reward_per_step": reward_sum / per_episode})
                 if imitating:
                     line["agreement"] = agree                               # the teacher agreement of every rollout of the episode
+                elif a.algo == "ppo":                                      # the last epoch's figures, averaged over the episode's rollouts
+                    line.update({"clip_fraction": sum(clip_frac) / len(clip_frac), "approx_kl": sum(kl) / len(kl)})
             print(json.dumps(line), flush=True)
         if a.checkpoint_every and (ep + 1) % a.checkpoint_every == 0:
             save_checkpoint(torch, world, ckpt, {"runner": runner.state_dict(), "reward": None if reward is None else reward.as_dict(),
                                                      "teacher_shaped": bool(a.teacher_shaped),
+                                                     "algo": a.algo, "ppo_epochs": a.ppo_epochs, "ppo_clip": a.ppo_clip, "gae_lambda": a.gae_lambda,
                                                      "episode": ep, "returns": returns})
     if rank == 0:
         os.makedirs(a.out, exist_ok=True)
