@@ -287,20 +287,33 @@ __device__ __forceinline__ double quad_perm_f64(double v) {
 }
 // All 64 lanes active; U a multiple of 4, 4 <= U <= 32.  q[0] = this lane's quad sum (Q_0 in the slot's first lane), q[j] = Q_j of the
 // lane's slot, or -0.0, for 1 <= j < 8: in flight when this returns.
-__device__ __forceinline__ void slot_quads(double v, int base, int ul, int U, double (&q)[kMaxQuads]) {
+// HOISTED: the seven gather addresses come from the caller (slot_quad_addrs, taken once before the step loop), else they are formed here.
+__device__ __forceinline__ int slot_quad_addr(int b4, int last, int j) {
+    return b4 + min(16 * j, last);                 // lane base + 4j (present: 4j <= U - 4) or base + U - 3 (absent: 4j >= U)
+}
+template <bool HOISTED = false>
+__device__ __forceinline__ void slot_quads(double v, int base, int ul, int U, double (&q)[kMaxQuads], const int *addr = nullptr) {
     v += quad_perm_f64<0xF5>(v);   // [1,1,3,3]
     v += quad_perm_f64<0xEE>(v);   // [2,3,2,3]
     q[0] = v;
     const double s = (ul & 3) ? -0.0 : v;          // lanes 4j: Q_j; the other lanes' sums are of no use: they hold the identity
     const int lo = __double2loint(s), hi = __double2hiint(s);
     int b4 = base << 2, last = 4 * U - 12;         // byte addresses (lane * 4): the slot's first lane; lane U - 3 of the slot, an identity
-    asm volatile("" : "+v"(b4), "+s"(last));       // (computed here, in the step: hoisted out of the step loop the seven addresses cost
-                                                   //  seven registers for the whole kernel)
+    if (!HOISTED) asm volatile("" : "+v"(b4), "+s"(last));   // (computed here, in the step: hoisted out of the step loop the seven addresses
+                                                             //  cost seven registers for the whole kernel)
 #pragma unroll
     for (int j = 1; j < kMaxQuads; ++j) {
-        const int a = b4 + min(16 * j, last);      // lane base + 4j (present: 4j <= U - 4) or base + U - 3 (absent: 4j >= U)
+        const int a = HOISTED ? addr[j] : slot_quad_addr(b4, last, j);
         q[j] = __hiloint2double(__builtin_amdgcn_ds_bpermute(a, hi), __builtin_amdgcn_ds_bpermute(a, lo));
     }
+}
+// The pinned multi-step kernels (one or two wavefronts per SIMD: 227 / 234 of 256 VGPRs before this) do pay the seven registers: formed in
+// the step the addresses were 7 s_min_i32 + 7 v_add_u32 of every step, each a full issue slot of a wavefront that is alone on its SIMD.
+__device__ __forceinline__ void slot_quad_addrs(int base, int U, int (&addr)[kMaxQuads]) {
+    const int b4 = base << 2, last = 4 * U - 12;
+    addr[0] = b4;
+#pragma unroll
+    for (int j = 1; j < kMaxQuads; ++j) { addr[j] = slot_quad_addr(b4, last, j); asm volatile("" : "+v"(addr[j])); }
 }
 __device__ __forceinline__ double slot_quads_sum(const double (&q)[kMaxQuads]) {   // valid in the slot's first lane
     return ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
@@ -480,17 +493,22 @@ __device__ __forceinline__ void walker_move(const HotConst &H, const LeanCoef &C
     if (c[3]) y = 2.0 * MAXC - y;
 }
 
-// Group owner, end of tick (ue_mobility.py:493-521): bounce flips, remaining flight length, arrival redraw.
-template <bool FAST>
-__device__ __forceinline__ void group_finish(const KParams &p, const LeanCoef &C, long long e, int g, uint32_t tick, const uint32_t touched[4],
-                                             double MAXC, double &ogfl, double &ogv, double &ogc, double &ogs) {
+// Group owner, end of tick (ue_mobility.py:493-521), in two halves: bounce flips; remaining flight length and arrival redraw.
+// The pinned multi-step kernels call them apart: the flips where a bounce was seen (rare), the rest in EVERY lane -- a lane that owns no group
+// holds zeros in og*, which stay zeros (0 - 0), and ogv > 0 never holds there: the redraw is the owners' alone.
+__device__ __forceinline__ void group_flips(int g, const uint32_t touched[4], double &ogc, double &ogs) {
     const uint32_t bit = 1u << g;
     if (touched[0] & bit) ogc = -ogc;
     if (touched[1] & bit) ogc = -ogc;
     if (touched[2] & bit) ogs = -ogs;
     if (touched[3] & bit) ogs = -ogs;
+}
+template <bool FAST, bool RARE = false>   // RARE: tell the compiler that arrivals are few (it then lays the redraw out behind the step loop)
+__device__ __forceinline__ void group_arrival(const KParams &p, const LeanCoef &C, long long e, int g, uint32_t tick, double MAXC,
+                                              double &ogfl, double &ogv, double &ogc, double &ogs) {
     ogfl = ogfl - ogv;                                    // :513
-    if (ogv > 0.0 && ogfl <= 0.0) {                       // :514
+    const bool arrived = ogv > 0.0 && ogfl <= 0.0;        // :514
+    if (RARE ? __builtin_expect(arrived, false) : arrived) {
         double ut, uf, uv, t1;
         if (UAV_INJ(p.inj_group)) {
             ut = p.inj_group[(e * p.Gr + g) * 3 + 0]; uf = p.inj_group[(e * p.Gr + g) * 3 + 1];
@@ -503,6 +521,12 @@ __device__ __forceinline__ void group_finish(const KParams &p, const LeanCoef &C
         ogfl = uf * MAXC;                                 // :520 FL_MAX = max(dimensions)
         ogv = uv * (p.grp_v_max - p.grp_v_min) + p.grp_v_min;  // :521
     }
+}
+template <bool FAST>
+__device__ __forceinline__ void group_finish(const KParams &p, const LeanCoef &C, long long e, int g, uint32_t tick, const uint32_t touched[4],
+                                             double MAXC, double &ogfl, double &ogv, double &ogc, double &ogs) {
+    group_flips(g, touched, ogc, ogs);
+    group_arrival<FAST>(p, C, e, g, tick, MAXC, ogfl, ogv, ogc, ogs);
 }
 
 // Received power P*gain of every UAV at one walker (channel.py:220-257), linear domain.
@@ -626,6 +650,20 @@ __device__ __forceinline__ void fifo_handover(const HotConst &H, int depth, int 
     else { r0 = r1; r1 = r2; r2 = best; remain = (r1 == r0) && (r2 == r0); }  // FIFO shift (:150-153)
     const bool changed = serving != best;                                     // :156 (newest row == best)
     if (remain && changed && (bestS - cur > H.ho_thr)) serving = best;        // :155-167
+}
+// The same push and decision by selects, for the pinned multi-step kernels.  `depth` is a per-env value, so the three cases above are three
+// exec-masked regions of every step (about 45 instructions with their mask bookkeeping, whichever case the lanes are in); as selects the
+// rows cost four v_cndmask and `remain` three compares.  Rows the case does not write keep their value, as above.
+__device__ __forceinline__ void fifo_handover_flat(const HotConst &H, int depth, int best, double bestS, double cur,
+                                                   int &serving, int &r0, int &r1, int &r2) {
+    const bool d1 = depth == 1, d2 = depth == 2, shift = !(d1 || d2);
+    const int n0 = shift ? r1 : r0;
+    const int n1 = d1 ? best : (shift ? r2 : r1);
+    const int n2 = d1 ? r2 : best;
+    const bool remain = (n1 == n0) && (d1 || n2 == n0);
+    r0 = n0; r1 = n1; r2 = n2;
+    const bool changed = serving != best;
+    if (remain && changed && (bestS - cur > H.ho_thr)) serving = best;
 }
 
 // The kernarg constants of env_finish.  PINNED (the pinned multi-step kernels): held in VGPRs for the whole launch.  Read from the
@@ -927,6 +965,19 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
     // taken at once, the gathered quads held across the stores would cost the registers of the third wavefront.
     constexpr bool QLATE = QSUM && PIN;
     double sq[kMaxQuads];
+    // DIET (the pinned multi-step kernels): the step's bookkeeping without exec-masked regions ("step diet").  A wavefront
+    // alone on its SIMD issues one instruction per ~4 cycles whatever its kind, so a mask saved, a branch and a mask restored around two
+    // integer adds cost what three float64 FMAs cost.  Every other kernel keeps the code it was tuned with: where three or more wavefronts
+    // share a SIMD the scalar instructions of one hide behind the vector instructions of another, and the unpinned multi-step kernel with
+    // the diet was 5 % SLOWER at 65 536 envs (40.56 against 38.52 us per step: fewer instructions, but 76 more v_readlane of spilled SGPRs).
+    // Two parts of it cost registers (seven for the addresses; about ten for the FIFO push by selects, which lengthens live ranges), and
+    // the pinned kernels for 8 UAVs hold 249 / 254 of the 256 VGPRs that let two wavefronts share a SIMD: ROOMY leaves those two out there.
+    constexpr bool DIET = MANY && PIN;
+    constexpr bool ROOMY = DIET && BT <= 4;
+    constexpr bool QHOIST = QLATE && ROOMY;            // the gather addresses of slot_quads, taken once (slot_quad_addrs)
+    int sq_addr[kMaxQuads];
+    if (QHOIST) slot_quad_addrs(base, U, sq_addr);
+    const unsigned long long live_mask = DIET ? __ballot(live) : 0ull;
     int n_outage = 0;
     unsigned long long ob = 0ull;
     OutPtrs om = p.out;                                // MANY: the current step's output blocks (dead code otherwise)
@@ -989,7 +1040,7 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
         // ---- mobility: next(self.mm); walker and group state stay in registers across ticks ----
         if (has_mobility(MODE)) {
             const bool aggregating = agg != 0;
-            if (gown) {                                          // ue_mobility.py:458-459
+            if (DIET || gown) {                                  // ue_mobility.py:458-459 (DIET: every lane; no owner, all zeros)
                 ogx = ogx + ogv * ogc;
                 ogy = ogy + ogv * ogs;
             }
@@ -998,14 +1049,31 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
             const double gv = __shfl(ogv, src, 64), gc = __shfl(ogc, src, 64), gs = __shfl(ogs, src, 64);
             bool c[4];
             walker_move(H, C, aggregating, hu, gx, gy, gv, gc, gs, MAXC, x, y, c);   // ue_mobility.py:455-505
-            c[0] = c[0] && live; c[1] = c[1] && live; c[2] = c[2] && live; c[3] = c[3] && live;
             uint32_t touched[4] = {0u, 0u, 0u, 0u};  // per slot: groups bounced at x<0, x>MAX, y<0, y>MAX
-            if (__ballot(c[0] || c[1] || c[2] || c[3]) != 0ull) {  // rare, wave-uniform branch
-                for (int g = 0; g < Gr; ++g) {
-                    const bool mine = gid == g;
+            if constexpr (DIET) {
+                // The four flags as lane masks straight from their compares, `&& live` one scalar AND each, the rare-path test a scalar OR
+                // chain; `touched` and the flips it causes live inside the rare branch (group_flips: nothing between here and the end of the
+                // tick reads ogc / ogs), so the common path carries neither.
+                const unsigned long long m[4] = {__ballot(c[0]) & live_mask, __ballot(c[1]) & live_mask, __ballot(c[2]) & live_mask,
+                                                 __ballot(c[3]) & live_mask};
+                if (__builtin_expect(((m[0] | m[1]) | (m[2] | m[3])) != 0ull, false)) {   // rare, wave-uniform: laid out behind the loop
+                    for (int g = 0; g < Gr; ++g) {
+                        const unsigned long long mine = __ballot(gid == g);
 #pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if ((__ballot(mine && c[k]) & slot_mask) != 0ull) touched[k] |= 1u << g;
+                        for (int k = 0; k < 4; ++k)
+                            if ((mine & m[k] & slot_mask) != 0ull) touched[k] |= 1u << g;
+                    }
+                    if (gown) group_flips(ul, touched, ogc, ogs);
+                }
+            } else {
+                c[0] = c[0] && live; c[1] = c[1] && live; c[2] = c[2] && live; c[3] = c[3] && live;
+                if (__ballot(c[0] || c[1] || c[2] || c[3]) != 0ull) {  // rare, wave-uniform branch
+                    for (int g = 0; g < Gr; ++g) {
+                        const bool mine = gid == g;
+#pragma unroll
+                        for (int k = 0; k < 4; ++k)
+                            if ((__ballot(mine && c[k]) & slot_mask) != 0ull) touched[k] |= 1u << g;
+                    }
                 }
             }
             if (UAV_INJ(p.inj_theta)) hu = hu_inj;                                       // new heading (:508)
@@ -1021,9 +1089,18 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
                     hu = heading_from(q0, q1, HB);
                 }
             }
-            if (gown) group_finish<FAST>(p, C, e, ul, tick, touched, MAXC, ogfl, ogv, ogc, ogs);   // :493-521
-            if (aggregating) { agg -= 1; if (agg == 0) deagg = p.deagg_len; }            // :472-473
-            else { deagg -= 1; if (deagg == 0) agg = p.agg_len; }                        // :486-487
+            if constexpr (DIET) {
+                group_arrival<FAST, true>(p, C, e, ul, tick, MAXC, ogfl, ogv, ogc, ogs);     // :513-521 (the flips: above)
+                // :472-473 / :486-487 by selects: both decrements, two compares -- no exec-masked region for two integers per env
+                const int a1 = agg - 1, d1 = deagg - 1;
+                const int agg_n = aggregating ? a1 : (d1 == 0 ? p.agg_len : agg);
+                const int deagg_n = aggregating ? (a1 == 0 ? p.deagg_len : deagg) : d1;
+                agg = agg_n; deagg = deagg_n;
+            } else {
+                if (gown) group_finish<FAST>(p, C, e, ul, tick, touched, MAXC, ogfl, ogv, ogc, ogs);   // :493-521
+                if (aggregating) { agg -= 1; if (agg == 0) deagg = p.deagg_len; }            // :472-473
+                else { deagg -= 1; if (deagg == 0) agg = p.agg_len; }                        // :486-487
+            }
         }
         tick += 1u;
         if (MODE == MODE_WARMUP) continue;                // warm-up: mobility only
@@ -1049,11 +1126,13 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
             } else {
                 // UpdateDroneNet, DL part (channel.py:141-174)
                 cur = sinr_db<BT, FAST>(p, H, C, pg, serving);       // serving UAV BEFORE any handover (:145-146)
-                fifo_handover(H, depth, best, bestS, cur, serving, r0, r1, r2);
+                if (ROOMY) fifo_handover_flat(H, depth, best, bestS, cur, serving, r0, r1, r2);
+                else fifo_handover(H, depth, best, bestS, cur, serving, r0, r1, r2);
             }
-            ob = (__ballot(live && (cur <= H.out_thr)) & slot_mask) >> base;               // :116 / :170
+            if (DIET) ob = (__ballot(cur <= H.out_thr) & live_mask & slot_mask) >> base;   // (the compare's own mask, `live` one scalar AND)
+            else ob = (__ballot(live && (cur <= H.out_thr)) & slot_mask) >> base;          // :116 / :170
             if (!is_reset(MODE)) n_outage = __popcll(ob & ~prev_out);                      // :171-174 newly outaged
-            if (QSUM) { slot_quads(live ? cur : 0.0, base, ul, U, sq); if (!QLATE) sum_cur = slot_quads_sum(sq); }
+            if (QSUM) { slot_quads<QHOIST>(live ? cur : 0.0, base, ul, U, sq, sq_addr); if (!QLATE) sum_cur = slot_quads_sum(sq); }
             else sum_cur = slot_sum(live ? cur : 0.0, ul, U);
         }
         if (MANY) {
@@ -1072,11 +1151,13 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
             if (!PATH && bown) { if (UAV_OUT(om.bs_xy)) { stx(om.bs_xy, 2u * ib32, bx); stx(om.bs_xy, 2u * ib32 + 1u, by); } }
             if (QLATE) sum_cur = slot_quads_sum(sq);
             if (it + 1 < n_ticks) {
-                if (head) env_finish<MODE, FAST, false>(K, om, st, e32, erec, tick, agg, deagg, depth, step_n, sum_cur, n_outage);
+                if (DIET) step_n += 1;                            // mobile_env.py:181 (DIET: here, so that env_finish's own + 1 is this value
+                                                                  //  and not a second add in a mask region of the head lanes)
+                if (head) env_finish<MODE, FAST, false>(K, om, st, e32, erec, tick, agg, deagg, depth, DIET ? step_n - 1 : step_n, sum_cur, n_outage);
                 out_next_step<FAST>(om, N, U, B);
                 prev_out = ob;                                    // channel.py:173  self.ue_out = new_out
                 depth = depth < 3 ? depth + 1 : depth;            // bestBS_buf grows to hoBufDepth, then shifts (:148-153)
-                step_n += 1;                                      // mobile_env.py:181
+                if (!DIET) step_n += 1;
             }
         }
     }
@@ -1205,7 +1286,8 @@ __device__ __forceinline__ void env_packed_entry(char *blob, const long long *ac
             const int nt = __builtin_amdgcn_readfirstlane(d.z), bits = __builtin_amdgcn_readfirstlane(d.w);
             if (nt <= 0) return true;
             if (Q > 0) __builtin_amdgcn_wave_barrier();                       // (the previous piece's reads of the LDS row are done)
-            if (Q == 2) { if (!sched_hand_off_wait(p, ew)) return false; }
+            if constexpr (Q == 2 && PIN) { if (__builtin_expect(!sched_hand_off_wait(p, ew), false)) return false; }   // (unlikely: the kernel's exit block then stays behind the last piece)
+            else if (Q == 2) { if (!sched_hand_off_wait(p, ew)) return false; }
             env_packed_body<BT, MODE, PLC, FAST, PIN, MANY, (Q == 0 ? 2 : (Q == 2 ? 1 : 0)), QSUM>(blob, actions, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, p, s_bs, wave, ew,
                                                                                                         t0, nt, e_lo, e_hi);
             if (Q == 0 && (bits & SCHED_PUBLISH)) sched_hand_off_publish(p, ew);
