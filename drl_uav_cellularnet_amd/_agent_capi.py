@@ -23,7 +23,7 @@ EXPORTS = ("uavagent_abi_version", "uavagent_last_error", "uavagent_sparse_rows_
            "uavagent_first_layer_wide_f32", "uavagent_first_layer_wide_from_obs_f32", "uavagent_rows_grad_wide_sort",
            "uavagent_rows_grad_wide_sums_f32", "uavagent_imitation_loss_grad_workspace_bytes", "uavagent_imitation_loss_grad_factored",
            "uavagent_soft_targets_f32", "uavagent_gae_f32", "uavagent_logp_factored_f32", "uavagent_ppo_loss_grad_factored_workspace_bytes",
-           "uavagent_ppo_loss_grad_factored")
+           "uavagent_ppo_loss_grad_factored", "uavagent_logp_f32", "uavagent_ppo_loss_grad_workspace_bytes", "uavagent_ppo_loss_grad")
 ABI_VERSION = 5
 
 _lib = None
@@ -136,6 +136,8 @@ def load():
         "uavagent_gae_f32": [_P, _P, _P, _I64, _I32, _F, _F, _P, _P, _P],
         "uavagent_logp_factored_f32": [_P, _I64, _P, _I64, _I32, _I32, _P, _P],
         "uavagent_ppo_loss_grad_factored": [_P, _I64, _P, _P, _P, _P, _P, _I64, _I32, _I32, _F, _F, _P, _P, _P, _P, _P],
+        "uavagent_logp_f32": [_P, _I64, _P, _I64, _I32, _P, _P],
+        "uavagent_ppo_loss_grad": [_P, _I64, _P, _P, _P, _P, _P, _I64, _I32, _F, _F, _P, _P, _P, _P, _P],
         "uavagent_gate_prepare": [],
     }
     for wide, narrow in (("uavagent_first_layer_wide_f32", "uavagent_first_layer_f32"),
@@ -159,6 +161,8 @@ def load():
     lib.uavagent_imitation_loss_grad_workspace_bytes.argtypes = [_I32, _I32]
     lib.uavagent_ppo_loss_grad_factored_workspace_bytes.restype = C.c_size_t
     lib.uavagent_ppo_loss_grad_factored_workspace_bytes.argtypes = [_I32, _I32]
+    lib.uavagent_ppo_loss_grad_workspace_bytes.restype = C.c_size_t
+    lib.uavagent_ppo_loss_grad_workspace_bytes.argtypes = [_I32]
     lib.uavagent_relu6_bwd_workspace_bytes.restype = C.c_size_t
     lib.uavagent_relu6_bwd_workspace_bytes.argtypes = [_I32]
     lib.uavagent_rows_grad_workspace_bytes.restype = C.c_size_t
@@ -590,7 +594,7 @@ def a2c_loss_grad_factored(logits, v, target, actions, n_heads, n_act, beta, dv_
 
 
 def gae(rewards, values, bootstrap, gamma, lam, adv_out=None, ret_out=None):
-    """GAE(lambda) in one launch (uavagent_gae_f32; factored.gae_reference states it): rewards and values float32 [T, N], bootstrap [N]
+    """GAE(lambda) in one launch (uavagent_gae_f32; agent.gae_reference states it): rewards and values float32 [T, N], bootstrap [N]
     (0 where the episode ended).  Returns (adv, ret), float32 [T, N]."""
     _f32c(rewards, "rewards")
     _f32c(values, "values")
@@ -663,6 +667,55 @@ def ppo_loss_grad_factored(logits, v, ret, adv, logp_old, actions, n_heads, n_ac
                                                     int(n_heads), int(n_act), float(beta), float(clip), _ptr(dv_out), _ptr(dbias_out),
                                                     _ptr(loss_out), _ptr(ws), _stream(logits.device))
     _check(rc, "uavagent_ppo_loss_grad_factored")
+
+
+def _joint_rows(what, logits, actions):
+    ld = _row_stride(logits, "logits")
+    M, A_ = logits.shape
+    if actions.dtype != torch.int64 or actions.numel() != M or not actions.is_contiguous():
+        raise UavAgentError("%s: actions must be a contiguous int64 [M] tensor" % what)
+    return ld, M, A_
+
+
+def logp(logits, actions, out=None):
+    """log pi(a | s) = log(p_a + 1e-5) per row under one softmax over the columns (uavagent_logp_f32): logits float32 [M, A] (possibly a column
+    slice of a wider buffer), actions int64 [M].  Returns float32 [M]."""
+    ld, M, A_ = _joint_rows("logp", logits, actions)
+    if out is None:
+        out = torch.empty((M,), dtype=torch.float32, device=logits.device)
+    else:
+        _f32c(out, "out")
+        if out.numel() != M:
+            raise UavAgentError("logp: out must hold M floats")
+    _same_device("logp", logits, actions, out)
+    with torch.cuda.device(logits.device):
+        rc = load().uavagent_logp_f32(_ptr(logits), ld, _ptr(actions), M, A_, _ptr(out), _stream(logits.device))
+    _check(rc, "uavagent_logp_f32")
+    return out
+
+
+def ppo_loss_grad_joint_workspace(n_actions, device):
+    n = load().uavagent_ppo_loss_grad_workspace_bytes(int(n_actions))
+    if n == 0:
+        raise UavAgentError("uavagent_ppo_loss_grad_workspace_bytes: need 1 <= n_actions <= 1024")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def ppo_loss_grad(logits, v, ret, adv, logp_old, actions, beta, clip, dv_out, dbias_out, loss_out, ws):
+    """The PPO form of a2c_loss_grad: in place, logits [M, A] <- d a_loss / d logits of the clipped surrogate with the entropy bonus; v, ret,
+    adv, logp_old float32 [M]; actions int64 [M].  loss_out: float64 [5] = (a_loss, c_loss, sum dv, clip_fraction, mean(logp_old - logp))."""
+    ld, M, A_ = _joint_rows("ppo_loss_grad", logits, actions)
+    for t, what in ((v, "v"), (ret, "ret"), (adv, "adv"), (logp_old, "logp_old")):
+        _f32c(t, what)
+        if t.numel() != M:
+            raise UavAgentError("ppo_loss_grad: %s must hold M floats" % what)
+    if loss_out.dtype != torch.float64 or loss_out.numel() < 5 or not loss_out.is_contiguous():
+        raise UavAgentError("ppo_loss_grad: loss_out must be a contiguous float64 tensor of 5 elements")
+    _same_device("ppo_loss_grad", logits, v, ret, adv, logp_old, actions, dv_out, dbias_out, loss_out, ws)
+    with torch.cuda.device(logits.device):
+        rc = load().uavagent_ppo_loss_grad(_ptr(logits), ld, _ptr(v), _ptr(ret), _ptr(adv), _ptr(logp_old), _ptr(actions), M, A_, float(beta),
+                                           float(clip), _ptr(dv_out), _ptr(dbias_out), _ptr(loss_out), _ptr(ws), _stream(logits.device))
+    _check(rc, "uavagent_ppo_loss_grad")
 
 
 def imitation_loss_grad_workspace(n_heads, n_act, device):

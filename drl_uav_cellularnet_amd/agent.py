@@ -131,6 +131,73 @@ def a2c_losses(a_prob, v, actions, v_target, beta=ENTROPY_BETA):
     return a_loss, c_loss
 
 
+# ---- PPO (DESIGN.md sections 22 and 23): GAE(lambda) advantages and the clipped surrogate in place of the chosen-action term ----------------
+def gae_reference(rewards, values, bootstrap, gamma, lam):
+    """GAE(lambda) as uavagent_gae_f32 computes it, in the dtype of rewards: rewards and values [T, N], bootstrap [N] (0 where the episode
+    ended);  delta[t] = r[t] + gamma v[t+1] - v[t] with v[T] := bootstrap;  adv[t] = delta[t] + gamma lam adv[t+1];  ret = adv + v.
+    -> (adv, ret).  lam = 1: ret is agent.nstep_returns; lam = 0: adv is the one-step TD error."""
+    T = rewards.shape[0]
+    values = values.to(rewards.dtype)
+    adv, run, next_v = torch.empty_like(rewards), torch.zeros_like(rewards[0]), bootstrap.to(rewards.dtype)
+    for t in range(T - 1, -1, -1):
+        run = (rewards[t] + gamma * next_v) - values[t] + (gamma * lam) * run
+        adv[t] = run
+        next_v = values[t]
+    return adv, adv + values
+
+
+def logp_joint(prob, actions):
+    """log pi(a | s) = log(p_a + 1e-5) of the actions [M] under prob [M, A] (the kernel's clamp of the actions into [0, A)) -> [M]."""
+    A = prob.shape[1]
+    return torch.log(prob.gather(1, actions.reshape(-1, 1).clamp(0, A - 1)).squeeze(1) + 1e-5)
+
+
+def _ppo_clipped(rho, adv, clip):
+    return ((adv > 0) & (rho > 1.0 + clip)) | ((adv < 0) & (rho < 1.0 - clip))
+
+
+def ppo_losses(prob, v, actions, adv, ret, logp_old, beta=ENTROPY_BETA, clip=0.2):
+    """(a_loss, c_loss) of PPO for one softmax over the joint actions, differentiable.  prob [M, A], v [M, 1], actions [M]; adv, ret and
+    logp_old [M] (or [M, 1]) are constants.  rho = exp(logp - logp_old); a row is clipped when (adv > 0 and rho > 1 + clip) or (adv < 0 and
+    rho < 1 - clip); s = clipped ? clamp(rho, 1 - clip, 1 + clip) adv : rho adv;  a_loss = mean(-s - beta H), H as in a2c_losses;
+    c_loss = mean((ret - v)^2)."""
+    M = prob.shape[0]
+    adv, ret, logp_old = (t.reshape(M).detach().to(prob.dtype) for t in (adv, ret, logp_old))
+    rho = torch.exp(logp_joint(prob, actions) - logp_old)
+    clipped = _ppo_clipped(rho.detach(), adv, clip)
+    s = torch.where(clipped, rho.detach().clamp(1.0 - clip, 1.0 + clip), rho) * adv       # a clipped row is a constant of the parameters
+    entropy = -(prob * torch.log(prob + 1e-5)).sum(dim=1)
+    a_loss = (-s - beta * entropy).mean()
+    c_loss = ((ret - v.reshape(M)) ** 2).mean()
+    return a_loss, c_loss
+
+
+def ppo_loss_grad_reference(logits, v, ret, adv, logp_old, actions, beta=ENTROPY_BETA, clip=0.2):
+    """The closed-form gradient uavagent_ppo_loss_grad implements, in PyTorch (dtype of logits): uavagent_a2c_loss_grad's statements with
+    its td replaced by w = clipped ? 0 : rho adv in the chosen-action term and td = ret - v in the critic's:
+        gp_j = beta (log(p_j + e) + p_j / (p_j + e)) - [j == d] w / (p_d + e);   d a_loss / d z_j = p_j (gp_j - sum_i p_i gp_i) / M
+    -> (dlogits [M, A], dv [M], dbias [A], (a_loss, c_loss, sum(dv), clip_fraction, mean(logp_old - logp)))."""
+    M, A = logits.shape
+    p = torch.softmax(logits, dim=1)
+    d = actions.reshape(-1, 1).clamp(0, A - 1)
+    adv, ret, logp_old = (t.reshape(M).to(logits.dtype) for t in (adv, ret, logp_old))
+    lp = torch.log(p + 1e-5)
+    hot = torch.zeros_like(p).scatter_(1, d, 1.0)
+    logp = logp_joint(p, actions)                                               # the one statement of logp: unchanged logits give rho == 1
+    rho = torch.exp(logp - logp_old)
+    clipped = _ppo_clipped(rho, adv, clip)
+    w = torch.where(clipped, torch.zeros_like(rho), rho * adv)
+    gp = beta * (lp + p / (p + 1e-5)) - hot * (w.reshape(M, 1) / (p + 1e-5))
+    dot = (p * gp).sum(dim=1, keepdim=True)
+    dz = p * (gp - dot) / M
+    td = ret - v.reshape(M).to(logits.dtype)
+    dv = -2.0 * td / M
+    h = -(p * lp).sum(dim=1)
+    s = torch.where(clipped, rho.clamp(1.0 - clip, 1.0 + clip), rho) * adv
+    a_loss = (-s - beta * h).mean()
+    return dz, dv, dz.sum(dim=0), (a_loss, (td ** 2).mean(), dv.sum(), float(clipped.double().mean()), (logp_old - logp).mean())
+
+
 class TFRMSProp:
     """tf.train.RMSPropOptimizer(learning_rate) as TF1 implements it (main.py:300-301):
         ms <- decay * ms + (1 - decay) * g^2         (ms initialised to ONES)
@@ -288,7 +355,7 @@ N_ACTOR_PARAMS = 6
 
 
 class FlatParams:
-    """All parameters of an ACNet as views of ONE flat float32 buffer, their gradients as views of a second one and the RMSProp
+    """All parameters of an ACNet as views of ONE flat buffer (float32: the parameters' dtype), their gradients as views of a second one and the RMSProp
     mean squares in a third (every view starts on a 256-byte boundary; the padding stays zero).  One buffer = one all-reduce
     with no gather / scatter copies, one fused optimiser launch per trunk, one memset to clear the gradients.  Autograd
     accumulates into the existing .grad views in place, so the reference (autograd) path fills the same buffer."""
@@ -306,9 +373,10 @@ class FlatParams:
         self.n_flat = off
         self.n_real = sum(p.numel() for p in params)
         self.actor_end = offs[getattr(net, "N_ACTOR_PARAMS", N_ACTOR_PARAMS)]   # [0, actor_end) actor trunk, [actor_end, n_flat) critic trunk
-        self.w = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.g = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.ms = torch.ones(off, dtype=torch.float32, device=dev)    # TF1: accumulator initialised to ones (main.py:300-301)
+        dt = params[0].dtype            # float32; a net made .double() (CPU tests of the reference path) keeps its precision
+        self.w = torch.zeros(off, dtype=dt, device=dev)
+        self.g = torch.zeros(off, dtype=dt, device=dev)
+        self.ms = torch.ones(off, dtype=dt, device=dev)    # TF1: accumulator initialised to ones (main.py:300-301)
         self.gv = {}
         with torch.no_grad():
             for k, p, o in zip(order, params, offs):
@@ -469,10 +537,11 @@ class A2CRunner:
         self.stats = {}
         self._tuning_frozen = False
         self._fwd_valid = False
+        self._ppo = None              # while ppo_update's epochs run: adv / ret / logp_old of the batch and the clip; the loss hooks answer with the PPO form
 
     def _ms_view(self, key):
         p = getattr(self.net, key)
-        off = (p.data_ptr() - self.flat.w.data_ptr()) // 4
+        off = (p.data_ptr() - self.flat.w.data_ptr()) // self.flat.w.element_size()
         return self.flat.ms[off:off + p.numel()].view_as(p)
 
     @property
@@ -529,7 +598,13 @@ class A2CRunner:
     def _loss_grad(self, logits, v, target, actions, dv, dbias, loss, ws):
         from . import _agent_capi as A
 
-        A.a2c_loss_grad(logits, v, target, actions, self.beta, dv, dbias, loss, ws)
+        if self._ppo is not None:      # ``target`` (the n-step returns update_fused computed) is not used: the batch's GAE returns take its place
+            s, b = self._ppo, self._upd
+            if "ws_ppo" not in b:
+                b["ws_ppo"] = A.ppo_loss_grad_joint_workspace(self.net.n_action, self.dev)
+            A.ppo_loss_grad(logits, v, s["ret"], s["adv"], s["logp_old"], actions, self.beta, s["clip"], dv, dbias, loss, b["ws_ppo"])
+        else:
+            A.a2c_loss_grad(logits, v, target, actions, self.beta, dv, dbias, loss, ws)
 
     def _policy(self, t, lo, hi):
         """The actor's layer 2, policy head and action draw for the rows [lo, hi) of step t (GPU)."""
@@ -850,7 +925,9 @@ class A2CRunner:
             logits_pad = torch.zeros((M, ldl), dtype=torch.float32, device=dev)
         self._upd = {"M": M, "own": own, "h1a": fw["h1a"], "h1c": fw["h1c"], "h2a": fw["h2a"], "logits": logits_pad[:, :NA],
                      "logits_pad": logits_pad, "h2c": f(M, H), "dh": f(M, H),
-                     "gcat": f(M, 2 * H), "v": f(M), "dv": f(M), "target": f(M), "loss": torch.zeros(3, dtype=torch.float64, device=dev),
+                     "gcat": f(M, 2 * H), "v": f(M), "dv": f(M), "target": f(M),
+                     "loss": torch.zeros(5, dtype=torch.float64, device=dev),      # the A2C kernel writes three sums, the PPO kernel five
+                    
                      "ws_loss": self._loss_workspace(), "ws_relu": A.relu6_bwd_workspace(H, dev),
                      "ws_rows": A.rows_grad_workspace(M, K, 2 * H, self.net.n_state, dev)}
         if self.hip_gemms:
@@ -1027,7 +1104,21 @@ class A2CRunner:
 
     def _losses(self, a_prob, v, actions, v_target):
         """(a_loss, c_loss) of a chunk, for update_reference (a runner with another policy head states its own)."""
+        if self._ppo is not None:
+            return self._ppo_chunk(a_prob, v, actions, ppo_losses)
         return a2c_losses(a_prob, v, actions, v_target, self.beta)
+
+    def _ppo_chunk(self, prob, v, actions, losses):
+        """_losses in PPO mode.  update_reference hands its chunks over in row order: the cursor finds the chunk's rows of the batch."""
+        s = self._ppo
+        n, lo = prob.shape[0], s["cursor"]
+        s["cursor"] = lo + n
+        adv, logp_old = s["adv"][lo:lo + n], s["logp_old"][lo:lo + n]
+        with torch.no_grad():
+            dl = self._logp(prob, actions, False) - logp_old
+            s["n_clipped"] += float(_ppo_clipped(torch.exp(dl), adv, s["clip"]).sum())
+            s["kl_sum"] += float(-dl.sum())
+        return losses(prob, v, actions, adv, s["ret"][lo:lo + n], logp_old, self.beta, s["clip"])
 
     def train_rollout(self):
         stats = self.update(*self.collect())
@@ -1036,6 +1127,129 @@ class A2CRunner:
             # graph capture of the host application, or with another pick in another process)
             freeze_gemm_tuning()
             self._tuning_frozen = True
+        return stats
+
+    # ---- PPO (DESIGN.md sections 22 and 23; the MLP runners, joint and factored head): GAE(lambda) advantages, then several full-batch epochs of update() in PPO mode on one rollout ----------
+    @staticmethod
+    def _check_ppo(epochs, clip, lam):
+        if int(epochs) != epochs or int(epochs) < 1:
+            raise ValueError("epochs must be an integer >= 1")
+        if not 0.0 < float(clip) < 1.0:
+            raise ValueError("clip must be in (0, 1)")
+        if not 0.0 <= float(lam) <= 1.0:
+            raise ValueError("lam must be in [0, 1]")
+
+    PPO = True                    # cnn_agent.CnnA2CRunner: False (its update has no PPO form)
+
+    def _require_ppo(self):
+        if not self.PPO:
+            raise NotImplementedError("%s: ppo_rollout / ppo_update are built for the MLP runners (A2CRunner, factored.FactoredA2CRunner)"
+                                      % type(self).__name__)
+
+    def _logp(self, x, actions, fused):
+        """log pi(a | s) [M] of the actions taken: ``fused``: x = the logits on the GPU, by kernel; else x = the policy output, in PyTorch
+        (factored.FactoredA2CRunner states the product policy's pair)."""
+        if fused:
+            from . import _agent_capi as A
+
+            return A.logp(x, actions)
+        return logp_joint(x, actions)
+
+    def _normalize_adv(self, adv):
+        """adv <- (adv - mean) / (std + 1e-8) over the batch; with more than one rank over ALL ranks' rows: one all-reduce of (sum, sum of
+        squares, count) in float64."""
+        import torch.distributed as dist
+
+        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+            return (adv - adv.mean()) / (adv.std(unbiased=False) + 1e-8)
+        a64 = adv.double()
+        s = torch.stack([a64.sum(), (a64 * a64).sum(), torch.tensor(float(adv.numel()), dtype=torch.float64, device=adv.device)])
+        if s.is_cuda and dist.get_backend() == "gloo":      # (as _allreduce_bucket: through the host)
+            host = s.cpu()
+            dist.all_reduce(host, op=dist.ReduceOp.SUM)
+            s = host.to(adv.device)
+        else:
+            dist.all_reduce(s, op=dist.ReduceOp.SUM)
+        mean = s[0] / s[2]
+        std = (s[1] / s[2] - mean * mean).clamp_min(0.0).sqrt()
+        return ((a64 - mean) / (std + 1e-8)).to(adv.dtype)
+
+    def ppo_rollout(self, epochs=4, clip=0.2, lam=0.95, normalize_adv=True):
+        """One rollout and ``epochs`` full-batch updates of PPO on it: GAE(lam) advantages under the critic as it stands after the rollout,
+        log pi_old from the rollout's own logits, then per epoch the clipped surrogate (ratio clipped to 1 +- clip) with the entropy bonus for
+        the actor and the squared error against the GAE returns for the critic -- update()'s forward, backward, all-reduce and rmsprop_tf1
+        step as they stand, with the loss hooks in PPO mode.  ``normalize_adv``: adv <- (adv - mean) / (std + 1e-8) over the batch (of all ranks).
+        With epochs=1, lam=1, normalize_adv=False this is train_rollout()'s update up to float32 rounding.
+        Returns the last epoch's stats with ``clip_fraction``, ``approx_kl`` (mean(logp_old - logp)) and ``epochs`` added."""
+        self._require_ppo()
+        self._check_ppo(epochs, clip, lam)
+        return self.ppo_update(*self.collect(), epochs=epochs, clip=clip, lam=lam, normalize_adv=normalize_adv)
+
+    @torch.no_grad()
+    def _ppo_prepare(self, idx_buf, act_buf, rew_buf, boot, lam, normalize_adv, fused):
+        """(adv, ret, logp_old), float32 [M], of the batch under the weights as they stand.  ``fused``: libuavagent's logp and GAE kernels on the
+        rollout's own logits and critic rows (recomputed if an update has overwritten them); else the PyTorch statements."""
+        T, N, K = idx_buf.shape
+        M = T * N
+        idx, act = idx_buf.reshape(M, K), act_buf.reshape(M)
+        if fused:
+            from . import _agent_capi as A
+
+            net, b = self.net, self._ensure_update_buffers(M, K)
+            if not (b["own"] and self._fwd_valid and idx_buf.data_ptr() == self.idx_buf.data_ptr()):
+                rows_sum = self._gather_kernels()[0]
+                rows_sum(idx.contiguous(), net.a_w1, net.a_b1, net.c_w1, net.c_b1, relu6=True, out_a=b["h1a"], out_c=b["h1c"])
+                if self.hip_gemms:
+                    self._refresh_transposed()
+                    A.gemm_rows(b["h1a"], self._wt["a_w2t"], b["h2a"], w_transposed=True, bias=net.a_b2, relu6=True)
+                    A.gemm_rows(b["h2a"], self._wt["a_w3t"], b["logits_pad"], w_transposed=True, bias=self._wt["a_b3p"])
+                else:
+                    torch.addmm(net.a_b2, b["h1a"], net.a_w2, out=b["h2a"]).clamp_(0.0, 6.0)
+                    torch.addmm(net.a_b3, b["h2a"], net.a_w3, out=b["logits"])
+                # the update's buffers now hold this batch's forward pass under the current weights: epoch 0 reuses it where they are the rollout's
+                self._fwd_valid = b["own"] and idx_buf.data_ptr() == self.idx_buf.data_ptr()
+            logp_old = self._logp(b["logits"], act.contiguous(), True)
+            if self.hip_gemms:
+                A.gemm_rows(b["h1c"], self._wt["c_w2t"], b["h2c"], w_transposed=True, bias=net.c_b2, relu6=True)
+            else:
+                torch.addmm(net.c_b2, b["h1c"], net.c_w2, out=b["h2c"]).clamp_(0.0, 6.0)
+            A.rowdot(b["h2c"], net.c_w3, net.c_b3, b["v"])
+            adv, ret = A.gae(rew_buf.contiguous(), b["v"].view(T, N), boot.contiguous(), self.gamma, lam)
+        else:
+            net, logp_old, values = self.net, [], []
+            for s in range(0, M, self.update_chunk):
+                e = min(M, s + self.update_chunk)
+                logp_old.append(self._logp(net.actor_only(idx[s:e]), act[s:e], False))
+                values.append(net.critic_only(idx[s:e]).reshape(-1))
+            logp_old = torch.cat(logp_old)
+            adv, ret = gae_reference(rew_buf, torch.cat(values).view(T, N), boot, self.gamma, lam)
+        adv, ret = adv.reshape(M), ret.reshape(M)
+        if normalize_adv:
+            adv = self._normalize_adv(adv)
+        return adv.contiguous(), ret.contiguous(), logp_old
+
+    def ppo_update(self, idx_buf, act_buf, rew_buf, boot, epochs=4, clip=0.2, lam=0.95, normalize_adv=True, fused=None):
+        """ppo_rollout's update on a collected batch.  ``fused``: None = update()'s choice, True / False = the kernels and update_fused /
+        the PyTorch statements and update_reference."""
+        self._require_ppo()
+        self._check_ppo(epochs, clip, lam)
+        if fused is None:
+            fused = self.fused_update and self.dev.type == "cuda"
+        adv, ret, logp_old = self._ppo_prepare(idx_buf, act_buf, rew_buf, boot, float(lam), bool(normalize_adv), fused)
+        self._ppo = {"adv": adv, "ret": ret, "logp_old": logp_old, "clip": float(clip)}
+        try:
+            for _ in range(int(epochs)):
+                self._ppo.update(cursor=0, n_clipped=0.0, kl_sum=0.0)
+                stats = (self.update_fused if fused else self.update_reference)(idx_buf, act_buf, rew_buf, boot)
+                self._fwd_valid = False                                    # the weights have moved: later epochs recompute the forward pass
+                if fused:
+                    loss = self._upd["loss"].cpu()
+                    stats["clip_fraction"], stats["approx_kl"] = float(loss[3]), float(loss[4])
+                else:
+                    stats["clip_fraction"], stats["approx_kl"] = self._ppo["n_clipped"] / adv.numel(), self._ppo["kl_sum"] / adv.numel()
+            stats["epochs"] = int(epochs)
+        finally:
+            self._ppo = None
         return stats
 
     # ---- checkpoint / resume (SURVEY.md section 5: the reference saves the actor only and cannot resume) -------------------------------

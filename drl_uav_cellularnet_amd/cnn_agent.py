@@ -218,6 +218,7 @@ class CnnA2CRunner(A2CRunner):
     activations at 8192 envs; an 8192 x 50 update runs in 100 chunks.  One process only: a process group of more than one rank is refused."""
 
     NET_KIND = "cnn"
+    PPO = False                   # ppo_rollout / ppo_update raise NotImplementedError: PPO is built for the MLP runners
 
     def __init__(self, env, net=None, rollout=50, gamma=GAMMA, beta=ENTROPY_BETA, lr_a=LR_A, lr_c=LR_C, seed=6, update_chunk=4096,
                  first_state="obs", fused_update=True):

@@ -76,6 +76,18 @@ __device__ __forceinline__ int greedy_wave(float bv, int bi) {
     }
     return bi < 0 ? 0 : bi;
 }
+// Sum / maximum of one value per lane over the 64 lanes of a wavefront, in every lane: a fixed butterfly (agent_learner.hip's loss, draw and
+// row-dot kernels and agent_ppo_joint.hip's; the same order in all of them, so equal inputs give equal bits).
+__device__ __forceinline__ float wave_sum_f(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ float wave_max_f(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
 // ---- the first layer's gather (agent_kernels.hip: <= 64 nodes, one wavefront pass; agent_wide.hip: <= 256 nodes) ----
 __device__ __forceinline__ void add4(float4 &s, const float4 &v) { s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
 // s += v * w with w in {0.0f, 1.0f} held in an SGPR: one v_fmac per component, like the add it replaces; v * 1 + s rounds exactly

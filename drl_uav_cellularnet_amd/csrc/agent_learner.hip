@@ -27,16 +27,7 @@ namespace {
 
 int fail2(int code, const std::string &msg) { return uavagent_internal::fail(code, msg); }   // one error string for both parts
 
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
+// (wave_sum_f / wave_max_f: agent_common.h)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // obs_indices: one thread per (env, node).  Node k < B: UAV k, plane 0; else UE k-B in plane 1 + serving UAV.

@@ -19,7 +19,7 @@ advantages and several clipped-surrogate epochs per rollout on the kernels of cs
 """
 import torch
 
-from .agent import ENTROPY_BETA, HIDDEN, A2CRunner, ACNet
+from .agent import ENTROPY_BETA, HIDDEN, A2CRunner, ACNet, _ppo_clipped, gae_reference      # noqa: F401 (gae_reference stays importable from here)
 from .cnn_agent import CnnA2CRunner, CnnACNet, _logits_cuda, _trunks_cuda, _value_cuda
 
 N_ACT = 5     # mobile_env.py:21
@@ -102,30 +102,12 @@ def loss_grad_factored_reference(logits, v, v_target, actions, n_heads, n_act=N_
 
 
 # ---- PPO: GAE(lambda) advantages and the clipped surrogate in place of the chosen-action term -----------------------
-def gae_reference(rewards, values, bootstrap, gamma, lam):
-    """GAE(lambda) as uavagent_gae_f32 computes it, in the dtype of rewards: rewards and values [T, N], bootstrap [N] (0 where the episode
-    ended);  delta[t] = r[t] + gamma v[t+1] - v[t] with v[T] := bootstrap;  adv[t] = delta[t] + gamma lam adv[t+1];  ret = adv + v.
-    -> (adv, ret).  lam = 1: ret is agent.nstep_returns; lam = 0: adv is the one-step TD error."""
-    T = rewards.shape[0]
-    values = values.to(rewards.dtype)
-    adv, run, next_v = torch.empty_like(rewards), torch.zeros_like(rewards[0]), bootstrap.to(rewards.dtype)
-    for t in range(T - 1, -1, -1):
-        run = (rewards[t] + gamma * next_v) - values[t] + (gamma * lam) * run
-        adv[t] = run
-        next_v = values[t]
-    return adv, adv + values
-
-
 def logp_factored(head_prob, actions):
     """log pi(a | s) = sum_b log(p_b[d_b] + 1e-5) of the JOINT actions [M] under head_prob [M, B, A] (the kernel's clamp of the actions) -> [M]."""
     p = _heads(head_prob)
     M, B, A = p.shape
     d = joint_to_digits(actions.reshape(-1).clamp(0, A ** B - 1), B, A)
     return torch.log(p.gather(2, d.unsqueeze(2)).squeeze(2) + 1e-5).sum(dim=1)
-
-
-def _ppo_clipped(rho, adv, clip):
-    return ((adv > 0) & (rho > 1.0 + clip)) | ((adv < 0) & (rho < 1.0 - clip))
 
 
 def ppo_losses_factored(head_prob, v, actions, adv, ret, logp_old, beta=ENTROPY_BETA, clip=0.2):
@@ -362,7 +344,6 @@ class FactoredA2CRunner(A2CRunner):
         self.u_buf = torch.empty((self.T, env.n_envs, net.n_heads), dtype=torch.float32, device=self.dev)
         self._imit = None             # "hard" / "soft" while imitate_rollout's update runs: the loss hooks answer with the imitation form
         self._imit_marks = None       # tools/bench_imitate.py: a list makes the imitation rollout record (phase, event) pairs into it
-        self._ppo = None              # while ppo_update's epochs run: adv / ret / logp_old of the batch and the clip; the loss hooks answer with the PPO form
 
     def _gather_kernels(self):
         from . import _agent_capi as A
@@ -386,6 +367,14 @@ class FactoredA2CRunner(A2CRunner):
 
         return A.loss_grad_factored_workspace(self.net.n_heads, self.net.n_act, self.dev)
 
+    def _logp(self, x, actions, fused):
+        net = self.net
+        if fused:
+            from . import _agent_capi as A
+
+            return A.logp_factored(x, actions, net.n_heads, net.n_act)
+        return logp_factored(x.reshape(-1, net.n_heads, net.n_act), actions)
+
     def _loss_grad(self, logits, v, target, actions, dv, dbias, loss, ws):
         from . import _agent_capi as A
 
@@ -404,16 +393,8 @@ class FactoredA2CRunner(A2CRunner):
     def _losses(self, a_prob, v, actions, v_target):
         net = self.net
         prob = a_prob.reshape(-1, net.n_heads, net.n_act)
-        if self._ppo is not None:      # update_reference hands its chunks over in row order: the cursor finds the chunk's rows of the batch
-            s = self._ppo
-            n, lo = prob.shape[0], s["cursor"]
-            s["cursor"] = lo + n
-            adv, logp_old = s["adv"][lo:lo + n], s["logp_old"][lo:lo + n]
-            with torch.no_grad():
-                dl = logp_factored(prob, actions) - logp_old
-                s["n_clipped"] += float(_ppo_clipped(torch.exp(dl), adv, s["clip"]).sum())
-                s["kl_sum"] += float(-dl.sum())
-            return ppo_losses_factored(prob, v, actions, adv, s["ret"][lo:lo + n], logp_old, self.beta, s["clip"])
+        if self._ppo is not None:
+            return self._ppo_chunk(prob, v, actions, ppo_losses_factored)
         if self._imit is None:
             return a2c_losses_factored(prob, v, actions, v_target, self.beta)
         # update_reference hands its chunks over in row order: the cursor finds the chunk's rows of q_buf
@@ -555,90 +536,4 @@ class FactoredA2CRunner(A2CRunner):
             stats["agreement"] = float(self._upd["loss"][3]) if fused else self._imit_agree / self.label_buf.numel()
         finally:
             self._imit = None
-        return stats
-
-    # ---- PPO: GAE(lambda) advantages, then several full-batch epochs of update() in PPO mode on one rollout ----------
-    @staticmethod
-    def _check_ppo(epochs, clip, lam):
-        if int(epochs) != epochs or int(epochs) < 1:
-            raise ValueError("epochs must be an integer >= 1")
-        if not 0.0 < float(clip) < 1.0:
-            raise ValueError("clip must be in (0, 1)")
-        if not 0.0 <= float(lam) <= 1.0:
-            raise ValueError("lam must be in [0, 1]")
-
-    def ppo_rollout(self, epochs=4, clip=0.2, lam=0.95, normalize_adv=True):
-        """One rollout and ``epochs`` full-batch updates of PPO on it: GAE(lam) advantages under the critic as it stands after the rollout,
-        log pi_old from the rollout's own logits, then per epoch the clipped surrogate (ratio clipped to 1 +- clip) with the entropy bonus for
-        the actor and the squared error against the GAE returns for the critic -- update()'s forward, backward, all-reduce and rmsprop_tf1
-        step as they stand, with the loss hooks in PPO mode.  ``normalize_adv``: adv <- (adv - mean) / (std + 1e-8) over the batch.
-        With epochs=1, lam=1, normalize_adv=False this is train_rollout()'s update up to float32 rounding.
-        Returns the last epoch's stats with ``clip_fraction``, ``approx_kl`` (mean(logp_old - logp)) and ``epochs`` added."""
-        self._check_ppo(epochs, clip, lam)
-        return self.ppo_update(*self.collect(), epochs=epochs, clip=clip, lam=lam, normalize_adv=normalize_adv)
-
-    @torch.no_grad()
-    def _ppo_prepare(self, idx_buf, act_buf, rew_buf, boot, lam, normalize_adv, fused):
-        """(adv, ret, logp_old), float32 [M], of the batch under the weights as they stand.  ``fused``: libuavagent's logp and GAE kernels on the
-        rollout's own logits and critic rows (recomputed if an update has overwritten them); else the PyTorch statements."""
-        T, N, K = idx_buf.shape
-        M = T * N
-        idx, act = idx_buf.reshape(M, K), act_buf.reshape(M)
-        if fused:
-            from . import _agent_capi as A
-
-            net, b = self.net, self._ensure_update_buffers(M, K)
-            if not (b["own"] and self._fwd_valid and idx_buf.data_ptr() == self.idx_buf.data_ptr()):
-                rows_sum = self._gather_kernels()[0]
-                rows_sum(idx.contiguous(), net.a_w1, net.a_b1, net.c_w1, net.c_b1, relu6=True, out_a=b["h1a"], out_c=b["h1c"])
-                if self.hip_gemms:
-                    self._refresh_transposed()
-                    A.gemm_rows(b["h1a"], self._wt["a_w2t"], b["h2a"], w_transposed=True, bias=net.a_b2, relu6=True)
-                    A.gemm_rows(b["h2a"], self._wt["a_w3t"], b["logits_pad"], w_transposed=True, bias=self._wt["a_b3p"])
-                else:
-                    torch.addmm(net.a_b2, b["h1a"], net.a_w2, out=b["h2a"]).clamp_(0.0, 6.0)
-                    torch.addmm(net.a_b3, b["h2a"], net.a_w3, out=b["logits"])
-                # the update's buffers now hold this batch's forward pass under the current weights: epoch 0 reuses it where they are the rollout's
-                self._fwd_valid = b["own"] and idx_buf.data_ptr() == self.idx_buf.data_ptr()
-            logp_old = A.logp_factored(b["logits"], act.contiguous(), net.n_heads, net.n_act)
-            if self.hip_gemms:
-                A.gemm_rows(b["h1c"], self._wt["c_w2t"], b["h2c"], w_transposed=True, bias=net.c_b2, relu6=True)
-            else:
-                torch.addmm(net.c_b2, b["h1c"], net.c_w2, out=b["h2c"]).clamp_(0.0, 6.0)
-            A.rowdot(b["h2c"], net.c_w3, net.c_b3, b["v"])
-            adv, ret = A.gae(rew_buf.contiguous(), b["v"].view(T, N), boot.contiguous(), self.gamma, lam)
-        else:
-            net, logp_old, values = self.net, [], []
-            for s in range(0, M, self.update_chunk):
-                e = min(M, s + self.update_chunk)
-                logp_old.append(logp_factored(net.actor_only(idx[s:e]).reshape(-1, net.n_heads, net.n_act), act[s:e]))
-                values.append(net.critic_only(idx[s:e]).reshape(-1))
-            logp_old = torch.cat(logp_old)
-            adv, ret = gae_reference(rew_buf, torch.cat(values).view(T, N), boot, self.gamma, lam)
-        adv, ret = adv.reshape(M), ret.reshape(M)
-        if normalize_adv:
-            adv = (adv - adv.mean()) / (adv.std(unbiased=False) + 1e-8)
-        return adv.contiguous(), ret.contiguous(), logp_old
-
-    def ppo_update(self, idx_buf, act_buf, rew_buf, boot, epochs=4, clip=0.2, lam=0.95, normalize_adv=True, fused=None):
-        """ppo_rollout's update on a collected batch.  ``fused``: None = update()'s choice, True / False = the kernels and update_fused /
-        the PyTorch statements and update_reference."""
-        self._check_ppo(epochs, clip, lam)
-        if fused is None:
-            fused = self.fused_update and self.dev.type == "cuda"
-        adv, ret, logp_old = self._ppo_prepare(idx_buf, act_buf, rew_buf, boot, float(lam), bool(normalize_adv), fused)
-        self._ppo = {"adv": adv, "ret": ret, "logp_old": logp_old, "clip": float(clip)}
-        try:
-            for _ in range(int(epochs)):
-                self._ppo.update(cursor=0, n_clipped=0.0, kl_sum=0.0)
-                stats = (self.update_fused if fused else self.update_reference)(idx_buf, act_buf, rew_buf, boot)
-                self._fwd_valid = False                                    # the weights have moved: later epochs recompute the forward pass
-                if fused:
-                    loss = self._upd["loss"].cpu()
-                    stats["clip_fraction"], stats["approx_kl"] = float(loss[3]), float(loss[4])
-                else:
-                    stats["clip_fraction"], stats["approx_kl"] = self._ppo["n_clipped"] / adv.numel(), self._ppo["kl_sum"] / adv.numel()
-            stats["epochs"] = int(epochs)
-        finally:
-            self._ppo = None
         return stats

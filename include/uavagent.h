@@ -311,6 +311,34 @@ int uavagent_ppo_loss_grad_factored(float *logits_inout, int64_t ld_logits, cons
                                     float beta, float clip, float *dv_out, float *dbias_out, double *loss_out /* [5] */,
                                     void *workspace, void *stream);
 
+/* ---- PPO for the joint head, one softmax over n_actions <= 1024 columns (csrc/agent_ppo_joint.hip; additive to ABI 5, the number stays;
+ * DESIGN.md section 23).  Layout and launch shape of uavagent_a2c_loss_grad: one wavefront per row at a time, lane l owns columns (or
+ * float4s) l, l + 64, ...; a fixed grid and a fixed order of every sum: bit-reproducible.  Both entry points choose between the dword form
+ * (library expf / logf, IEEE division) and the float4 form (hardware exp2 / log / rcp, next-row prefetch) by that function's rule: float4 when
+ * `logits` is 16-byte aligned, ld_logits % 4 == 0 and ld_logits >= roundup4(n_actions).  Given the same pointer, ld and n_actions the two
+ * pick the same form, and a row's softmax and log(p_d + 1e-5) are one device function per form: on the same logits and actions they hold
+ * the same bits.  Actions outside [0, n_actions) are clamped into it, never used as an index.  Refused before any HIP call: n_actions
+ * outside [1, 1024], negative rows, ld_logits < n_actions, clip outside (0, 1) or not finite, and (with at least one row) a null pointer.
+ * Zero rows: no launch, nothing written. ---- */
+
+/* logp_out[r] = log(p_d + 1e-5), p = softmax(logits[r, 0 .. n_actions)), d = actions[r]. */
+int uavagent_logp_f32(const float *logits, int64_t ld_logits, const int64_t *actions, int64_t n_rows, int32_t n_actions, float *logp_out,
+                      void *stream);
+
+/* The clipped surrogate with one softmax per row.  lp = log(p_d + 1e-5);  rho = exp(lp - logp_old);  the row is clipped when (adv > 0 and
+ * rho > 1 + clip) or (adv < 0 and rho < 1 - clip);  s = clipped ? clamp(rho, 1 - clip, 1 + clip) * adv : rho * adv;
+ *   a_loss = mean(-s - beta * H),  H = -sum_j p_j log(p_j + 1e-5);  c_loss = mean((ret - v)^2);  dv = -2 (ret - v) / M;
+ *   gp_j = beta (log(p_j + e) + p_j / (p_j + e)) - [j == d] w / (p_d + e),  w = clipped ? 0 : rho * adv;
+ *   d a_loss / d logit_j = p_j (gp_j - sum_i p_i gp_i) / M         -- uavagent_a2c_loss_grad's statements with its td replaced by w:
+ * with logp_old == lp (uavagent_logp_f32 on the same buffer), v == 0 and ret == adv the gradient, dbias, dv, c_loss and sum(dv) are that
+ * function's at v_target = adv, bit for bit.  IN / OUT as there (the float4 form writes zeros into columns [n_actions, roundup4(n_actions)),
+ * no other column >= n_actions is touched); loss_out double[5] = {a_loss, c_loss, sum(dv), clip_fraction, mean(logp_old - lp)}.
+ * `workspace`: uavagent_ppo_loss_grad_workspace_bytes(n_actions) bytes (0 = n_actions not served), 8-byte aligned. */
+size_t uavagent_ppo_loss_grad_workspace_bytes(int32_t n_actions);
+int uavagent_ppo_loss_grad(float *logits_inout, int64_t ld_logits, const float *v, const float *ret, const float *adv, const float *logp_old,
+                           const int64_t *actions, int64_t m_rows, int32_t n_actions, float beta, float clip, float *dv_out,
+                           float *dbias_out, double *loss_out /* [5] */, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

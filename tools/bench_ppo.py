@@ -9,7 +9,13 @@ process, the two sides of every pair taken in turns after one untimed turn:
 Every repeat is kept, with minimum, median and maximum, and the ratio of every pair per repeat with the same spread.  No threshold.
 Writes profiles/ppo_bench.json and prints it as one line.
 
-  python tools/bench_ppo.py [--rollout 50] [--repeats 7] [--inner 20]"""
+--joint: the same method for the joint 625-way head (A2CRunner.ppo_rollout) instead:
+  kernels, at M = 409 600 rows, A = 625, ld = 640 (8192 envs x 50 steps of 4 UAVs; the float4 form): uavagent_ppo_loss_grad against
+    uavagent_a2c_loss_grad, and uavagent_logp_f32 alone;
+  rollouts, at 8192 envs x 4 UAV x 40 UE, G = 100: ppo_rollout(epochs=1) and ppo_rollout(epochs=4) against train_rollout.
+Writes profiles/ppo_joint_bench.json.
+
+  python tools/bench_ppo.py [--joint] [--rollout 50] [--repeats 7] [--inner 20]"""
 import argparse
 import json
 import os
@@ -21,6 +27,8 @@ sys.path.insert(0, ROOT)
 KERNEL_SHAPES = [(51200, 16), (409600, 4)]
 ROLLOUT_SHAPE = (1024, 16, 200)
 N_ACT = 5
+JOINT_KERNEL_SHAPE = (409600, 625, 640)      # rows, actions, row stride of the logits
+JOINT_ROLLOUT_SHAPE = (8192, 4, 40)
 
 
 def spread(v):
@@ -37,12 +45,16 @@ def main():
     ap.add_argument("--rollout", type=int, default=50)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--inner", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ppo_bench.json"))
+    ap.add_argument("--joint", action="store_true", help="the joint 625-way head (A2CRunner) instead of the factored one")
+    ap.add_argument("--out", default=None, help="default: profiles/ppo_bench.json, with --joint profiles/ppo_joint_bench.json")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "ppo_joint_bench.json" if a.joint else "ppo_bench.json")
     import torch
 
     from drl_uav_cellularnet_amd import BatchedMobiEnv
     from drl_uav_cellularnet_amd import _agent_capi as A
+    from drl_uav_cellularnet_amd.agent import A2CRunner
     from drl_uav_cellularnet_amd.factored import FactoredA2CRunner
 
     dev, T = "cuda:0", a.rollout
@@ -61,6 +73,79 @@ def main():
             pairs.append((e0, e1))
         torch.cuda.synchronize()
         return sorted(p.elapsed_time(q) for p, q in pairs)[a.inner // 2] * 1e3
+
+    def timed(fn):
+        e0, e1 = ev(), ev()
+        e0.record()
+        st = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), st
+
+    def rollouts(runners):
+        """train_rollout / ppo_rollout(epochs=1) / ppo_rollout(epochs=4) of three runners of one shape, in turns -> (ms per call, last stats)."""
+        forms = {"a2c": lambda: timed(runners["a2c"].train_rollout), "ppo1": lambda: timed(lambda: runners["ppo1"].ppo_rollout(epochs=1)),
+                 "ppo4": lambda: timed(lambda: runners["ppo4"].ppo_rollout(epochs=4))}
+        raw, last = {k: [] for k in forms}, {}
+        for rep in range(a.repeats + 1):                                    # turn 0 is untimed: graph capture, allocations, first launches
+            for k, fn in forms.items():
+                t, last[k] = fn()
+                if rep > 0:
+                    raw[k].append(t)
+        return raw, {k: {s: last[k].get(s) for s in ("a_loss", "c_loss", "clip_fraction", "approx_kl", "mean_reward")} for k in last}
+
+    def finish(result, runners):
+        line = json.dumps(result)
+        print(line, flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+        for r in runners.values():
+            r.env.close()
+
+    if a.joint:
+        M, NA, LD = JOINT_KERNEL_SHAPE
+        g = torch.Generator().manual_seed(23)
+        src = torch.zeros(M, LD, device=dev)
+        src[:, :NA] = (torch.randn(M, NA, generator=g) * 2).to(dev)
+        work = torch.empty_like(src)
+        v, ret, adv = (torch.randn(M, generator=g).to(dev) for _ in range(3))
+        act = torch.randint(0, NA, (M,), generator=g).to(dev)
+        old = src.clone()
+        old[:, :NA] += (torch.randn(M, NA, generator=g) * 0.3).to(dev)
+        logp_old = A.logp(old[:, :NA], act)                                 # about a quarter of the rows clipped, as in the tests
+        del old
+        dv, db = torch.empty(M, device=dev), torch.empty(NA, device=dev)
+        loss = torch.zeros(5, dtype=torch.float64, device=dev)
+        ws_p, ws_a = A.ppo_loss_grad_joint_workspace(NA, dev), A.loss_grad_workspace(NA, dev)
+        restore = lambda: work.copy_(src)
+        forms = {
+            "ppo_loss": lambda: median_us(lambda: A.ppo_loss_grad(work[:, :NA], v, ret, adv, logp_old, act, 0.001, 0.2, dv, db, loss, ws_p), restore),
+            "a2c_loss": lambda: median_us(lambda: A.a2c_loss_grad(work[:, :NA], v, ret, act, 0.001, dv, db, loss, ws_a), restore),
+            "logp": lambda: median_us(lambda: A.logp(src[:, :NA], act, out=dv)),
+        }
+        raw = {k: [] for k in forms}
+        for rep in range(a.repeats + 1):                                    # turn 0 is untimed: first launches
+            for k, fn in forms.items():
+                t = fn()
+                if rep > 0:
+                    raw[k].append(t)
+        restore()
+        A.ppo_loss_grad(work[:, :NA], v, ret, adv, logp_old, act, 0.001, 0.2, dv, db, loss, ws_p)
+        result = {"bench": "ppo_joint", "rollout": T, "repeats": a.repeats, "inner": a.inner, "device": torch.cuda.get_device_name(0),
+                  "kernels_us": {"rows": M, "n_actions": NA, "ld": LD, "form": "float4", "clip_fraction_of_the_inputs": float(loss[3]),
+                                 "bytes_moved_a2c": 2 * M * LD * 4 + M * 20, "bytes_moved_ppo": 2 * M * LD * 4 + M * 28,
+                                 "ppo_loss_over_a2c_loss": pair(raw["ppo_loss"], raw["a2c_loss"]), "logp": spread(raw["logp"])}}
+        del src, work
+        N, B, U = JOINT_ROLLOUT_SHAPE
+        runners = {k: A2CRunner(BatchedMobiEnv(N, nBS=B, nUE=U, grid_n=100, device=dev), rollout=T) for k in ("a2c", "ppo1", "ppo4")}
+        raw, last = rollouts(runners)
+        result["rollouts_ms"] = {"envs": N, "n_bs": B, "n_ue": U, "grid": 100, "rollout_form": "persistent" if runners["a2c"]._persistent else
+                                 ("halves" if runners["a2c"]._halves else "plain"),
+                                 "ppo_epochs_1_over_train_rollout": pair(raw["ppo1"], raw["a2c"]),
+                                 "ppo_epochs_4_over_train_rollout": pair(raw["ppo4"], raw["a2c"]), "last_stats": last}
+        finish(result, runners)
+        return
 
     result = {"bench": "ppo", "n_act": N_ACT, "rollout": T, "repeats": a.repeats, "inner": a.inner, "device": torch.cuda.get_device_name(0),
               "kernels_us": [], "rollouts_ms": None}
@@ -101,34 +186,12 @@ def main():
     N, B, U = ROLLOUT_SHAPE
     runners = {k: FactoredA2CRunner(BatchedMobiEnv(N, nBS=B, nUE=U, grid_n=100, device=dev), rollout=T) for k in ("a2c", "ppo1", "ppo4")}
 
-    def timed(fn):
-        e0, e1 = ev(), ev()
-        e0.record()
-        st = fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1), st
-
-    forms = {"a2c": lambda: timed(runners["a2c"].train_rollout), "ppo1": lambda: timed(lambda: runners["ppo1"].ppo_rollout(epochs=1)),
-             "ppo4": lambda: timed(lambda: runners["ppo4"].ppo_rollout(epochs=4))}
-    raw, last = {k: [] for k in forms}, {}
-    for rep in range(a.repeats + 1):                                        # turn 0 is untimed: graph capture, allocations, first launches
-        for k, fn in forms.items():
-            t, last[k] = fn()
-            if rep > 0:
-                raw[k].append(t)
+    raw, last = rollouts(runners)
     result["rollouts_ms"] = {"envs": N, "n_bs": B, "n_ue": U, "grid": 100,
                              "ppo_epochs_1_over_train_rollout": pair(raw["ppo1"], raw["a2c"]),
                              "ppo_epochs_4_over_train_rollout": pair(raw["ppo4"], raw["a2c"]),
-                             "last_stats": {k: {s: last[k].get(s) for s in ("a_loss", "c_loss", "clip_fraction", "approx_kl", "mean_reward")}
-                                            for k in last}}
-    line = json.dumps(result)
-    print(line, flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
-    for r in runners.values():
-        r.env.close()
+                             "last_stats": last}
+    finish(result, runners)
 
 
 if __name__ == "__main__":

@@ -11,6 +11,7 @@ actor parameters (Global_A_PARA: here a named .npz, agent.save_actor_npz -- load
                                                    # the first 2 episodes imitate the coordinate search (imitate_rollout), then A2C
   python tools/train_a2c.py --net mlp-factored --n-bs 16 --n-ue 200 --workers 1024 --algo ppo --ppo-epochs 4 --ppo-clip 0.2 --gae-lambda 0.95
                                                    # PPO in place of A2C: GAE advantages, 4 clipped-surrogate epochs per rollout (ppo_rollout)
+  python tools/train_a2c.py --net mlp --workers 8192 --algo ppo --ppo-epochs 4  # PPO for the joint 625-way head (A2CRunner.ppo_rollout)
   python -m torch.distributed.run --nproc-per-node 8 tools/train_a2c.py ...     # one process per GPU, gradients all-reduced (RCCL)"""
 import argparse
 import json
@@ -82,6 +83,19 @@ def algo_refusal(checkpoint, algo):
     return None
 
 
+PPO_NETS = ("mlp", "mlp-factored")      # the runners with ppo_rollout (the CNN runners raise NotImplementedError)
+
+
+def ppo_flags_error(net, algo, ppo_epochs, ppo_clip, gae_lambda):
+    """What is wrong with --algo / --ppo-epochs / --ppo-clip / --gae-lambda for this --net, or None."""
+    ppo_flags = algo != "a2c" or ppo_epochs != 4 or ppo_clip != 0.2 or gae_lambda != 0.95
+    if ppo_flags and net not in PPO_NETS:
+        return "--algo / --ppo-epochs / --ppo-clip / --gae-lambda are for --net mlp and --net mlp-factored"
+    if ppo_epochs < 1 or not 0.0 < ppo_clip < 1.0 or not 0.0 <= gae_lambda <= 1.0:
+        return "--ppo-epochs must be >= 1, --ppo-clip in (0, 1) and --gae-lambda in [0, 1]"
+    return None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="train/run")
@@ -111,9 +125,9 @@ def main():
                     "(default: hard labels)")
     ap.add_argument("--teacher-shaped", action="store_true", help="the teacher values its candidates under the chosen reward "
                     "(imitate_rollout(shaped_teacher=True)): needs a reward flag and --teacher coordinate or search")
-    ap.add_argument("--algo", choices=("a2c", "ppo"), default="a2c", help="mlp-factored: the update after the imitation episodes -- a2c "
-                    "(train_rollout: n-step returns, one gradient step per rollout) or ppo (FactoredA2CRunner.ppo_rollout: GAE advantages, "
-                    "several clipped-surrogate epochs per rollout)")
+    ap.add_argument("--algo", choices=("a2c", "ppo"), default="a2c", help="mlp and mlp-factored: the update (after the imitation episodes) -- a2c "
+                    "(train_rollout: n-step returns, one gradient step per rollout) or ppo (ppo_rollout: GAE advantages, several "
+                    "clipped-surrogate epochs per rollout)")
     ap.add_argument("--ppo-epochs", type=int, default=4, help="--algo ppo: full-batch epochs per rollout")
     ap.add_argument("--ppo-clip", type=float, default=0.2, help="--algo ppo: the probability ratio is clipped to 1 +- this")
     ap.add_argument("--gae-lambda", type=float, default=0.95, help="--algo ppo: lambda of the advantage estimate")
@@ -135,11 +149,9 @@ def main():
         ap.error("--imitate-episodes must be >= 0 and --imitate-mix in [0, 1]")
     if a.imitate_tau is not None and (a.teacher != "coordinate" or not a.imitate_tau > 0):
         ap.error("--imitate-tau must be > 0 and needs --teacher coordinate")
-    ppo_flags = a.algo != "a2c" or a.ppo_epochs != 4 or a.ppo_clip != 0.2 or a.gae_lambda != 0.95
-    if ppo_flags and a.net != "mlp-factored":
-        ap.error("--algo / --ppo-epochs / --ppo-clip / --gae-lambda are for --net mlp-factored")
-    if a.ppo_epochs < 1 or not 0.0 < a.ppo_clip < 1.0 or not 0.0 <= a.gae_lambda <= 1.0:
-        ap.error("--ppo-epochs must be >= 1, --ppo-clip in (0, 1) and --gae-lambda in [0, 1]")
+    msg = ppo_flags_error(a.net, a.algo, a.ppo_epochs, a.ppo_clip, a.gae_lambda)
+    if msg:
+        ap.error(msg)
     import numpy as np
     import torch
 
@@ -216,6 +228,8 @@ def main():
                     line["agreement"] = agree                               # the teacher agreement of every rollout of the episode
                 elif a.algo == "ppo":                                      # the last epoch's figures, averaged over the episode's rollouts
                     line.update({"clip_fraction": sum(clip_frac) / len(clip_frac), "approx_kl": sum(kl) / len(kl)})
+            elif a.algo == "ppo":
+                line.update({"phase": "ppo", "clip_fraction": sum(clip_frac) / len(clip_frac), "approx_kl": sum(kl) / len(kl)})
             print(json.dumps(line), flush=True)
         if a.checkpoint_every and (ep + 1) % a.checkpoint_every == 0:
             save_checkpoint(torch, world, ckpt, {"runner": runner.state_dict(), "reward": None if reward is None else reward.as_dict(),
