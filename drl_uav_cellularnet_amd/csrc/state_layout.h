@@ -60,4 +60,18 @@ UAVENV_HD StateOffsets compute_layout(long long n_envs, int n_ue, int n_bs, int 
     return L;
 }
 
+// Multi-step launches whose kernels address their [T][...] outputs as `base + 32-bit byte offset` (uavenv_kernels.h: OutOffs): is every
+// byte of a T-step launch within such an offset?  The largest output is ue_xy / cur_sinr, T x N x U x 4 bytes; the cell blocks the step
+// loop reads are T x N x B x 8 bytes.  Both must be BELOW 2^32: an offset is at most the array's size minus the access's.
+inline bool many_steps_in_range(long long n_steps, long long n_envs, long long n_ue, long long n_bs) {
+    const unsigned long long lim = 1ull << 32, block = (unsigned long long)n_envs * (unsigned long long)(4 * n_ue > 8 * n_bs ? 4 * n_ue : 8 * n_bs);
+    return n_steps <= 0 || block == 0 || (block < lim && (unsigned long long)n_steps <= (lim - 1) / block);
+}
+// The most steps of such a launch (at least 1: one step is what a single-step launch addresses, and uavenv_create admits no array above 4 GiB).
+inline long long many_steps_max(long long n_envs, long long n_ue, long long n_bs) {
+    const unsigned long long block = (unsigned long long)n_envs * (unsigned long long)(4 * n_ue > 8 * n_bs ? 4 * n_ue : 8 * n_bs);
+    const unsigned long long t = block == 0 ? 0x7FFFFFFFull : ((1ull << 32) - 1) / block;
+    return t < 1 ? 1 : (t > 0x7FFFFFFFull ? 0x7FFFFFFFll : (long long)t);
+}
+
 }  // namespace uavk

@@ -235,10 +235,26 @@ extern "C" int uavenv_step_many(uavenv_t *h, const int64_t *actions_dev, int n_s
     DeviceGuard guard(h->device);
     if (int rc_dev = poisoned(h, "step_many")) return rc_dev;
     if (h->packed) {   // one launch: state stays in registers across the steps (env_kernel_packed<..., MANY = true>)
-        KParams p = h->kp;
-        fill_call(p, nullptr, out);
-        p.actions = (const long long *)actions_dev; p.n_ticks = n_steps;
-        return launch_many<1>(h, p, n_steps, (hipStream_t)stream);
+        // The kernels that read the UAV path address block t of an output as base + 32-bit byte offset (uavenv_kernels.h: OutOffs).  A call
+        // whose outputs outgrow that (state_layout.h: many_steps_in_range) runs as several launches, each below the bound and each on its
+        // own blocks: the state passes through memory between them, as it does between two calls.
+        long long per = n_steps;
+        {
+            KParams q = h->kp;
+            fill_call(q, nullptr, out);
+            if (call_reads_path(h, q) && !uavk::many_steps_in_range(n_steps, h->N, h->cfg.n_ue, h->cfg.n_bs))
+                per = uavk::many_steps_max(h->N, h->cfg.n_ue, h->cfg.n_bs);
+        }
+        for (long long t = 0; t < n_steps; t += per) {
+            const int n = (int)(n_steps - t < per ? n_steps - t : per);
+            KParams p = h->kp;
+            UavEnvOut blk;
+            if (out && t > 0) blk = out_block(*out, t, h->N, h->cfg.n_ue, h->cfg.n_bs);
+            fill_call(p, nullptr, (out && t > 0) ? &blk : out);
+            p.actions = (const long long *)actions_dev + t * h->N; p.n_ticks = n;
+            if (int rc = launch_many<1>(h, p, n, (hipStream_t)stream)) return rc;
+        }
+        return UAVENV_OK;
     }
     // multi-pass handles (n_ue > 64): one single-step launch per step on the same stream, each writing its own output block
     for (int t = 0; t < n_steps; ++t) {

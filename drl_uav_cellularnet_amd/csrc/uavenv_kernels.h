@@ -728,7 +728,8 @@ __device__ __forceinline__ void env_finish(const FinConst &K, const OutPtrs &o, 
 }
 
 // Multi-step launches (uavenv_step_many): every output array holds one block per step, [T][...]; the pointers move on by one
-// block after each step (uniform 64-bit adds on the scalar unit).  A null (skipped) output stays null.
+// block after each step (uniform 64-bit adds on the scalar unit).  A null (skipped) output stays null.  (The unpinned and the checked
+// kernels; the pinned ones keep the pointers fixed: OutOffs below.)
 template <bool FAST>
 __device__ __forceinline__ void out_next_step(OutPtrs &o, long long N, int U, int B) {
     const long long nu = N * U, nb2 = N * B * 2;
@@ -762,6 +763,41 @@ __device__ __forceinline__ void out_skip_steps(OutPtrs &o, long long t0, long lo
     if (UAV_OUT64(o.cur_sinr_f64)) o.cur_sinr_f64 += nu;
     if (UAV_OUT64(o.mean_sinr_f64)) o.mean_sinr_f64 += n;
     if (UAV_OUT64(o.reward_f64)) o.reward_f64 += n;
+}
+
+// The same blocks addressed the other way round (the pinned multi-step kernels, many_o32 below): the nine
+// output pointers stay what the kernarg block holds, and the step is in four per-lane 32-bit BYTE offsets, each moved on by its block's
+// size after a step (one v_add_u32 with a scalar stride).  An access is `uniform base + 32-bit offset`, the SGPR-base form of ldx / stx:
+// no 64-bit pointer is advanced on the scalar unit (nine s_add_u32 / s_addc_u32 pairs per step) and no 64-bit address is formed in front
+// of a store (eight v_lshl_add_u64 per step).  Precondition, kept by the host (state_layout.h: many_steps_in_range; uavenv_step_many cuts
+// a longer call into several launches): the largest output of the launch, T x N x U x 4 bytes, and its T cell blocks are below 4 GiB.
+struct OutOffs {
+    uint32_t w4, w1, e4, e1;     // walker x 4 bytes (ue_xy, cur_sinr), walker x 1 (serving), env x 4 (step_n, reward, mean_sinr, n_out), env x 1 (done)
+};
+// Access at a byte offset that is made opaque in the access's own basic block (cf. block_local): hipcc then neither turns base + offset
+// into a 64-bit induction variable of the step loop nor forms the address in another block, where it could no longer fold it into the access.
+__device__ __forceinline__ void off_local(uint32_t &a) { asm volatile("" : "+v"(a)); }
+template <class T, class V> __device__ __forceinline__ void stb(T *base, uint32_t byte_off, V v, uint32_t plus = 0u) {
+    *reinterpret_cast<T *>(reinterpret_cast<char *>(base) + byte_off + (size_t)plus) = (T)v;
+}
+template <class T> __device__ __forceinline__ T ldb(const T *base, uint32_t byte_off, uint32_t plus = 0u) {
+    return *reinterpret_cast<const T *>(reinterpret_cast<const char *>(base) + byte_off + (size_t)plus);
+}
+// Which kernels: the PINNED multi-step kernels (they read the UAV path: FAST, BT <= 8, every output present, no float64 copies).  Not the
+// unpinned ones: there the nine bases, now live in SGPR pairs through the whole step, are spilled and reloaded -- the plain unpinned loop
+// grew from 1245 to 1267 instructions (v_readlane 111 -> 186, SGPR spills 98 -> 109) -- so those keep the advancing pointers.
+template <int BT, bool FAST, bool PIN, bool MANY> constexpr bool many_o32() { return MANY && FAST && PIN && BT <= 8; }
+// A step's per-env outputs at the offsets of its block: env_finish's values, expression for expression.
+__device__ __forceinline__ void env_outputs_at(const FinConst &K, const OutPtrs &o, OutOffs &f, int step_n, double sum_cur, int n_outage) {
+    const double mean = sum_cur * K.inv_U;
+    const double reward = step_reward(K, sum_cur, n_outage);
+    step_n += 1;
+    off_local(f.e4); off_local(f.e1);
+    stb(o.step_n, f.e4, step_n);
+    stb(o.done, f.e1, (uint8_t)(step_n >= K.max_step));
+    stb(o.reward, f.e4, (float)reward);
+    stb(o.mean_sinr, f.e4, (float)mean);
+    stb(o.n_out, f.e4, n_outage);
 }
 
 // ================================================================================================
@@ -981,11 +1017,21 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
     int n_outage = 0;
     unsigned long long ob = 0ull;
     OutPtrs om = p.out;                                // MANY: the current step's output blocks (dead code otherwise)
-    if (MANY) out_skip_steps<FAST>(om, t0, N, U, B);
+    // O32: the bases stay put and the step is in 32-bit byte offsets (OutOffs).  `oc`: the same for the cell blocks of out.bs_xy the step
+    // loop reads -- the block of the step that is prefetched next.
+    constexpr bool O32 = many_o32<BT, FAST, PIN, MANY>();
+    const uint32_t n32 = (uint32_t)N, nu32 = n32 * (uint32_t)U;
+    OutOffs of = {4u * iu32, iu32, 4u * e32, e32};
+    uint32_t oc = e32 * (uint32_t)(BT * 8);
+    if (O32) {                                         // a piece starts at step t0
+        const uint32_t t = (uint32_t)t0;
+        of.w4 += t * (4u * nu32); of.w1 += t * nu32; of.e4 += t * (4u * n32); of.e1 += t * n32; oc += t * (n32 * (uint32_t)(BT * 8));
+    } else if (MANY) out_skip_steps<FAST>(om, t0, N, U, B);
     if (PATH) {                                        // the cells of step t0: plain loads, also in a hand-off piece (an earlier KERNEL wrote them)
 #pragma unroll
         for (int b = 0; b < BT; b += 2) {
-            const int4 q = ldx(reinterpret_cast<const int4 *>(om.bs_xy), e32 * (uint32_t)(BT / 2) + (uint32_t)(b / 2));
+            const int4 q = O32 ? ldb(reinterpret_cast<const int4 *>(om.bs_xy), oc, (uint32_t)(b / 2) * 16u)
+                               : ldx(reinterpret_cast<const int4 *>(om.bs_xy), e32 * (uint32_t)(BT / 2) + (uint32_t)(b / 2));
             bsx[b] = q.x; bsy[b] = q.y; bsx[b + 1] = q.z; bsy[b + 1] = q.w;
         }
     }
@@ -995,7 +1041,12 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
     for (int it = 0; it < n_ticks; ++it) {
         long long act_next = 0;
         int4 cells_next[PATH ? BT / 2 : 1];
-        if (PATH) {                                    // prefetch the next step's cells (after the last step: this step's again, unused)
+        if (PATH && O32) {                             // prefetch the next step's cells (after the last step: this step's again, unused)
+            oc += (it + 1 < n_ticks) ? n32 * (uint32_t)(BT * 8) : 0u;
+            off_local(oc);
+#pragma unroll
+            for (int b = 0; b < BT / 2; ++b) cells_next[b] = ldb(reinterpret_cast<const int4 *>(om.bs_xy), oc, (uint32_t)b * 16u);
+        } else if (PATH) {
             const int4 *nxt = reinterpret_cast<const int4 *>(om.bs_xy + ((it + 1 < n_ticks) ? 2 * N * BT : 0));
 #pragma unroll
             for (int b = 0; b < BT / 2; ++b) cells_next[b] = ldx(nxt, e32 * (uint32_t)(BT / 2) + (uint32_t)b);
@@ -1142,7 +1193,14 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
 #pragma unroll
                 for (int b = 0; b < BT; b += 2) { bsx[b] = cells_next[b / 2].x; bsy[b] = cells_next[b / 2].y; bsx[b + 1] = cells_next[b / 2].z; bsy[b + 1] = cells_next[b / 2].w; }
             } else act = act_next;                                // (BS_move, the only reader of `act`, is done; after the last step: unused)
-            if (live) {
+            if (O32) {
+                if (live) {
+                    off_local(of.w4); off_local(of.w1);
+                    stb(om.ue_xy, of.w4, (int16_t)ix); stb(om.ue_xy, of.w4, (int16_t)iy, 2u);
+                    stb(om.serving, of.w1, (int8_t)serving);
+                    stb(om.cur_sinr, of.w4, (float)cur);
+                }
+            } else if (live) {
                 if (UAV_OUT(om.ue_xy)) { stx(om.ue_xy, 2u * iu32, (int16_t)ix); stx(om.ue_xy, 2u * iu32 + 1u, (int16_t)iy); }
                 if (UAV_OUT(om.serving)) stx(om.serving, iu32, (int8_t)serving);
                 if (UAV_OUT(om.cur_sinr)) stx(om.cur_sinr, iu32, (float)cur);
@@ -1153,8 +1211,13 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
             if (it + 1 < n_ticks) {
                 if (DIET) step_n += 1;                            // mobile_env.py:181 (DIET: here, so that env_finish's own + 1 is this value
                                                                   //  and not a second add in a mask region of the head lanes)
-                if (head) env_finish<MODE, FAST, false>(K, om, st, e32, erec, tick, agg, deagg, depth, DIET ? step_n - 1 : step_n, sum_cur, n_outage);
-                out_next_step<FAST>(om, N, U, B);
+                if (O32) {
+                    if (head) env_outputs_at(K, om, of, DIET ? step_n - 1 : step_n, sum_cur, n_outage);
+                    of.w4 += 4u * nu32; of.w1 += nu32; of.e4 += 4u * n32; of.e1 += n32;       // the next step's blocks
+                } else {
+                    if (head) env_finish<MODE, FAST, false>(K, om, st, e32, erec, tick, agg, deagg, depth, DIET ? step_n - 1 : step_n, sum_cur, n_outage);
+                    out_next_step<FAST>(om, N, U, B);
+                }
                 prev_out = ob;                                    // channel.py:173  self.ue_out = new_out
                 depth = depth < 3 ? depth + 1 : depth;            // bestBS_buf grows to hoBufDepth, then shifts (:148-153)
                 if (!DIET) step_n += 1;
@@ -1202,7 +1265,10 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
         const uint32_t ew = block_local<!PIN>(e32);
         if (MODE != MODE_WARMUP) stx_c<STC>(st.out_bits, ew, ob);                                // :116 / :173
         // (MANY: outputs of the LAST step + the record; depth / step_n are the values that step started from)
-        env_finish<MODE, FAST, true, true, STC>(K, MANY ? om : pout, st, ew, erec, tick, agg, deagg, depth, step_n, sum_cur, n_outage);
+        if (O32) {
+            env_outputs_at(K, om, of, step_n, sum_cur, n_outage);
+            env_finish<MODE, FAST, true, false, STC>(K, om, st, ew, erec, tick, agg, deagg, depth, step_n, sum_cur, n_outage);
+        } else env_finish<MODE, FAST, true, true, STC>(K, MANY ? om : pout, st, ew, erec, tick, agg, deagg, depth, step_n, sum_cur, n_outage);
     }
 }
 

@@ -1,0 +1,25 @@
+"""CPU: the range guard of the pinned multi-step kernels' 32-bit output offsets (csrc/state_layout.h: many_steps_in_range, many_steps_max),
+called from a stand-alone host program at the boundary -- T x N x U x 4 bytes equal to 2^32 - 4, to 2^32 and one element past it, the
+same for the cell blocks -- so that no large buffer is needed.  uavenv_step_many cuts a call that fails the predicate into launches of
+many_steps_max steps, each of which passes it."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_many_range_guard_at_the_boundary(tmp_path):
+    exe = os.path.join(tmp_path, "many_range_check")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-o", exe, os.path.join(ROOT, "tests", "native", "many_range_check.cpp")])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    rows = {}
+    for line in r.stdout.splitlines():
+        name, want, got = line.split()[:3]
+        rows[name] = (want, got)
+    print(r.stdout)
+    for name in ("pow2_below", "pow2_at", "pow2_max", "minus4", "minus4_bytes", "exact", "exact_one_less_step", "plus4", "plus4_bytes", "plus4_max",
+                 "cells_below", "cells_at", "cells_max", "bench", "bench_max", "degenerate_steps"):
+        assert name in rows, name
+        assert rows[name][0] == rows[name][1], (name, rows[name])
+    assert "max_consistent" not in rows, rows["max_consistent"]
+    assert r.returncode == 0
