@@ -502,8 +502,9 @@ class BatchedMobiEnv:
         return [buf[i] for i in range(min(n.value, 256))]
 
     def path_launches(self):
-        """Launches of the UAV path kernel on this handle so far (uavenv_debug_path_launches): one per step_many call that runs the FAST
-        step kernels with 4 or 8 UAVs, none for any other call.  Test hook."""
+        """Launches of the UAV path kernel on this handle so far (uavenv_debug_path_launches): one per launch piece of a
+        step_many call that runs the FAST step kernels with 4 or 8 UAVs (a call is one piece unless its outputs reach 4 GiB, or the bound
+        that UAVENV_DEBUG_MANY_OFFSET_LIMIT lowered), none for any other call.  Test hook."""
         n = C.c_longlong(0)
         _capi.check(self._lib.uavenv_debug_path_launches(self._h, C.byref(n)))
         return int(n.value)

@@ -63,15 +63,35 @@ UAVENV_HD StateOffsets compute_layout(long long n_envs, int n_ue, int n_bs, int 
 // Multi-step launches whose kernels address their [T][...] outputs as `base + 32-bit byte offset` (uavenv_kernels.h: OutOffs): is every
 // byte of a T-step launch within such an offset?  The largest output is ue_xy / cur_sinr, T x N x U x 4 bytes; the cell blocks the step
 // loop reads are T x N x B x 8 bytes.  Both must be BELOW 2^32: an offset is at most the array's size minus the access's.
-inline bool many_steps_in_range(long long n_steps, long long n_envs, long long n_ue, long long n_bs) {
-    const unsigned long long lim = 1ull << 32, block = (unsigned long long)n_envs * (unsigned long long)(4 * n_ue > 8 * n_bs ? 4 * n_ue : 8 * n_bs);
+// `lim` is the exclusive byte bound, 2^32 for every caller but a test: a handle created under UAVENV_DEBUG_MANY_OFFSET_LIMIT carries a
+// LOWER one (uavenv_host.hip: uavenv_create), so that the cut of a call into several launches runs at sizes a test can afford.  The bound
+// can only be tightened: 0 counts as 1 and anything above 2^32 as 2^32 here too, because beyond 2^32 the offsets would wrap and the
+// kernel would store outside its buffers.
+constexpr unsigned long long kManyOffsetLimit = 1ull << 32;
+inline unsigned long long many_offset_limit(unsigned long long lim) { return lim < 1 ? 1 : (lim > kManyOffsetLimit ? kManyOffsetLimit : lim); }
+inline unsigned long long many_block_bytes(long long n_envs, long long n_ue, long long n_bs) {
+    return (unsigned long long)n_envs * (unsigned long long)(4 * n_ue > 8 * n_bs ? 4 * n_ue : 8 * n_bs);
+}
+inline bool many_steps_in_range(long long n_steps, long long n_envs, long long n_ue, long long n_bs, unsigned long long lim = kManyOffsetLimit) {
+    const unsigned long long block = many_block_bytes(n_envs, n_ue, n_bs);
+    lim = many_offset_limit(lim);
     return n_steps <= 0 || block == 0 || (block < lim && (unsigned long long)n_steps <= (lim - 1) / block);
 }
 // The most steps of such a launch (at least 1: one step is what a single-step launch addresses, and uavenv_create admits no array above 4 GiB).
-inline long long many_steps_max(long long n_envs, long long n_ue, long long n_bs) {
-    const unsigned long long block = (unsigned long long)n_envs * (unsigned long long)(4 * n_ue > 8 * n_bs ? 4 * n_ue : 8 * n_bs);
-    const unsigned long long t = block == 0 ? 0x7FFFFFFFull : ((1ull << 32) - 1) / block;
+// A bound at or below one block's size therefore means "one step per launch", although that one step does not pass the predicate.
+inline long long many_steps_max(long long n_envs, long long n_ue, long long n_bs, unsigned long long lim = kManyOffsetLimit) {
+    const unsigned long long block = many_block_bytes(n_envs, n_ue, n_bs);
+    const unsigned long long t = block == 0 ? 0x7FFFFFFFull : (many_offset_limit(lim) - 1) / block;
     return t < 1 ? 1 : (t > 0x7FFFFFFFull ? 0x7FFFFFFFll : (long long)t);
+}
+// How uavenv_step_many cuts a call of n_steps: the steps of every launch piece but the last, which takes the remainder (pieces of `per`
+// steps at t = 0, per, 2 per, ... while t < n_steps).  Only a call whose step kernels read the UAV path (`reads_path`) addresses its outputs
+// through 32-bit offsets; every other call, and every call inside the bound, is one piece.  At least 1, so the walk over the pieces ends.
+inline long long many_steps_per_piece(long long n_steps, long long n_envs, long long n_ue, long long n_bs, unsigned long long lim, bool reads_path) {
+    if (n_steps < 1) return 1;
+    if (!reads_path || many_steps_in_range(n_steps, n_envs, n_ue, n_bs, lim)) return n_steps;
+    const long long per = many_steps_max(n_envs, n_ue, n_bs, lim);
+    return per < n_steps ? per : n_steps;
 }
 
 }  // namespace uavk

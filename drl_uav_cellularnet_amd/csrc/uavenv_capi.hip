@@ -187,12 +187,19 @@ extern "C" int uavenv_step_range(uavenv_t *h, const int64_t *actions_dev, int64_
 }
 
 // The producer of a FAST multi-step call with BT <= 8 (uavenv_path_kernel.h): the UAV cells of all n_steps steps into out.bs_xy and the cells
-// after the last step into the state, ONE launch per call -- not per piece of a schedule -- on the caller's stream, immediately before the
-// step kernel, which reads them.  The same predicate as launch_env's `fast`: every FAST multi-step launch reads the path, no checked one does.
+// after the last step into the state, ONE launch per launch piece of the call (uavenv_step_many: one piece unless the outputs outgrow the
+// 32-bit offsets) -- not per piece of a schedule -- on the caller's stream, immediately before the step kernel, which reads them.  The same
+// predicate as launch_env's `fast`: every FAST multi-step launch reads the path, no checked one does.
 // With uavenv_launch_timing on its dispatch is timed like the step kernel's.  It is counted on the handle (uavenv_debug_path_launches), in
 // neither census: those list the instantiations of the env step's dispatch and of the side entry points.
-static bool call_reads_path(const uavenv_t *h, const KParams &p) {
+bool uavenv_internal::handle_reads_path(const uavenv_t *h) {
+    return h->packed && (h->cfg.n_bs == h->bt) && (h->bt <= uavk::kPathMaxBs);
+}
+bool uavenv_internal::call_reads_path(const uavenv_t *h, const KParams &p) {
     return h->packed && call_is_fast(p) && (p.B == h->bt) && (h->bt <= uavk::kPathMaxBs);
+}
+long long uavenv_internal::many_piece_steps(const uavenv_t *h, int n_steps, bool reads_path) {
+    return uavk::many_steps_per_piece(n_steps, h->N, h->cfg.n_ue, h->cfg.n_bs, h->many_lim, reads_path);
 }
 static int launch_path(uavenv_t *h, const KParams &p, int n_steps, hipStream_t s) {
     uavk::PathParams q;
@@ -237,14 +244,11 @@ extern "C" int uavenv_step_many(uavenv_t *h, const int64_t *actions_dev, int n_s
     if (h->packed) {   // one launch: state stays in registers across the steps (env_kernel_packed<..., MANY = true>)
         // The kernels that read the UAV path address block t of an output as base + 32-bit byte offset (uavenv_kernels.h: OutOffs).  A call
         // whose outputs outgrow that (state_layout.h: many_steps_in_range) runs as several launches, each below the bound and each on its
-        // own blocks: the state passes through memory between them, as it does between two calls.
-        long long per = n_steps;
-        {
-            KParams q = h->kp;
-            fill_call(q, nullptr, out);
-            if (call_reads_path(h, q) && !uavk::many_steps_in_range(n_steps, h->N, h->cfg.n_ue, h->cfg.n_bs))
-                per = uavk::many_steps_max(h->N, h->cfg.n_ue, h->cfg.n_bs);
-        }
+        // own blocks: the state passes through memory between them, as it does between two calls.  many_piece_steps says how the call is
+        // cut, here and for uavenv_step_many_prepare / uavenv_debug_rotation_info.
+        KParams q = h->kp;
+        fill_call(q, nullptr, out);
+        const long long per = many_piece_steps(h, n_steps, call_reads_path(h, q));
         for (long long t = 0; t < n_steps; t += per) {
             const int n = (int)(n_steps - t < per ? n_steps - t : per);
             KParams p = h->kp;

@@ -52,6 +52,8 @@ struct uavenv {
     int timing, n_timed;
     long long path_launches;  // launches of uav_path_kernel on this handle (uavenv_debug_path_launches)
     int force_pin;  // UAVENV_FORCE_PIN read ONCE at create (experiments: tools/pin_sweep.sh): -1 unset, 0 / 1 forced
+    unsigned long long many_lim;  // exclusive byte bound of a multi-step launch's 32-bit output offsets (state_layout.h): 2^32, or the LOWER value
+                                  // of UAVENV_DEBUG_MANY_OFFSET_LIMIT read once at create (test hook: cuts small calls into several launches)
     double *ul_gain_dev;  // [N, B, B] pair means of uavenv_link_rates when the caller does not ask for them (n_ue <= 64 and n_bs <= 8 only, else null)
     UavEnvStateLayout lay;
     uavk::KParams kp;  // constants + state pointers, per-call fields patched at launch
@@ -64,7 +66,14 @@ int poisoned(const uavenv *h, const char *what);
 void fill_call(uavk::KParams &p, const UavEnvInject *inj, const UavEnvOut *out);
 bool call_is_fast(const uavk::KParams &p);
 UavEnvOut out_block(const UavEnvOut &o, long long t, long long N, long long U, long long B);   // block t of [T][...] outputs; null members stay null
-int rotation_plan(uavenv *h, int n_steps, hipStream_t stream);   // uavenv_host.hip: index into h->rot_plans of the schedule uavenv_step_many runs, or -1 (plain launch)
+int rotation_plan(uavenv *h, int n_steps, hipStream_t stream);   // uavenv_host.hip: index into h->rot_plans of the schedule ONE LAUNCH of n_steps runs, or -1 (plain launch)
+// Does a multi-step call with these per-call fields run the step kernels that read the UAV path (uavenv_path_kernel.h)?  The same predicate
+// as launch_env's `fast`: every FAST multi-step launch reads the path, no checked one does.  handle_reads_path: the same for a call that
+// asks for the nine standard outputs and nothing else, which is what uavenv_step_many_prepare and uavenv_debug_rotation_info speak about.
+bool handle_reads_path(const uavenv *h);
+bool call_reads_path(const uavenv *h, const uavk::KParams &p);
+// The steps of every launch piece but the last of a uavenv_step_many call of n_steps (state_layout.h: many_steps_per_piece, on the handle's bound).
+long long many_piece_steps(const uavenv *h, int n_steps, bool reads_path);
 
 // ---- from run-time values to a template instantiation ----------------------------------------------------------------------------------
 // f is a generic lambda; it reads the constant as decltype(c)::value and leaves out, with `if constexpr`, the combinations that have no kernel.

@@ -4,6 +4,7 @@
 // (The device pass of this unit compiles nothing at all: uavenv_kernels.h gives every unit that includes it a copy of init_kernel.)
 #ifndef __HIP_DEVICE_COMPILE__
 #include <atomic>
+#include <cerrno>
 #include <cmath>
 #include <cstdlib>
 #include <algorithm>
@@ -174,6 +175,17 @@ extern "C" int uavenv_create(const UavEnvConfig *cfg, int64_t n_envs, int device
     h->spin_us = 2000000u;
     if (const char *f = std::getenv("UAVENV_HANDOFF_SPIN_US")) { const long long v = std::atoll(f); if (v > 0 && v < 60000000ll) h->spin_us = (uint32_t)v; }
     if (const char *f = std::getenv("UAVENV_DEBUG_DROP_PUBLISH")) h->drop_publish = (f[0] == '1') ? 1 : 0;
+    // Test hook: a LOWER bound for the 32-bit output offsets of a multi-step launch, in bytes (decimal), so that uavenv_step_many cuts calls
+    // of a few kilobytes as it would cut one of 4 GiB.  Only 1 <= v <= 2^32 is taken; unparsable text, 0, negative values and anything above
+    // 2^32 leave the default: the bound cannot be raised, beyond it the offsets would wrap and the kernel would store outside its buffers.
+    // A bound at or below one step's block means one step per launch (state_layout.h: many_steps_max is at least 1).
+    h->many_lim = uavk::kManyOffsetLimit;
+    if (const char *f = std::getenv("UAVENV_DEBUG_MANY_OFFSET_LIMIT")) {
+        char *end = nullptr;
+        errno = 0;
+        const long long v = std::strtoll(f, &end, 10);
+        if (errno == 0 && end != f && *end == '\0' && v >= 1 && (unsigned long long)v <= uavk::kManyOffsetLimit) h->many_lim = (unsigned long long)v;
+    }
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) cus = 256;
@@ -657,15 +669,19 @@ extern "C" int uavenv_debug_schedule(int64_t n_wavefronts, int64_t n_slots, int 
 extern "C" int uavenv_step_many_prepare(uavenv_t *h, int n_steps) {
     if (!h || n_steps < 0) return fail(UAVENV_E_INVALID, "step_many_prepare: null handle or negative n_steps");
     DeviceGuard guard(h->device);
-    (void)rotation_plan(h, n_steps, nullptr);      // builds + uploads + caches the schedule when one applies
+    // builds + uploads + caches the schedule when one applies: of the call's launch pieces (many_piece_steps: one piece of n_steps unless
+    // the outputs outgrow the 32-bit offsets, else pieces of `per` steps and a shorter last one)
+    const long long per = many_piece_steps(h, n_steps, handle_reads_path(h));
+    (void)rotation_plan(h, (int)per, nullptr);
+    if (n_steps > per && n_steps % per != 0) (void)rotation_plan(h, (int)(n_steps % per), nullptr);
     return UAVENV_OK;
 }
 
-// Test hook: the schedule uavenv_step_many would use for n_steps (0 launches = plain launch).
+// Test hook: the schedule uavenv_step_many would use for n_steps (0 launches = plain launch); of its first launch piece where it cuts the call.
 extern "C" int uavenv_debug_rotation_info(uavenv_t *h, int n_steps, int *n_launches, long long *slots) {
     if (!h || n_steps < 0) return fail(UAVENV_E_INVALID, "debug_rotation_info: null handle or negative n_steps");
     DeviceGuard guard(h->device);
-    const int i = rotation_plan(h, n_steps, nullptr);
+    const int i = rotation_plan(h, (int)many_piece_steps(h, n_steps, handle_reads_path(h)), nullptr);
     if (n_launches) *n_launches = i >= 0 ? (*h->rot_plans)[(size_t)i].n_launches : 0;
     if (slots) *slots = i >= 0 ? (*h->rot_plans)[(size_t)i].slots : 0;
     return UAVENV_OK;

@@ -215,7 +215,9 @@ void uavenv_debug_side_variant_reset(void);
 
 /* Optional: prepare a multi-step call of n_steps ahead of time.  The first uavenv_step_many call with a new n_steps may build and
  * upload a launch schedule (a few hundred microseconds of host time, synchronous); a caller that times the call (bench.py) or must not
- * stall in it builds the schedule here instead.  Idempotent; 0 when there is nothing to prepare for this handle / n_steps. */
+ * stall in it builds the schedule here instead.  Idempotent; 0 when there is nothing to prepare for this handle / n_steps.  Where
+ * uavenv_step_many cuts a call of n_steps into several launches (outputs of 4 GiB and more, below), the schedules prepared are those of
+ * its pieces: of the common piece length and of the shorter last piece.  The call is taken to ask for the nine standard outputs. */
 int uavenv_step_many_prepare(uavenv_t *h, int n_steps);
 
 /* Test hook: how uavenv_step_many would run n_steps on this handle: *n_launches = 0 for the plain single
@@ -224,12 +226,18 @@ int uavenv_step_many_prepare(uavenv_t *h, int n_steps);
  * uavenv_create: UAVENV_ROTATE=0 never rotate, =1 rotate whenever a valid schedule exists; UAVENV_ROTATE_SLOTS=k plan as if the
  * device had k SIMDs (lets small batches exercise the schedule);
  * UAVENV_HANDOFF_SPIN_US=n spin budget of one hand-off wait (default 2 000 000); UAVENV_DEBUG_DROP_PUBLISH=1 builds schedules
- * whose hand-offs are never signalled (the time-out path's test). */
+ * whose hand-offs are never signalled (the time-out path's test).
+ * A call whose [n_steps][...] outputs reach 4 GiB runs as several launches, each below that bound and on its own output blocks (the
+ * pinned kernels address a block as base + 32-bit byte offset); for such a call this reports the plan of its FIRST piece, which is
+ * that of every piece but a shorter last one (ask for that length to see its plan).  UAVENV_DEBUG_MANY_OFFSET_LIMIT=v (bytes, decimal;
+ * read once in uavenv_create; taken only for 1 <= v <= 2^32, anything else leaves 2^32) LOWERS that bound so that tests can run the cut at
+ * small sizes; it cannot raise it.  A bound at or below one step's output block means one step per launch. */
 int uavenv_debug_rotation_info(uavenv_t *h, int n_steps, int *n_launches, long long *slots);
 
 /* Test hook: *n = launches of the UAV path kernel on this handle so far.  A uavenv_step_many call that runs the FAST step kernels with
- * n_bs = 4 or 8 (all nine standard outputs, no float64 copies, one launch: n_ue <= 64) launches it once, before the step kernel: the cells
- * of every step go to out->bs_xy_dev and the step kernel reads them there instead of moving the UAVs itself.  No other call launches it. */
+ * n_bs = 4 or 8 (all nine standard outputs, no float64 copies, one launch: n_ue <= 64) launches it once per launch piece (one piece,
+ * unless the outputs reach 4 GiB: see uavenv_debug_rotation_info), before the piece's step kernel: the cells of every step go to
+ * out->bs_xy_dev and the step kernel reads them there instead of moving the UAVs itself.  No other call launches it. */
 int uavenv_debug_path_launches(uavenv_t *h, long long *n);
 
 /* Duration of the multi-step launches themselves, for callers that time SHORT calls (bench.py's 20-step region lasts 0.1 ms: a pair of
