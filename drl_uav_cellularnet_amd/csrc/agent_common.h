@@ -1,13 +1,29 @@
-// Shared by the two translation units of libuavagent.so (not part of the C ABI: hidden visibility).
+// Shared by the seven translation units of libuavagent.so (agent_kernels, agent_learner, agent_gemm, agent_factored, agent_wide, agent_ppo,
+// agent_ppo_joint .hip; not part of the C ABI: hidden visibility): the host helpers every entry point uses, then the device statements more
+// than one unit needs bit for bit.  The loss gradients have headers of their own: agent_loss_joint.h, agent_loss_factored.h.
 #pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <string>
 
+#include "../../include/uavagent.h"
+
 namespace uavagent_internal {
-// Records the thread-local message uavagent_last_error() returns and hands `code` back.
+// Records the thread-local message uavagent_last_error() returns and hands `code` back (defined in agent_kernels.hip).
 __attribute__((visibility("hidden"))) int fail(int code, const std::string &msg);
 }  // namespace uavagent_internal
+using uavagent_internal::fail;
+
+// After a launch: UAVAGENT_OK, or UAVAGENT_E_HIP with the runtime's message behind `what`.
+inline int launch_ok(const char *what) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(UAVAGENT_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    return UAVAGENT_OK;
+}
+inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }                                            // workspace sections start 256-byte aligned
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }               // (true for a null pointer)
 
 // Softmax numerator exp(x - max) of the ACTION DRAW (uavagent_sample_actions and the actor head's fused draw: the two must stay bit-identical),
 // x - max <= 0: the hardware's exp2 (v_exp_f32, ~1 ulp; the scaled argument adds <= 2e-6 relative at x - max = -35) instead of the

@@ -25,13 +25,10 @@
 #include <string>
 #include <type_traits>
 
-#include "../../include/uavagent.h"
 #include "agent_common.h"
 #include "rollout_gate.h"
 
 namespace {
-
-int fail3(int code, const std::string &msg) { return uavagent_internal::fail(code, msg); }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -1510,8 +1507,6 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_kernel(const float *__restri
     }
 }
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1566,7 +1561,7 @@ template <int PLAN> int tn_plan_check() {
 extern "C" int uavagent_debug_tn_plan_check(int32_t plan) {
     if (plan == 13) return tn_plan_check<13>();
     if (plan == 20) return tn_plan_check<20>();
-    return fail3(UAVAGENT_E_INVALID, "tn_plan_check: plans 13 and 20 exist");
+    return fail(UAVAGENT_E_INVALID, "tn_plan_check: plans 13 and 20 exist");
 }
 
 extern "C" size_t uavagent_gemm_tn_workspace_bytes(int64_t m_rows, int32_t n_j) {
@@ -1576,12 +1571,12 @@ extern "C" size_t uavagent_gemm_tn_workspace_bytes(int64_t m_rows, int32_t n_j) 
 
 extern "C" int uavagent_gemm_tn_f32(const float *a, const float *b, int64_t m_rows, int32_t n_i, int32_t n_j, int64_t ldb, float *c, int64_t ldc,
                                     float *dbias_out, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!a || !b || !c || !workspace) return fail3(UAVAGENT_E_INVALID, "gemm_tn: null pointer");
+    if (!a || !b || !c || !workspace) return fail(UAVAGENT_E_INVALID, "gemm_tn: null pointer");
     if (m_rows < 1 || n_i < 4 || n_i > 200 || (n_i & 3) || n_j < 1 || n_j > 640 || ldb < n_j || ldc < n_j || ldb > 65536)
-        return fail3(UAVAGENT_E_INVALID, "gemm_tn: need m_rows >= 1, n_i % 4 == 0 in [4, 200], 1 <= n_j <= 640, n_j <= ldb <= 65536, ldc >= n_j");
-    if (!aligned16(a) || !aligned16(workspace)) return fail3(UAVAGENT_E_INVALID, "gemm_tn: a and workspace must be 16-byte aligned");
+        return fail(UAVAGENT_E_INVALID, "gemm_tn: need m_rows >= 1, n_i % 4 == 0 in [4, 200], 1 <= n_j <= 640, n_j <= ldb <= 65536, ldc >= n_j");
+    if (!aligned16(a) || !aligned16(workspace)) return fail(UAVAGENT_E_INVALID, "gemm_tn: a and workspace must be 16-byte aligned");
     const TnShape s = tn_shape(m_rows, n_j);
-    if (workspace_bytes < s.ws_bytes) return fail3(UAVAGENT_E_INVALID, "gemm_tn: workspace smaller than uavagent_gemm_tn_workspace_bytes()");
+    if (workspace_bytes < s.ws_bytes) return fail(UAVAGENT_E_INVALID, "gemm_tn: workspace smaller than uavagent_gemm_tn_workspace_bytes()");
     hipStream_t st = (hipStream_t)stream;
     f32x4 *slabs = reinterpret_cast<f32x4 *>(workspace);
     // float4 staging of b: rows start on 16-byte boundaries and the columns up to the next multiple of 4 past n_j exist (inside the row
@@ -1597,7 +1592,7 @@ extern "C" int uavagent_gemm_tn_f32(const float *a, const float *b, int64_t m_ro
     } while (0)
     if (s.plan == 13) UAV_TN(13); else UAV_TN(20);
 #undef UAV_TN
-    if (hipGetLastError() != hipSuccess) return fail3(UAVAGENT_E_HIP, "gemm_tn: launch failed");
+    if (hipGetLastError() != hipSuccess) return fail(UAVAGENT_E_HIP, "gemm_tn: launch failed");
     return UAVAGENT_OK;
 }
 
@@ -1620,12 +1615,12 @@ static int actor_head_launch(const char *what, bool greedy, const float *h1, con
                              float *logits_out, int64_t ld_logits, int64_t *actions_out, void *stream) {
     const std::string w(what);
     if (!h1 || !w2t || !b2 || !w3t_padded || !b3_padded || (!greedy && !uniforms) || !h2_out || !logits_out || !actions_out)
-        return fail3(UAVAGENT_E_INVALID, w + ": null pointer");
+        return fail(UAVAGENT_E_INVALID, w + ": null pointer");
     if (n_hidden != kHdH || n_actions <= 576 || n_actions > kHdNP || ld_logits < kHdNP || (ld_logits & 3) || n_rows < 0)
-        return fail3(UAVAGENT_E_INVALID, w + ": built for 200 hidden units and 577..640 actions (the reference's 625 = 5^4; 10 policy columns "
+        return fail(UAVAGENT_E_INVALID, w + ": built for 200 hidden units and 577..640 actions (the reference's 625 = 5^4; 10 policy columns "
                                              "per lane, like uavagent_sample_actions at that width), ld_logits >= 640 and a multiple of 4");
     if (!aligned16(h1) || !aligned16(w2t) || !aligned16(w3t_padded) || !aligned16(h2_out) || !aligned16(logits_out))
-        return fail3(UAVAGENT_E_INVALID, w + ": matrices must be 16-byte aligned");
+        return fail(UAVAGENT_E_INVALID, w + ": matrices must be 16-byte aligned");
     if (n_rows == 0) return UAVAGENT_OK;
     // 32-row workgroups while they give every CU one (a whole rollout batch of 8192 rows on 256 CUs); 16-row workgroups for fewer rows (half a
     // batch on its own stream): the time of a workgroup is its weight stream, so fewer, larger workgroups would only leave CUs idle
@@ -1640,7 +1635,7 @@ static int actor_head_launch(const char *what, bool greedy, const float *h1, con
     if (greedy) { if (small) UAV_HEAD(1, true); else UAV_HEAD(2, true); }
     else { if (small) UAV_HEAD(1, false); else UAV_HEAD(2, false); }
 #undef UAV_HEAD
-    if (hipGetLastError() != hipSuccess) return fail3(UAVAGENT_E_HIP, w + ": launch failed");
+    if (hipGetLastError() != hipSuccess) return fail(UAVAGENT_E_HIP, w + ": launch failed");
     return UAVAGENT_OK;
 }
 
@@ -1663,14 +1658,14 @@ static uint32_t *g_gate_err_host = nullptr, *g_gate_err_dev = nullptr;
 extern "C" int uavagent_gate_prepare(void) {
     if (g_gate_err_host != nullptr) return UAVAGENT_OK;
     void *hp = nullptr, *dp = nullptr;
-    if (hipHostMalloc(&hp, 64, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) return fail3(UAVAGENT_E_HIP, "gate_prepare: hipHostMalloc failed");
+    if (hipHostMalloc(&hp, 64, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) return fail(UAVAGENT_E_HIP, "gate_prepare: hipHostMalloc failed");
     std::memset(hp, 0, 64);
-    if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) { (void)hipHostFree(hp); return fail3(UAVAGENT_E_HIP, "gate_prepare: hipHostGetDevicePointer failed"); }
+    if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) { (void)hipHostFree(hp); return fail(UAVAGENT_E_HIP, "gate_prepare: hipHostGetDevicePointer failed"); }
     g_gate_err_host = static_cast<uint32_t *>(hp); g_gate_err_dev = static_cast<uint32_t *>(dp);
     return UAVAGENT_OK;
 }
 extern "C" int uavagent_device_error(uint32_t *code) {
-    if (!code) return fail3(UAVAGENT_E_INVALID, "device_error: null pointer");
+    if (!code) return fail(UAVAGENT_E_INVALID, "device_error: null pointer");
     *code = g_gate_err_host ? *(volatile uint32_t *)g_gate_err_host : 0u;
     return UAVAGENT_OK;
 }
@@ -1684,25 +1679,25 @@ extern "C" int uavagent_actor_head_gated_f32(const float *h1, const float *w2t, 
                                              float *h2_out, float *logits_out, int64_t ld_logits, int64_t *actions_out, uint32_t *gate_obs,
                                              uint32_t *gate_actions, uint32_t *claim, uint32_t spin_us, void *stream) {
     if (!h1 || !w2t || !b2 || !w3t_padded || !b3_padded || !uniforms || !h2_out || !logits_out || !actions_out || !gate_obs || !gate_actions || !claim)
-        return fail3(UAVAGENT_E_INVALID, "actor_head_gated: null pointer");
+        return fail(UAVAGENT_E_INVALID, "actor_head_gated: null pointer");
     if (n_hidden != kHdH || n_actions <= 576 || n_actions > kHdNP || ld_logits < kHdNP || (ld_logits & 3) || n_rows < 1 || n_steps < 1)
-        return fail3(UAVAGENT_E_INVALID, "actor_head_gated: built for 200 hidden units and 577..640 actions, ld_logits >= 640 and a multiple of 4, "
+        return fail(UAVAGENT_E_INVALID, "actor_head_gated: built for 200 hidden units and 577..640 actions, ld_logits >= 640 and a multiple of 4, "
                                          "n_rows >= 1, n_steps >= 1");
     if (!aligned16(h1) || !aligned16(w2t) || !aligned16(w3t_padded) || !aligned16(h2_out) || !aligned16(logits_out) || (n_rows & 3))
-        return fail3(UAVAGENT_E_INVALID, "actor_head_gated: matrices must be 16-byte aligned and n_rows a multiple of 4 (every step's block of rows "
+        return fail(UAVAGENT_E_INVALID, "actor_head_gated: matrices must be 16-byte aligned and n_rows a multiple of 4 (every step's block of rows "
                                          "starts 16-byte aligned)");
-    if (g_gate_err_dev == nullptr) return fail3(UAVAGENT_E_INVALID, "actor_head_gated: call uavagent_gate_prepare() first (it allocates the error word)");
+    if (g_gate_err_dev == nullptr) return fail(UAVAGENT_E_INVALID, "actor_head_gated: call uavagent_gate_prepare() first (it allocates the error word)");
     if (*(volatile uint32_t *)g_gate_err_host != 0u)
-        return fail3(UAVAGENT_E_DEVICE, "actor_head_gated: an earlier gated launch timed out on the device (uavagent_device_error); clear it first");
+        return fail(UAVAGENT_E_DEVICE, "actor_head_gated: an earlier gated launch timed out on the device (uavagent_device_error); clear it first");
     const long long pairs = ((n_rows + 15) / 16 + 1) / 2;
     const unsigned grid = (unsigned)std::min<long long>(pairs, cu_count_of_current_device());
     constexpr size_t lds_bytes = (size_t)HdPlan<1>::LdsF * sizeof(float);
     static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void *>(&actor_head_gated_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (attr_rc != hipSuccess) return fail3(UAVAGENT_E_HIP, "actor_head_gated: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+    if (attr_rc != hipSuccess) return fail(UAVAGENT_E_HIP, "actor_head_gated: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
     hipLaunchKernelGGL(actor_head_gated_kernel, dim3(grid), dim3(kHdThr), lds_bytes, (hipStream_t)stream, h1, w2t, b2, w3t_padded, b3_padded, uniforms,
                        (long long)n_rows, (int)n_steps, (int)n_actions, h2_out, logits_out, (long long)ld_logits,
                        reinterpret_cast<long long *>(actions_out), gate_obs, gate_actions, claim, g_gate_err_dev, spin_us ? spin_us : 2000000u);
-    if (hipGetLastError() != hipSuccess) return fail3(UAVAGENT_E_HIP, "actor_head_gated: launch failed");
+    if (hipGetLastError() != hipSuccess) return fail(UAVAGENT_E_HIP, "actor_head_gated: launch failed");
     return UAVAGENT_OK;
 }
 
@@ -1714,25 +1709,25 @@ extern "C" size_t uavagent_gemm_rows_workspace_bytes(int64_t m_rows) {
 extern "C" int uavagent_gemm_rows_f32(const float *a, int64_t lda, const float *w, int64_t ldw, int32_t w_transposed, int64_t m_rows, int32_t k,
                                       int32_t n, const float *bias, int32_t relu6, const float *relu6_mask_h, int64_t ldh, float *c, int64_t ldc,
                                       float *colsum_out, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!a || !w || !c) return fail3(UAVAGENT_E_INVALID, "gemm_rows: null pointer");
+    if (!a || !w || !c) return fail(UAVAGENT_E_INVALID, "gemm_rows: null pointer");
     if (m_rows < 1 || k < 1 || n < 1 || n > 1024 || lda < k || ldc < n || ldw < (w_transposed ? k : n) || lda > 65536 || ldw > 65536)
-        return fail3(UAVAGENT_E_INVALID, "gemm_rows: need m_rows, k >= 1, 1 <= n <= 1024, k <= lda <= 65536, ldc >= n, row length of w <= ldw <= 65536");
-    if (relu6_mask_h && (bias || relu6)) return fail3(UAVAGENT_E_INVALID, "gemm_rows: the relu6-mask epilogue excludes bias / relu6");
-    if (relu6_mask_h && ldh < n) return fail3(UAVAGENT_E_INVALID, "gemm_rows: ldh < n");
+        return fail(UAVAGENT_E_INVALID, "gemm_rows: need m_rows, k >= 1, 1 <= n <= 1024, k <= lda <= 65536, ldc >= n, row length of w <= ldw <= 65536");
+    if (relu6_mask_h && (bias || relu6)) return fail(UAVAGENT_E_INVALID, "gemm_rows: the relu6-mask epilogue excludes bias / relu6");
+    if (relu6_mask_h && ldh < n) return fail(UAVAGENT_E_INVALID, "gemm_rows: ldh < n");
     hipStream_t st = (hipStream_t)stream;
     const bool vec = aligned16(a) && aligned16(w) && aligned16(c) && aligned16(bias) && aligned16(relu6_mask_h) && (lda % 4 == 0) && (ldw % 4 == 0) &&
                      (ldc % 4 == 0) && (ldh % 4 == 0) && (k % 4 == 0) && (n % 4 == 0);
     if (n > 208 && !(vec && w_transposed))
-        return fail3(UAVAGENT_E_INVALID, "gemm_rows: n > 208 needs the aligned w_transposed form (N is then cut into slices)");
+        return fail(UAVAGENT_E_INVALID, "gemm_rows: n > 208 needs the aligned w_transposed form (N is then cut into slices)");
     const dim3 grid((unsigned)((m_rows + kRowsBM - 1) / kRowsBM)), blk(256);
     const int epi = relu6_mask_h ? 2 : ((bias || relu6) ? 1 : 0);
     long long n_part_resident = 0;
     float *colp = nullptr;
     if (colsum_out) {
-        if (n > 208) return fail3(UAVAGENT_E_INVALID, "gemm_rows: column sums exist for n <= 208");
-        if (!vec) return fail3(UAVAGENT_E_INVALID, "gemm_rows: column sums need the aligned path (16-byte aligned operands, strides / k / n multiples of 4)");
+        if (n > 208) return fail(UAVAGENT_E_INVALID, "gemm_rows: column sums exist for n <= 208");
+        if (!vec) return fail(UAVAGENT_E_INVALID, "gemm_rows: column sums need the aligned path (16-byte aligned operands, strides / k / n multiples of 4)");
         if (!workspace || !aligned16(workspace) || workspace_bytes < uavagent_gemm_rows_workspace_bytes(m_rows))
-            return fail3(UAVAGENT_E_INVALID, "gemm_rows: column sums need a 16-byte aligned workspace of uavagent_gemm_rows_workspace_bytes()");
+            return fail(UAVAGENT_E_INVALID, "gemm_rows: column sums need a 16-byte aligned workspace of uavagent_gemm_rows_workspace_bytes()");
         colp = reinterpret_cast<float *>(workspace);
     }
 #define UAV_ARGS grid, blk, 0, st, a, (long long)lda, w, (long long)ldw, (int)k, (int)n, (long long)m_rows, bias, (int)relu6, relu6_mask_h, (long long)ldh, c, (long long)ldc
@@ -1760,7 +1755,7 @@ extern "C" int uavagent_gemm_rows_f32(const float *a, int64_t lda, const float *
         // W^T resident in LDS, persistent workgroups (gemm_rows_resident_kernel): the update's 200-wide layers
         const int n_cu = cu_count_of_current_device();          // per device: a process may drive several
         const int nA = (n_cu * kRsNBA + (kRsNBA + kRsNBB) / 2) / (kRsNBA + kRsNBB) < n_cu ? (n_cu * kRsNBA + (kRsNBA + kRsNBB) / 2) / (kRsNBA + kRsNBB) : n_cu - 1;
-        if (colp && hipMemsetAsync(colp, 0, (size_t)nA * kNP * sizeof(float), st) != hipSuccess) return fail3(UAVAGENT_E_HIP, "gemm_rows: memset failed");
+        if (colp && hipMemsetAsync(colp, 0, (size_t)nA * kNP * sizeof(float), st) != hipSuccess) return fail(UAVAGENT_E_HIP, "gemm_rows: memset failed");
         const dim3 g2((unsigned)n_cu), b2(kRsThr);
         if (epi == 0) hipLaunchKernelGGL((gemm_rows_resident_kernel<0>), g2, b2, 0, st, a, (long long)lda, w, (long long)ldw, (int)n, (long long)m_rows, bias, (int)relu6, relu6_mask_h, (long long)ldh, c, (long long)ldc, colp, nA);
         else if (epi == 1) hipLaunchKernelGGL((gemm_rows_resident_kernel<1>), g2, b2, 0, st, a, (long long)lda, w, (long long)ldw, (int)n, (long long)m_rows, bias, (int)relu6, relu6_mask_h, (long long)ldh, c, (long long)ldc, colp, nA);
@@ -1793,6 +1788,6 @@ extern "C" int uavagent_gemm_rows_f32(const float *a, int64_t lda, const float *
         const long long n_part = n_part_resident ? n_part_resident : (w_transposed && m_rows <= 32768) ? (m_rows + 63) / 64 : (long long)grid.x;     // partial rows the kernel that ran wrote
         hipLaunchKernelGGL(rows_colsum_reduce, dim3((n + 63) / 64), dim3(1024), 0, st, colp, n_part, (int)n, colsum_out);
     }
-    if (hipGetLastError() != hipSuccess) return fail3(UAVAGENT_E_HIP, "gemm_rows: launch failed");
+    if (hipGetLastError() != hipSuccess) return fail(UAVAGENT_E_HIP, "gemm_rows: launch failed");
     return UAVAGENT_OK;
 }

@@ -12,7 +12,6 @@
 
 #include <string>
 
-#include "../../include/uavagent.h"
 #include "agent_common.h"
 
 namespace {
@@ -23,7 +22,6 @@ int fail(int code, const std::string &msg) { g_err = msg; return code; }
 }  // namespace uavagent_internal
 
 namespace {
-using uavagent_internal::fail;
 
 // KT > 0: K known at compile time (24 = 4 UAV + 20 UE, 44 = 4 + 40), so the row loop unrolls by UNR with no remainder --
 // v_readlane is a convergent operation and hipcc will not unroll a loop around it when the trip count is a run-time value.
@@ -99,8 +97,6 @@ __global__ __launch_bounds__(256) void sparse_rows_sum_kernel(const float *__res
         *reinterpret_cast<float4 *>(reinterpret_cast<char *>(oc) + o + lane_off) = sc;
     }
 }
-
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
 
@@ -184,8 +180,6 @@ int first_layer_launch(const float *w_a, const float *bias_a, float *out_a, cons
     }
 #undef UAVAGENT_LAUNCH_
 #undef UAVAGENT_LAUNCH
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(UAVAGENT_E_HIP, std::string("sparse_rows_sum launch: ") + hipGetErrorString(e));
-    return UAVAGENT_OK;
+    return launch_ok("sparse_rows_sum launch");
 }
 }  // namespace

@@ -20,12 +20,10 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "../../include/uavagent.h"
 #include "agent_common.h"
+#include "agent_loss_joint.h"
 
 namespace {
-
-int fail2(int code, const std::string &msg) { return uavagent_internal::fail(code, msg); }   // one error string for both parts
 
 // (wave_sum_f / wave_max_f: agent_common.h)
 
@@ -114,20 +112,45 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float *__restric
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// a2c_loss_grad (main.py:64-74), rows = samples, grid-stride over rows, one wavefront per row at a time:
+// a2c_loss_grad (main.py:64-74), rows = samples:
 //   p = softmax(logits);  td = v_target - v;  c_loss = td^2;  a_loss = -(beta * H + log(p[a] + 1e-5) * stop_gradient(td)),
 //   H = -sum p log(p + 1e-5).   d a_loss / d p_j = beta (log(p_j + e) + p_j / (p_j + e)) - [j == a] td / (p_a + e)   =: gp_j
-//   d a_loss / d logit_i = p_i (gp_i - sum_j p_j gp_j);   d c_loss / d v = -2 td;   both scaled by 1/M (the means of :66,:74).
-// The logits are overwritten with their gradient.  Column sums of that gradient (= the gradient of the output bias) and the
-// loss sums are accumulated per wavefront and reduced by colsum_reduce_kernel in a fixed order.  Nothing here needs a running
-// sum over columns, so lane l owns columns l, l + 64, ... (the sampling kernel's contiguous-per-lane layout made every load
-// instruction touch a 2.5 KB span for 256 useful bytes: 0.99 ms for 2 GB of traffic).
+// The row loops, in their dword and float4 forms, are agent_loss_joint.h's (loss_rows / loss_rows_vec); this is their A2C policy: the
+// weight of the chosen-action term is td.  The action is NOT clamped: a row whose action lies outside [0, A) has no chosen-action term.
 // ---------------------------------------------------------------------------------------------------------------------
+struct A2CPolicy {
+    static constexpr int kSums = 3;                       // a_loss, c_loss, sum dv
+    const float *v, *target;
+    const long long *act;
+    struct Row { float td; int a; };
+    __device__ __forceinline__ Row row(long long r, int) const { return {target[r] - v[r], (int)act[r]}; }
+    template <bool HW> __device__ __forceinline__ float weight(const Row &rw, float) const { return rw.td; }
+    // The sum's two roundings, as every instantiation has always computed them (left to contraction they differed between kernels, and moved
+    // with the text): FUSED, the float4 kernels for more than 256 columns, fuse the chosen-action product onto the rounded entropy bonus; the
+    // others round both products and add.
+    template <bool FUSED>
+    __device__ __forceinline__ float actor_loss(const Row &rw, float beta, float h, float lpa) const {
+#pragma clang fp contract(off)
+        return FUSED ? -__builtin_fmaf(lpa, rw.td, beta * h) : -(beta * h + lpa * rw.td);
+    }
+    __device__ __forceinline__ void extra_sums(const Row &, double (&)[1]) const {}
+};
+
 template <int PER>
 __global__ __launch_bounds__(256) void a2c_loss_grad_kernel(float *__restrict__ logits, const float *__restrict__ v,
                                                             const float *__restrict__ target, const long long *__restrict__ act,
                                                             long long M, int A, long long ld, float beta, float inv_m, float *__restrict__ dv,
                                                             float *__restrict__ col_partial, double *__restrict__ loss_partial) {
+    loss_rows<PER>(A2CPolicy{v, target, act}, logits, M, A, ld, beta, inv_m, dv, col_partial, loss_partial);
+}
+// PER = 4 (129 .. 256 columns, rows not 16-byte aligned) keeps the statements without the policy object: every form of loss_rows<4, A2CPolicy>
+// tried came out at 620 instructions against this text's 609 (profiles/loss_fold_listings.txt).
+template <>
+__global__ __launch_bounds__(256) void a2c_loss_grad_kernel<4>(float *__restrict__ logits, const float *__restrict__ v,
+                                                               const float *__restrict__ target, const long long *__restrict__ act,
+                                                               long long M, int A, long long ld, float beta, float inv_m, float *__restrict__ dv,
+                                                               float *__restrict__ col_partial, double *__restrict__ loss_partial) {
+    constexpr int PER = 4;
     const int lane = threadIdx.x & 63;
     const long long wave = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const long long n_waves = (long long)gridDim.x * 4;
@@ -138,33 +161,19 @@ __global__ __launch_bounds__(256) void a2c_loss_grad_kernel(float *__restrict__ 
     for (long long r = wave; r < M; r += n_waves) {
         float *row = logits + r * ld;
         float p[PER];
-        float mx = -3.0e38f;
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int c = k * 64 + lane;          // coalesced: a load instruction reads 64 consecutive floats
-            p[k] = (c < A) ? row[c] : -3.0e38f;
-            mx = fmaxf(mx, p[k]);
-        }
-        mx = wave_max_f(mx);
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int c = k * 64 + lane;          // coalesced: a load instruction reads 64 consecutive floats
-            p[k] = (c < A) ? expf(p[k] - mx) : 0.f;
-            s += p[k];
-        }
-        const float inv = 1.f / wave_sum_f(s);
+        const float inv = row_numerators<PER>(row, A, lane, p);
         const float td = target[r] - v[r];
         const int a = (int)act[r];
         float gp[PER];
         float h = 0.f, dot = 0.f, lpa = 0.f, pa = 0.f;
 #pragma unroll
         for (int k = 0; k < PER; ++k) {
-            const int c = k * 64 + lane;          // coalesced: a load instruction reads 64 consecutive floats
-            p[k] *= inv;
-            const float lp = logf(p[k] + 1e-5f);
-            h -= p[k] * lp;                                         // entropy term (:71-72); p == 0 on padding lanes
-            gp[k] = beta * (lp + p[k] / (p[k] + 1e-5f));
+            const int c = k * 64 + lane;
+            float q;
+            prob_eps(p[k], inv, p[k], q);
+            const float lp = logf(q);
+            h -= p[k] * lp;
+            gp[k] = beta * (lp + p[k] / q);
             if (c == a) { lpa = lp; pa = p[k]; }
         }
         lpa = wave_sum_f(lpa);
@@ -172,14 +181,14 @@ __global__ __launch_bounds__(256) void a2c_loss_grad_kernel(float *__restrict__ 
         h = wave_sum_f(h);
 #pragma unroll
         for (int k = 0; k < PER; ++k) {
-            const int c = k * 64 + lane;          // coalesced: a load instruction reads 64 consecutive floats
+            const int c = k * 64 + lane;
             if (c == a) gp[k] -= td / (pa + 1e-5f);
             dot += p[k] * gp[k];
         }
         dot = wave_sum_f(dot);
 #pragma unroll
         for (int k = 0; k < PER; ++k) {
-            const int c = k * 64 + lane;          // coalesced: a load instruction reads 64 consecutive floats
+            const int c = k * 64 + lane;
             const float g = p[k] * (gp[k] - dot) * inv_m;
             if (c < A) { row[c] = g; csum[k] += g; }
         }
@@ -187,181 +196,37 @@ __global__ __launch_bounds__(256) void a2c_loss_grad_kernel(float *__restrict__ 
             const float g = -2.f * td * inv_m;
             dv[r] = g;
             sdv += (double)g;
-            la += (double)(-(beta * h + lpa * td));                 // :73-74
-            lc += (double)(td * td);                                // :66
+            la += (double)A2CPolicy{v, target, act}.actor_loss<false>({td, a}, beta, h, lpa);
+            lc += (double)(td * td);
         }
     }
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
-        const int c = k * 64 + lane;          // coalesced: a load instruction reads 64 consecutive floats
+        const int c = k * 64 + lane;
         if (c < A) col_partial[wave * A + c] = csum[k];
     }
     if (lane == 0) { loss_partial[wave * 3] = la; loss_partial[wave * 3 + 1] = lc; loss_partial[wave * 3 + 2] = sdv; }
 }
 
-// The same pass for rows that start 16-byte aligned (ld a multiple of 4: the learner's logits live in rows of 640 floats with a zero tail):
-// a lane moves whole float4s (float4 index l, l + 64, ...: a wave instruction touches 1 KB of one row) and the per-element
-// transcendentals are the hardware's (v_exp_f32 / v_log_f32 / v_rcp_f32, ~1 ulp) instead of the library's correctly-handled-everywhere
-// expf / logf / IEEE division: at 625 columns the first form spends ~50 VALU instructions per element -- 0.33 ms of pure issue for the
-// update's 2.56e8 elements -- and ran at 3.3-3.9 TB/s; this one is bound by its 2 x 1.05 GB of traffic.  Operand ranges make the fast
-// forms safe: x - max <= 0 (no overflow; underflow to 0 is the exact limit), p + 1e-5 in [1e-5, 1.00001] (normal, no special cases).
-// Padding elements of the last float4 (columns >= A) are read (zero tail) but excluded from every sum and written back as zeros.
 template <int PERV>
 __global__ __launch_bounds__(256) void a2c_loss_grad_vec_kernel(float *__restrict__ logits, const float *__restrict__ v,
                                                                 const float *__restrict__ target, const long long *__restrict__ act,
                                                                 long long M, int A, long long ld, float beta, float inv_m, float *__restrict__ dv,
                                                                 float *__restrict__ col_partial, double *__restrict__ loss_partial) {
-    const int lane = threadIdx.x & 63;
-    const long long wave = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const long long n_waves = (long long)gridDim.x * 4;
-    const int nv = (A + 3) >> 2;                         // float4s of a row that hold at least one real column
-    float4 csum[PERV];
-#pragma unroll
-    for (int k = 0; k < PERV; ++k) csum[k] = float4{0.f, 0.f, 0.f, 0.f};
-    double la = 0.0, lc = 0.0, sdv = 0.0;
-    constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
-    // the NEXT row of this wavefront is loaded while the current one is computed and stored (two rows in flight per wavefront)
-    float4 nxt[PERV];
-    auto load_row = [&](long long r) {
-        const float4 *row = reinterpret_cast<const float4 *>(logits + r * ld);
-#pragma unroll
-        for (int k = 0; k < PERV; ++k) {
-            const int i4 = k * 64 + lane;
-            nxt[k] = float4{0.f, 0.f, 0.f, 0.f};
-            if (i4 < nv) nxt[k] = row[i4];
-        }
-    };
-    if (wave < M) load_row(wave);
-    for (long long r = wave; r < M; r += n_waves) {
-        float4 *row = reinterpret_cast<float4 *>(logits + r * ld);
-        float x[PERV][4];
-        float mx = -3.0e38f;
-#pragma unroll
-        for (int k = 0; k < PERV; ++k) {
-            const float4 q = nxt[k];
-            x[k][0] = q.x; x[k][1] = q.y; x[k][2] = q.z; x[k][3] = q.w;
-        }
-        const float td = target[r] - v[r];
-        const int a = (int)act[r];
-        if (r + n_waves < M) load_row(r + n_waves);
-#pragma unroll
-        for (int k = 0; k < PERV; ++k) {
-            const int i4 = k * 64 + lane;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (i4 * 4 + j >= A) x[k][j] = -3.0e38f;
-                mx = fmaxf(mx, x[k][j]);
-            }
-        }
-        mx = wave_max_f(mx);
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < PERV; ++k)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const bool ok = (k * 64 + lane) * 4 + j < A;
-                x[k][j] = ok ? __builtin_amdgcn_exp2f((x[k][j] - mx) * kLog2e) : 0.f;
-                s += x[k][j];
-            }
-        const float inv = __builtin_amdgcn_rcpf(wave_sum_f(s));
-        float gp[PERV][4];
-        float h = 0.f, lpa = 0.f, pa = 0.f;
-#pragma unroll
-        for (int k = 0; k < PERV; ++k)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int c = (k * 64 + lane) * 4 + j;
-                const float p = x[k][j] * inv;
-                x[k][j] = p;
-                const float q = p + 1e-5f;
-                const float lp = __builtin_amdgcn_logf(q) * kLn2;
-                h -= p * lp;                                             // entropy term (:71-72); p == 0 on padding elements
-                gp[k][j] = beta * (lp + p * __builtin_amdgcn_rcpf(q));
-                if (c == a) { lpa = lp; pa = p; }
-            }
-        lpa = wave_sum_f(lpa);
-        pa = wave_sum_f(pa);
-        h = wave_sum_f(h);
-        const float tda = td * __builtin_amdgcn_rcpf(pa + 1e-5f);
-        float dot = 0.f;
-#pragma unroll
-        for (int k = 0; k < PERV; ++k)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int c = (k * 64 + lane) * 4 + j;
-                if (c == a) gp[k][j] -= tda;
-                dot += x[k][j] * gp[k][j];
-            }
-        dot = wave_sum_f(dot);
-#pragma unroll
-        for (int k = 0; k < PERV; ++k) {
-            const int i4 = k * 64 + lane;
-            float g[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) g[j] = (i4 * 4 + j < A) ? x[k][j] * (gp[k][j] - dot) * inv_m : 0.f;
-            if (i4 < nv) {
-                row[i4] = float4{g[0], g[1], g[2], g[3]};
-                csum[k].x += g[0]; csum[k].y += g[1]; csum[k].z += g[2]; csum[k].w += g[3];
-            }
-        }
-        if (lane == 0) {
-            const float g = -2.f * td * inv_m;
-            dv[r] = g;
-            sdv += (double)g;
-            la += (double)(-(beta * h + lpa * td));                 // :73-74
-            lc += (double)(td * td);                                // :66
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < PERV; ++k) {
-        const int c0 = (k * 64 + lane) * 4;
-        const float cs[4] = {csum[k].x, csum[k].y, csum[k].z, csum[k].w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (c0 + j < A) col_partial[wave * A + c0 + j] = cs[j];
-    }
-    if (lane == 0) { loss_partial[wave * 3] = la; loss_partial[wave * 3 + 1] = lc; loss_partial[wave * 3 + 2] = sdv; }
+    loss_rows_vec<PERV>(A2CPolicy{v, target, act}, logits, M, A, ld, beta, inv_m, dv, col_partial, loss_partial);
 }
 
-// out[c] = sum_w partial[w][c] in a FIXED order (deterministic): a block owns 64 columns; its 16 slab-threads per column each add
-// a contiguous slab of the partial rows in ascending order (64 consecutive floats per load instruction: coalesced), then the
-// 16 slab sums are added in slab order.  (The first version, one thread per column over all 4096 partial rows, took 0.99 ms per
-// call, 5.9 ms per update: profiles/r02b_a2c_profile_fused_first.txt.)
+// The second stage, two launches (colsum_block / loss_sums_wave: agent_loss_joint.h).  colsum_reduce_kernel serves relu6_bwd too.
 __global__ __launch_bounds__(1024) void colsum_reduce_kernel(const float *__restrict__ partial, long long n_part, int C,
                                                              float *__restrict__ out) {
     __shared__ float slab_sum[16][64];
-    const int cl = threadIdx.x & 63, slab = threadIdx.x >> 6;          // 16 slabs x 64 columns
-    const int c = blockIdx.x * 64 + cl;
-    const long long per = (n_part + 15) / 16;
-    const long long w0 = slab * per, w1 = (w0 + per < n_part) ? w0 + per : n_part;
-    float s = 0.f;
-    if (c < C) {
-        long long w = w0;
-        for (; w + 4 <= w1; w += 4) {                                   // four independent loads in flight, added in order
-            const float a0 = partial[w * C + c], a1 = partial[(w + 1) * C + c], a2 = partial[(w + 2) * C + c], a3 = partial[(w + 3) * C + c];
-            s += a0; s += a1; s += a2; s += a3;
-        }
-        for (; w < w1; ++w) s += partial[w * C + c];
-    }
-    slab_sum[slab][cl] = s;
-    __syncthreads();
-    if (slab == 0 && c < C) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) t += slab_sum[k][cl];
-        out[c] = t;
-    }
+    colsum_block(partial, n_part, C, out, blockIdx.x, slab_sum);
 }
-// One wavefront: lane l adds the partials w = l, l + 64, ... in ascending order, then a fixed shuffle tree (deterministic).
-// (A single thread over all 4096 partials took 0.53 ms: profiles/r02b_a2c_profile_fused_second.txt.)
 __global__ __launch_bounds__(64) void loss_reduce_kernel(const double *__restrict__ partial, long long n_part, double inv_m,
                                                          double *__restrict__ out) {
-    const int lane = threadIdx.x;
-    double a = 0.0, c = 0.0, d = 0.0;
-    for (long long w = lane; w < n_part; w += 64) { a += partial[w * 3]; c += partial[w * 3 + 1]; d += partial[w * 3 + 2]; }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { a += __shfl_xor(a, off, 64); c += __shfl_xor(c, off, 64); d += __shfl_xor(d, off, 64); }
-    if (lane == 0) { out[0] = a * inv_m; out[1] = c * inv_m; out[2] = d; }   // mean actor loss, mean critic loss, sum of dv (= d loss / d b3c)
+    double a[3];
+    loss_sums_wave<3>(partial, n_part, threadIdx.x, a);
+    if (threadIdx.x == 0) { out[0] = a[0] * inv_m; out[1] = a[1] * inv_m; out[2] = a[2]; }   // mean actor loss, mean critic loss, sum of dv (= d loss / d b3c)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -618,30 +483,16 @@ __global__ __launch_bounds__(256) void nstep_returns_kernel(const float *__restr
     }
 }
 
-bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-// fixed reduction grids (results depend on them: keep them constants of the library, not of the device)
-constexpr int kLossBlocks = 1024;     // x 4 wavefronts
+// fixed reduction grids (results depend on them: keep them constants of the library, not of the device; kLossBlocks: agent_loss_joint.h)
 constexpr int kReluBlocks = 1024;
 
-int per_lane_cols(int A) { return (A + 63) / 64; }
-
-}  // namespace
-
-namespace {
-int launch_ok(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail2(UAVAGENT_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    return UAVAGENT_OK;
-}
 }  // namespace
 
 extern "C" int uavagent_obs_indices(const int16_t *ue_xy, const int32_t *bs_xy, const int8_t *serving, int64_t n_envs, int32_t n_ue,
                                     int32_t n_bs, int32_t grid, int64_t *idx_out, void *stream) {
-    if (n_envs < 0 || n_ue < 1 || n_bs < 1 || grid < 1) return fail2(UAVAGENT_E_INVALID, "obs_indices: bad shape");
+    if (n_envs < 0 || n_ue < 1 || n_bs < 1 || grid < 1) return fail(UAVAGENT_E_INVALID, "obs_indices: bad shape");
     if (n_envs == 0) return UAVAGENT_OK;
-    if (!ue_xy || !bs_xy || !serving || !idx_out) return fail2(UAVAGENT_E_INVALID, "obs_indices: null pointer");
+    if (!ue_xy || !bs_xy || !serving || !idx_out) return fail(UAVAGENT_E_INVALID, "obs_indices: null pointer");
     const long long total = (long long)n_envs * (n_ue + n_bs);
     hipLaunchKernelGGL(obs_indices_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ue_xy, bs_xy,
                        serving, (long long)n_envs, (int)n_ue, (int)n_bs, (int)grid, reinterpret_cast<long long *>(idx_out));
@@ -651,32 +502,26 @@ extern "C" int uavagent_obs_indices(const int16_t *ue_xy, const int32_t *bs_xy, 
 extern "C" int uavagent_sample_actions(const float *logits, int64_t ld_logits, const float *uniforms, int64_t n_rows, int32_t n_actions,
                                        int64_t *actions_out, float *prob_out, void *stream) {
     if (n_rows < 0 || n_actions < 1 || n_actions > 1024 || ld_logits < n_actions)
-        return fail2(UAVAGENT_E_INVALID, "sample_actions: need 1 <= n_actions <= 1024 and ld_logits >= n_actions");
+        return fail(UAVAGENT_E_INVALID, "sample_actions: need 1 <= n_actions <= 1024 and ld_logits >= n_actions");
     if (n_rows == 0) return UAVAGENT_OK;
-    if (!logits || !uniforms || !actions_out) return fail2(UAVAGENT_E_INVALID, "sample_actions: null pointer");
+    if (!logits || !uniforms || !actions_out) return fail(UAVAGENT_E_INVALID, "sample_actions: null pointer");
     const dim3 grid((unsigned)((n_rows + 3) / 4)), blk(256);
     hipStream_t s = (hipStream_t)stream;
     long long *ao = reinterpret_cast<long long *>(actions_out);
-#define UAVAGENT_SAMPLE(P_) hipLaunchKernelGGL((sample_actions_kernel<P_>), grid, blk, 0, s, logits, (long long)ld_logits, uniforms, (long long)n_rows, (int)n_actions, ao, prob_out)
-    switch (per_lane_cols(n_actions)) {
-        case 1: UAVAGENT_SAMPLE(1); break;
-        case 2: UAVAGENT_SAMPLE(2); break;
-        case 3: case 4: UAVAGENT_SAMPLE(4); break;
-        case 5: case 6: case 7: case 8: UAVAGENT_SAMPLE(8); break;
-        case 9: case 10: UAVAGENT_SAMPLE(10); break;
-        default: UAVAGENT_SAMPLE(16); break;
-    }
-#undef UAVAGENT_SAMPLE
+    dispatch_per_dword(n_actions, [&](auto per) {                       // the draw has one form: PER consecutive columns per lane
+        hipLaunchKernelGGL((sample_actions_kernel<decltype(per)::value>), grid, blk, 0, s, logits, (long long)ld_logits, uniforms,
+                           (long long)n_rows, (int)n_actions, ao, prob_out);
+    });
     return launch_ok("sample_actions");
 }
 
 extern "C" int uavagent_argmax_rows_f32(const float *logits, int64_t ld_logits, int64_t n_rows, int32_t n_actions, int64_t *actions_out,
                                         void *stream) {
     if (n_rows < 0 || n_actions < 1 || n_actions > 1024 || ld_logits < n_actions)
-        return fail2(UAVAGENT_E_INVALID, "argmax_rows: need 1 <= n_actions <= 1024 and ld_logits >= n_actions");
+        return fail(UAVAGENT_E_INVALID, "argmax_rows: need 1 <= n_actions <= 1024 and ld_logits >= n_actions");
     if (n_rows == 0) return UAVAGENT_OK;
-    if (!logits || !actions_out) return fail2(UAVAGENT_E_INVALID, "argmax_rows: null pointer");
-    if (n_rows > 4ll * 0x7FFFFFFFll) return fail2(UAVAGENT_E_INVALID, "argmax_rows: n_rows too large for one launch");
+    if (!logits || !actions_out) return fail(UAVAGENT_E_INVALID, "argmax_rows: null pointer");
+    if (n_rows > 4ll * 0x7FFFFFFFll) return fail(UAVAGENT_E_INVALID, "argmax_rows: n_rows too large for one launch");
     hipLaunchKernelGGL(argmax_rows_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, (long long)ld_logits,
                        (long long)n_rows, (int)n_actions, reinterpret_cast<long long *>(actions_out));
     return launch_ok("argmax_rows");
@@ -691,35 +536,21 @@ extern "C" int uavagent_a2c_loss_grad(float *logits_inout, int64_t ld_logits, co
                                       int64_t m_rows, int32_t n_actions, float beta, float *dv_out, float *dbias_out,
                                       double *loss_out, void *workspace, void *stream) {
     if (m_rows < 1 || n_actions < 1 || n_actions > 1024 || ld_logits < n_actions)
-        return fail2(UAVAGENT_E_INVALID, "a2c_loss_grad: need m_rows >= 1, 1 <= n_actions <= 1024, ld_logits >= n_actions");
+        return fail(UAVAGENT_E_INVALID, "a2c_loss_grad: need m_rows >= 1, 1 <= n_actions <= 1024, ld_logits >= n_actions");
     if (!logits_inout || !v || !v_target || !actions || !dv_out || !dbias_out || !loss_out || !workspace)
-        return fail2(UAVAGENT_E_INVALID, "a2c_loss_grad: null pointer");
+        return fail(UAVAGENT_E_INVALID, "a2c_loss_grad: null pointer");
     hipStream_t s = (hipStream_t)stream;
     const long long waves = (long long)kLossBlocks * 4;
     float *colp = reinterpret_cast<float *>(workspace);
     double *lossp = reinterpret_cast<double *>(reinterpret_cast<char *>(workspace) + up256((size_t)waves * n_actions * sizeof(float)));
     const float inv_m = 1.0f / (float)m_rows;
     const long long *ac = reinterpret_cast<const long long *>(actions);
-#define UAVAGENT_LOSS(P_) hipLaunchKernelGGL((a2c_loss_grad_kernel<P_>), dim3(kLossBlocks), dim3(256), 0, s, logits_inout, v, v_target, ac, \
-                                             (long long)m_rows, (int)n_actions, (long long)ld_logits, beta, inv_m, dv_out, colp, lossp)
-    // rows that start 16-byte aligned (the learner's: ld 640): the float4 form
-    const bool vec = ((reinterpret_cast<uintptr_t>(logits_inout) & 15) == 0) && ((ld_logits & 3) == 0) && (ld_logits >= ((n_actions + 3) & ~3));
-#define UAVAGENT_LOSSV(P_) hipLaunchKernelGGL((a2c_loss_grad_vec_kernel<P_>), dim3(kLossBlocks), dim3(256), 0, s, logits_inout, v, v_target, ac, \
-                                              (long long)m_rows, (int)n_actions, (long long)ld_logits, beta, inv_m, dv_out, colp, lossp)
-    if (vec) {
-        const int nv = (n_actions + 3) / 4;
-        if (nv <= 64) UAVAGENT_LOSSV(1); else if (nv <= 128) UAVAGENT_LOSSV(2); else if (nv <= 192) UAVAGENT_LOSSV(3); else UAVAGENT_LOSSV(4);
-    } else
-    switch (per_lane_cols(n_actions)) {
-        case 1: UAVAGENT_LOSS(1); break;
-        case 2: UAVAGENT_LOSS(2); break;
-        case 3: case 4: UAVAGENT_LOSS(4); break;
-        case 5: case 6: case 7: case 8: UAVAGENT_LOSS(8); break;
-        case 9: case 10: UAVAGENT_LOSS(10); break;
-        default: UAVAGENT_LOSS(16); break;
-    }
-#undef UAVAGENT_LOSS
-#undef UAVAGENT_LOSSV
+    dispatch_per(use_vec(logits_inout, ld_logits, n_actions), n_actions, [&](auto vec, auto per) {
+        constexpr int P = decltype(per)::value;
+        auto kernel = [] { if constexpr (decltype(vec)::value) return a2c_loss_grad_vec_kernel<P>; else return a2c_loss_grad_kernel<P>; }();
+        hipLaunchKernelGGL(kernel, dim3(kLossBlocks), dim3(256), 0, s, logits_inout, v, v_target, ac, (long long)m_rows, (int)n_actions,
+                           (long long)ld_logits, beta, inv_m, dv_out, colp, lossp);
+    });
     if (int rc = launch_ok("a2c_loss_grad")) return rc;
     hipLaunchKernelGGL(colsum_reduce_kernel, dim3((n_actions + 63) / 64), dim3(1024), 0, s, colp, waves, (int)n_actions, dbias_out);
     hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(64), 0, s, lossp, waves, 1.0 / (double)m_rows, loss_out);
@@ -730,11 +561,11 @@ extern "C" size_t uavagent_relu6_bwd_workspace_bytes(int32_t n_cols) { return 2 
 
 extern "C" int uavagent_relu6_bwd(const float *dy, const float *y, const float *dv, const float *w3, int64_t m_rows, int32_t n_cols,
                                   float *dx_out, int64_t ldx, float *dbias_out, float *dw3_out, void *workspace, void *stream) {
-    if (m_rows < 1 || n_cols < 4 || n_cols > 256 || (n_cols & 3)) return fail2(UAVAGENT_E_INVALID, "relu6_bwd: n_cols must be a multiple of 4 in [4, 256], m_rows >= 1");
+    if (m_rows < 1 || n_cols < 4 || n_cols > 256 || (n_cols & 3)) return fail(UAVAGENT_E_INVALID, "relu6_bwd: n_cols must be a multiple of 4 in [4, 256], m_rows >= 1");
     const bool outer = (dy == nullptr);
-    if (!y || !dx_out || !dbias_out || !workspace || (outer && (!dv || !w3 || !dw3_out))) return fail2(UAVAGENT_E_INVALID, "relu6_bwd: null pointer");
-    if (ldx < n_cols || (ldx & 3) || !al16(dy) || !al16(y) || !al16(dx_out) || !al16(w3))
-        return fail2(UAVAGENT_E_INVALID, "relu6_bwd: buffers must be 16-byte aligned, ldx a multiple of 4 and >= n_cols");
+    if (!y || !dx_out || !dbias_out || !workspace || (outer && (!dv || !w3 || !dw3_out))) return fail(UAVAGENT_E_INVALID, "relu6_bwd: null pointer");
+    if (ldx < n_cols || (ldx & 3) || !aligned16(dy) || !aligned16(y) || !aligned16(dx_out) || !aligned16(w3))
+        return fail(UAVAGENT_E_INVALID, "relu6_bwd: buffers must be 16-byte aligned, ldx a multiple of 4 and >= n_cols");
     hipStream_t s = (hipStream_t)stream;
     const long long waves = (long long)kReluBlocks * 4;
     float *p0 = reinterpret_cast<float *>(workspace);
@@ -755,7 +586,7 @@ int rows_ws(int64_t n_pairs, int32_t ncol, int64_t n_rows, RowsWs &w) {
     size_t tmp = 0;
     uint32_t *nk = nullptr;
     const hipError_t e = rocprim::radix_sort_pairs(nullptr, tmp, nk, nk, nk, nk, n, 0u, sort_bits(n_rows), (hipStream_t)0);
-    if (e != hipSuccess) return fail2(UAVAGENT_E_HIP, std::string("rows_grad: rocprim size query: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(UAVAGENT_E_HIP, std::string("rows_grad: rocprim size query: ") + hipGetErrorString(e));
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off += up256(bytes); return o; };
     w.keys_in = take(n * 4); w.keys_out = take(n * 4); w.samp_in = take(n * 4); w.samp_out = take(n * 4);
@@ -778,19 +609,19 @@ namespace {
 // Nothing in the sort or in stages A and B depends on k beyond samp = pair / k: the 64-node exports and the wide ones (k <= 256, the
 // nodes of uavagent_first_layer_wide_f32) share these two functions and differ in the bound they pass.
 int bad_shape(int k_max) {
-    return fail2(UAVAGENT_E_INVALID, "rows_grad: need m_rows >= 1, 1 <= k <= " + std::to_string(k_max) + ", h a multiple of 4 in [4, 256], 1 or 2 tables");
+    return fail(UAVAGENT_E_INVALID, "rows_grad: need m_rows >= 1, 1 <= k <= " + std::to_string(k_max) + ", h a multiple of 4 in [4, 256], 1 or 2 tables");
 }
 
 int rows_grad_sort_impl(int k_max, const int64_t *idx, int64_t m_rows, int32_t k, int32_t n_cols_total, int64_t n_rows, void *workspace,
                         size_t workspace_bytes, void *stream) {
     if (m_rows < 1 || k < 1 || k > k_max || n_cols_total < 4 || n_cols_total > 512 || (n_cols_total & 3) || n_rows < 1) return bad_shape(k_max);
-    if (!idx || !workspace) return fail2(UAVAGENT_E_INVALID, "rows_grad: null pointer");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return fail2(UAVAGENT_E_INVALID, "rows_grad: g and the tables must be 16-byte aligned, the workspace 256-byte aligned");
+    if (!idx || !workspace) return fail(UAVAGENT_E_INVALID, "rows_grad: null pointer");
+    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return fail(UAVAGENT_E_INVALID, "rows_grad: g and the tables must be 16-byte aligned, the workspace 256-byte aligned");
     const long long n_pairs = (long long)m_rows * k;
-    if (n_pairs > 0x7FFFFFFFll || (unsigned long long)n_rows >= 0xFFFFFFF0ull) return fail2(UAVAGENT_E_INVALID, "rows_grad: too many pairs / rows for 32-bit keys");
+    if (n_pairs > 0x7FFFFFFFll || (unsigned long long)n_rows >= 0xFFFFFFF0ull) return fail(UAVAGENT_E_INVALID, "rows_grad: too many pairs / rows for 32-bit keys");
     RowsWs w;
     if (int rc = rows_ws(n_pairs, n_cols_total, n_rows, w)) return rc;
-    if (workspace_bytes < w.total) return fail2(UAVAGENT_E_INVALID, "rows_grad: workspace smaller than uavagent_rows_grad_workspace_bytes()");
+    if (workspace_bytes < w.total) return fail(UAVAGENT_E_INVALID, "rows_grad: workspace smaller than uavagent_rows_grad_workspace_bytes()");
     hipStream_t s = (hipStream_t)stream;
     char *ws = reinterpret_cast<char *>(workspace);
     uint32_t *keys_in = reinterpret_cast<uint32_t *>(ws + w.keys_in), *keys_out = reinterpret_cast<uint32_t *>(ws + w.keys_out);
@@ -800,22 +631,22 @@ int rows_grad_sort_impl(int k_max, const int64_t *idx, int64_t m_rows, int32_t k
     if (int rc = launch_ok("rows_grad keys")) return rc;
     size_t tmp = w.sort_tmp_bytes;
     const hipError_t e = rocprim::radix_sort_pairs(ws + w.sort_tmp, tmp, keys_in, keys_out, samp_in, samp_out, (size_t)n_pairs, 0u, sort_bits(n_rows), s);
-    if (e != hipSuccess) return fail2(UAVAGENT_E_HIP, std::string("rows_grad: rocprim radix_sort_pairs: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(UAVAGENT_E_HIP, std::string("rows_grad: rocprim radix_sort_pairs: ") + hipGetErrorString(e));
     return UAVAGENT_OK;
 }
 
 int rows_grad_sums_impl(int k_max, const float *g, int64_t m_rows, int32_t k, int32_t h, int32_t n_tables, int64_t n_rows, float *dw0_out,
                         float *dw1_out, void *workspace, size_t workspace_bytes, void *stream) {
     if (m_rows < 1 || k < 1 || k > k_max || h < 4 || h > 256 || (h & 3) || (n_tables != 1 && n_tables != 2) || n_rows < 1) return bad_shape(k_max);
-    if (!g || !dw0_out || (n_tables == 2 && !dw1_out) || !workspace) return fail2(UAVAGENT_E_INVALID, "rows_grad: null pointer");
-    if (!al16(g) || !al16(dw0_out) || !al16(dw1_out) || (reinterpret_cast<uintptr_t>(workspace) & 255u))
-        return fail2(UAVAGENT_E_INVALID, "rows_grad: g and the tables must be 16-byte aligned, the workspace 256-byte aligned");
+    if (!g || !dw0_out || (n_tables == 2 && !dw1_out) || !workspace) return fail(UAVAGENT_E_INVALID, "rows_grad: null pointer");
+    if (!aligned16(g) || !aligned16(dw0_out) || !aligned16(dw1_out) || (reinterpret_cast<uintptr_t>(workspace) & 255u))
+        return fail(UAVAGENT_E_INVALID, "rows_grad: g and the tables must be 16-byte aligned, the workspace 256-byte aligned");
     const long long n_pairs = (long long)m_rows * k;
-    if (n_pairs > 0x7FFFFFFFll || (unsigned long long)n_rows >= 0xFFFFFFF0ull) return fail2(UAVAGENT_E_INVALID, "rows_grad: too many pairs / rows for 32-bit keys");
+    if (n_pairs > 0x7FFFFFFFll || (unsigned long long)n_rows >= 0xFFFFFFF0ull) return fail(UAVAGENT_E_INVALID, "rows_grad: too many pairs / rows for 32-bit keys");
     const int ncol = h * n_tables;
     RowsWs w;
     if (int rc = rows_ws(n_pairs, ncol, n_rows, w)) return rc;
-    if (workspace_bytes < w.total) return fail2(UAVAGENT_E_INVALID, "rows_grad: workspace smaller than uavagent_rows_grad_workspace_bytes()");
+    if (workspace_bytes < w.total) return fail(UAVAGENT_E_INVALID, "rows_grad: workspace smaller than uavagent_rows_grad_workspace_bytes()");
     hipStream_t s = (hipStream_t)stream;
     char *ws = reinterpret_cast<char *>(workspace);
     const uint32_t *keys_out = reinterpret_cast<const uint32_t *>(ws + w.keys_out), *samp_out = reinterpret_cast<const uint32_t *>(ws + w.samp_out);
@@ -824,7 +655,7 @@ int rows_grad_sums_impl(int k_max, const float *g, int64_t m_rows, int32_t k, in
     // rows nobody touches keep a zero gradient
     hipError_t e = hipMemsetAsync(dw0_out, 0, (size_t)n_rows * h * sizeof(float), s);
     if (e == hipSuccess && n_tables == 2) e = hipMemsetAsync(dw1_out, 0, (size_t)n_rows * h * sizeof(float), s);
-    if (e != hipSuccess) return fail2(UAVAGENT_E_HIP, std::string("rows_grad: memset: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(UAVAGENT_E_HIP, std::string("rows_grad: memset: ") + hipGetErrorString(e));
     const long long chunks = (n_pairs + kChunk - 1) / kChunk;
     const unsigned blocks = (unsigned)((chunks + 3) / 4);
     hipLaunchKernelGGL(rows_sum_stage_a, dim3(blocks), dim3(256), 0, s, keys_out, samp_out, n_pairs, (uint32_t)n_rows, g, (int)(ncol / 4),
@@ -857,19 +688,19 @@ extern "C" int uavagent_rows_grad_f32(const int64_t *idx, const float *g, int64_
                                       int64_t n_rows, float *dw0_out, float *dw1_out, void *workspace, size_t workspace_bytes,
                                       void *stream) {
     if (h < 4 || h > 256 || (h & 3) || (n_tables != 1 && n_tables != 2))
-        return fail2(UAVAGENT_E_INVALID, "rows_grad: need m_rows >= 1, 1 <= k <= 64, h a multiple of 4 in [4, 256], 1 or 2 tables");
-    if (!idx || !g || !dw0_out || (n_tables == 2 && !dw1_out) || !workspace) return fail2(UAVAGENT_E_INVALID, "rows_grad: null pointer");
-    if (!al16(g) || !al16(dw0_out) || !al16(dw1_out) || (reinterpret_cast<uintptr_t>(workspace) & 255u))
-        return fail2(UAVAGENT_E_INVALID, "rows_grad: g and the tables must be 16-byte aligned, the workspace 256-byte aligned");
+        return fail(UAVAGENT_E_INVALID, "rows_grad: need m_rows >= 1, 1 <= k <= 64, h a multiple of 4 in [4, 256], 1 or 2 tables");
+    if (!idx || !g || !dw0_out || (n_tables == 2 && !dw1_out) || !workspace) return fail(UAVAGENT_E_INVALID, "rows_grad: null pointer");
+    if (!aligned16(g) || !aligned16(dw0_out) || !aligned16(dw1_out) || (reinterpret_cast<uintptr_t>(workspace) & 255u))
+        return fail(UAVAGENT_E_INVALID, "rows_grad: g and the tables must be 16-byte aligned, the workspace 256-byte aligned");
     if (int rc = uavagent_rows_grad_sort(idx, m_rows, k, h * n_tables, n_rows, workspace, workspace_bytes, stream)) return rc;
     return uavagent_rows_grad_sums_f32(g, m_rows, k, h, n_tables, n_rows, dw0_out, dw1_out, workspace, workspace_bytes, stream);
 }
 
 extern "C" int uavagent_rowdot_f32(const float *y, const float *w, const float *bias, int64_t m_rows, int32_t n_cols, float *out,
                                    void *stream) {
-    if (m_rows < 0 || n_cols < 4 || n_cols > 256 || (n_cols & 3)) return fail2(UAVAGENT_E_INVALID, "rowdot: n_cols must be a multiple of 4 in [4, 256]");
+    if (m_rows < 0 || n_cols < 4 || n_cols > 256 || (n_cols & 3)) return fail(UAVAGENT_E_INVALID, "rowdot: n_cols must be a multiple of 4 in [4, 256]");
     if (m_rows == 0) return UAVAGENT_OK;
-    if (!y || !w || !out || !al16(y) || !al16(w)) return fail2(UAVAGENT_E_INVALID, "rowdot: null or unaligned (16 B) pointer");
+    if (!y || !w || !out || !aligned16(y) || !aligned16(w)) return fail(UAVAGENT_E_INVALID, "rowdot: null or unaligned (16 B) pointer");
     const long long blocks = (m_rows + 3) / 4 < 2048 ? (m_rows + 3) / 4 : 2048;
     hipLaunchKernelGGL(rowdot_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, y, w, bias, (long long)m_rows, (int)(n_cols / 4), out);
     return launch_ok("rowdot");
@@ -877,9 +708,9 @@ extern "C" int uavagent_rowdot_f32(const float *y, const float *w, const float *
 
 extern "C" int uavagent_nstep_returns_f32(const float *rewards, const float *bootstrap, int64_t n_envs, int32_t n_steps, float gamma,
                                           float *out, void *stream) {
-    if (n_envs < 0 || n_steps < 0) return fail2(UAVAGENT_E_INVALID, "nstep_returns: negative size");
+    if (n_envs < 0 || n_steps < 0) return fail(UAVAGENT_E_INVALID, "nstep_returns: negative size");
     if (n_envs == 0 || n_steps == 0) return UAVAGENT_OK;
-    if (!rewards || !bootstrap || !out) return fail2(UAVAGENT_E_INVALID, "nstep_returns: null pointer");
+    if (!rewards || !bootstrap || !out) return fail(UAVAGENT_E_INVALID, "nstep_returns: null pointer");
     hipLaunchKernelGGL(nstep_returns_kernel, dim3((unsigned)((n_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rewards, bootstrap,
                        (long long)n_envs, (int)n_steps, gamma, out);
     return launch_ok("nstep_returns");
@@ -887,9 +718,9 @@ extern "C" int uavagent_nstep_returns_f32(const float *rewards, const float *boo
 
 extern "C" int uavagent_rmsprop_tf1(float *w, float *ms, const float *g, int64_t n, float lr, float decay, float eps, float g_scale,
                                     void *stream) {
-    if (n < 0) return fail2(UAVAGENT_E_INVALID, "rmsprop: negative n");
+    if (n < 0) return fail(UAVAGENT_E_INVALID, "rmsprop: negative n");
     if (n == 0) return UAVAGENT_OK;
-    if (!w || !ms || !g || !al16(w) || !al16(ms) || !al16(g)) return fail2(UAVAGENT_E_INVALID, "rmsprop: null or unaligned (16 B) pointer");
+    if (!w || !ms || !g || !aligned16(w) || !aligned16(ms) || !aligned16(g)) return fail(UAVAGENT_E_INVALID, "rmsprop: null or unaligned (16 B) pointer");
     const long long n4 = (n + 3) / 4;
     hipLaunchKernelGGL(rmsprop_tf1_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, ms, g, (long long)n, lr,
                        decay, eps, g_scale);

@@ -18,11 +18,9 @@
 
 #include <string>
 
-#include "../../include/uavagent.h"
 #include "agent_common.h"
 
 namespace {
-using uavagent_internal::fail;
 
 constexpr int kMaxNodes = 256, kPasses = kMaxNodes / 64;
 
@@ -94,8 +92,6 @@ __global__ __launch_bounds__(256) void wide_rows_sum_kernel(const float *__restr
     }
 }
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 int wide_launch(const float *w_a, const float *bias_a, float *out_a, const float *w_c, const float *bias_c, float *out_c,
                 const int64_t *idx, const ObsSrc *obs, int64_t m_rows, int32_t k, int32_t h, int64_t n_rows, int32_t relu6, void *stream) {
     if (m_rows < 0 || n_rows < 1 || k < 1 || k > kMaxNodes)
@@ -133,9 +129,7 @@ int wide_launch(const float *w_a, const float *bias_a, float *out_a, const float
     }
 #undef UAVAGENT_WIDE_
 #undef UAVAGENT_WIDE
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(UAVAGENT_E_HIP, std::string("first_layer_wide launch: ") + hipGetErrorString(e));
-    return UAVAGENT_OK;
+    return launch_ok("first_layer_wide launch");
 }
 }  // namespace
 

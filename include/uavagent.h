@@ -329,7 +329,7 @@ int uavagent_logp_f32(const float *logits, int64_t ld_logits, const int64_t *act
  * rho > 1 + clip) or (adv < 0 and rho < 1 - clip);  s = clipped ? clamp(rho, 1 - clip, 1 + clip) * adv : rho * adv;
  *   a_loss = mean(-s - beta * H),  H = -sum_j p_j log(p_j + 1e-5);  c_loss = mean((ret - v)^2);  dv = -2 (ret - v) / M;
  *   gp_j = beta (log(p_j + e) + p_j / (p_j + e)) - [j == d] w / (p_d + e),  w = clipped ? 0 : rho * adv;
- *   d a_loss / d logit_j = p_j (gp_j - sum_i p_i gp_i) / M         -- uavagent_a2c_loss_grad's statements with its td replaced by w:
+ *   d a_loss / d logit_j = p_j (gp_j - sum_i p_i gp_i) / M         -- uavagent_a2c_loss_grad's row loop (csrc/agent_loss_joint.h) under another policy, td replaced by w:
  * with logp_old == lp (uavagent_logp_f32 on the same buffer), v == 0 and ret == adv the gradient, dbias, dv, c_loss and sum(dv) are that
  * function's at v_target = adv, bit for bit.  IN / OUT as there (the float4 form writes zeros into columns [n_actions, roundup4(n_actions)),
  * no other column >= n_actions is touched); loss_out double[5] = {a_loss, c_loss, sum(dv), clip_fraction, mean(logp_old - lp)}.
