@@ -127,6 +127,19 @@ UAVENV_HD double lm_exp2(double x, const LeanCoef &c) {
 }
 
 // sin(pi x), cos(pi x), |x| < 2^30.  q = rint(2x), r = x - q/2 exact in [-1/4, 1/4]; Taylor in r; quadrant fix-up.
+// X3 (the pinned multi-step kernels): each sign flip is one shift and one three-input bit op on the HIGH word,
+// hi ^ ((n << 30) & 0x80000000) with n = q for the sine and q + 1 for the cosine -- bit 1 of n lands on bit 31, the mask drops bit 0 -- and
+// the low word passes through.  Without it: and, shift, xor.  The same doubles either way.
+template <bool X3>
+UAVENV_HD double lm_flip_by_bit1(double v, int n) {
+    unsigned long long b;
+    __builtin_memcpy(&b, &v, 8);
+    const uint32_t hi = xor_and<X3>((uint32_t)(b >> 32), (uint32_t)n << 30, 0x80000000u);
+    b = (unsigned long long)hi << 32 | (uint32_t)b;
+    __builtin_memcpy(&v, &b, 8);
+    return v;
+}
+template <bool X3 = false>
 UAVENV_HD void lm_sincospi(double x, const LeanCoef &c, double *s_out, double *c_out) {
     const double q = rint(x + x);
     const double r = fma(q, -0.5, x);
@@ -141,6 +154,11 @@ UAVENV_HD void lm_sincospi(double x, const LeanCoef &c, double *s_out, double *c
     const double so = odd ? cr : sr, co = odd ? sr : cr;   // q mod 4: 0 (s,c)  1 (c,-s)  2 (-s,-c)  3 (-c,s)
     // sign flips as integer XORs on the sign bit: per-lane booleans live in SGPR pairs on gfx9 and the kernels are
     // SGPR-bound (spills show up as v_readlane/v_writelane), so only `odd` is a boolean here.
+    if constexpr (X3) {
+        *s_out = lm_flip_by_bit1<true>(so, iq);
+        *c_out = lm_flip_by_bit1<true>(co, iq + 1);
+        return;
+    }
     const unsigned long long ss = (unsigned long long)(unsigned)(iq & 2) << 62;         // bit 1 of q     -> bit 63
     const unsigned long long cs = (unsigned long long)(unsigned)((iq + 1) & 2) << 62;   // bit 1 of (q+1) -> bit 63
     *s_out = lm_xor_sign(so, ss);

@@ -21,13 +21,41 @@ enum DrawSite : uint32_t {  // Philox counter word 3
 
 struct U4 { uint32_t x, y, z, w; };
 
+// Truth tables of gfx950's three-input bit op (v_bitop3_b32 d, a, b, c: bit i of d = table bit (a_i << 2 | b_i << 1 | c_i)).  A table is
+// the wanted function applied to the three operand patterns: a = 0xF0, b = 0xCC, c = 0xAA.
+constexpr uint32_t kBitopA = 0xF0, kBitopB = 0xCC, kBitopC = 0xAA;
+constexpr uint32_t kBitopXor3 = kBitopA ^ kBitopB ^ kBitopC;        // a ^ b ^ c
+constexpr uint32_t kBitopXorAnd = kBitopA ^ (kBitopB & kBitopC);    // a ^ (b & c)
+static_assert((0xF0 ^ 0xCC ^ 0xAA) == 0x96 && kBitopXor3 == 0x96, "table of a ^ b ^ c");
+static_assert((0xF0 ^ (0xCC & 0xAA)) == 0x78 && kBitopXorAnd == 0x78, "table of a ^ (b & c)");
+
+// a ^ b ^ c.  X3 in gfx950 device code: ONE v_bitop3_b32 (hipcc emits two v_xor_b32 for the plain expression); the same integer either way.
+template <bool X3>
+UAVENV_HD uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__gfx950__)
+    if constexpr (X3) return __builtin_amdgcn_bitop3_b32(a, b, c, kBitopXor3);
+#endif
+    return a ^ b ^ c;
+}
+// a ^ (b & c), the same way (lean_math.h: a sign flip under a mask).
+template <bool X3>
+UAVENV_HD uint32_t xor_and(uint32_t a, uint32_t b, uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__gfx950__)
+    if constexpr (X3) return __builtin_amdgcn_bitop3_b32(a, b, c, kBitopXorAnd);
+#endif
+    return a ^ (b & c);
+}
+
+// X3: the two xors of a round's new c0 / c2 as one three-input bit op each (the pinned multi-step kernels).  Host
+// code and X3 = false keep the two xors; the stream is the same.
+template <bool X3 = false>
 UAVENV_HD U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
         const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        const uint32_t n0 = xor3<X3>((uint32_t)(p1 >> 32), c1, k0);
+        const uint32_t n2 = xor3<X3>((uint32_t)(p0 >> 32), c3, k1);
         c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }

@@ -319,9 +319,10 @@ __device__ __forceinline__ double slot_quads_sum(const double (&q)[kMaxQuads]) {
     return ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
 }
 
+template <bool X3 = false>   // X3: philox.h (three-input bit ops; the pinned multi-step kernels)
 __device__ __forceinline__ void philox_u2(const KParams &p, uint32_t env, uint32_t tick, uint32_t idx, uint32_t dom,
                                           double &u0, double &u1) {
-    const U4 r = philox4x32_10(p.env_id_base + env, tick, idx, dom, p.key0, p.key1);
+    const U4 r = philox4x32_10<X3>(p.env_id_base + env, tick, idx, dom, p.key0, p.key1);
     u0 = u53(r.x, r.y);
     u1 = u53(r.z, r.w);
 }
@@ -344,8 +345,9 @@ __device__ __forceinline__ void philox_u2(const KParams &p, uint32_t env, uint32
 //              u53(q.x, q.y), angle fraction q.z * 2^-32): samples with bit 6 of s clear take the cosine branch, the others the sine branch
 //              -- s and s + 64 are consecutive samples of ONE lane (lane l sums samples l, l + 64, ...), so one call serves both.
 __host__ __device__ constexpr bool quad_draws(int B) { return B > 8; }
+template <bool X3 = false>
 __device__ __forceinline__ U4 philox_raw(const KParams &p, uint32_t env, uint32_t tick, uint32_t idx, uint32_t dom) {
-    return philox4x32_10(p.env_id_base + env, tick, idx, dom, p.key0, p.key1);
+    return philox4x32_10<X3>(p.env_id_base + env, tick, idx, dom, p.key0, p.key1);
 }
 __device__ __forceinline__ double heading_from(const U4 &q0, const U4 &q1, int HB) {
     return (HB >= 2) ? u53(q0.w, q1.w) : (double)q0.w * (1.0 / 4294967296.0);
@@ -463,11 +465,12 @@ __device__ __forceinline__ void bs_move_serial(const KParams &p, unsigned a, int
 // One next() of reference_point_group for one walker (ue_mobility.py:455-505): own step along the heading
 // drawn last tick, group step (+ pull towards the group centre while aggregating), then the four ordered
 // bounce tests.  c[k] report which tests fired (they flip the GROUP heading, once per group and test).
+template <bool X3 = false>
 __device__ __forceinline__ void walker_move(const HotConst &H, const LeanCoef &C, bool aggregating, double hu, double gx,
                                             double gy, double gv, double gc, double gs, double MAXC, double &x, double &y,
                                             bool c[4]) {
     double sn, cs;
-    lm_sincospi(2.0 * hu, C, &sn, &cs);       // theta = 2*pi*u  (:437,508)
+    lm_sincospi<X3>(2.0 * hu, C, &sn, &cs);   // theta = 2*pi*u  (:437,508)
     x = x + H.vel * cs;                       // :455
     y = y + H.vel * sn;                       // :456
     // cos/sin of c_theta = arctan2(g_y - y, g_x - x) (:467) are the normalised components of the vector to the
@@ -503,7 +506,7 @@ __device__ __forceinline__ void group_flips(int g, const uint32_t touched[4], do
     if (touched[2] & bit) ogs = -ogs;
     if (touched[3] & bit) ogs = -ogs;
 }
-template <bool FAST, bool RARE = false>   // RARE: tell the compiler that arrivals are few (it then lays the redraw out behind the step loop)
+template <bool FAST, bool RARE = false, bool X3 = false>   // RARE: tell the compiler that arrivals are few (it then lays the redraw out behind the step loop)
 __device__ __forceinline__ void group_arrival(const KParams &p, const LeanCoef &C, long long e, int g, uint32_t tick, double MAXC,
                                               double &ogfl, double &ogv, double &ogc, double &ogs) {
     ogfl = ogfl - ogv;                                    // :513
@@ -514,10 +517,10 @@ __device__ __forceinline__ void group_arrival(const KParams &p, const LeanCoef &
             ut = p.inj_group[(e * p.Gr + g) * 3 + 0]; uf = p.inj_group[(e * p.Gr + g) * 3 + 1];
             uv = p.inj_group[(e * p.Gr + g) * 3 + 2];
         } else {
-            philox_u2(p, (uint32_t)e, tick, (uint32_t)g, DOM_GROUP_A, ut, uf);
-            philox_u2(p, (uint32_t)e, tick, (uint32_t)g, DOM_GROUP_B, uv, t1);
+            philox_u2<X3>(p, (uint32_t)e, tick, (uint32_t)g, DOM_GROUP_A, ut, uf);
+            philox_u2<X3>(p, (uint32_t)e, tick, (uint32_t)g, DOM_GROUP_B, uv, t1);
         }
-        lm_sincospi(2.0 * ut, C, &ogs, &ogc);             // :517-519
+        lm_sincospi<X3>(2.0 * ut, C, &ogs, &ogc);             // :517-519
         ogfl = uf * MAXC;                                 // :520 FL_MAX = max(dimensions)
         ogv = uv * (p.grp_v_max - p.grp_v_min) + p.grp_v_min;  // :521
     }
@@ -537,7 +540,7 @@ __device__ __forceinline__ void group_finish(const KParams &p, const LeanCoef &C
 // k_pl = P*10^((ant-a-eq)/10), k_0 = P*10^((ant-eq)/10) are folded on the host (float64 pow).
 // bsx/bsy: this env's UAV cells, in registers.  f ~ N(mean, sd) per (UE, UAV): injected, or Box-Muller on
 // Philox uniforms (one call -> two UAVs), replacing np.random.normal (channel.py:240).
-template <int BT, bool PLC, bool FAST, bool PRE>
+template <int BT, bool PLC, bool FAST, bool PRE, bool X3 = false>
 __device__ __forceinline__ void rx_power(const KParams &p, const HotConst &H, const LeanCoef &C, long long e, uint32_t tick, int u, bool act,
                                          long long iu, int ix, int iy, const int (&bsx)[BT], const int (&bsy)[BT],
                                          const U4 &q0, const U4 &q1, double pg[BT]) {
@@ -557,23 +560,23 @@ __device__ __forceinline__ void rx_power(const KParams &p, const HotConst &H, co
             } else if (quad_draws(B)) {
                 // quad mode (B > 8; a compile-time fact in the FAST variants, where B == BT): one Philox call per four UAVs,
                 // 32-bit radius uniform and angle fraction per pair
-                if ((b2 & 3) == 0) qq = philox_raw(p, (uint32_t)e, tick, (uint32_t)(u * ((B + 3) >> 2) + (b2 >> 2)), DOM_FADING);
+                if ((b2 & 3) == 0) qq = philox_raw<X3>(p, (uint32_t)e, tick, (uint32_t)(u * ((B + 3) >> 2) + (b2 >> 2)), DOM_FADING);
                 const uint32_t wr = (b2 & 3) == 0 ? qq.x : qq.z, wa = (b2 & 3) == 0 ? qq.y : qq.w;
                 const double u0 = (double)wr * (1.0 / 4294967296.0);
                 const double t = -2.0 * lm_logc(1.0 - u0, C);      // 1-u0 in [2^-32, 1]
                 const double r = (t > 0.0) ? t * lm_rsqrt(t) : 0.0;
                 double sa, ca;
-                lm_sincospi((double)wa * (1.0 / 2147483648.0), C, &sa, &ca);
+                lm_sincospi<X3>((double)wa * (1.0 / 2147483648.0), C, &sa, &ca);
                 f0 = H.sh_mean + H.sh_sd * (r * ca);
                 f1 = H.sh_mean + H.sh_sd * (r * sa);
             } else {
                 const U4 q = (PRE && b2 == 0) ? q0 : ((PRE && b2 == 2) ? q1 :
-                             philox_raw(p, (uint32_t)e, tick, (uint32_t)(u * ((B + 1) >> 1) + (b2 >> 1)), DOM_FADING));
+                             philox_raw<X3>(p, (uint32_t)e, tick, (uint32_t)(u * ((B + 1) >> 1) + (b2 >> 1)), DOM_FADING));
                 const double u0 = u53(q.x, q.y);
                 const double t = -2.0 * lm_logc(1.0 - u0, C);      // 1-u0 in [2^-53, 1]: positive, normal
                 const double r = (t > 0.0) ? t * lm_rsqrt(t) : 0.0;   // sqrt(t); t == 0 only when u0 == 0
                 double sa, ca;
-                lm_sincospi((double)q.z * (1.0 / 2147483648.0), C, &sa, &ca);   // angle = 2*pi * q.z / 2^32
+                lm_sincospi<X3>((double)q.z * (1.0 / 2147483648.0), C, &sa, &ca);   // angle = 2*pi * q.z / 2^32
                 f0 = H.sh_mean + H.sh_sd * (r * ca);
                 f1 = H.sh_mean + H.sh_sd * (r * sa);
             }
@@ -1009,6 +1012,10 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
     // Two parts of it cost registers (seven for the addresses; about ten for the FIFO push by selects, which lengthens live ranges), and
     // the pinned kernels for 8 UAVs hold 249 / 254 of the 256 VGPRs that let two wavefronts share a SIMD: ROOMY leaves those two out there.
     constexpr bool DIET = MANY && PIN;
+    // X3 (the same kernels): Philox's round xors and lm_sincospi's sign flips as gfx950's three-input bit ops (philox.h, lean_math.h): the same
+    // integers and doubles in about 40 fewer issue slots per step.  The unpinned multi-step kernels would spill more SGPRs for it (DESIGN.md
+    // section 4d); the single-step kernels keep the two-xor form, which the multi-step tests compare against bit for bit.
+    constexpr bool X3 = MANY && PIN;
     constexpr bool ROOMY = DIET && BT <= 4;
     constexpr bool QHOIST = QLATE && ROOMY;            // the gather addresses of slot_quads, taken once (slot_quad_addrs)
     int sq_addr[kMaxQuads];
@@ -1099,7 +1106,7 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
             const double gx = __shfl(ogx, src, 64), gy = __shfl(ogy, src, 64);
             const double gv = __shfl(ogv, src, 64), gc = __shfl(ogc, src, 64), gs = __shfl(ogs, src, 64);
             bool c[4];
-            walker_move(H, C, aggregating, hu, gx, gy, gv, gc, gs, MAXC, x, y, c);   // ue_mobility.py:455-505
+            walker_move<X3>(H, C, aggregating, hu, gx, gy, gv, gc, gs, MAXC, x, y, c);   // ue_mobility.py:455-505
             uint32_t touched[4] = {0u, 0u, 0u, 0u};  // per slot: groups bounced at x<0, x>MAX, y<0, y>MAX
             if constexpr (DIET) {
                 // The four flags as lane masks straight from their compares, `&& live` one scalar AND each, the rare-path test a scalar OR
@@ -1131,17 +1138,17 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
             else {
                 if (quad_draws(B)) {                                    // B > 8: the heading has its own call (B is the run-time
                                                                         // count in the checked variants: the warm-up kernel has BT = 4)
-                    const U4 hq = philox_raw(p, (uint32_t)e, tick, (uint32_t)u, DOM_HEADING);
+                    const U4 hq = philox_raw<X3>(p, (uint32_t)e, tick, (uint32_t)u, DOM_HEADING);
                     hu = u53(hq.x, hq.y);
                 } else {
                     const int HB = (B + 1) >> 1;
-                    q0 = philox_raw(p, (uint32_t)e, tick, (uint32_t)(u * HB), DOM_FADING);
-                    q1 = (HB >= 2) ? philox_raw(p, (uint32_t)e, tick, (uint32_t)(u * HB + 1), DOM_FADING) : q0;
+                    q0 = philox_raw<X3>(p, (uint32_t)e, tick, (uint32_t)(u * HB), DOM_FADING);
+                    q1 = (HB >= 2) ? philox_raw<X3>(p, (uint32_t)e, tick, (uint32_t)(u * HB + 1), DOM_FADING) : q0;
                     hu = heading_from(q0, q1, HB);
                 }
             }
             if constexpr (DIET) {
-                group_arrival<FAST, true>(p, C, e, ul, tick, MAXC, ogfl, ogv, ogc, ogs);     // :513-521 (the flips: above)
+                group_arrival<FAST, true, X3>(p, C, e, ul, tick, MAXC, ogfl, ogv, ogc, ogs);     // :513-521 (the flips: above)
                 // :472-473 / :486-487 by selects: both decrements, two compares -- no exec-masked region for two integers per env
                 const int a1 = agg - 1, d1 = deagg - 1;
                 const int agg_n = aggregating ? a1 : (d1 == 0 ? p.agg_len : agg);
@@ -1165,7 +1172,7 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
         // ---- channel update (one per reset / step; Philox time = the tick just executed) ------------------
         {
             double pg[BT];
-            rx_power<BT, PLC, FAST, FAST && has_mobility(MODE)>(p, H, C, e, tick - 1u, u, live, iu, ix, iy, bsx, bsy, q0, q1, pg);
+            rx_power<BT, PLC, FAST, FAST && has_mobility(MODE), X3>(p, H, C, e, tick - 1u, u, live, iu, ix, iy, bsx, bsy, q0, q1, pg);
             double best_pg;
             const int best = argmax_pg<BT, FAST>(p, pg, best_pg);
             const double bestS = sinr_db_px<BT, FAST>(p, H, C, pg, best, best_pg);

@@ -77,6 +77,12 @@
 #define S_CNDMASK64(i) asm volatile("v_cndmask_b32 %0, %0, %1, %2" : "+v"(u[i]) : "v"(x), "s"(mask));          /* lane mask in an ordinary SGPR pair */
 #define S_XOR_S(i)  asm volatile("v_xor_b32 %0, %1, %0" : "+v"(u[i]) : "s"(xs));                                /* 32-bit SGPR data operand */
 #define S_FMA64_S(i) asm volatile("v_fma_f64 %0, %1, %2, %0" : "+v"(d[i]) : "s"(as_bits), "v"(b));                 /* 64-bit SGPR data operand, as the unpinned kernel reads its constants */
+// gfx950's three-input bit op (truth table 0x96 = a ^ b ^ c), as the pinned multi-step kernels' Philox rounds use it: two VGPRs and one SGPR.
+#define S_BITOP3(i) asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0x96" : "+v"(u[i]) : "v"(x), "v"(y));
+#define S_BITOP3_S(i) asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0x96" : "+v"(u[i]) : "v"(x), "s"(xs));
+// dependent chains: every instruction reads the result of the one before it
+#define S_XOR_CHAIN(i) asm volatile("v_xor_b32 %0, %0, %1" : "+v"(u[0]) : "v"(x));
+#define S_BITOP3_CHAIN(i) asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0x96" : "+v"(u[0]) : "v"(x), "s"(xs));
 #define S_SNOP(i)   asm volatile("s_nop 0");
 #define S_EMPTY(i)  asm volatile("" ::: "memory");
 
@@ -135,6 +141,10 @@ KERNEL(v_mov_b64, S_MOV64, DSUM)
 KERNEL(v_lshl_add_u64, S_LSHLADD64, QSUM)
 KERNEL(v_cmp_eq_u32, S_CMP, USUM + CYSUM)
 KERNEL(ds_bpermute_b32, S_BPERM, USUM)
+KERNEL(v_bitop3_b32, S_BITOP3, USUM)
+KERNEL(v_bitop3_b32_sgprsrc, S_BITOP3_S, USUM)
+KERNEL(v_xor_b32_chain, S_XOR_CHAIN, USUM)
+KERNEL(v_bitop3_b32_chain, S_BITOP3_CHAIN, USUM)
 
 #define CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { std::fprintf(stderr, "%s: %s\n", #call, hipGetErrorString(e_)); std::exit(1); } } while (0)
 
@@ -167,7 +177,7 @@ int main() {
     const Entry table[] = {E(empty_loop), E(s_nop_0), E(v_fma_f32), E(v_fma_f64), E(v_mul_f64), E(v_add_f64), E(v_rcp_f64), E(v_rsq_f64),
                            E(v_ldexp_f64), E(v_frexp_mant_f64), E(v_cvt_f64_u32), E(v_mad_u64_u32), E(v_mul_lo_u32), E(v_mul_hi_u32),
                            E(v_xor_b32), E(v_add_u32), E(v_cndmask_b32), E(v_cndmask_b32_vccfresh), E(v_cndmask_b32_sgprmask), E(v_xor_b32_sgprsrc), E(v_fma_f64_sgprsrc), E(mix_no_select), E(mix_1in32_select_vcc), E(mix_1in32_select_sgprmask), E(mix_1in8_select_vcc), E(mix_1in8_select_sgprmask), E(v_mov_b32), E(v_mov_b64), E(v_lshl_add_u64), E(v_cmp_eq_u32),
-                           E(ds_bpermute_b32)};
+                           E(ds_bpermute_b32), E(v_xor_b32), E(v_bitop3_b32), E(v_bitop3_b32_sgprsrc), E(v_xor_b32_chain), E(v_bitop3_b32_chain)};
     std::printf("# s_memtime ticks per wave-instruction, %d instances, best of 4 warm launches (mean over waves; max over waves)\n",
                 ITERS * OPS_PER_ITER);
     std::printf("%-26s %22s %30s %30s\n", "opcode", "1 wave (64 threads)", "4 waves, 1/SIMD (256 thr)", "8 waves, 2/SIMD (512 thr)");
