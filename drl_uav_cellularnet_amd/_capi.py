@@ -93,7 +93,7 @@ EXPORTS = ("uavenv_abi_version", "uavenv_last_error", "uavenv_default_config", "
            "uavenv_init", "uavenv_warmup", "uavenv_reset", "uavenv_reset_trace", "uavenv_step", "uavenv_step_range", "uavenv_rollout_gated", "uavenv_gradient_actions", "uavenv_step_gradient", "uavenv_search_actions", "uavenv_step_search", "uavenv_coordinate_actions", "uavenv_step_coordinate", "uavenv_eval_accumulate", "uavenv_default_rate_config", "uavenv_link_rates", "uavenv_default_reward_config", "uavenv_shape_reward", "uavenv_coordinate_actions_shaped", "uavenv_search_actions_shaped", "uavenv_step_coordinate_shaped", "uavenv_step_search_shaped", "uavenv_debug_shaped_variant_count", "uavenv_debug_shaped_variant_info", "uavenv_debug_shaped_variant_reset", "uavenv_step_many", "uavenv_step_seq", "uavenv_step_trace",
            "uavenv_obs_dense", "uavenv_obs_dense_update", "uavenv_sinr_area", "uavenv_sinr_area_at",
            "uavenv_debug_variant_count", "uavenv_debug_variant_info", "uavenv_debug_variant_reset",
-           "uavenv_debug_side_variant_count", "uavenv_debug_side_variant_info", "uavenv_debug_side_variant_reset", "uavenv_debug_rotation_info", "uavenv_debug_path_launches", "uavenv_step_many_prepare", "uavenv_device_error", "uavenv_launch_timing", "uavenv_launch_times_us", "uavenv_debug_schedule",
+           "uavenv_debug_side_variant_count", "uavenv_debug_side_variant_info", "uavenv_debug_side_variant_reset", "uavenv_debug_rotation_info", "uavenv_debug_path_launches", "uavenv_debug_many_form", "uavenv_debug_many_launches", "uavenv_step_many_prepare", "uavenv_device_error", "uavenv_launch_timing", "uavenv_launch_times_us", "uavenv_debug_schedule",
            "uavenv_state_layout", "uavenv_get_state", "uavenv_set_state", "uavenv_philox4x32_10", "uavenv_lean_math_eval")
 
 _lib = None
@@ -167,6 +167,8 @@ def load():
     lib.uavenv_debug_side_variant_reset.restype = None
     lib.uavenv_debug_rotation_info.argtypes = [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
     lib.uavenv_debug_path_launches.argtypes = [_P, C.POINTER(C.c_longlong)]
+    lib.uavenv_debug_many_form.argtypes = [_P, C.c_int, C.POINTER(C.c_int)]
+    lib.uavenv_debug_many_launches.argtypes = [_P, C.POINTER(C.c_longlong)]
     lib.uavenv_step_many_prepare.argtypes = [_P, C.c_int]
     lib.uavenv_device_error.argtypes = [_P, C.POINTER(C.c_uint32)]
     lib.uavenv_launch_timing.argtypes = [_P, C.c_int]

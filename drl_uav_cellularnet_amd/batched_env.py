@@ -509,6 +509,23 @@ class BatchedMobiEnv:
         _capi.check(self._lib.uavenv_debug_path_launches(self._h, C.byref(n)))
         return int(n.value)
 
+    MANY_FORMS = ("none", "owners", "rounds", "carry")      # UAVENV_MANY_FORM_* of include/uavenv.h
+
+    def many_form(self, n_steps):
+        """Which step kernel a step_many call of n_steps runs on this handle (uavenv_debug_many_form): "owners" (owner lanes broadcast the
+        group motion every step), "rounds" (the same, six-round sum), "carry" (walker lanes carry it: pinned, at most 8 UAVs, every group
+        has a member) or "none" (n_ue > 64).  Test hook."""
+        f = C.c_int(0)
+        _capi.check(self._lib.uavenv_debug_many_form(self._h, int(n_steps), C.byref(f)))
+        return self.MANY_FORMS[f.value]
+
+    def many_launches(self):
+        """Launches of the multi-step step kernels on this handle so far, by form (uavenv_debug_many_launches): what was launched, counted at
+        the launch.  Test hook."""
+        n = (C.c_longlong * 4)()
+        _capi.check(self._lib.uavenv_debug_many_launches(self._h, n))
+        return {name: int(n[i]) for i, name in enumerate(self.MANY_FORMS) if i}
+
     def step_many(self, actions, out=None, refresh_out=True):
         """T consecutive step() calls in ONE launch (uavenv_step_many) for actions that do not depend on the observations in
         between: ``actions`` int64 [T, N] on this device.  Returns a dict of [T, ...] tensors (block t = what step t returned;

@@ -94,4 +94,17 @@ inline long long many_steps_per_piece(long long n_steps, long long n_envs, long 
     return per < n_steps ? per : n_steps;
 }
 
+// Which multi-step kernel a pinned FAST call with at most 8 UAVs runs (uavenv_capi.hip: launch_env; here, so that a host program can ask too).
+// slot_sum_in_quads: the per-env SINR sum in two levels (uavenv_kernels.h: slot_quads) serves U a multiple of 4 up to 32.
+// many_groups_carried: in env_kernel_many_carry the WALKER lanes carry their group's motion across the step loop, and the owner lanes fetch
+// it back from a member lane before the state store -- so every group needs a member, which check_config does not ask for (an ownerless
+// group's state must still evolve: the kernels with owner lanes do that), and the kernel exists for the two-level sum only.
+UAVENV_HD constexpr bool slot_sum_in_quads(int U) { return (U & 3) == 0 && U <= 32; }
+inline bool many_groups_carried(int U, int n_groups, const int32_t *group_size) {
+    if (!slot_sum_in_quads(U) || n_groups < 1) return false;
+    for (int g = 0; g < n_groups; ++g)
+        if (group_size[g] < 1) return false;
+    return true;
+}
+
 }  // namespace uavk

@@ -96,22 +96,28 @@ static int launch_env(uavenv_t *h, const KParams &p_in, hipStream_t s, long long
     // Multi-step launches: the pinned loop wins below one wavefront per SIMD too (1536 envs: 3.47 us per step unpinned; the lone-wave
     // argument above is about materialising constants once per LAUNCH, which a 100-step launch amortises).
     // (a rotation schedule launches S = k x SIMDs slots for its W > S env-wavefronts: the wavefronts that are resident count)
-    if (MANY) pin = fast && ((launch_waves > 0 ? launch_waves : waves) <= 2 * h->n_simd);
+    if (MANY) pin = many_launch_pinned(h, fast, launch_waves > 0 ? launch_waves : waves);
     // A RANGE launch exists to run beside other kernels of the caller (the A2C rollout's other half: an MFMA workgroup of 8 wavefronts x 128
     // VGPRs per CU).  The pinned variant's 251 VGPRs per wavefront leave no SIMD with two of them room for that workgroup, which then starts
     // only when the env launch drains (rocprofv3 timeline, profiles/r04g_*): ranges run unpinned (90 VGPRs).
     if (n_range > 0) pin = false;
-    if (h->force_pin >= 0) pin = fast && (h->force_pin == 1);   // experiments only (read once in uavenv_create)
+    if (h->force_pin >= 0) pin = fast && (h->force_pin == 1);   // experiments only (read once in uavenv_create; many_launch_pinned has applied it too)
     // Multi-step launches: env_kernel_packed<..., MANY> takes the per-env SINR sum in two levels and exists for U a multiple of 4 up to 32
     // (slot_sum_in_quads); every other U runs env_kernel_many_rounds, the same step loop with slot_sum's six rounds.  One census slot for both.
     const bool rounds = MANY && !uavk::slot_sum_in_quads(p.U);
+    // ... and where every RPGM group has a member, the pinned kernels for at most 8 UAVs have a form whose walker lanes carry their group's
+    // motion (env_kernel_many_carry: no broadcast of it in the step loop).  The same census slot again.
+    const bool carry = MANY && many_launch_carries(h, pin);
     const int var = pin ? VAR_PIN : (fast ? VAR_FAST : VAR_CHECKED);
     auto packed = [&](auto bt_c, auto plc_c, auto var_c, auto sch_c) {
         constexpr int BT = decltype(bt_c)::value, VAR = decltype(var_c)::value;
         constexpr bool PLC = decltype(plc_c)::value, SCH = decltype(sch_c)::value, FAST = var_fast(VAR), PIN = var_pin(VAR);
         if constexpr (MANY) {
-            if (rounds) launch_packed(env_kernel_many_rounds<BT, PLC, FAST, PIN, SCH>);
-            else launch_packed(env_kernel_packed<BT, M, PLC, FAST, PIN, true, SCH>);
+            // (h->many_launches: what was launched, counted where it is launched -- uavenv_debug_many_launches)
+            if (rounds) { launch_packed(env_kernel_many_rounds<BT, PLC, FAST, PIN, SCH>); h->many_launches[UAVENV_MANY_FORM_ROUNDS] += 1; }
+            else if (PIN && BT <= uavk::kPathMaxBs && carry) {
+                if constexpr (PIN && BT <= uavk::kPathMaxBs) { launch_packed(env_kernel_many_carry<BT, PLC, SCH>); h->many_launches[UAVENV_MANY_FORM_CARRY] += 1; }
+            } else { launch_packed(env_kernel_packed<BT, M, PLC, FAST, PIN, true, SCH>); h->many_launches[UAVENV_MANY_FORM_OWNERS] += 1; }
         } else {
             launch_packed(env_kernel_packed<BT, M, PLC, FAST, PIN>);
         }
@@ -184,6 +190,16 @@ extern "C" int uavenv_step_range(uavenv_t *h, const int64_t *actions_dev, int64_
     fill_call(p, inj, out);
     p.actions = (const long long *)actions_dev; p.n_ticks = 1;
     return launch_env<MODE_STEP>(h, p, (hipStream_t)stream, 0, first_env, n_envs);
+}
+
+// Which multi-step kernel a launch takes (launch_env above; uavenv_debug_many_form asks the same two).  `waves`: the wavefronts the launch
+// puts on the device -- a schedule's slots, else one per env-wavefront.
+bool uavenv_internal::many_launch_pinned(const uavenv_t *h, bool fast, long long waves) {
+    if (h->force_pin >= 0) return fast && (h->force_pin == 1);
+    return fast && (waves <= 2 * h->n_simd);
+}
+bool uavenv_internal::many_launch_carries(const uavenv_t *h, bool pin) {
+    return pin && h->packed && (h->bt <= uavk::kPathMaxBs) && uavk::many_groups_carried(h->cfg.n_ue, h->cfg.n_groups, h->cfg.group_size);
 }
 
 // The producer of a FAST multi-step call with BT <= 8 (uavenv_path_kernel.h): the UAV cells of all n_steps steps into out.bs_xy and the cells

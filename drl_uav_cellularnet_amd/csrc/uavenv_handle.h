@@ -51,6 +51,7 @@ struct uavenv {
     std::vector<hipEvent_t> *tev;
     int timing, n_timed;
     long long path_launches;  // launches of uav_path_kernel on this handle (uavenv_debug_path_launches)
+    long long many_launches[4];  // launches of the multi-step step kernels on this handle, by UAVENV_MANY_FORM_* (uavenv_debug_many_launches)
     int force_pin;  // UAVENV_FORCE_PIN read ONCE at create (experiments: tools/pin_sweep.sh): -1 unset, 0 / 1 forced
     unsigned long long many_lim;  // exclusive byte bound of a multi-step launch's 32-bit output offsets (state_layout.h): 2^32, or the LOWER value
                                   // of UAVENV_DEBUG_MANY_OFFSET_LIMIT read once at create (test hook: cuts small calls into several launches)
@@ -72,6 +73,12 @@ int rotation_plan(uavenv *h, int n_steps, hipStream_t stream);   // uavenv_host.
 // asks for the nine standard outputs and nothing else, which is what uavenv_step_many_prepare and uavenv_debug_rotation_info speak about.
 bool handle_reads_path(const uavenv *h);
 bool call_reads_path(const uavenv *h, const uavk::KParams &p);
+// Which multi-step kernel a launch takes (uavenv_capi.hip: launch_env; uavenv_debug_many_form).  many_launch_pinned: the PIN variant, from the
+// wavefronts the launch puts on the device (a schedule's slots, else one per env-wavefront).  many_launch_carries: env_kernel_many_carry, the
+// pinned form whose walker lanes carry their group's motion -- at most 8 UAVs, the two-level sum and a member in every group
+// (state_layout.h: many_groups_carried).
+bool many_launch_pinned(const uavenv *h, bool fast, long long waves);
+bool many_launch_carries(const uavenv *h, bool pin);
 // The steps of every launch piece but the last of a uavenv_step_many call of n_steps (state_layout.h: many_steps_per_piece, on the handle's bound).
 long long many_piece_steps(const uavenv *h, int n_steps, bool reads_path);
 

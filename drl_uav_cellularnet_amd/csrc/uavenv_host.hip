@@ -693,6 +693,25 @@ extern "C" int uavenv_debug_path_launches(uavenv_t *h, long long *n) {
     return UAVENV_OK;
 }
 
+extern "C" int uavenv_debug_many_form(uavenv_t *h, int n_steps, int *form) {
+    if (!h || !form || n_steps < 0) return fail(UAVENV_E_INVALID, "debug_many_form: null argument or negative n_steps");
+    *form = UAVENV_MANY_FORM_NONE;
+    if (!h->packed) return UAVENV_OK;
+    DeviceGuard guard(h->device);
+    // as launch_many / launch_env decide: the schedule's slots or one wavefront per env-wavefront; FAST as for the nine standard outputs
+    const int i = rotation_plan(h, (int)many_piece_steps(h, n_steps, handle_reads_path(h)), nullptr);
+    const long long waves = i >= 0 ? (*h->rot_plans)[(size_t)i].slots : (h->N + h->kp.epw - 1) / h->kp.epw;
+    const bool pin = many_launch_pinned(h, h->cfg.n_bs == h->bt, waves);
+    *form = !uavk::slot_sum_in_quads(h->cfg.n_ue) ? UAVENV_MANY_FORM_ROUNDS : many_launch_carries(h, pin) ? UAVENV_MANY_FORM_CARRY : UAVENV_MANY_FORM_OWNERS;
+    return UAVENV_OK;
+}
+
+extern "C" int uavenv_debug_many_launches(uavenv_t *h, long long counts[4]) {
+    if (!h || !counts) return fail(UAVENV_E_INVALID, "debug_many_launches: null argument");
+    for (int f = 0; f < 4; ++f) counts[f] = h->many_launches[f];
+    return UAVENV_OK;
+}
+
 extern "C" int uavenv_state_layout(const uavenv_t *h, UavEnvStateLayout *layout) {
     if (!h || !layout) return fail(UAVENV_E_INVALID, "state_layout: null argument");
     *layout = h->lay;

@@ -277,7 +277,7 @@ __device__ __forceinline__ double slot_sum(double v, int ul, int U) {
 // addition is made.  -0.0 is the identity of IEEE addition in round-to-nearest for EVERY x (x + -0.0 = x, also for x = -0.0 and
 // x = +0.0; float64 denormals are not flushed), and -0.0 + -0.0 = -0.0, so an all-absent subtree is absent for its parent in turn.
 // (+0.0 would not do: -0.0 + +0.0 = +0.0 changes a partial sum of -0.0.)
-__host__ __device__ constexpr bool slot_sum_in_quads(int U) { return (U & 3) == 0 && U <= 32; }
+// (slot_sum_in_quads(U) itself: state_layout.h, beside many_groups_carried, the other predicate that picks a multi-step kernel.)
 constexpr int kMaxQuads = 8;
 template <int CTRL>   // quad_perm [a,b,c,d] = a | b << 2 | c << 4 | d << 6.  (A 64-bit VALU op takes no quad_perm itself: two v_mov_b32)
 __device__ __forceinline__ double quad_perm_f64(double v) {
@@ -465,26 +465,47 @@ __device__ __forceinline__ void bs_move_serial(const KParams &p, unsigned a, int
 // One next() of reference_point_group for one walker (ue_mobility.py:455-505): own step along the heading
 // drawn last tick, group step (+ pull towards the group centre while aggregating), then the four ordered
 // bounce tests.  c[k] report which tests fired (they flip the GROUP heading, once per group and test).
-template <bool X3 = false>
+// ON_DEMAND (the pinned multi-step kernels): the pull -- the vector to the group centre, its v_rsq_f64 and the two selects, about 23
+// instructions -- only in a step in which some live lane of the wavefront aggregates (`any_agg`, wave-uniform: one scalar test).  With the
+// shipped phase lengths that is 364 of an episode's 2000 steps, and envs reset together share the phase.  The same operations on the same
+// values in the same order: the pull reads the position after the own step, which the group step does not touch.
+template <bool X3 = false, bool ON_DEMAND = false>
 __device__ __forceinline__ void walker_move(const HotConst &H, const LeanCoef &C, bool aggregating, double hu, double gx,
                                             double gy, double gv, double gc, double gs, double MAXC, double &x, double &y,
-                                            bool c[4]) {
+                                            bool c[4], bool any_agg = true) {
     double sn, cs;
     lm_sincospi<X3>(2.0 * hu, C, &sn, &cs);   // theta = 2*pi*u  (:437,508)
     x = x + H.vel * cs;                       // :455
     y = y + H.vel * sn;                       // :456
-    // cos/sin of c_theta = arctan2(g_y - y, g_x - x) (:467) are the normalised components of the vector to the
-    // group centre; arctan2(0, 0) = 0 gives (1, 0).
-    const double dxc = gx - x, dyc = gy - y;
-    const double r2 = dxc * dxc + dyc * dyc;
-    const double rinv = lm_rsqrt(r2);         // r2 == 0 gives a non-finite value; the selects below discard it
-    const double cc = (r2 > 0.0) ? dxc * rinv : 1.0;
-    const double sc = (r2 > 0.0) ? dyc * rinv : 0.0;
-    x = x + gv * gc;                          // :469 / :483
-    y = y + gv * gs;                          // :470 / :484
-    if (aggregating) {                        // :461-470 (per-lane select: slots may be in different phases)
-        x = x + H.aggr * cc;
-        y = y + H.aggr * sc;
+    if constexpr (ON_DEMAND) {
+        const double xo = x, yo = y;          // after the own step: what the pull is aimed from
+        x = x + gv * gc;                      // :469 / :483
+        y = y + gv * gs;                      // :470 / :484
+        if (__builtin_expect(any_agg, false)) {   // wave-uniform; laid out behind the step loop
+            const double dxc = gx - xo, dyc = gy - yo;
+            const double r2 = dxc * dxc + dyc * dyc;
+            const double rinv = lm_rsqrt(r2);
+            const double cc = (r2 > 0.0) ? dxc * rinv : 1.0;
+            const double sc = (r2 > 0.0) ? dyc * rinv : 0.0;
+            if (aggregating) {                // (per-lane select: slots may be in different phases)
+                x = x + H.aggr * cc;
+                y = y + H.aggr * sc;
+            }
+        }
+    } else {
+        // cos/sin of c_theta = arctan2(g_y - y, g_x - x) (:467) are the normalised components of the vector to the
+        // group centre; arctan2(0, 0) = 0 gives (1, 0).
+        const double dxc = gx - x, dyc = gy - y;
+        const double r2 = dxc * dxc + dyc * dyc;
+        const double rinv = lm_rsqrt(r2);     // r2 == 0 gives a non-finite value; the selects below discard it
+        const double cc = (r2 > 0.0) ? dxc * rinv : 1.0;
+        const double sc = (r2 > 0.0) ? dyc * rinv : 0.0;
+        x = x + gv * gc;                      // :469 / :483
+        y = y + gv * gs;                      // :470 / :484
+        if (aggregating) {                    // :461-470 (per-lane select: slots may be in different phases)
+            x = x + H.aggr * cc;
+            y = y + H.aggr * sc;
+        }
     }
     c[0] = x < 0.0;                           // :490-493
     if (c[0]) x = -x;
@@ -498,7 +519,9 @@ __device__ __forceinline__ void walker_move(const HotConst &H, const LeanCoef &C
 
 // Group owner, end of tick (ue_mobility.py:493-521), in two halves: bounce flips; remaining flight length and arrival redraw.
 // The pinned multi-step kernels call them apart: the flips where a bounce was seen (rare), the rest in EVERY lane -- a lane that owns no group
-// holds zeros in og*, which stay zeros (0 - 0), and ogv > 0 never holds there: the redraw is the owners' alone.
+// holds zeros in og*, which stay zeros (0 - 0), and ogv > 0 never holds there: the redraw is the owners' alone.  In env_kernel_many_carry (CARRY)
+// every live lane holds its GROUP's motion and calls both with g = its group: all members of a group flip and redraw alike, from the same
+// Philox counter; there the lanes with zeros are those that are not live.
 __device__ __forceinline__ void group_flips(int g, const uint32_t touched[4], double &ogc, double &ogs) {
     const uint32_t bit = 1u << g;
     if (touched[0] & bit) ogc = -ogc;
@@ -891,7 +914,7 @@ __device__ __forceinline__ void many_retire_loads() {
 struct NoPolicy {
     static constexpr bool kLookAhead = false, kAfterTick = false;
 };
-template <int BT, int MODE, bool PLC, bool FAST, bool PIN, bool MANY, int HO = 0, bool QSUM = false, class POLICY = NoPolicy>
+template <int BT, int MODE, bool PLC, bool FAST, bool PIN, bool MANY, int HO = 0, bool QSUM = false, class POLICY = NoPolicy, bool CARRY = false>
 __device__ __forceinline__ void env_packed_body(char *blob, const long long *actions, const int8_t *gid_of_u, long long N, int U, int EPW,
                                                 int Gr, int B_rt, int lane_magic, const KParams &p, int (*s_bs)[kMaxEpw][2 * kMaxBs],
                                                 const int wave, const long long ew, const int t0, const int nt, const int e_lo, const int e_hi,
@@ -900,6 +923,7 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
     static_assert(!LOOK || (is_step(MODE) && !MANY && !PIN && HO == 0), "the look-ahead is one plain step");
     static_assert(!POLICY::kAfterTick || (LOOK && BT <= 8), "a policy that takes over after the tick is a look-ahead with every UAV cell in registers");
     static_assert(!QSUM || MANY, "the two-level per-env sum is the multi-step kernels'");
+    static_assert(!CARRY || (many_o32<BT, FAST, PIN, MANY>() && QSUM), "walker lanes carry the group motion in the pinned two-level multi-step kernels only");
     constexpr bool LDC = (HO & 1) != 0, STC = (HO & 2) != 0, ACC = (HO & 4) != 0;
     const OutPtrs &pout = po != nullptr ? *po : p.out;
     const int lane = threadIdx.x & 63;
@@ -990,6 +1014,19 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
     // Only now touch the parameter struct: its (cold) kernarg fetch overlaps the global loads issued above.
     __builtin_amdgcn_sched_barrier(0);
     kernarg_warm<(int)sizeof(KParams)>();
+    // CARRY (env_kernel_many_carry): from here to the state store og* is the motion of the group this lane WALKS in, not of the group it
+    // owns: one broadcast from the owner lanes now, none in the step loop.  Every live lane of a group then runs the owner's arithmetic on
+    // the owner's values -- advance, flips, flight length, arrival redraw (same Philox counter: env, tick, gid) -- and so holds the owner's
+    // bits at every step.  Lanes that are not live hold zeros: ogv > 0 never holds there and they never raise the rare-branch test.
+    // (A lane that is not live fetches from itself: it owns no group, so its zeros.)  Here, right behind kernarg_warm: the parameter fetch is in
+    // flight while the broadcast waits for the group records.  Behind the pinned constants below, the scheduled kernel spilled 47 SGPRs against
+    // the broadcasting kernel's 45.
+    if constexpr (CARRY) {
+        const int src = live ? slot * U + gid : lane;
+        const double bx_ = __shfl(ogx, src, 64), by_ = __shfl(ogy, src, 64), bf_ = __shfl(ogfl, src, 64);
+        const double bv_ = __shfl(ogv, src, 64), bc_ = __shfl(ogc, src, 64), bs_ = __shfl(ogs, src, 64);
+        ogx = bx_; ogy = by_; ogfl = bf_; ogv = bv_; ogc = bc_; ogs = bs_;
+    }
     const LeanCoef C = lm_make_coef<PIN>();   // polynomial coefficients, pinned in VGPRs once per kernel (lean_math.h)
     const HotConst H = make_hot<PIN>(p);      // hot kernarg doubles, pinned in VGPRs (frees ~30 SGPRs)
     const double MAXC = H.maxc;
@@ -1103,10 +1140,11 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
                 ogy = ogy + ogv * ogs;
             }
             const int src = base + gid;
-            const double gx = __shfl(ogx, src, 64), gy = __shfl(ogy, src, 64);
-            const double gv = __shfl(ogv, src, 64), gc = __shfl(ogc, src, 64), gs = __shfl(ogs, src, 64);
+            const double gx = CARRY ? ogx : __shfl(ogx, src, 64), gy = CARRY ? ogy : __shfl(ogy, src, 64);
+            const double gv = CARRY ? ogv : __shfl(ogv, src, 64), gc = CARRY ? ogc : __shfl(ogc, src, 64), gs = CARRY ? ogs : __shfl(ogs, src, 64);
             bool c[4];
-            walker_move<X3>(H, C, aggregating, hu, gx, gy, gv, gc, gs, MAXC, x, y, c);   // ue_mobility.py:455-505
+            // (DIET: the pull towards the group centre only in a step in which some live lane aggregates)
+            walker_move<X3, DIET>(H, C, aggregating, hu, gx, gy, gv, gc, gs, MAXC, x, y, c, DIET ? (__ballot(aggregating) & live_mask) != 0ull : true);   // ue_mobility.py:455-505
             uint32_t touched[4] = {0u, 0u, 0u, 0u};  // per slot: groups bounced at x<0, x>MAX, y<0, y>MAX
             if constexpr (DIET) {
                 // The four flags as lane masks straight from their compares, `&& live` one scalar AND each, the rare-path test a scalar OR
@@ -1121,7 +1159,8 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
                         for (int k = 0; k < 4; ++k)
                             if ((mine & m[k] & slot_mask) != 0ull) touched[k] |= 1u << g;
                     }
-                    if (gown) group_flips(ul, touched, ogc, ogs);
+                    if (CARRY) { if (live) group_flips(gid, touched, ogc, ogs); }
+                    else if (gown) group_flips(ul, touched, ogc, ogs);
                 }
             } else {
                 c[0] = c[0] && live; c[1] = c[1] && live; c[2] = c[2] && live; c[3] = c[3] && live;
@@ -1148,7 +1187,7 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
                 }
             }
             if constexpr (DIET) {
-                group_arrival<FAST, true, X3>(p, C, e, ul, tick, MAXC, ogfl, ogv, ogc, ogs);     // :513-521 (the flips: above)
+                group_arrival<FAST, true, X3>(p, C, e, CARRY ? gid : ul, tick, MAXC, ogfl, ogv, ogc, ogs);     // :513-521 (the flips: above)
                 // :472-473 / :486-487 by selects: both decrements, two compares -- no exec-masked region for two integers per env
                 const int a1 = agg - 1, d1 = deagg - 1;
                 const int agg_n = aggregating ? a1 : (d1 == 0 ? p.agg_len : agg);
@@ -1259,6 +1298,18 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
             if (UAV_OUT64(pout.cur_sinr_f64)) stx(pout.cur_sinr_f64, iw, cur);
         }
     }
+    if constexpr (CARRY) {
+        // The owner lanes take their group's motion back.  Every live lane PUSHES its six doubles to the owner lane of its group
+        // (ds_permute_b32: the forward permute; where several lanes name one destination, one of them is taken -- any will do, and the two
+        // halves of a double may come from different ones: the members of a group hold the same bits).  The launcher guarantees every owner
+        // lane a member (many_groups_carried), so no search for a representative lane is needed.  A lane that is not live pushes to itself.
+        const int dst = (live ? base + gid : lane) << 2;
+        auto push = [&](double v) {
+            const int lo = __builtin_amdgcn_ds_permute(dst, __double2loint(v)), hi = __builtin_amdgcn_ds_permute(dst, __double2hiint(v));
+            return __hiloint2double(hi, lo);
+        };
+        ogx = push(ogx); ogy = push(ogy); ogfl = push(ogfl); ogv = push(ogv); ogc = push(ogc); ogs = push(ogs);
+    }
     if (gown) {
         const uint32_t gw = block_local<!PIN>(ig32);
         stx_c<STC>(st.grp, gw, GrpRec{ogx, ogy, ogfl, ogv, ogc, ogs});
@@ -1321,7 +1372,7 @@ __device__ __forceinline__ bool sched_hand_off_wait(const KParams &p, int ew) {
 // live through the whole kernel (160 -> 173 VGPRs unpinned, 237 -> 241 pinned); compiled alone the two-level form needs fewer than the six
 // rounds did (156 / 229).  env_kernel_packed<..., MANY = true> is the two-level kernel, env_kernel_many_rounds the one for every other U.
 // (`p` by value, as the kernels take it: through a reference the single-step reset kernel compiled to one instruction less than before.)
-template <int BT, int MODE, bool PLC, bool FAST, bool PIN, bool MANY, bool SCHED, bool QSUM>
+template <int BT, int MODE, bool PLC, bool FAST, bool PIN, bool MANY, bool SCHED, bool QSUM, bool CARRY = false>
 __device__ __forceinline__ void env_packed_entry(char *blob, const long long *actions, const int8_t *gid_of_u, long long N, int U, int EPW,
                                                  int Gr, int B_rt, int lane_magic, int wave0, int e_lo, int e_hi, const KParams p) {
     static_assert(!MANY || MODE == MODE_STEP, "multi-step launches exist for MobiEnvironment.step only");
@@ -1342,7 +1393,7 @@ __device__ __forceinline__ void env_packed_entry(char *blob, const long long *ac
         // (Inlined copies of the body rather than a rolled loop around one: with the rolled loop hipcc allocated 330 VGPRs for the
         // pinned kernel instead of 233 -- one wavefront per SIMD -- and doubled its SGPR spills.)
         if (!SCHED) {
-            env_packed_body<BT, MODE, PLC, FAST, PIN, MANY, 0, QSUM>(blob, actions, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, p, s_bs, wave, gw, 0, p.n_ticks, e_lo, e_hi);
+            env_packed_body<BT, MODE, PLC, FAST, PIN, MANY, 0, QSUM, NoPolicy, CARRY>(blob, actions, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, p, s_bs, wave, gw, 0, p.n_ticks, e_lo, e_hi);
             return;
         }
         const int4 *sched = p.sched;
@@ -1361,7 +1412,7 @@ __device__ __forceinline__ void env_packed_entry(char *blob, const long long *ac
             if (Q > 0) __builtin_amdgcn_wave_barrier();                       // (the previous piece's reads of the LDS row are done)
             if constexpr (Q == 2 && PIN) { if (__builtin_expect(!sched_hand_off_wait(p, ew), false)) return false; }   // (unlikely: the kernel's exit block then stays behind the last piece)
             else if (Q == 2) { if (!sched_hand_off_wait(p, ew)) return false; }
-            env_packed_body<BT, MODE, PLC, FAST, PIN, MANY, (Q == 0 ? 2 : (Q == 2 ? 1 : 0)), QSUM>(blob, actions, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, p, s_bs, wave, ew,
+            env_packed_body<BT, MODE, PLC, FAST, PIN, MANY, (Q == 0 ? 2 : (Q == 2 ? 1 : 0)), QSUM, NoPolicy, CARRY>(blob, actions, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, p, s_bs, wave, ew,
                                                                                                         t0, nt, e_lo, e_hi);
             if (Q == 0 && (bits & SCHED_PUBLISH)) sched_hand_off_publish(p, ew);
             return true;
@@ -1383,6 +1434,17 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void env_kernel_many_rounds(ch
                                                                                    const int8_t *gid_of_u, long long N, int U, int EPW,
                                                                                    int Gr, int B_rt, int lane_magic, int wave0, int e_lo, int e_hi, const KParams p) {
     env_packed_entry<BT, MODE_STEP, PLC, FAST, PIN, true, SCHED, false>(blob, actions, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, wave0, e_lo, e_hi, p);
+}
+
+// The pinned FAST multi-step kernels (BT <= 8, two-level sum) for a batch in which every RPGM group has a member (many_groups_carried):
+// the walker lanes carry their group's motion across the step loop (CARRY in env_packed_body), so the loop holds no broadcast of it --
+// ten ds_bpermute_b32, a wait and an address add per step less.  A kernel of its own for the reason SCHED and the rounds kernel are: as a
+// branch of env_kernel_packed both forms' loop invariants would stay live.  env_kernel_packed stays the form for every other batch.
+template <int BT, bool PLC, bool SCHED>
+__global__ __launch_bounds__(64 * kWavesPerBlock) void env_kernel_many_carry(char *blob, const long long *actions,
+                                                                                  const int8_t *gid_of_u, long long N, int U, int EPW,
+                                                                                  int Gr, int B_rt, int lane_magic, int wave0, int e_lo, int e_hi, const KParams p) {
+    env_packed_entry<BT, MODE_STEP, PLC, true, true, true, SCHED, true, true>(blob, actions, gid_of_u, N, U, EPW, Gr, B_rt, lane_magic, wave0, e_lo, e_hi, p);
 }
 
 // ================================================================================================

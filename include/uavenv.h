@@ -35,7 +35,8 @@ extern "C" {
                                 *      uavenv_step_gradient;
                                 * 9: + uavenv_eval_accumulate / UavEnvEvalAcc (a step's outputs folded into per-env totals and a serving-SINR histogram);
                                 * 10: + uavenv_debug_side_variant_* (side census: the kernels launched outside the env step's dispatch);
-                                *      uavenv_rollout_gated refuses n_ue + n_bs > 64 */
+                                *      uavenv_rollout_gated refuses n_ue + n_bs > 64
+                                *      (additive since, the number stays: uavenv_debug_many_form, uavenv_debug_many_launches) */
 #define UAVENV_MAX_GROUPS 16
 #define UAVENV_MAX_BS 32
 
@@ -239,6 +240,19 @@ int uavenv_debug_rotation_info(uavenv_t *h, int n_steps, int *n_launches, long l
  * unless the outputs reach 4 GiB: see uavenv_debug_rotation_info), before the piece's step kernel: the cells of every step go to
  * out->bs_xy_dev and the step kernel reads them there instead of moving the UAVs itself.  No other call launches it. */
 int uavenv_debug_path_launches(uavenv_t *h, long long *n);
+
+/* Test hook: *form = the step kernel a uavenv_step_many call of n_steps (nine standard outputs) runs on this handle, of its first launch
+ * piece where the call is cut.  UAVENV_MANY_FORM_NONE: a handle that does not run the packed kernels (n_ue > 64, or
+ * a slot too narrow for its owner lanes: n_ue < max(n_bs, n_groups)), one single-step launch per step.  OWNERS: the lanes that own the RPGM
+ * groups advance them and broadcast their motion to the walker lanes every step (two-level SINR sum: n_ue a multiple of 4 up to 32).
+ * ROUNDS: the same with the six-round sum, for every other n_ue.  CARRY: the walker lanes carry their group's motion themselves and
+ * the owner lanes take it back before the state store -- pinned launches (between one and two wavefronts per SIMD, or fewer) of at most
+ * 8 UAVs where OWNERS would run and every group has a member.  All forms compute the same bits. */
+enum { UAVENV_MANY_FORM_NONE = 0, UAVENV_MANY_FORM_OWNERS = 1, UAVENV_MANY_FORM_ROUNDS = 2, UAVENV_MANY_FORM_CARRY = 3 };
+int uavenv_debug_many_form(uavenv_t *h, int n_steps, int *form);
+/* Test hook: counts[f] = launches of the multi-step step kernel of form f (UAVENV_MANY_FORM_*; [0] stays 0) on this handle so far, counted
+ * where the kernel is launched: what ran, where uavenv_debug_many_form says what would. */
+int uavenv_debug_many_launches(uavenv_t *h, long long counts[4]);
 
 /* Duration of the multi-step launches themselves, for callers that time SHORT calls (bench.py's 20-step region lasts 0.1 ms: a pair of
  * HIP events recorded on the stream around the call are two marker packets that cost it 10 us).  uavenv_launch_timing(h, 1) makes every
