@@ -23,7 +23,8 @@ EXPORTS = ("uavagent_abi_version", "uavagent_last_error", "uavagent_sparse_rows_
            "uavagent_first_layer_wide_f32", "uavagent_first_layer_wide_from_obs_f32", "uavagent_rows_grad_wide_sort",
            "uavagent_rows_grad_wide_sums_f32", "uavagent_imitation_loss_grad_workspace_bytes", "uavagent_imitation_loss_grad_factored",
            "uavagent_soft_targets_f32", "uavagent_gae_f32", "uavagent_logp_factored_f32", "uavagent_ppo_loss_grad_factored_workspace_bytes",
-           "uavagent_ppo_loss_grad_factored", "uavagent_logp_f32", "uavagent_ppo_loss_grad_workspace_bytes", "uavagent_ppo_loss_grad")
+           "uavagent_ppo_loss_grad_factored", "uavagent_logp_f32", "uavagent_ppo_loss_grad_workspace_bytes", "uavagent_ppo_loss_grad",
+           "uavagent_sumsq_workspace_bytes", "uavagent_sumsq_f32", "uavagent_adam_f32", "uavagent_rmsprop_tf1_clipped")
 ABI_VERSION = 5
 
 _lib = None
@@ -138,6 +139,9 @@ def load():
         "uavagent_ppo_loss_grad_factored": [_P, _I64, _P, _P, _P, _P, _P, _I64, _I32, _I32, _F, _F, _P, _P, _P, _P, _P],
         "uavagent_logp_f32": [_P, _I64, _P, _I64, _I32, _P, _P],
         "uavagent_ppo_loss_grad": [_P, _I64, _P, _P, _P, _P, _P, _I64, _I32, _F, _F, _P, _P, _P, _P, _P],
+        "uavagent_sumsq_f32": [_P, _I64, _P, _P, _P],
+        "uavagent_adam_f32": [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _I64, _F, _P, _F, _P],
+        "uavagent_rmsprop_tf1_clipped": [_P, _P, _P, _I64, _F, _F, _F, _F, _P, _F, _P],
         "uavagent_gate_prepare": [],
     }
     for wide, narrow in (("uavagent_first_layer_wide_f32", "uavagent_first_layer_f32"),
@@ -163,6 +167,8 @@ def load():
     lib.uavagent_ppo_loss_grad_factored_workspace_bytes.argtypes = [_I32, _I32]
     lib.uavagent_ppo_loss_grad_workspace_bytes.restype = C.c_size_t
     lib.uavagent_ppo_loss_grad_workspace_bytes.argtypes = [_I32]
+    lib.uavagent_sumsq_workspace_bytes.restype = C.c_size_t
+    lib.uavagent_sumsq_workspace_bytes.argtypes = [_I64]
     lib.uavagent_relu6_bwd_workspace_bytes.restype = C.c_size_t
     lib.uavagent_relu6_bwd_workspace_bytes.argtypes = [_I32]
     lib.uavagent_rows_grad_workspace_bytes.restype = C.c_size_t
@@ -438,6 +444,62 @@ def rmsprop_tf1(w, ms, g, lr, decay=0.9, eps=1e-10, g_scale=1.0):
         rc = load().uavagent_rmsprop_tf1(_ptr(w), _ptr(ms), _ptr(g), w.numel(), float(lr), float(decay), float(eps), float(g_scale),
                                          _stream(w.device))
     _check(rc, "uavagent_rmsprop_tf1")
+
+
+SUMSQ_SPAN = 1024      # floats one workgroup of uavagent_sumsq_f32 covers per pass of its grid of at most SUMSQ_BLOCKS workgroups
+SUMSQ_BLOCKS = 1024
+
+
+def sumsq_workspace(n, device):
+    """The caller-owned workspace of sumsq() for n floats (float64 partials, one per workgroup)."""
+    return torch.empty(load().uavagent_sumsq_workspace_bytes(int(n)) // 8, dtype=torch.float64, device=device)
+
+
+def _sumsq_arg(sumsq, max_norm, like):
+    if sumsq is None:
+        return None, 0.0
+    if sumsq.dtype != torch.float64 or sumsq.device != like.device or sumsq.numel() < 1:
+        raise UavAgentError("sumsq must be a float64 tensor on the gradient's device")
+    if max_norm is None:
+        raise UavAgentError("sumsq needs max_norm")
+    return _ptr(sumsq), float(max_norm)
+
+
+def sumsq(g, out, workspace):
+    """out[0] (float64, device) = sum of g[i]^2 in float64, bit-reproducible (uavagent_sumsq_f32); an empty g gives 0."""
+    _f32c(g, "g")
+    _same_device("uavagent_sumsq_f32", g, out, workspace)
+    if out.dtype != torch.float64 or workspace.dtype != torch.float64 or out.numel() < 1:
+        raise UavAgentError("sumsq: out and workspace must be float64 tensors")
+    if g.numel() == 0:
+        out[:1].zero_()
+        return out
+    lib = load()
+    if workspace.numel() * 8 < lib.uavagent_sumsq_workspace_bytes(g.numel()):
+        raise UavAgentError("sumsq: workspace smaller than uavagent_sumsq_workspace_bytes()")
+    with torch.cuda.device(g.device):
+        rc = lib.uavagent_sumsq_f32(_ptr(g), g.numel(), _ptr(out), _ptr(workspace), _stream(g.device))
+    _check(rc, "uavagent_sumsq_f32")
+    return out
+
+
+def adam(w, m, v, g, lr, step, betas=(0.9, 0.999), eps=1e-8, g_scale=1.0, sumsq=None, max_norm=None):
+    """torch.optim.Adam's step number ``step`` (1, 2, ...) on flat buffers; with ``sumsq`` (float64 [1], device: sumsq()'s result) the
+    gradient is clipped to ``max_norm`` by the rule of clip_grad_norm_, the coefficient computed on the device."""
+    sp, mn = _sumsq_arg(sumsq, max_norm, w)
+    with torch.cuda.device(w.device):
+        rc = load().uavagent_adam_f32(_ptr(w), _ptr(m), _ptr(v), _ptr(g), w.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                      int(step), float(g_scale), sp, mn, _stream(w.device))
+    _check(rc, "uavagent_adam_f32")
+
+
+def rmsprop_tf1_clipped(w, ms, g, lr, decay=0.9, eps=1e-10, g_scale=1.0, sumsq=None, max_norm=None):
+    """rmsprop_tf1 on the gradient clipped to ``max_norm`` (see adam); sumsq=None or an inactive clip give rmsprop_tf1's bits."""
+    sp, mn = _sumsq_arg(sumsq, max_norm, w)
+    with torch.cuda.device(w.device):
+        rc = load().uavagent_rmsprop_tf1_clipped(_ptr(w), _ptr(ms), _ptr(g), w.numel(), float(lr), float(decay), float(eps), float(g_scale),
+                                                 sp, mn, _stream(w.device))
+    _check(rc, "uavagent_rmsprop_tf1_clipped")
 
 
 def _row_stride(t, what):

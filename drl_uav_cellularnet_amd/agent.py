@@ -17,6 +17,8 @@ writes (ue_xy, serving, bs_xy) -- no dense (N, B+1, G, G) tensor is ever materia
 Gradients are synchronised with one flat all-reduce per update (RCCL over xGMI when launched one process per GPU).
 """
 
+import math
+
 import torch
 import torch.nn.functional as F
 
@@ -230,6 +232,46 @@ class TFRMSProp:
             m.copy_(s)
 
 
+class Adam:
+    """torch.optim.Adam(lr, betas, eps) without weight decay and amsgrad, on the parameters' .grad (an extension, the
+    reference trains with RMSProp only):
+        m <- b1 m + (1 - b1) g;  v <- b2 v + (1 - b2) g^2;  p <- p - [lr / (1 - b1^t)] m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+    The caller holds the step number t = 1, 2, ... (the runner advances it only for steps that were taken)."""
+
+    def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8):
+        self.params = list(params)
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.m = [torch.zeros_like(p) for p in self.params]
+        self.v = [torch.zeros_like(p) for p in self.params]
+
+    @torch.no_grad()
+    def step(self, t):
+        b1, b2 = self.betas
+        grads = [p.grad for p in self.params]
+        torch._foreach_mul_(self.m, b1)
+        torch._foreach_add_(self.m, grads, alpha=1.0 - b1)
+        torch._foreach_mul_(self.v, b2)
+        torch._foreach_addcmul_(self.v, grads, grads, value=1.0 - b2)
+        denom = torch._foreach_sqrt(self.v)
+        torch._foreach_div_(denom, math.sqrt(1.0 - b2 ** int(t)))
+        torch._foreach_add_(denom, self.eps)
+        torch._foreach_addcdiv_(self.params, self.m, denom, value=-self.lr / (1.0 - b1 ** int(t)))
+
+    def zero_grad(self):
+        for p in self.params:
+            if p.grad is not None:
+                p.grad.zero_()
+
+
+def clip_coefficient(g, max_norm):
+    """(coef, norm) of torch.nn.utils.clip_grad_norm_ for one flat gradient slice: norm = ||g||_2 summed in float64,
+    coef = min(1, max_norm / (norm + 1e-6)).  A norm that is not finite gives coef 1: the caller skips the step."""
+    norm = float(g.detach().double().pow(2).sum().sqrt())
+    if not math.isfinite(norm):
+        return 1.0, norm
+    return min(1.0, float(max_norm) / (norm + 1e-6)), norm
+
+
 def nstep_returns(rewards, bootstrap, gamma=GAMMA):
     """a2c_single_thread.py:176-183: value_estimate = r + gamma * value_estimate, backwards over the rollout.
     rewards [T, N], bootstrap [N] (v(s_T), or 0 where the episode ended) -> targets [T, N]."""
@@ -362,7 +404,7 @@ class FlatParams:
 
     ALIGN = 64   # floats
 
-    def __init__(self, net):
+    def __init__(self, net, adam=False):
         order = getattr(net, "PARAM_ORDER", PARAM_ORDER)              # the net's own order (CnnACNet) or the MLP's
         params = [getattr(net, k) for k in order]
         dev = params[0].device
@@ -377,6 +419,9 @@ class FlatParams:
         self.w = torch.zeros(off, dtype=dt, device=dev)
         self.g = torch.zeros(off, dtype=dt, device=dev)
         self.ms = torch.ones(off, dtype=dt, device=dev)    # TF1: accumulator initialised to ones (main.py:300-301)
+        # Adam's moments, only where Adam is the optimiser (two more buffers of the parameters' size); they start at zero
+        self.m = torch.zeros(off, dtype=dt, device=dev) if adam else None
+        self.v = torch.zeros(off, dtype=dt, device=dev) if adam else None
         self.gv = {}
         with torch.no_grad():
             for k, p, o in zip(order, params, offs):
@@ -405,9 +450,9 @@ class A2CRunner:
     def __init__(self, env, net=None, rollout=50, gamma=GAMMA, beta=ENTROPY_BETA, lr_a=LR_A, lr_c=LR_C, seed=6,
                  update_chunk=65536, first_state="obs", collect_launch="graph", fused_update=True, tune_gemms=False, hip_gemms=True,
                  overlap_allreduce=True, fused_head=True, fused_obs=True, pipeline_halves=True, force_exchange=False,
-                 persistent_rollout="auto"):
+                 persistent_rollout="auto", optimizer="rmsprop", max_grad_norm=None, adam_betas=(0.9, 0.999), adam_eps=1e-8):
         self._init_common(env, net if net is not None else ACNet(env.observation_space_dim, env.action_space_dim, seed=seed), rollout, gamma,
-                          beta, lr_a, lr_c, seed, update_chunk, first_state, tune_gemms)
+                          beta, lr_a, lr_c, seed, update_chunk, first_state, tune_gemms, optimizer, max_grad_norm, adam_betas, adam_eps)
         if collect_launch not in ("graph", "eager"):
             raise ValueError("collect_launch must be 'graph' or 'eager'")
         self.collect_launch = collect_launch
@@ -494,9 +539,26 @@ class A2CRunner:
     NET_KIND = "mlp"
     FUSED_OBS_MAX_NODES = 64      # uavagent_first_layer_from_obs_f32: one lane per node (factored.FactoredA2CRunner: the wide form's 256)
 
-    def _init_common(self, env, net, rollout, gamma, beta, lr_a, lr_c, seed, update_chunk, first_state, tune_gemms):
+    OPTIMIZERS = ("rmsprop", "adam")
+
+    def _init_common(self, env, net, rollout, gamma, beta, lr_a, lr_c, seed, update_chunk, first_state, tune_gemms, optimizer="rmsprop",
+                     max_grad_norm=None, adam_betas=(0.9, 0.999), adam_eps=1e-8):
         """What every runner over a BatchedMobiEnv sets up (A2CRunner and cnn_agent.CnnA2CRunner): the net in FlatParams with its two
-        TF1 RMSProp views, the rollout buffers, the first state, the episode bookkeeping and the action-sampling generator."""
+        optimiser views (TF1 RMSProp, or Adam: DESIGN.md section 24), the rollout buffers, the first state, the episode bookkeeping and the
+        action-sampling generator."""
+        if optimizer not in self.OPTIMIZERS:
+            raise ValueError("optimizer must be one of %s" % (self.OPTIMIZERS,))
+        if max_grad_norm is not None and not (math.isfinite(float(max_grad_norm)) and float(max_grad_norm) > 0.0):
+            raise ValueError("max_grad_norm must be None or a finite number > 0")
+        b1, b2 = (float(x) for x in adam_betas)
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0 and math.isfinite(float(adam_eps)) and float(adam_eps) > 0.0):
+            raise ValueError("adam_betas must lie in [0, 1) and adam_eps must be > 0")
+        self.optimizer = optimizer
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.adam_betas, self.adam_eps = (b1, b2), float(adam_eps)
+        # Adam's step numbers, (actor, critic): the two networks are two optimisers, and a step that the clip skipped (a gradient norm that
+        # is not finite) does not count
+        self.opt_step = [0, 0]
         self.env = env
         self.dev = env.device
         # the env's reward spec (BatchedMobiEnv.set_reward) as it is now: it decides the form of the rollout, and a captured rollout
@@ -505,14 +567,31 @@ class A2CRunner:
         self.gemm_tuning = enable_gemm_tuning() if (tune_gemms and self.dev.type == "cuda") else False
         self.G, self.B = env.grid_n, env.nBS
         self.net = net.to(self.dev)
-        self.flat = FlatParams(self.net)
+        adam = optimizer == "adam"
+        self.flat = FlatParams(self.net, adam=adam)
         self.lr_a, self.lr_c = float(lr_a), float(lr_c)
-        self.opt_a = TFRMSProp(self.net.actor_params(), lr_a)       # reference path only; shares FlatParams' accumulators
-        self.opt_c = TFRMSProp(self.net.critic_params(), lr_c)
+        # reference path only; both share FlatParams' accumulators
+        if adam:
+            self.opt_a = Adam(self.net.actor_params(), lr_a, self.adam_betas, self.adam_eps)
+            self.opt_c = Adam(self.net.critic_params(), lr_c, self.adam_betas, self.adam_eps)
+        else:
+            self.opt_a = TFRMSProp(self.net.actor_params(), lr_a)
+            self.opt_c = TFRMSProp(self.net.critic_params(), lr_c)
         order = getattr(self.net, "PARAM_ORDER", PARAM_ORDER)
         n_actor = getattr(self.net, "N_ACTOR_PARAMS", N_ACTOR_PARAMS)
         for opt, keys in ((self.opt_a, order[:n_actor]), (self.opt_c, order[n_actor:])):
-            opt.ms = [self._ms_view(k) for k in keys]
+            if adam:
+                opt.m = [self._flat_view(self.flat.m, k) for k in keys]
+                opt.v = [self._flat_view(self.flat.v, k) for k in keys]
+            else:
+                opt.ms = [self._ms_view(k) for k in keys]
+        # the clip's sums of squares (actor, critic) stay on the device between the reduction and the step; read back with the loss
+        self._sumsq = self._sumsq_ws = None
+        if self.max_grad_norm is not None and self.dev.type == "cuda":
+            from . import _agent_capi as _A
+
+            self._sumsq = torch.zeros(2, dtype=torch.float64, device=self.dev)
+            self._sumsq_ws = _A.sumsq_workspace(self.flat.n_flat, self.dev)
         self.T, self.gamma, self.beta = int(rollout), float(gamma), float(beta)
         self.update_chunk = int(update_chunk)
         self.gen = torch.Generator(device=self.dev).manual_seed(int(seed) + 1000 * int(env.env_id_base + 1))
@@ -539,10 +618,13 @@ class A2CRunner:
         self._fwd_valid = False
         self._ppo = None              # while ppo_update's epochs run: adv / ret / logp_old of the batch and the clip; the loss hooks answer with the PPO form
 
-    def _ms_view(self, key):
+    def _flat_view(self, buf, key):
         p = getattr(self.net, key)
         off = (p.data_ptr() - self.flat.w.data_ptr()) // self.flat.w.element_size()
-        return self.flat.ms[off:off + p.numel()].view_as(p)
+        return buf[off:off + p.numel()].view_as(p)
+
+    def _ms_view(self, key):
+        return self._flat_view(self.flat.ms, key)
 
     @property
     def idx(self):
@@ -1061,16 +1143,76 @@ class A2CRunner:
         else:
             g_scale = self._allreduce()
         ev1.record()
-        A.rmsprop_tf1(fl.w[:ae], fl.ms[:ae], fl.g[:ae], self.lr_a, g_scale=g_scale)
-        A.rmsprop_tf1(fl.w[ae:], fl.ms[ae:], fl.g[ae:], self.lr_c, g_scale=g_scale)
-        loss = b["loss"].cpu()                                        # (synchronises)
+        self._optimizer_step(g_scale)
+        loss, clip_stats = self._read_loss(b["loss"], g_scale)        # (synchronises)
         self.stats = {"a_loss": float(loss[0]), "c_loss": float(loss[1]), "mean_reward": float(rew_buf.mean()),
                       "grad_elems": fl.n_real, "running_r": self.running_r, "allreduce_ms": ev0.elapsed_time(ev1),
                       "forward_reused": bool(reuse), "hip_gemms": bool(hip),
                       # two buckets (critic trunk, then actor trunk): the first one's time is hidden behind the actor's backward pass
                       "allreduce_overlapped_ms": e_c0.elapsed_time(e_c1) if two_buckets else None,
                       "allreduce_buckets": [4 * (fl.n_flat - ae), 4 * ae] if two_buckets else None}
+        self.stats.update(clip_stats)
         return self.stats
+
+    # ---- the optimiser step: ONE place for A2C, the PPO epochs and imitation, for every runner ------------------
+    def _optimizer_step(self, g_scale):
+        """The step of both networks on the flat buffers (GPU), behind the gradient exchange: per network -- the actor's slice
+        [0, actor_end) and the critic's [actor_end, n_flat) are two optimisers with two learning rates -- the sum of squares of the exchanged
+        gradient where max_grad_norm is set, then uavagent_adam_f32 or uavagent_rmsprop_tf1_clipped, which read that sum on the device and
+        fold g_scale = 1 / world into the norm (every rank computes the same coefficient).  The defaults (rmsprop, no clip) launch exactly the
+        two uavagent_rmsprop_tf1 calls of the reference's optimiser."""
+        from . import _agent_capi as A
+
+        fl, ae = self.flat, self.flat.actor_end
+        if self.optimizer == "rmsprop" and self.max_grad_norm is None:
+            A.rmsprop_tf1(fl.w[:ae], fl.ms[:ae], fl.g[:ae], self.lr_a, g_scale=g_scale)
+            A.rmsprop_tf1(fl.w[ae:], fl.ms[ae:], fl.g[ae:], self.lr_c, g_scale=g_scale)
+            return
+        for i, (lo, hi, lr) in enumerate(((0, ae, self.lr_a), (ae, fl.n_flat, self.lr_c))):
+            ss = None
+            if self.max_grad_norm is not None:
+                ss = A.sumsq(fl.g[lo:hi], self._sumsq[i:i + 1], self._sumsq_ws)
+            if self.optimizer == "adam":
+                A.adam(fl.w[lo:hi], fl.m[lo:hi], fl.v[lo:hi], fl.g[lo:hi], lr, self.opt_step[i] + 1, betas=self.adam_betas, eps=self.adam_eps,
+                       g_scale=g_scale, sumsq=ss, max_norm=self.max_grad_norm)
+            else:
+                A.rmsprop_tf1_clipped(fl.w[lo:hi], fl.ms[lo:hi], fl.g[lo:hi], lr, g_scale=g_scale, sumsq=ss, max_norm=self.max_grad_norm)
+
+    def _read_loss(self, loss_dev, g_scale):
+        """(the loss sums on the host, the clip's stats): ONE .cpu() for both, the update's only synchronisation.  Also counts the steps."""
+        if self.max_grad_norm is None:
+            return loss_dev.cpu(), self._count_steps(None)
+        both = torch.cat([loss_dev, self._sumsq]).cpu()
+        norms = [float(g_scale) * math.sqrt(x) if x >= 0.0 else float("nan") for x in both[-2:].tolist()]
+        return both[:-2], self._count_steps(norms)
+
+    def _count_steps(self, norms):
+        """Advances the step numbers of the networks whose step was taken; -> the stats of a clipped update ({} without max_grad_norm):
+        the norms before clipping, whether each was clipped, whether a step was skipped (a norm that is not finite)."""
+        if norms is None:
+            self.opt_step = [s + 1 for s in self.opt_step]
+            return {}
+        ok = [math.isfinite(x) for x in norms]
+        self.opt_step = [s + int(k) for s, k in zip(self.opt_step, ok)]
+        clipped = [k and self.max_grad_norm / (x + 1e-6) < 1.0 for x, k in zip(norms, ok)]
+        return {"grad_norm_a": norms[0], "grad_norm_c": norms[1], "clipped_a": bool(clipped[0]), "clipped_c": bool(clipped[1]),
+                "skipped_step": not all(ok)}
+
+    def _reference_step(self):
+        """_optimizer_step's decisions with the reference forms, on flat.g as exchanged and scaled: per network the coefficient of
+        clip_coefficient applied to the gradient in place, then TFRMSProp / Adam.  -> the clip's stats."""
+        fl, ae = self.flat, self.flat.actor_end
+        norms = [] if self.max_grad_norm is not None else None
+        for i, (opt, lo, hi) in enumerate(((self.opt_a, 0, ae), (self.opt_c, ae, fl.n_flat))):
+            if norms is not None:
+                coef, norm = clip_coefficient(fl.g[lo:hi], self.max_grad_norm)
+                norms.append(norm)
+                if not math.isfinite(norm):
+                    continue
+                if coef < 1.0:
+                    fl.g[lo:hi].mul_(coef)
+            opt.step(self.opt_step[i] + 1) if self.optimizer == "adam" else opt.step()
+        return self._count_steps(norms)
 
     def update_reference(self, idx_buf, act_buf, rew_buf, boot):
         """The same update through autograd (the form round 1 shipped), chunked to bound activation memory; gradients
@@ -1092,10 +1234,10 @@ class A2CRunner:
         g_scale = self._allreduce()
         if g_scale != 1.0:
             self.flat.g.mul_(g_scale)
-        self.opt_a.step()
-        self.opt_c.step()
+        clip_stats = self._reference_step()
         self.stats = {"a_loss": a_tot, "c_loss": c_tot, "mean_reward": float(rew_buf.mean()), "grad_elems": self.flat.n_real,
                       "running_r": self.running_r, "allreduce_ms": None}
+        self.stats.update(clip_stats)
         return self.stats
 
     def _reference_forward(self, idx):
@@ -1259,10 +1401,13 @@ class A2CRunner:
         env = self.env
         blob = torch.empty(env._lay.total_bytes, dtype=torch.uint8, device=self.dev)
         env.copy_state_to(blob)
-        return {"format": 1, "n_envs": env.n_envs, "n_bs": env.nBS, "n_ue": env.nUE, "grid_n": env.grid_n, "rollout": self.T,
-                "w": self.flat.w.detach().cpu(), "ms": self.flat.ms.detach().cpu(), "env_state": blob.cpu(), "env_out": env._arena.cpu(),
-                "idx": self.idx_buf[self.T].cpu(), "ep_r": self.ep_r.cpu(), "running_r": self.running_r,
-                "last_episode_return": self.last_episode_return, "gen_state": self.gen.get_state().cpu()}
+        sd = {"format": 1, "n_envs": env.n_envs, "n_bs": env.nBS, "n_ue": env.nUE, "grid_n": env.grid_n, "rollout": self.T,
+              "w": self.flat.w.detach().cpu(), "ms": self.flat.ms.detach().cpu(), "env_state": blob.cpu(), "env_out": env._arena.cpu(),
+              "idx": self.idx_buf[self.T].cpu(), "ep_r": self.ep_r.cpu(), "running_r": self.running_r,
+              "last_episode_return": self.last_episode_return, "gen_state": self.gen.get_state().cpu()}
+        if self.optimizer == "adam":      # (the default optimiser's dict keeps exactly the keys it had)
+            sd.update({"optimizer": "adam", "opt_step": list(self.opt_step), "m": self.flat.m.detach().cpu(), "v": self.flat.v.detach().cpu()})
+        return sd
 
     def load_state_dict(self, sd):
         env = self.env
@@ -1271,9 +1416,16 @@ class A2CRunner:
             raise ValueError("checkpoint holds a %s network, this runner trains a %s one" % (sd.get("net", "mlp"), self.NET_KIND))
         if sd.get("format") != 1 or shape != (env.n_envs, env.nBS, env.nUE, env.grid_n, self.T):
             raise ValueError("checkpoint was written for another configuration: %r" % (shape,))
+        if sd.get("optimizer", "rmsprop") != self.optimizer:
+            raise ValueError("checkpoint was written with optimizer %r, this runner steps with %r" % (sd.get("optimizer", "rmsprop"),
+                                                                                                     self.optimizer))
         with torch.no_grad():
             self.flat.w.copy_(sd["w"])
             self.flat.ms.copy_(sd["ms"])
+            if self.optimizer == "adam":
+                self.flat.m.copy_(sd["m"])
+                self.flat.v.copy_(sd["v"])
+                self.opt_step = [int(x) for x in sd["opt_step"]]
             env.copy_state_from(sd["env_state"].to(self.dev))
             env._arena.copy_(sd["env_out"])
             self.idx_buf[self.T].copy_(sd["idx"])

@@ -221,7 +221,7 @@ class CnnA2CRunner(A2CRunner):
     PPO = False                   # ppo_rollout / ppo_update raise NotImplementedError: PPO is built for the MLP runners
 
     def __init__(self, env, net=None, rollout=50, gamma=GAMMA, beta=ENTROPY_BETA, lr_a=LR_A, lr_c=LR_C, seed=6, update_chunk=4096,
-                 first_state="obs", fused_update=True):
+                 first_state="obs", fused_update=True, optimizer="rmsprop", max_grad_norm=None, adam_betas=(0.9, 0.999), adam_eps=1e-8):
         import torch.distributed as dist
 
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
@@ -230,7 +230,8 @@ class CnnA2CRunner(A2CRunner):
             net = CnnACNet(env.nBS, env.grid_n, env.action_space_dim, seed=seed)
         if not isinstance(net, CnnACNet):
             raise TypeError("CnnA2CRunner trains a CnnACNet")
-        self._init_common(env, net, rollout, gamma, beta, lr_a, lr_c, seed, update_chunk, first_state, False)
+        self._init_common(env, net, rollout, gamma, beta, lr_a, lr_c, seed, update_chunk, first_state, False, optimizer, max_grad_norm,
+                          adam_betas, adam_eps)
         self.fused_update = bool(fused_update)
         self.force_exchange = False
         self._roll = None
@@ -421,12 +422,11 @@ class CnnA2CRunner(A2CRunner):
             gv["c_lc2_b"].add_(b["t_d2_b"])
             gv["c_v_k"].add_(b["t_v_k"].view(DENSE, 1))
             self._trunk_backward("c", ix, tc, b, mc, dh)
-        ae = fl.actor_end
-        A.rmsprop_tf1(fl.w[:ae], fl.ms[:ae], fl.g[:ae], self.lr_a)
-        A.rmsprop_tf1(fl.w[ae:], fl.ms[ae:], fl.g[ae:], self.lr_c)
-        loss = b["loss_sum"].cpu()                                   # (synchronises)
+        self._optimizer_step(1.0)                                    # (one process only: nothing to exchange)
+        loss, clip_stats = self._read_loss(b["loss_sum"], 1.0)       # (synchronises)
         self.stats = {"a_loss": float(loss[0]), "c_loss": float(loss[1]), "mean_reward": float(rew_buf.mean()), "grad_elems": fl.n_real,
                       "running_r": self.running_r, "allreduce_ms": None, "chunks": (M + chunk - 1) // chunk}
+        self.stats.update(clip_stats)
         return self.stats
 
     def state_dict(self):

@@ -1,5 +1,5 @@
-// Shared by the seven translation units of libuavagent.so (agent_kernels, agent_learner, agent_gemm, agent_factored, agent_wide, agent_ppo,
-// agent_ppo_joint .hip; not part of the C ABI: hidden visibility): the host helpers every entry point uses, then the device statements more
+// Shared by the eight translation units of libuavagent.so (agent_kernels, agent_learner, agent_gemm, agent_factored, agent_wide, agent_ppo,
+// agent_ppo_joint, agent_optim .hip; not part of the C ABI: hidden visibility): the host helpers every entry point uses, then the device statements more
 // than one unit needs bit for bit.  The loss gradients have headers of their own: agent_loss_joint.h, agent_loss_factored.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -103,6 +103,12 @@ __device__ __forceinline__ float wave_max_f(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
     return v;
+}
+// One element of the TF1 RMSProp step (agent_learner.hip's rmsprop_tf1_kernel and agent_optim.hip's clipped form: one statement, so an
+// inactive clip gives the unclipped kernel's bits): gk = g * s already applied by the caller.
+__device__ __forceinline__ void rmsprop_tf1_elem(float &w, float &ms, float gk, float lr, float decay, float eps) {
+    ms = decay * ms + (1.f - decay) * gk * gk;
+    w -= lr * gk / sqrtf(ms + eps);
 }
 // ---- the first layer's gather (agent_kernels.hip: <= 64 nodes, one wavefront pass; agent_wide.hip: <= 256 nodes) ----
 __device__ __forceinline__ void add4(float4 &s, const float4 &v) { s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }

@@ -432,18 +432,16 @@ __global__ __launch_bounds__(256) void rmsprop_tf1_kernel(float *__restrict__ w,
         float4 mm = reinterpret_cast<float4 *>(ms)[i4];
         float4 ww = reinterpret_cast<float4 *>(w)[i4];
         gg.x *= g_scale; gg.y *= g_scale; gg.z *= g_scale; gg.w *= g_scale;
-        mm.x = decay * mm.x + (1.f - decay) * gg.x * gg.x; mm.y = decay * mm.y + (1.f - decay) * gg.y * gg.y;
-        mm.z = decay * mm.z + (1.f - decay) * gg.z * gg.z; mm.w = decay * mm.w + (1.f - decay) * gg.w * gg.w;
-        ww.x -= lr * gg.x / sqrtf(mm.x + eps); ww.y -= lr * gg.y / sqrtf(mm.y + eps);
-        ww.z -= lr * gg.z / sqrtf(mm.z + eps); ww.w -= lr * gg.w / sqrtf(mm.w + eps);
+        rmsprop_tf1_elem(ww.x, mm.x, gg.x, lr, decay, eps); rmsprop_tf1_elem(ww.y, mm.y, gg.y, lr, decay, eps);
+        rmsprop_tf1_elem(ww.z, mm.z, gg.z, lr, decay, eps); rmsprop_tf1_elem(ww.w, mm.w, gg.w, lr, decay, eps);
         reinterpret_cast<float4 *>(ms)[i4] = mm;
         reinterpret_cast<float4 *>(w)[i4] = ww;
     } else {
         for (long long k = i; k < n; ++k) {
-            const float gk = g[k] * g_scale;
-            const float m = decay * ms[k] + (1.f - decay) * gk * gk;
+            float wk = w[k], m = ms[k];
+            rmsprop_tf1_elem(wk, m, g[k] * g_scale, lr, decay, eps);
             ms[k] = m;
-            w[k] -= lr * gk / sqrtf(m + eps);
+            w[k] = wk;
         }
     }
 }

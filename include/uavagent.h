@@ -124,6 +124,34 @@ int uavagent_nstep_returns_f32(const float *rewards, const float *bootstrap, int
 int uavagent_rmsprop_tf1(float *w, float *ms, const float *g, int64_t n, float lr, float decay, float eps, float g_scale,
                          void *stream);
 
+/* ---- Optimiser steps beyond the reference's (csrc/agent_optim.hip; still ABI 5): Adam and gradient clipping by global norm, on the same
+ * flat buffers.  Asynchronous on `stream`, no allocation; a negative code for null or unaligned pointers (float buffers and the workspace
+ * 16 bytes, the float64 sum 8), negative n, and hyper-parameters that are not finite or out of range.  n == 0: no launch, no pointer is
+ * looked at. ---- */
+
+/* sumsq_out[0] = sum of g[i]^2 over n floats, every square and every partial sum in float64 (1e-20 and 1e4 neither underflow nor overflow).
+ * A fixed grid writes one partial per workgroup to the workspace, a last pass adds them in a fixed order: no atomics, the same bits from
+ * call to call.  One workgroup covers 1024 floats per pass, the grid has at most 1024 workgroups.  Workspace: the bytes the _bytes call
+ * answers; its content before the call does not matter. */
+size_t uavagent_sumsq_workspace_bytes(int64_t n);
+int uavagent_sumsq_f32(const float *g, int64_t n, double *sumsq_out, void *workspace, void *stream);
+
+/* The gradient's scale s of both steps below.  sumsq == NULL: s = g_scale (no clipping).  Else, with *sumsq read on the device:
+ *   norm = g_scale * sqrt(*sumsq);  coef = min(1, max_norm / (norm + 1e-6)) in float64;  s = (float)(g_scale * coef)
+ * -- torch.nn.utils.clip_grad_norm_ on the scaled gradient; coef == 1 gives s == g_scale bit for bit.  A *sumsq that is not finite skips
+ * the step: no workgroup writes anything, the call still returns 0 (the caller sees it when it reads the sum back). */
+
+/* torch.optim.Adam without weight decay and amsgrad, step = 1, 2, ...:  gs = g * s;  m <- beta1 m + (1 - beta1) gs;
+ *   v <- beta2 v + (1 - beta2) gs^2;  w <- w - [lr / (1 - beta1^step)] m / (sqrt(v) / sqrt(1 - beta2^step) + eps).
+ * The two bias corrections are computed on the host in double and rounded to float.  betas in [0, 1), eps > 0, max_norm > 0 where sumsq is given. */
+int uavagent_adam_f32(float *w, float *m, float *v, const float *g, int64_t n, float lr, float beta1, float beta2, float eps, int64_t step,
+                      float g_scale, const double *sumsq, float max_norm, void *stream);
+
+/* The step of the TF1 RMSProp call above on gs = g * s: the same device statement per element, so sumsq == NULL or an inactive clip give
+ * that call's bits. */
+int uavagent_rmsprop_tf1_clipped(float *w, float *ms, const float *g, int64_t n, float lr, float decay, float eps, float g_scale,
+                                 const double *sumsq, float max_norm, void *stream);
+
 /* ---- ABI 3: float32 MFMA GEMMs for the 200-wide layers (csrc/agent_gemm.hip; v_mfma_f32_16x16x4_f32, exact float32 products summed
  * in k order inside a tile).  They replace torch.mm / torch.addmm in the update for the shapes the reference's network has
  * (main.py:143-156: 200 hidden units, 625 actions); anything else stays with the BLAS library. ---- */

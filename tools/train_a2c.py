@@ -15,6 +15,7 @@ actor parameters (Global_A_PARA: here a named .npz, agent.save_actor_npz -- load
   python -m torch.distributed.run --nproc-per-node 8 tools/train_a2c.py ...     # one process per GPU, gradients all-reduced (RCCL)"""
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -131,6 +132,12 @@ def main():
     ap.add_argument("--ppo-epochs", type=int, default=4, help="--algo ppo: full-batch epochs per rollout")
     ap.add_argument("--ppo-clip", type=float, default=0.2, help="--algo ppo: the probability ratio is clipped to 1 +- this")
     ap.add_argument("--gae-lambda", type=float, default=0.95, help="--algo ppo: lambda of the advantage estimate")
+    ap.add_argument("--optimizer", choices=("rmsprop", "adam"), default="rmsprop", help="the step of both networks: the reference's TF1 RMSProp "
+                    "or Adam (an extension; DESIGN.md section 24)")
+    ap.add_argument("--max-grad-norm", type=float, default=None, help="clip each network's gradient to this global norm (default: no clip)")
+    ap.add_argument("--adam-eps", type=float, default=1e-8)
+    ap.add_argument("--adam-beta1", type=float, default=0.9)
+    ap.add_argument("--adam-beta2", type=float, default=0.999)
     from drl_uav_cellularnet_amd import rewards
 
     rewards.add_reward_arguments(ap)                                       # --reward / --sinr-cap / --sep-threshold / --sep-weight / --collide-threshold
@@ -152,6 +159,11 @@ def main():
     msg = ppo_flags_error(a.net, a.algo, a.ppo_epochs, a.ppo_clip, a.gae_lambda)
     if msg:
         ap.error(msg)
+    if a.max_grad_norm is not None and not a.max_grad_norm > 0:
+        ap.error("--max-grad-norm must be > 0")
+    if not (0.0 <= a.adam_beta1 < 1.0 and 0.0 <= a.adam_beta2 < 1.0 and a.adam_eps > 0):
+        ap.error("--adam-beta1 / --adam-beta2 must lie in [0, 1) and --adam-eps must be > 0")
+    opt = {"optimizer": a.optimizer, "max_grad_norm": a.max_grad_norm, "adam_betas": (a.adam_beta1, a.adam_beta2), "adam_eps": a.adam_eps}
     import numpy as np
     import torch
 
@@ -172,18 +184,18 @@ def main():
     if a.net == "cnn-factored":
         from drl_uav_cellularnet_amd.factored import FactoredCnnA2CRunner
 
-        runner = FactoredCnnA2CRunner(env, rollout=a.rollout, first_state=a.first_state)
+        runner = FactoredCnnA2CRunner(env, rollout=a.rollout, first_state=a.first_state, **opt)
     elif a.net == "mlp-factored":
         from drl_uav_cellularnet_amd.factored import FactoredA2CRunner
 
-        runner = FactoredA2CRunner(env, rollout=a.rollout, first_state=a.first_state, tune_gemms=not a.no_gemm_tuning)
+        runner = FactoredA2CRunner(env, rollout=a.rollout, first_state=a.first_state, tune_gemms=not a.no_gemm_tuning, **opt)
     elif a.net == "cnn":
         from drl_uav_cellularnet_amd.cnn_agent import CnnA2CRunner
 
-        runner = CnnA2CRunner(env, rollout=a.rollout, first_state=a.first_state)
+        runner = CnnA2CRunner(env, rollout=a.rollout, first_state=a.first_state, **opt)
     else:
         runner = A2CRunner(env, rollout=a.rollout, first_state=a.first_state, tune_gemms=not a.no_gemm_tuning,
-                           persistent_rollout="auto" if a.rollout_form == "auto" else False)
+                           persistent_rollout="auto" if a.rollout_form == "auto" else False, **opt)
     per_episode = int(env.cfg.max_step) // a.rollout                       # a2c_single_thread.py:108
     returns, t0, first_ep = [], time.time(), 0
     ckpt = os.path.join(a.out, "checkpoint_rank%d.pt" % rank)
@@ -205,6 +217,7 @@ def main():
     for ep in range(first_ep, a.episodes):
         imitating = ep < a.imitate_episodes                                # a function of the episode counter alone
         reward_sum, agree, clip_frac, kl = 0.0, [], [], []
+        norms, n_clipped, n_skipped = [0.0, 0.0], [0, 0], 0                # --max-grad-norm: the episode's gradient norms before clipping
         for r in range(per_episode):
             if imitating:
                 st = runner.imitate_rollout(teacher=a.teacher, mix=a.imitate_mix, tau=a.imitate_tau, shaped_teacher=a.teacher_shaped)
@@ -216,6 +229,12 @@ def main():
             else:
                 st = runner.train_rollout()
             reward_sum += st["mean_reward"]
+            if a.max_grad_norm is not None:                                # (PPO: the last epoch's)
+                n_skipped += int(st["skipped_step"])
+                for i, k in enumerate("ac"):
+                    if math.isfinite(st["grad_norm_" + k]):
+                        norms[i] = max(norms[i], st["grad_norm_" + k])
+                    n_clipped[i] += int(st["clipped_" + k])
         returns.append(runner.running_r)                                   # GLOBAL_RUNNING_R, :169-172
         if rank == 0:
             line = {"episode": ep, "episode_return": runner.last_episode_return, "running_return": runner.running_r,
@@ -230,6 +249,10 @@ def main():
                     line.update({"clip_fraction": sum(clip_frac) / len(clip_frac), "approx_kl": sum(kl) / len(kl)})
             elif a.algo == "ppo":
                 line.update({"phase": "ppo", "clip_fraction": sum(clip_frac) / len(clip_frac), "approx_kl": sum(kl) / len(kl)})
+            if a.max_grad_norm is not None:
+                line.update({"grad_norm_a": st["grad_norm_a"], "grad_norm_c": st["grad_norm_c"], "max_grad_norm_a": norms[0],
+                             "max_grad_norm_c": norms[1], "clipped_a": n_clipped[0] / per_episode, "clipped_c": n_clipped[1] / per_episode,
+                             "skipped_steps": n_skipped})
             print(json.dumps(line), flush=True)
         if a.checkpoint_every and (ep + 1) % a.checkpoint_every == 0:
             save_checkpoint(torch, world, ckpt, {"runner": runner.state_dict(), "reward": None if reward is None else reward.as_dict(),
