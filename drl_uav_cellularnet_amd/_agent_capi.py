@@ -17,7 +17,7 @@ EXPORTS = ("uavagent_abi_version", "uavagent_last_error", "uavagent_sparse_rows_
            "uavagent_relu6_bwd_workspace_bytes", "uavagent_relu6_bwd", "uavagent_rowdot_f32",
            "uavagent_rows_grad_workspace_bytes", "uavagent_rows_grad_f32", "uavagent_rows_grad_sort", "uavagent_rows_grad_sums_f32", "uavagent_nstep_returns_f32", "uavagent_rmsprop_tf1",
            "uavagent_gemm_rows_f32", "uavagent_gemm_rows_workspace_bytes", "uavagent_gemm_tn_workspace_bytes", "uavagent_gemm_tn_f32",
-           "uavagent_debug_tn_plan_check", "uavagent_actor_head_f32", "uavagent_actor_head_gated_f32", "uavagent_gate_prepare",
+           "uavagent_debug_tn_plan_check", "uavagent_debug_rows_family", "uavagent_actor_head_f32", "uavagent_actor_head_gated_f32", "uavagent_gate_prepare",
            "uavagent_device_error", "uavagent_device_error_clear", "uavagent_actor_head_greedy_f32", "uavagent_argmax_rows_f32",
            "uavagent_choose_factored_f32", "uavagent_loss_grad_factored_workspace_bytes", "uavagent_a2c_loss_grad_factored",
            "uavagent_first_layer_wide_f32", "uavagent_first_layer_wide_from_obs_f32", "uavagent_rows_grad_wide_sort",
@@ -177,6 +177,8 @@ def load():
     lib.uavagent_gemm_tn_workspace_bytes.argtypes = [_I64, _I32]
     lib.uavagent_debug_tn_plan_check.restype = C.c_int
     lib.uavagent_debug_tn_plan_check.argtypes = [_I32]
+    lib.uavagent_debug_rows_family.restype = C.c_char_p
+    lib.uavagent_debug_rows_family.argtypes = [_I64, _I32, _I32, _I32, _I32]
     lib.uavagent_gemm_rows_workspace_bytes.restype = C.c_size_t
     lib.uavagent_gemm_rows_workspace_bytes.argtypes = [_I64]
     if lib.uavagent_abi_version() != ABI_VERSION:

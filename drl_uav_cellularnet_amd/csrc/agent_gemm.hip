@@ -314,12 +314,13 @@ __global__ __launch_bounds__(256) void gemm_tn_reduce(const f32x4 *__restrict__ 
 }
 
 // =====================================================================================================================
-// Rows GEMM:  C[m, n] = epilogue( sum_k A[m, k] * Wop[k, n] ),  n < N <= 208, K any.
+// Rows GEMM:  C[m, n] = epilogue( sum_k A[m, k] * Wop[k, n] ),  n < N <= 1024, K any.
 //   NT = false:  Wop = W        (W [K, N] row-major: a forward layer,  x @ W)
 //   NT = true:   Wop = W^T      (W [N, K] row-major: backwards through a layer,  dy @ W^T)
 //   EPI 0 none;  1: + bias[n], then relu6 when asked (tf.nn.relu6);  2: relu6 backwards, C = (0 < H[m, n] < 6) ? sum : 0 with H the
 //   layer's forward output (main.py:147-148,153).
-// Four kernels, chosen by uavagent_gemm_rows_f32:
+// Five kernels, chosen by rows_plan (N <= 208 in one piece; the aligned W^T forms also take N <= 1024, cut into slices across blockIdx.y):
+//   gemm_rows_resident_kernel  dy @ W^T at K = 200 and many rows: W^T resident in LDS, persistent workgroups (the update's 200-wide layers)
 //   gemm_rows_glds_kernel   dy @ W^T / x @ (W^T)^T, aligned operands, K % 40 == 0: LDS-DMA ring (the MLP learner's 200 / 640; not K = 32, 100)
 //   gemm_rows_nt_kernel     the same product for any K % 4 == 0: register-staged, k-contiguous tiles, wide fragment reads
 //   gemm_rows_vec_kernel    x @ W with W [K, N] as stored (n-contiguous W tile [k][208], A tile [row][22]: stride 22 puts the 16 rows x
@@ -332,6 +333,43 @@ constexpr int kRowsATile = kRowsBM * kRowsLD;                                   
 constexpr int kRowsWTile = (kRowsBK * kNP > kNP * kRowsLD) ? kRowsBK * kNP : kNP * kRowsLD;   // 4576 floats
 constexpr int kRowsLDC = 212;                                                   // epilogue staging row stride (848 B = 53 x 16)
 static_assert(4 * 16 * kRowsLDC <= 2 * (kRowsATile + kRowsWTile), "epilogue staging must fit the tile buffers");
+
+// ---- What the epilogues of the rows kernels share.  The output maths of one float4 (rows_out1: of one float, the dword kernel's): EPI 1 adds
+// the bias, then relu6 when asked; EPI 2 keeps v where the layer's forward output h lies strictly inside (0, 6).  (bv / h may be unset otherwise.)
+template <int EPI>
+__device__ __forceinline__ float4 rows_out4(float4 v, const float4 &bv, int relu6, const float4 &h) {
+    if (EPI == 1) {
+        v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
+        if (relu6) { v.x = fminf(fmaxf(v.x, 0.f), 6.f); v.y = fminf(fmaxf(v.y, 0.f), 6.f); v.z = fminf(fmaxf(v.z, 0.f), 6.f); v.w = fminf(fmaxf(v.w, 0.f), 6.f); }
+    }
+    if (EPI == 2) {
+        v.x = (h.x > 0.f && h.x < 6.f) ? v.x : 0.f; v.y = (h.y > 0.f && h.y < 6.f) ? v.y : 0.f;
+        v.z = (h.z > 0.f && h.z < 6.f) ? v.z : 0.f; v.w = (h.w > 0.f && h.w < 6.f) ? v.w : 0.f;
+    }
+    return v;
+}
+template <int EPI>
+__device__ __forceinline__ float rows_out1(float v, float bv, int relu6, float h) {
+    if (EPI == 1) { v += bv; if (relu6) v = fminf(fmaxf(v, 0.0f), 6.0f); }
+    if (EPI == 2) v = (h > 0.0f && h < 6.0f) ? v : 0.0f;
+    return v;
+}
+
+// The cross-wave finish of the column sums: the waves' running sums `cs` go to S [NWAVE][52 float4] at the start of the workgroup's LDS (over the
+// staging patches: the caller has a barrier between its last store pass and this call), wave 0 adds them in wave order and writes the workgroup's
+// partial row (dst = that row + n0; a slice owns its columns).  writes = the lanes of wave 0 that store: 4 lane < nloc (nt, glds), or all 52 (vec).
+template <int NWAVE>
+__device__ __forceinline__ void rows_colsum_finish(float *lds, const int wave, const int lane, const float4 &cs, const bool writes, float *__restrict__ dst) {
+    float4 *S = reinterpret_cast<float4 *>(lds);
+    if (lane < 52) S[wave * 52 + lane] = cs;
+    __syncthreads();
+    if (wave == 0 && writes) {
+        float4 t = S[lane];
+#pragma unroll
+        for (int w = 1; w < NWAVE; ++w) { const float4 u = S[w * 52 + lane]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
+        *reinterpret_cast<float4 *>(dst + lane * 4) = t;
+    }
+}
 
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_rows_vec_kernel(const float *__restrict__ A, long long lda, const float *__restrict__ W, long long ldw,
@@ -436,7 +474,8 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_vec_kernel(const float *__re
     // cb * 16 + r), then lane l < N / 4 moves float4 number l of one whole row per instruction: 800 contiguous bytes per wave-instruction
     // for C (and for H) instead of dword accesses that touch 64 bytes per row.  Each lane thereby owns 4 fixed columns, so the column
     // sums of what is stored (the bias gradient of the layer below, col_partial != nullptr) are a running float4 per lane: rows ascending
-    // inside the wave, then the 4 waves in order, then the workgroups in order (rows_colsum_reduce): bit-reproducible. ----
+    // inside the wave, then the 4 waves in order (rows_colsum_finish), then the workgroups in order (rows_colsum_reduce): bit-reproducible.
+    // (nt and glds stage and store alike, each in its own words: as one function they left the bounds of profiles/rows_fold_listings.txt) ----
     float *E = lds + wave * (16 * kRowsLDC);
     float4 cs = float4{0.f, 0.f, 0.f, 0.f};
     const bool col_ok = lane < n4;
@@ -453,33 +492,16 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_vec_kernel(const float *__re
         for (int row = 0; row < 16; ++row) {
             const long long m = m0 + wave * 32 + rb * 16 + row;
             if (col_ok && m < M) {
-                float4 v = *reinterpret_cast<const float4 *>(E + row * kRowsLDC + lane * 4);
-                if (EPI == 1) {
-                    v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-                    if (relu6) { v.x = fminf(fmaxf(v.x, 0.f), 6.f); v.y = fminf(fmaxf(v.y, 0.f), 6.f); v.z = fminf(fmaxf(v.z, 0.f), 6.f); v.w = fminf(fmaxf(v.w, 0.f), 6.f); }
-                }
-                if (EPI == 2) {
-                    const float4 h = *reinterpret_cast<const float4 *>(H + m * ldh + lane * 4);
-                    v.x = (h.x > 0.f && h.x < 6.f) ? v.x : 0.f; v.y = (h.y > 0.f && h.y < 6.f) ? v.y : 0.f;
-                    v.z = (h.z > 0.f && h.z < 6.f) ? v.z : 0.f; v.w = (h.w > 0.f && h.w < 6.f) ? v.w : 0.f;
-                }
+                float4 h;
+                if (EPI == 2) h = *reinterpret_cast<const float4 *>(H + m * ldh + lane * 4);
+                const float4 v = rows_out4<EPI>(*reinterpret_cast<const float4 *>(E + row * kRowsLDC + lane * 4), bv, relu6, h);
                 *reinterpret_cast<float4 *>(C + m * ldc + lane * 4) = v;
                 cs.x += v.x; cs.y += v.y; cs.z += v.z; cs.w += v.w;
             }
         }
         __syncthreads();
     }
-    if (col_partial != nullptr) {
-        float4 *S = reinterpret_cast<float4 *>(lds);                       // [4 waves][52 float4]
-        if (lane < 52) S[wave * 52 + lane] = cs;
-        __syncthreads();
-        if (wave == 0 && lane < 52) {
-            float4 t = S[lane];
-#pragma unroll
-            for (int w = 1; w < 4; ++w) { const float4 u = S[w * 52 + lane]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
-            *reinterpret_cast<float4 *>(col_partial + (long long)blockIdx.x * kNP + lane * 4) = t;
-        }
-    }
+    if (col_partial != nullptr) rows_colsum_finish<4>(lds, wave, lane, cs, lane < 52, col_partial + (long long)blockIdx.x * kNP);
 }
 
 // out[c] = sum over workgroups of col_partial[wg][c], in a fixed order: a block owns 64 columns, 16 slab-threads per column each add a
@@ -519,7 +541,7 @@ __global__ __launch_bounds__(1024) void rows_colsum_reduce(const float *__restri
 //   BM = 128: 4 waves x 32 rows x NB column blocks, 2 workgroups per CU (the update: M = rollout x envs rows);
 //   BM =  64: 4 waves x 16 rows x NB column blocks, N cut into slices of NB blocks across blockIdx.y (the rollout's M = envs rows: 8192 rows
 //             give 256 / 512 workgroups at NB = 7 / 10).
-// Epilogues as gemm_rows_vec_kernel; the column sums (col_partial) exist for single-slice launches only.
+// Epilogues as gemm_rows_vec_kernel; column sums (col_partial) for N <= 208: one slice, or two (64 x 7), each writing its own columns of the partial row.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int kNtBK = 20, kNtLD = 24;
 
@@ -654,33 +676,14 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_nt_kernel(const float *__res
         for (int row = 0; row < 16; ++row) {
             const long long m = m0 + wave * (16 * RBW) + rb * 16 + row;
             if (col_ok && m < M) {
-                float4 v = *reinterpret_cast<const float4 *>(E + row * LDC + lane * 4);
-                if (EPI == 1) {
-                    v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-                    if (relu6) { v.x = fminf(fmaxf(v.x, 0.f), 6.f); v.y = fminf(fmaxf(v.y, 0.f), 6.f); v.z = fminf(fmaxf(v.z, 0.f), 6.f); v.w = fminf(fmaxf(v.w, 0.f), 6.f); }
-                }
-                if (EPI == 2) {
-                    const float4 h = hv[row];
-                    v.x = (h.x > 0.f && h.x < 6.f) ? v.x : 0.f; v.y = (h.y > 0.f && h.y < 6.f) ? v.y : 0.f;
-                    v.z = (h.z > 0.f && h.z < 6.f) ? v.z : 0.f; v.w = (h.w > 0.f && h.w < 6.f) ? v.w : 0.f;
-                }
+                const float4 v = rows_out4<EPI>(*reinterpret_cast<const float4 *>(E + row * LDC + lane * 4), bv, relu6, hv[row]);
                 *reinterpret_cast<float4 *>(C + m * ldc + n0 + lane * 4) = v;
                 cs.x += v.x; cs.y += v.y; cs.z += v.z; cs.w += v.w;
             }
         }
         __syncthreads();
     }
-    if (col_partial != nullptr) {                                          // (host: N <= 208; a slice owns its columns of the partial row)
-        float4 *S = reinterpret_cast<float4 *>(lds);                       // [4 waves][52 float4]
-        if (lane < 52) S[wave * 52 + lane] = cs;
-        __syncthreads();
-        if (wave == 0 && col_ok) {
-            float4 t = S[lane];
-#pragma unroll
-            for (int w = 1; w < 4; ++w) { const float4 u = S[w * 52 + lane]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
-            *reinterpret_cast<float4 *>(col_partial + (long long)blockIdx.x * kNP + n0 + lane * 4) = t;
-        }
-    }
+    if (col_partial != nullptr) rows_colsum_finish<4>(lds, wave, lane, cs, col_ok, col_partial + (long long)blockIdx.x * kNP + n0);   // (host: N <= 208)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -829,31 +832,14 @@ __global__ __launch_bounds__(BM * 4) void gemm_rows_glds_kernel(const float *__r
     for (int row = 0; row < 16; ++row) {
         const long long m = m0 + wave * 16 + row;
         if (col_ok && m < M) {
-            float4 v = *reinterpret_cast<const float4 *>(E + row * LDC + lane * 4);
-            if (EPI == 1) {
-                v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-                if (relu6) { v.x = fminf(fmaxf(v.x, 0.f), 6.f); v.y = fminf(fmaxf(v.y, 0.f), 6.f); v.z = fminf(fmaxf(v.z, 0.f), 6.f); v.w = fminf(fmaxf(v.w, 0.f), 6.f); }
-            }
-            if (EPI == 2) {
-                const float4 h = hv[row];
-                v.x = (h.x > 0.f && h.x < 6.f) ? v.x : 0.f; v.y = (h.y > 0.f && h.y < 6.f) ? v.y : 0.f;
-                v.z = (h.z > 0.f && h.z < 6.f) ? v.z : 0.f; v.w = (h.w > 0.f && h.w < 6.f) ? v.w : 0.f;
-            }
+            const float4 v = rows_out4<EPI>(*reinterpret_cast<const float4 *>(E + row * LDC + lane * 4), bv, relu6, hv[row]);
             *reinterpret_cast<float4 *>(C + m * ldc + n0 + lane * 4) = v;
             cs.x += v.x; cs.y += v.y; cs.z += v.z; cs.w += v.w;
         }
     }
-    if (col_partial != nullptr) {          // (host: N <= 208) rows ascending inside a wave, then the waves in order, then the workgroups
-        __syncthreads();
-        float4 *S = reinterpret_cast<float4 *>(lds);                       // [NWAVE][52 float4]
-        if (lane < 52) S[wave * 52 + lane] = cs;
-        __syncthreads();
-        if (wave == 0 && col_ok) {
-            float4 t = S[lane];
-#pragma unroll
-            for (int w = 1; w < NWAVE; ++w) { const float4 u = S[w * 52 + lane]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
-            *reinterpret_cast<float4 *>(col_partial + (long long)blockIdx.x * kNP + n0 + lane * 4) = t;
-        }
+    if (col_partial != nullptr) {          // (host: N <= 208)
+        __syncthreads();                   // every wave has read its patch: the sums go over them
+        rows_colsum_finish<NWAVE>(lds, wave, lane, cs, col_ok, col_partial + (long long)blockIdx.x * kNP + n0);
     }
 }
 
@@ -990,16 +976,7 @@ __device__ __forceinline__ void rows_resident_body(const float *__restrict__ A, 
             const int row = 2 * i + half;
             const long long m = t * 16 + row;
             if (col_ok && m < M) {
-                float4 v = *reinterpret_cast<const float4 *>(E + row * LDC + L * 4);
-                if (EPI == 1) {
-                    v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-                    if (relu6) { v.x = fminf(fmaxf(v.x, 0.f), 6.f); v.y = fminf(fmaxf(v.y, 0.f), 6.f); v.z = fminf(fmaxf(v.z, 0.f), 6.f); v.w = fminf(fmaxf(v.w, 0.f), 6.f); }
-                }
-                if (EPI == 2) {
-                    const float4 hh = hv[i];
-                    v.x = (hh.x > 0.f && hh.x < 6.f) ? v.x : 0.f; v.y = (hh.y > 0.f && hh.y < 6.f) ? v.y : 0.f;
-                    v.z = (hh.z > 0.f && hh.z < 6.f) ? v.z : 0.f; v.w = (hh.w > 0.f && hh.w < 6.f) ? v.w : 0.f;
-                }
+                const float4 v = rows_out4<EPI>(*reinterpret_cast<const float4 *>(E + row * LDC + L * 4), bv, relu6, hv[i]);
                 *reinterpret_cast<float4 *>(C + m * ldc + n0 + L * 4) = v;
                 cs.x += v.x; cs.y += v.y; cs.z += v.z; cs.w += v.w;
             }
@@ -1409,11 +1386,11 @@ __global__ __launch_bounds__(kHdThr) __attribute__((amdgpu_num_vgpr(rollout_gate
     }
 }
 
-template <bool NT, bool VEC, int EPI>
+// The general form: any K, N <= 208, any alignment (the aligned shapes run the kernels above); dword loads, direct epilogue.
+template <bool NT, int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_rows_kernel(const float *__restrict__ A, long long lda, const float *__restrict__ W, long long ldw,
                                                             int K, int N, long long M, const float *__restrict__ bias, int relu6,
                                                             const float *__restrict__ H, long long ldh, float *__restrict__ C, long long ldc) {
-    static_assert(!VEC, "the aligned shapes run gemm_rows_vec_kernel");
     __shared__ __attribute__((aligned(16))) float lds[2 * (kRowsATile + kRowsWTile)];
     float *const sA = lds, *const sW = lds + 2 * kRowsATile;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1497,10 +1474,7 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_kernel(const float *__restri
                 for (int t = 0; t < 4; ++t) {
                     const long long m = m0 + wave * 32 + rb * 16 + 4 * q + t;
                     if (m < M) {
-                        float v = acc[rb][cb][t];
-                        if (EPI == 1) { v += bv; if (relu6) v = fminf(fmaxf(v, 0.0f), 6.0f); }
-                        if (EPI == 2) { const float h = H[m * ldh + col]; v = (h > 0.0f && h < 6.0f) ? v : 0.0f; }
-                        C[m * ldc + col] = v;
+                        C[m * ldc + col] = rows_out1<EPI>(acc[rb][cb][t], bv, relu6, (EPI == 2) ? H[m * ldh + col] : 0.0f);
                     }
                 }
         }
@@ -1609,18 +1583,28 @@ static int cu_count_of_current_device() {
     return v;
 }
 
+// What every head entry asks of the arguments they share, in the order the entries report it (each in its own words, with what it adds).
+enum HeadArgs { kHeadArgsOk, kHeadArgsNull, kHeadArgsShape, kHeadArgsAlign };
+static HeadArgs actor_head_args(bool needs_uniforms, const float *h1, const float *w2t, const float *b2, const float *w3t_padded,
+                                const float *b3_padded, const float *uniforms, int32_t n_hidden, int32_t n_actions, const float *h2_out,
+                                const float *logits_out, int64_t ld_logits, const int64_t *actions_out) {
+    if (!h1 || !w2t || !b2 || !w3t_padded || !b3_padded || (needs_uniforms && !uniforms) || !h2_out || !logits_out || !actions_out) return kHeadArgsNull;
+    if (n_hidden != kHdH || n_actions <= 576 || n_actions > kHdNP || ld_logits < kHdNP || (ld_logits & 3)) return kHeadArgsShape;
+    if (!aligned16(h1) || !aligned16(w2t) || !aligned16(w3t_padded) || !aligned16(h2_out) || !aligned16(logits_out)) return kHeadArgsAlign;
+    return kHeadArgsOk;
+}
+
 // Checks and launch rule shared by the sampling head and the greedy head (`greedy`: the GREEDY instantiations, uniforms unused).
 static int actor_head_launch(const char *what, bool greedy, const float *h1, const float *w2t, const float *b2, const float *w3t_padded,
                              const float *b3_padded, const float *uniforms, int64_t n_rows, int32_t n_hidden, int32_t n_actions, float *h2_out,
                              float *logits_out, int64_t ld_logits, int64_t *actions_out, void *stream) {
     const std::string w(what);
-    if (!h1 || !w2t || !b2 || !w3t_padded || !b3_padded || (!greedy && !uniforms) || !h2_out || !logits_out || !actions_out)
-        return fail(UAVAGENT_E_INVALID, w + ": null pointer");
-    if (n_hidden != kHdH || n_actions <= 576 || n_actions > kHdNP || ld_logits < kHdNP || (ld_logits & 3) || n_rows < 0)
+    const HeadArgs bad = actor_head_args(!greedy, h1, w2t, b2, w3t_padded, b3_padded, uniforms, n_hidden, n_actions, h2_out, logits_out, ld_logits, actions_out);
+    if (bad == kHeadArgsNull) return fail(UAVAGENT_E_INVALID, w + ": null pointer");
+    if (bad == kHeadArgsShape || n_rows < 0)
         return fail(UAVAGENT_E_INVALID, w + ": built for 200 hidden units and 577..640 actions (the reference's 625 = 5^4; 10 policy columns "
                                              "per lane, like uavagent_sample_actions at that width), ld_logits >= 640 and a multiple of 4");
-    if (!aligned16(h1) || !aligned16(w2t) || !aligned16(w3t_padded) || !aligned16(h2_out) || !aligned16(logits_out))
-        return fail(UAVAGENT_E_INVALID, w + ": matrices must be 16-byte aligned");
+    if (bad == kHeadArgsAlign) return fail(UAVAGENT_E_INVALID, w + ": matrices must be 16-byte aligned");
     if (n_rows == 0) return UAVAGENT_OK;
     // 32-row workgroups while they give every CU one (a whole rollout batch of 8192 rows on 256 CUs); 16-row workgroups for fewer rows (half a
     // batch on its own stream): the time of a workgroup is its weight stream, so fewer, larger workgroups would only leave CUs idle
@@ -1678,12 +1662,12 @@ extern "C" int uavagent_actor_head_gated_f32(const float *h1, const float *w2t, 
                                              const float *uniforms, int64_t n_rows, int32_t n_steps, int32_t n_hidden, int32_t n_actions,
                                              float *h2_out, float *logits_out, int64_t ld_logits, int64_t *actions_out, uint32_t *gate_obs,
                                              uint32_t *gate_actions, uint32_t *claim, uint32_t spin_us, void *stream) {
-    if (!h1 || !w2t || !b2 || !w3t_padded || !b3_padded || !uniforms || !h2_out || !logits_out || !actions_out || !gate_obs || !gate_actions || !claim)
-        return fail(UAVAGENT_E_INVALID, "actor_head_gated: null pointer");
-    if (n_hidden != kHdH || n_actions <= 576 || n_actions > kHdNP || ld_logits < kHdNP || (ld_logits & 3) || n_rows < 1 || n_steps < 1)
+    const HeadArgs bad = actor_head_args(true, h1, w2t, b2, w3t_padded, b3_padded, uniforms, n_hidden, n_actions, h2_out, logits_out, ld_logits, actions_out);
+    if (bad == kHeadArgsNull || !gate_obs || !gate_actions || !claim) return fail(UAVAGENT_E_INVALID, "actor_head_gated: null pointer");
+    if (bad == kHeadArgsShape || n_rows < 1 || n_steps < 1)
         return fail(UAVAGENT_E_INVALID, "actor_head_gated: built for 200 hidden units and 577..640 actions, ld_logits >= 640 and a multiple of 4, "
                                          "n_rows >= 1, n_steps >= 1");
-    if (!aligned16(h1) || !aligned16(w2t) || !aligned16(w3t_padded) || !aligned16(h2_out) || !aligned16(logits_out) || (n_rows & 3))
+    if (bad == kHeadArgsAlign || (n_rows & 3))
         return fail(UAVAGENT_E_INVALID, "actor_head_gated: matrices must be 16-byte aligned and n_rows a multiple of 4 (every step's block of rows "
                                          "starts 16-byte aligned)");
     if (g_gate_err_dev == nullptr) return fail(UAVAGENT_E_INVALID, "actor_head_gated: call uavagent_gate_prepare() first (it allocates the error word)");
@@ -1706,88 +1690,99 @@ extern "C" size_t uavagent_gemm_rows_workspace_bytes(int64_t m_rows) {
     return (size_t)((m_rows + 63) / 64) * kNP * sizeof(float);          // one partial row per workgroup of the 64-row kernels (the most)
 }
 
+namespace {
+// The launch of uavagent_gemm_rows_f32 for a shape, decided in one place: the kernel, its tile and grid, and the partial rows of column
+// sums it leaves for rows_colsum_reduce.  Pure host arithmetic (`n_cu` is asked only where the grid is one workgroup per CU).
+enum RowsKernel { kRowsResident, kRowsGlds, kRowsNt, kRowsVec, kRowsGeneral };
+struct RowsPlan {
+    const char *family;                  // the launch's name (tests/gemm_cases.py: ROWS_FAMILIES); nullptr: the shape is refused
+    RowsKernel kernel;
+    bool vec;                            // the aligned path: 16-byte aligned operands, strides / k / n multiples of 4
+    int bm, nb, n_a;                     // rows and 16-column blocks of a workgroup's tile (glds, nt); resident: workgroups of the 7-block type
+    unsigned grid_x, grid_y, threads;
+    long long n_part;                    // partial rows written when there is a workspace: one per grid_x (resident: per n_a)
+};
+bool rows_shape_ok(long long m_rows, int k, int n) { return m_rows >= 1 && k >= 1 && n >= 1 && n <= 1024; }   // the entry's ranges
+RowsPlan rows_plan(long long m_rows, int k, int n, bool w_transposed, bool aligned, int (*n_cu)()) {     // (a shape inside rows_shape_ok)
+    RowsPlan p = {};
+    p.vec = aligned && (k % 4 == 0) && (n % 4 == 0);
+    if (n > 208 && !(p.vec && w_transposed)) return p;                 // refused: only the aligned W^T kernels cut N into slices
+    p.bm = kRowsBM; p.nb = kRB; p.threads = 256;
+    if (w_transposed && p.vec && k == kRsK && n > kRsNBA * 16 && n <= 208 && m_rows > 32768) {
+        // W^T resident in LDS, persistent workgroups, one per CU (gemm_rows_resident_kernel): the update's 200-wide layers
+        const int cus = n_cu(), share = (cus * kRsNBA + (kRsNBA + kRsNBB) / 2) / (kRsNBA + kRsNBB);
+        p.family = "resident"; p.kernel = kRowsResident; p.threads = kRsThr; p.n_a = share < cus ? share : cus - 1;
+        p.grid_x = (unsigned)cus; p.grid_y = 1; p.n_part = p.n_a; return p;
+    }
+    if (w_transposed && p.vec) {
+        // glds: LDS-DMA ring (K % 40 == 0); nt: k-contiguous register-staged tiles (any K % 4 == 0).  Few rows (a rollout step): 64-row
+        // workgroups and N in slices, so that 8192 rows still give >= 256 workgroups; many rows (the update): 128-row workgroups.
+        // (glds, 64-row workgroups with a 2-stage ring: two of them fit a CU's LDS and cover each other's prologue / epilogue; measured at
+        //  8192 rows against a 3-stage ring with one workgroup per CU: 12.3 vs 13.3 us at N = 200, 26.2 vs 31.2 us at N = 640)
+        static const char *const names[2][4] = {{"nt64x7", "nt64x10", "nt128x13", "nt128x10"}, {"glds64x7", "glds64x10", "glds128x13", "glds128x10"}};
+        const bool gl = (k % kGlBK == 0), few = m_rows <= 32768;
+        p.kernel = gl ? kRowsGlds : kRowsNt; p.bm = few ? 64 : 128; p.nb = few ? (n <= 224 ? 7 : 10) : (n <= 208 ? 13 : 10);
+        p.family = names[gl][(few ? 0 : 2) + (p.nb == 10)]; p.threads = gl ? (unsigned)p.bm * 4 : 256;
+    } else if (p.vec) { p.family = "vec"; p.kernel = kRowsVec; }      // x @ W with W [K, N] as stored: n-contiguous W tile, register-staged
+    else { p.family = w_transposed ? "general_nt" : "general_nn"; p.kernel = kRowsGeneral; }
+    p.grid_x = (unsigned)((m_rows + p.bm - 1) / p.bm); p.grid_y = (unsigned)((n + p.nb * 16 - 1) / (p.nb * 16)); p.n_part = p.grid_x;
+    return p;
+}
+
+// Run-time -> compile-time: f(std::integral_constant<int, epi>{}), f(RowsTile<bm, nb>{}) for the plan's tile.
+template <class F> void with_epi(int epi, F f) {
+    if (epi == 0) f(std::integral_constant<int, 0>{}); else if (epi == 1) f(std::integral_constant<int, 1>{}); else f(std::integral_constant<int, 2>{});
+}
+template <int BM_, int NB_> struct RowsTile { static constexpr int BM = BM_, NB = NB_; };
+template <class F> void with_tile(const RowsPlan &p, F f) {
+    if (p.bm == 64) { if (p.nb == 7) f(RowsTile<64, 7>{}); else f(RowsTile<64, 10>{}); }
+    else if (p.nb == 13) f(RowsTile<128, 13>{}); else f(RowsTile<128, 10>{});
+}
+}  // namespace
+
+// Test hook (host only, no GPU): the family of the launch uavagent_gemm_rows_f32 makes for a shape, NULL where it refuses the shape.
+extern "C" const char *uavagent_debug_rows_family(int64_t m_rows, int32_t k, int32_t n, int32_t w_transposed, int32_t aligned) {
+    return rows_shape_ok(m_rows, k, n) ? rows_plan(m_rows, k, n, w_transposed != 0, aligned != 0, [] { return 256; }).family : nullptr;
+}
+
 extern "C" int uavagent_gemm_rows_f32(const float *a, int64_t lda, const float *w, int64_t ldw, int32_t w_transposed, int64_t m_rows, int32_t k,
                                       int32_t n, const float *bias, int32_t relu6, const float *relu6_mask_h, int64_t ldh, float *c, int64_t ldc,
                                       float *colsum_out, void *workspace, size_t workspace_bytes, void *stream) {
     if (!a || !w || !c) return fail(UAVAGENT_E_INVALID, "gemm_rows: null pointer");
-    if (m_rows < 1 || k < 1 || n < 1 || n > 1024 || lda < k || ldc < n || ldw < (w_transposed ? k : n) || lda > 65536 || ldw > 65536)
+    if (!rows_shape_ok(m_rows, k, n) || lda < k || ldc < n || ldw < (w_transposed ? k : n) || lda > 65536 || ldw > 65536)
         return fail(UAVAGENT_E_INVALID, "gemm_rows: need m_rows, k >= 1, 1 <= n <= 1024, k <= lda <= 65536, ldc >= n, row length of w <= ldw <= 65536");
     if (relu6_mask_h && (bias || relu6)) return fail(UAVAGENT_E_INVALID, "gemm_rows: the relu6-mask epilogue excludes bias / relu6");
     if (relu6_mask_h && ldh < n) return fail(UAVAGENT_E_INVALID, "gemm_rows: ldh < n");
     hipStream_t st = (hipStream_t)stream;
-    const bool vec = aligned16(a) && aligned16(w) && aligned16(c) && aligned16(bias) && aligned16(relu6_mask_h) && (lda % 4 == 0) && (ldw % 4 == 0) &&
-                     (ldc % 4 == 0) && (ldh % 4 == 0) && (k % 4 == 0) && (n % 4 == 0);
-    if (n > 208 && !(vec && w_transposed))
-        return fail(UAVAGENT_E_INVALID, "gemm_rows: n > 208 needs the aligned w_transposed form (N is then cut into slices)");
-    const dim3 grid((unsigned)((m_rows + kRowsBM - 1) / kRowsBM)), blk(256);
-    const int epi = relu6_mask_h ? 2 : ((bias || relu6) ? 1 : 0);
-    long long n_part_resident = 0;
+    const bool aligned = aligned16(a) && aligned16(w) && aligned16(c) && aligned16(bias) && aligned16(relu6_mask_h) && !(lda % 4) && !(ldw % 4) && !(ldc % 4) && !(ldh % 4);
+    const RowsPlan p = rows_plan(m_rows, k, n, w_transposed != 0, aligned, cu_count_of_current_device);   // (per device: a process may drive several)
+    if (!p.family) return fail(UAVAGENT_E_INVALID, "gemm_rows: n > 208 needs the aligned w_transposed form (N is then cut into slices)");
     float *colp = nullptr;
     if (colsum_out) {
         if (n > 208) return fail(UAVAGENT_E_INVALID, "gemm_rows: column sums exist for n <= 208");
-        if (!vec) return fail(UAVAGENT_E_INVALID, "gemm_rows: column sums need the aligned path (16-byte aligned operands, strides / k / n multiples of 4)");
+        if (!p.vec) return fail(UAVAGENT_E_INVALID, "gemm_rows: column sums need the aligned path (16-byte aligned operands, strides / k / n multiples of 4)");
         if (!workspace || !aligned16(workspace) || workspace_bytes < uavagent_gemm_rows_workspace_bytes(m_rows))
             return fail(UAVAGENT_E_INVALID, "gemm_rows: column sums need a 16-byte aligned workspace of uavagent_gemm_rows_workspace_bytes()");
         colp = reinterpret_cast<float *>(workspace);
     }
-#define UAV_ARGS grid, blk, 0, st, a, (long long)lda, w, (long long)ldw, (int)k, (int)n, (long long)m_rows, bias, (int)relu6, relu6_mask_h, (long long)ldh, c, (long long)ldc
-#define UAV_NT(BM_, NB_)                                                                                             \
-    do {                                                                                                             \
-        const dim3 g2((unsigned)((m_rows + BM_ - 1) / BM_), (unsigned)((n + NB_ * 16 - 1) / (NB_ * 16)));               \
-        if (epi == 0) hipLaunchKernelGGL((gemm_rows_nt_kernel<BM_, NB_, 0>), g2, blk, 0, st, a, (long long)lda, w, (long long)ldw, (int)k, (int)n, (long long)m_rows, bias, (int)relu6, relu6_mask_h, (long long)ldh, c, (long long)ldc, colp); \
-        else if (epi == 1) hipLaunchKernelGGL((gemm_rows_nt_kernel<BM_, NB_, 1>), g2, blk, 0, st, a, (long long)lda, w, (long long)ldw, (int)k, (int)n, (long long)m_rows, bias, (int)relu6, relu6_mask_h, (long long)ldh, c, (long long)ldc, colp); \
-        else hipLaunchKernelGGL((gemm_rows_nt_kernel<BM_, NB_, 2>), g2, blk, 0, st, a, (long long)lda, w, (long long)ldw, (int)k, (int)n, (long long)m_rows, bias, (int)relu6, relu6_mask_h, (long long)ldh, c, (long long)ldc, colp); \
-    } while (0)
-#define UAV_ROWS_E(NT_)        /* the general form: dword loads */                                                    \
-    do {                                                                                                             \
-        if (epi == 0) hipLaunchKernelGGL((gemm_rows_kernel<NT_, false, 0>), UAV_ARGS);                                \
-        else if (epi == 1) hipLaunchKernelGGL((gemm_rows_kernel<NT_, false, 1>), UAV_ARGS);                           \
-        else hipLaunchKernelGGL((gemm_rows_kernel<NT_, false, 2>), UAV_ARGS);                                         \
-    } while (0)
-#define UAV_GL(BM_, NB_, NS_)                                                                                         \
-    do {                                                                                                             \
-        const dim3 g2((unsigned)((m_rows + BM_ - 1) / BM_), (unsigned)((n + NB_ * 16 - 1) / (NB_ * 16))), b2(BM_ * 4);  \
-        if (epi == 0) hipLaunchKernelGGL((gemm_rows_glds_kernel<BM_, NB_, NS_, 0>), g2, b2, 0, st, a, (long long)lda, w, (long long)ldw, (int)k, (int)n, (long long)m_rows, bias, (int)relu6, relu6_mask_h, (long long)ldh, c, (long long)ldc, colp); \
-        else if (epi == 1) hipLaunchKernelGGL((gemm_rows_glds_kernel<BM_, NB_, NS_, 1>), g2, b2, 0, st, a, (long long)lda, w, (long long)ldw, (int)k, (int)n, (long long)m_rows, bias, (int)relu6, relu6_mask_h, (long long)ldh, c, (long long)ldc, colp); \
-        else hipLaunchKernelGGL((gemm_rows_glds_kernel<BM_, NB_, NS_, 2>), g2, b2, 0, st, a, (long long)lda, w, (long long)ldw, (int)k, (int)n, (long long)m_rows, bias, (int)relu6, relu6_mask_h, (long long)ldh, c, (long long)ldc, colp); \
-    } while (0)
-    if (w_transposed && vec && k == kRsK && n > kRsNBA * 16 && n <= 208 && m_rows > 32768) {
-        // W^T resident in LDS, persistent workgroups (gemm_rows_resident_kernel): the update's 200-wide layers
-        const int n_cu = cu_count_of_current_device();          // per device: a process may drive several
-        const int nA = (n_cu * kRsNBA + (kRsNBA + kRsNBB) / 2) / (kRsNBA + kRsNBB) < n_cu ? (n_cu * kRsNBA + (kRsNBA + kRsNBB) / 2) / (kRsNBA + kRsNBB) : n_cu - 1;
-        if (colp && hipMemsetAsync(colp, 0, (size_t)nA * kNP * sizeof(float), st) != hipSuccess) return fail(UAVAGENT_E_HIP, "gemm_rows: memset failed");
-        const dim3 g2((unsigned)n_cu), b2(kRsThr);
-        if (epi == 0) hipLaunchKernelGGL((gemm_rows_resident_kernel<0>), g2, b2, 0, st, a, (long long)lda, w, (long long)ldw, (int)n, (long long)m_rows, bias, (int)relu6, relu6_mask_h, (long long)ldh, c, (long long)ldc, colp, nA);
-        else if (epi == 1) hipLaunchKernelGGL((gemm_rows_resident_kernel<1>), g2, b2, 0, st, a, (long long)lda, w, (long long)ldw, (int)n, (long long)m_rows, bias, (int)relu6, relu6_mask_h, (long long)ldh, c, (long long)ldc, colp, nA);
-        else hipLaunchKernelGGL((gemm_rows_resident_kernel<2>), g2, b2, 0, st, a, (long long)lda, w, (long long)ldw, (int)n, (long long)m_rows, bias, (int)relu6, relu6_mask_h, (long long)ldh, c, (long long)ldc, colp, nA);
-        n_part_resident = nA;
-    } else if (w_transposed && vec && (k % kGlBK == 0)) {
-        // LDS-DMA ring (gemm_rows_glds_kernel).  Few rows (a rollout step): 64-row workgroups, N in slices; many rows: 128-row workgroups.
-        // (64-row workgroups with a 2-stage ring: two of them fit a CU's LDS and cover each other's prologue / epilogue; measured at 8192
-        //  rows against a 3-stage ring with one workgroup per CU: 12.3 vs 13.3 us at N = 200, 26.2 vs 31.2 us at N = 640)
-        if (m_rows <= 32768) { if (n <= 224) UAV_GL(64, 7, 2); else UAV_GL(64, 10, 2); }
-        else if (n <= 208) UAV_GL(128, 13, 2);
-        else UAV_GL(128, 10, 2);
-    } else if (w_transposed && vec) {
-        // k-contiguous tiles, wide fragment reads (gemm_rows_nt_kernel).  Few rows (a rollout step): 64-row workgroups and N in slices,
-        // so that 8192 rows still give >= 256 workgroups; many rows (the update): 128-row workgroups over all <= 208 columns.
-        if (m_rows <= 32768) { if (n <= 224) UAV_NT(64, 7); else UAV_NT(64, 10); }
-        else if (n <= 208) UAV_NT(128, 13);
-        else UAV_NT(128, 10);
-    } else if (w_transposed) UAV_ROWS_E(true);
-    else if (vec) {                                     // x @ W with W [K, N] as stored: n-contiguous W tile, register-staged
-        if (epi == 0) hipLaunchKernelGGL((gemm_rows_vec_kernel<0>), UAV_ARGS, colp);
-        else if (epi == 1) hipLaunchKernelGGL((gemm_rows_vec_kernel<1>), UAV_ARGS, colp);
-        else hipLaunchKernelGGL((gemm_rows_vec_kernel<2>), UAV_ARGS, colp);
-    } else UAV_ROWS_E(false);
-#undef UAV_NT
-#undef UAV_GL
-#undef UAV_ROWS_E
-#undef UAV_ARGS
-    if (colp) {
-        const long long n_part = n_part_resident ? n_part_resident : (w_transposed && m_rows <= 32768) ? (m_rows + 63) / 64 : (long long)grid.x;     // partial rows the kernel that ran wrote
-        hipLaunchKernelGGL(rows_colsum_reduce, dim3((n + 63) / 64), dim3(1024), 0, st, colp, n_part, (int)n, colsum_out);
-    }
+    if (p.kernel == kRowsResident && colp && hipMemsetAsync(colp, 0, (size_t)p.n_a * kNP * sizeof(float), st) != hipSuccess) return fail(UAVAGENT_E_HIP, "gemm_rows: memset failed");
+    const dim3 grid(p.grid_x, p.grid_y), blk(p.threads);
+    const long long M = m_rows, lda_ = lda, ldw_ = ldw, ldh_ = ldh, ldc_ = ldc;
+    const int K = k, N = n, r6 = relu6;
+    with_epi(relu6_mask_h ? 2 : ((bias || relu6) ? 1 : 0), [&](auto epi) {
+        constexpr int EPI = decltype(epi)::value;
+        if (p.kernel == kRowsResident)
+            hipLaunchKernelGGL((gemm_rows_resident_kernel<EPI>), grid, blk, 0, st, a, lda_, w, ldw_, N, M, bias, r6, relu6_mask_h, ldh_, c, ldc_, colp, p.n_a);
+        else if (p.kernel == kRowsGlds)
+            with_tile(p, [&](auto t) { hipLaunchKernelGGL((gemm_rows_glds_kernel<decltype(t)::BM, decltype(t)::NB, 2, EPI>), grid, blk, 0, st, a, lda_, w, ldw_, K, N, M, bias, r6, relu6_mask_h, ldh_, c, ldc_, colp); });
+        else if (p.kernel == kRowsNt)
+            with_tile(p, [&](auto t) { hipLaunchKernelGGL((gemm_rows_nt_kernel<decltype(t)::BM, decltype(t)::NB, EPI>), grid, blk, 0, st, a, lda_, w, ldw_, K, N, M, bias, r6, relu6_mask_h, ldh_, c, ldc_, colp); });
+        else if (p.kernel == kRowsVec)
+            hipLaunchKernelGGL((gemm_rows_vec_kernel<EPI>), grid, blk, 0, st, a, lda_, w, ldw_, K, N, M, bias, r6, relu6_mask_h, ldh_, c, ldc_, colp);
+        else        // the general form, dword loads: W transposed, or as stored
+            hipLaunchKernelGGL((w_transposed ? gemm_rows_kernel<true, EPI> : gemm_rows_kernel<false, EPI>), grid, blk, 0, st, a, lda_, w, ldw_, K, N, M, bias, r6, relu6_mask_h, ldh_, c, ldc_);
+    });
+    if (colp) hipLaunchKernelGGL(rows_colsum_reduce, dim3((n + 63) / 64), dim3(1024), 0, st, colp, p.n_part, (int)n, colsum_out);
     if (hipGetLastError() != hipSuccess) return fail(UAVAGENT_E_HIP, "gemm_rows: launch failed");
     return UAVAGENT_OK;
 }

@@ -235,6 +235,11 @@ size_t uavagent_gemm_tn_workspace_bytes(int64_t m_rows, int32_t n_j);
 /* Test hook (host only): the dW kernel deals the 13 x 13 (plan 13) or 13 x 20 (plan 20) output blocks of a tile out to 8 wavefronts of equal
  * shape; > 0 = MFMAs issued per k-step when every block has exactly one owner, negative on a hole or an overlap. */
 int uavagent_debug_tn_plan_check(int32_t plan);
+/* Test hook (host only, no device): the kernel family uavagent_gemm_rows_f32 launches for a shape -- "resident", "glds64x7", "glds64x10",
+ * "glds128x13", "glds128x10", "nt64x7", "nt64x10", "nt128x13", "nt128x10", "vec", "general_nt" or "general_nn" (a static string) -- from the
+ * same plan the entry launches from; NULL where the entry refuses the shape.  aligned: every pointer on 16 bytes and every row stride a
+ * multiple of 4 floats.  Additive export: the ABI number stays. */
+const char *uavagent_debug_rows_family(int64_t m_rows, int32_t k, int32_t n, int32_t w_transposed, int32_t aligned);
 int uavagent_gemm_tn_f32(const float *a, const float *b, int64_t m_rows, int32_t n_i, int32_t n_j, int64_t ldb, float *c, int64_t ldc,
                          float *dbias_out, void *workspace, size_t workspace_bytes, void *stream);
 

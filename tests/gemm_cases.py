@@ -26,36 +26,37 @@ TN_FAMILIES = ((13, True), (13, False), (20, True), (20, False))
 
 # ---- the dispatch, restated ---------------------------------------------------------------------------------------------------------------
 def family(M, K, N, w_transposed, aligned):
-    """The kernel uavagent_gemm_rows_f32 launches (csrc/agent_gemm.hip:1723-1787), restated.  `aligned`: every pointer on 16 bytes and every
-    row stride a multiple of 4 floats.  libuavagent has no launch census, so nothing ties this to the library but the reader: a change of the
-    dispatch has to be repeated here, and a drift shows only as a family of the table that no longer runs where its tag says."""
-    vec = aligned and K % 4 == 0 and N % 4 == 0                                     # :1723
-    if N > 208 and not (vec and w_transposed):                                     # :1725
+    """The kernel uavagent_gemm_rows_f32 launches (rows_plan, csrc/agent_gemm.hip), restated.  `aligned`: every pointer on 16 bytes and every
+    row stride a multiple of 4 floats.  The library answers the same question from the plan it launches from (uavagent_debug_rows_family, host
+    only), and tests/test_gemm_cases.py holds the two together over the table and a sweep of the thresholds: a change of the dispatch that is
+    not repeated here fails there."""
+    vec = aligned and K % 4 == 0 and N % 4 == 0                                     # rows_plan: vec
+    if N > 208 and not (vec and w_transposed):                                     # rows_plan: the slicing rule
         raise ValueError("n > 208 needs the aligned w_transposed form")
-    if w_transposed and vec and K == 200 and 112 < N <= 208 and M > 32768:         # :1759  kRsK = 200, kRsNBA * 16 = 112
+    if w_transposed and vec and K == 200 and 112 < N <= 208 and M > 32768:         # rows_plan: kRsK = 200, kRsNBA * 16 = 112
         return "resident"
     if w_transposed and vec:
-        kind = "glds" if K % 40 == 0 else "nt"                                     # :1769 / :1776  kGlBK = 40
-        if M <= 32768:                                                             # :1773 / :1779
+        kind = "glds" if K % 40 == 0 else "nt"                                     # rows_plan: kGlBK = 40
+        if M <= 32768:                                                             # rows_plan: few
             return kind + ("64x7" if N <= 224 else "64x10")
-        return kind + ("128x13" if N <= 208 else "128x10")                         # :1774 / :1780
+        return kind + ("128x13" if N <= 208 else "128x10")
     if w_transposed:
-        return "general_nt"                                                        # :1782
-    return "vec" if vec else "general_nn"                                          # :1783 / :1787
+        return "general_nt"
+    return "vec" if vec else "general_nn"
 
 
 def colsum_allowed(K, N, aligned):
-    """uavagent_gemm_rows_f32 takes colsum_out on the aligned path for n <= 208 (csrc/agent_gemm.hip:1731-1735)."""
+    """uavagent_gemm_rows_f32 takes colsum_out on the aligned path for n <= 208 (its colsum_out checks)."""
     return aligned and K % 4 == 0 and N % 4 == 0 and N <= 208
 
 
 def tn_family(J, ldb, b_aligned):
-    """(plan, bvec) of uavagent_gemm_tn_f32 (csrc/agent_gemm.hip:1525 and :1589), restated like family()."""
+    """(plan, bvec) of uavagent_gemm_tn_f32 (tn_shape's plan and the entry's bvec), restated like family()."""
     return (13 if J <= 208 else 20), bool(b_aligned and ldb % 4 == 0 and ldb >= ((J + 3) & ~3))
 
 
 def tn_splits(M, J):
-    """(n_split, rows_per_split) of tn_shape (csrc/agent_gemm.hip:1523-1534)."""
+    """(n_split, rows_per_split) of tn_shape (csrc/agent_gemm.hip)."""
     n_jt = 1 if J <= 208 else (J + 319) // 320
     want = max(256 // n_jt, 8)
     chunks = (M + 31) // 32

@@ -93,6 +93,10 @@ def test_gemm_host_logic_without_gpu():
     assert lib.uavagent_debug_tn_plan_check(13) == 8 * 22          # 169 real blocks of 176 issued
     assert lib.uavagent_debug_tn_plan_check(20) == 8 * 33          # 260 of 264
     assert lib.uavagent_debug_tn_plan_check(7) == -1
+    # the launch plan of gemm_rows, asked on the host: a static name, NULL where the entry refuses the shape (the sweep: test_gemm_cases.py)
+    assert lib.uavagent_debug_rows_family(409600, 200, 200, 1, 1) == b"resident" and lib.uavagent_debug_rows_family(8192, 200, 640, 1, 1) == b"glds64x10"
+    assert lib.uavagent_debug_rows_family(8192, 200, 200, 0, 1) == b"vec" and lib.uavagent_debug_rows_family(8192, 200, 200, 0, 0) == b"general_nn"
+    assert lib.uavagent_debug_rows_family(1000, 200, 640, 0, 1) is None and lib.uavagent_debug_rows_family(1000, 200, 2000, 1, 1) is None
     one = ctypes.c_void_p(16)
     # one slab per workgroup: 256 splits x 8 waves x 22 blocks x 64 lanes x 16 B at the update's size; two J tiles x 128 splits x 33 blocks for 625
     assert lib.uavagent_gemm_tn_workspace_bytes(409600, 200) == 256 * 8 * 22 * 64 * 16

@@ -59,6 +59,42 @@ def test_dispatch_restatement_at_its_thresholds():
         G.family(100, 200, 212, True, False)
 
 
+def _library_family(M, K, N, w_transposed, aligned):
+    from drl_uav_cellularnet_amd import _agent_capi
+
+    name = _agent_capi.load().uavagent_debug_rows_family(M, K, N, int(w_transposed), int(aligned))
+    return None if name is None else name.decode()
+
+
+def test_library_plans_the_family_the_table_names():
+    """uavagent_debug_rows_family (the plan uavagent_gemm_rows_f32 launches from, asked on the host) against the restatement, row by row."""
+    for c in G.ROWS:
+        assert _library_family(c.M, c.K, c.N, c.w_transposed, not c.offset) == G.family(c.M, c.K, c.N, c.w_transposed, not c.offset) == c.family, \
+            G.rows_id(c)
+
+
+def test_library_and_restatement_agree_across_every_threshold():
+    """Both sides of every bound of the dispatch (rows 32768, K % 4, K % 40, K = 200, N 112 / 208 / 224, N % 4, alignment, w_transposed): the
+    same family, and the library returns NULL exactly where the restatement raises."""
+    seen, refused = set(), 0
+    for M in (1, 32768, 32769):
+        for K in (1, 4, 36, 40, 44, 200, 204, 640):
+            for N in (1, 4, 112, 116, 208, 212, 224, 228, 640, 1024):
+                for wt in (False, True):
+                    for aligned in (False, True):
+                        got = _library_family(M, K, N, wt, aligned)
+                        try:
+                            want = G.family(M, K, N, wt, aligned)
+                        except ValueError:
+                            want = None
+                        assert got == want, (M, K, N, wt, aligned)
+                        seen.add(got)
+                        refused += got is None
+    assert seen == set(G.ROWS_FAMILIES) | {None} and refused > 0
+    for shape in ((0, 4, 4), (4, 0, 4), (4, 4, 0), (4, 4, 1025)):               # outside the entry's ranges: refused as well
+        assert _library_family(*shape, True, True) is None
+
+
 @pytest.mark.parametrize("c", G.ROWS, ids=G.rows_id)
 def test_integer_operands_keep_every_partial_sum_exact(c):
     for tri in ((False, True) if G.colsum_allowed(c.K, c.N, not c.offset) else (False,)):
