@@ -24,7 +24,8 @@ EXPORTS = ("uavagent_abi_version", "uavagent_last_error", "uavagent_sparse_rows_
            "uavagent_rows_grad_wide_sums_f32", "uavagent_imitation_loss_grad_workspace_bytes", "uavagent_imitation_loss_grad_factored",
            "uavagent_soft_targets_f32", "uavagent_gae_f32", "uavagent_logp_factored_f32", "uavagent_ppo_loss_grad_factored_workspace_bytes",
            "uavagent_ppo_loss_grad_factored", "uavagent_logp_f32", "uavagent_ppo_loss_grad_workspace_bytes", "uavagent_ppo_loss_grad",
-           "uavagent_sumsq_workspace_bytes", "uavagent_sumsq_f32", "uavagent_adam_f32", "uavagent_rmsprop_tf1_clipped")
+           "uavagent_sumsq_workspace_bytes", "uavagent_sumsq_f32", "uavagent_adam_f32", "uavagent_rmsprop_tf1_clipped",
+           "uavagent_ppo_shuffle_rows")
 ABI_VERSION = 5
 
 _lib = None
@@ -139,6 +140,7 @@ def load():
         "uavagent_ppo_loss_grad_factored": [_P, _I64, _P, _P, _P, _P, _P, _I64, _I32, _I32, _F, _F, _P, _P, _P, _P, _P],
         "uavagent_logp_f32": [_P, _I64, _P, _I64, _I32, _P, _P],
         "uavagent_ppo_loss_grad": [_P, _I64, _P, _P, _P, _P, _P, _I64, _I32, _F, _F, _P, _P, _P, _P, _P],
+        "uavagent_ppo_shuffle_rows": [_P, _I64, _I64, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
         "uavagent_sumsq_f32": [_P, _I64, _P, _P, _P],
         "uavagent_adam_f32": [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _I64, _F, _P, _F, _P],
         "uavagent_rmsprop_tf1_clipped": [_P, _P, _P, _I64, _F, _F, _F, _F, _P, _F, _P],
@@ -780,6 +782,42 @@ def ppo_loss_grad(logits, v, ret, adv, logp_old, actions, beta, clip, dv_out, db
         rc = load().uavagent_ppo_loss_grad(_ptr(logits), ld, _ptr(v), _ptr(ret), _ptr(adv), _ptr(logp_old), _ptr(actions), M, A_, float(beta),
                                            float(clip), _ptr(dv_out), _ptr(dbias_out), _ptr(loss_out), _ptr(ws), _stream(logits.device))
     _check(rc, "uavagent_ppo_loss_grad")
+
+
+def ppo_shuffle_rows(rows, idx, act, adv, ret, logp, out=None):
+    """The five per-row arrays of a PPO batch in the order of ``rows``, one launch (uavagent_ppo_shuffle_rows): rows int64 [n] (row numbers of
+    the flattened batch, clamped into it; they may repeat), idx int64 [.., k], act int64 and adv / ret / logp float32 with one element per row
+    of idx.  ``out``: the five outputs (idx [n, k], act / adv / ret / logp [n]) to write into, none overlapping its source.  Returns
+    (idx, act, adv, ret, logp): minibatch j of m rows is their slice [j * m, (j + 1) * m)."""
+    i64c = lambda t: t.dtype == torch.int64 and t.is_contiguous()
+    if not i64c(rows) or rows.dim() != 1:
+        raise UavAgentError("ppo_shuffle_rows: rows must be a contiguous int64 [n] tensor")
+    if not i64c(idx) or idx.dim() < 2 or not 1 <= idx.shape[-1] <= WIDE_NODES:
+        raise UavAgentError("ppo_shuffle_rows: idx must be a contiguous int64 [.., k] tensor with 1 <= k <= %d" % WIDE_NODES)
+    k = idx.shape[-1]
+    n, n_src = rows.numel(), idx.numel() // k
+    if not i64c(act) or act.numel() != n_src:
+        raise UavAgentError("ppo_shuffle_rows: act must be a contiguous int64 tensor with one element per row of idx")
+    for t, what in ((adv, "adv"), (ret, "ret"), (logp, "logp")):
+        _f32c(t, what)
+        if t.numel() != n_src:
+            raise UavAgentError("ppo_shuffle_rows: %s must hold one float per row of idx" % what)
+    if out is None:
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=idx.device)
+        out = (torch.empty((n, k), dtype=torch.int64, device=idx.device), torch.empty((n,), dtype=torch.int64, device=idx.device), f(n), f(n), f(n))
+    o_idx, o_act, o_adv, o_ret, o_logp = out
+    if not i64c(o_idx) or o_idx.numel() != n * k or not i64c(o_act) or o_act.numel() != n:
+        raise UavAgentError("ppo_shuffle_rows: out[0] must be a contiguous int64 [n, k] tensor and out[1] a contiguous int64 [n] one")
+    for t, what in ((o_adv, "out[2]"), (o_ret, "out[3]"), (o_logp, "out[4]")):
+        _f32c(t, what)
+        if t.numel() != n:
+            raise UavAgentError("ppo_shuffle_rows: %s must hold n floats" % what)
+    _same_device("ppo_shuffle_rows", rows, idx, act, adv, ret, logp, *out)
+    with torch.cuda.device(idx.device):
+        rc = load().uavagent_ppo_shuffle_rows(_ptr(rows), n, n_src, _ptr(idx), k, _ptr(act), _ptr(adv), _ptr(ret), _ptr(logp), _ptr(o_idx),
+                                              _ptr(o_act), _ptr(o_adv), _ptr(o_ret), _ptr(o_logp), _stream(idx.device))
+    _check(rc, "uavagent_ppo_shuffle_rows")
+    return o_idx, o_act, o_adv, o_ret, o_logp
 
 
 def imitation_loss_grad_workspace(n_heads, n_act, device):

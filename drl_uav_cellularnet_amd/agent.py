@@ -534,7 +534,8 @@ class A2CRunner:
 
             _A.gate_prepare()
         self._graph = None
-        self._upd = None
+        self._upd = None              # the update's buffer set in use ...
+        self._upd_sets = {}           # ... of the sets kept, by row count (_ensure_update_buffers)
 
     NET_KIND = "mlp"
     FUSED_OBS_MAX_NODES = 64      # uavagent_first_layer_from_obs_f32: one lane per node (factored.FactoredA2CRunner: the wide form's 256)
@@ -617,6 +618,7 @@ class A2CRunner:
         self._tuning_frozen = False
         self._fwd_valid = False
         self._ppo = None              # while ppo_update's epochs run: adv / ret / logp_old of the batch and the clip; the loss hooks answer with the PPO form
+        self._mb = None               # ppo_update with minibatches, fused: the permuted copy of the batch (_minibatch_buffers)
 
     def _flat_view(self, buf, key):
         p = getattr(self.net, key)
@@ -993,8 +995,14 @@ class A2CRunner:
     def _ensure_update_buffers(self, M, K):
         from . import _agent_capi as A
 
-        if self._upd is not None and self._upd["M"] == M:
+        # One set per row count, the two last used kept: the rollout's own M rows and a PPO minibatch's m live side by side (``_upd`` is the
+        # set in use: the loss hooks read it)
+        sets = self._upd_sets
+        if M in sets:
+            self._upd = sets[M] = sets.pop(M)                  # (re-inserted: the dict's order is the order of use)
             return self._upd
+        while len(sets) >= 2:
+            sets.pop(next(iter(sets)))
         H, NA, dev = HIDDEN, self.net.n_action, self.dev
         f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         own = self._fwd is not None and M == self.T * self.env.n_envs      # the rollout's own buffers double as the update's
@@ -1018,6 +1026,7 @@ class A2CRunner:
                               "ws_cs": A.gemm_rows_workspace(M, dev)})
             if self._exchanging() and self.overlap_allreduce:    # one table gradient per trunk: each needs its g rows contiguous
                 self._upd.update({"g_a": f(M, H), "g_c": f(M, H)})
+        sets[M] = self._upd
         return self._upd
 
     def _actor_backward(self, b, g):
@@ -1271,7 +1280,7 @@ class A2CRunner:
             self._tuning_frozen = True
         return stats
 
-    # ---- PPO (DESIGN.md sections 22 and 23; the MLP runners, joint and factored head): GAE(lambda) advantages, then several full-batch epochs of update() in PPO mode on one rollout ----------
+    # ---- PPO (DESIGN.md sections 22 and 23; the MLP runners, joint and factored head): GAE(lambda) advantages, then several epochs of update() in PPO mode on one rollout, full-batch or in shuffled minibatches (section 25) ----------
     @staticmethod
     def _check_ppo(epochs, clip, lam):
         if int(epochs) != epochs or int(epochs) < 1:
@@ -1316,16 +1325,64 @@ class A2CRunner:
         std = (s[1] / s[2] - mean * mean).clamp_min(0.0).sqrt()
         return ((a64 - mean) / (std + 1e-8)).to(adv.dtype)
 
-    def ppo_rollout(self, epochs=4, clip=0.2, lam=0.95, normalize_adv=True):
-        """One rollout and ``epochs`` full-batch updates of PPO on it: GAE(lam) advantages under the critic as it stands after the rollout,
-        log pi_old from the rollout's own logits, then per epoch the clipped surrogate (ratio clipped to 1 +- clip) with the entropy bonus for
-        the actor and the squared error against the GAE returns for the critic -- update()'s forward, backward, all-reduce and rmsprop_tf1
+    @staticmethod
+    def _check_minibatches(M, epochs, minibatches, target_kl, rows):
+        """-> minibatches as an int; ValueError for what ppo_update cannot split or stop on (before anything is touched)."""
+        if isinstance(minibatches, bool) or int(minibatches) != minibatches or int(minibatches) < 1:
+            raise ValueError("minibatches must be an integer >= 1")
+        if M % int(minibatches):
+            raise ValueError("minibatches = %d does not divide the batch of M = %d rows" % (int(minibatches), M))
+        if target_kl is not None and not (math.isfinite(float(target_kl)) and float(target_kl) > 0.0):
+            raise ValueError("target_kl must be finite and > 0")
+        if rows is not None:
+            if not torch.is_tensor(rows) or rows.dtype != torch.int64 or tuple(rows.shape) != (int(epochs), M):
+                raise ValueError("rows must be an int64 [epochs, M] = [%d, %d] tensor" % (int(epochs), M))
+            if not torch.equal(torch.sort(rows, dim=1).values.cpu(), torch.arange(M).expand(int(epochs), M)):
+                raise ValueError("rows: every row must be a permutation of range(M = %d)" % M)
+        return int(minibatches)
+
+    def ppo_rollout(self, epochs=4, clip=0.2, lam=0.95, normalize_adv=True, minibatches=1, target_kl=None, rows=None):
+        """One rollout and ``epochs`` epochs of PPO on it: GAE(lam) advantages under the critic as it stands after the rollout,
+        log pi_old from the rollout's own logits, then per step the clipped surrogate (ratio clipped to 1 +- clip) with the entropy bonus for
+        the actor and the squared error against the GAE returns for the critic -- update()'s forward, backward, all-reduce and optimiser
         step as they stand, with the loss hooks in PPO mode.  ``normalize_adv``: adv <- (adv - mean) / (std + 1e-8) over the batch (of all ranks).
         With epochs=1, lam=1, normalize_adv=False this is train_rollout()'s update up to float32 rounding.
-        Returns the last epoch's stats with ``clip_fraction``, ``approx_kl`` (mean(logp_old - logp)) and ``epochs`` added."""
+
+        ``minibatches`` = k (it must divide M = T * N): every epoch draws a permutation of the M rows from the runner's
+        generator and takes k optimiser steps, step j on rows [j * M / k, (j + 1) * M / k) of the permuted batch.  Advantages, their
+        normalisation and log pi_old are the whole batch's, computed once.  ``rows``: int64 [epochs, M], the permutations to use in place of
+        drawn ones (the generator is then left alone).  With k = 1 and no ``rows`` an epoch is one step on the batch as it lies, as ever.
+        ``target_kl``: after every epoch, kl = the mean over its steps of the loss's mean(logp_old - logp), over all ranks; kl > target_kl
+        skips the epochs that remain.  That is the k1 estimator: each step measures it BEFORE stepping, it may be negative, and with k = 1
+        the first epoch's is exactly 0, so that a stop comes after the second epoch at the earliest.  Its sampling error falls with the row
+        count: at production batches (51 200 to 409 600 rows) it is far below any useful target, at a few hundred rows it is not.
+
+        Returns the last step's stats with ``clip_fraction`` and ``approx_kl`` (the last epoch's means over its steps), ``epochs`` (epochs
+        run), ``minibatches``, ``early_stop`` and ``approx_kl_epochs`` (every epoch's kl, as compared with the target) added."""
         self._require_ppo()
         self._check_ppo(epochs, clip, lam)
-        return self.ppo_update(*self.collect(), epochs=epochs, clip=clip, lam=lam, normalize_adv=normalize_adv)
+        self._check_minibatches(self.T * self.env.n_envs, epochs, minibatches, target_kl, rows)
+        return self.ppo_update(*self.collect(), epochs=epochs, clip=clip, lam=lam, normalize_adv=normalize_adv, minibatches=minibatches,
+                               target_kl=target_kl, rows=rows)
+
+    def _mean_over_ranks(self, x):
+        """The mean of a host float over the ranks (itself with one rank), as _normalize_adv exchanges its sums."""
+        import torch.distributed as dist
+
+        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+            return x
+        t = torch.tensor([x], dtype=torch.float64, device="cpu" if dist.get_backend() == "gloo" else self.dev)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        return float(t[0]) / dist.get_world_size()
+
+    def _minibatch_buffers(self, M, K, like):
+        """The permuted copy of a batch's five per-row arrays (fused path), kept from call to call: ppo_shuffle_rows writes it once per epoch."""
+        mb = self._mb
+        if mb is None or mb["key"] != (M, K):
+            e = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=like.device)
+            mb = self._mb = {"key": (M, K), "out": (e((M, K), torch.int64), e((M,), torch.int64), e((M,), torch.float32),
+                                                    e((M,), torch.float32), e((M,), torch.float32))}
+        return mb["out"]
 
     @torch.no_grad()
     def _ppo_prepare(self, idx_buf, act_buf, rew_buf, boot, lam, normalize_adv, fused):
@@ -1370,26 +1427,71 @@ class A2CRunner:
             adv = self._normalize_adv(adv)
         return adv.contiguous(), ret.contiguous(), logp_old
 
-    def ppo_update(self, idx_buf, act_buf, rew_buf, boot, epochs=4, clip=0.2, lam=0.95, normalize_adv=True, fused=None):
+    def ppo_update(self, idx_buf, act_buf, rew_buf, boot, epochs=4, clip=0.2, lam=0.95, normalize_adv=True, fused=None, minibatches=1,
+                   target_kl=None, rows=None):
         """ppo_rollout's update on a collected batch.  ``fused``: None = update()'s choice, True / False = the kernels and update_fused /
-        the PyTorch statements and update_reference."""
+        the PyTorch statements and update_reference.  With minibatches (or ``rows``) the batch's five per-row arrays are permuted once per
+        epoch -- fused: ONE uavagent_ppo_shuffle_rows launch; else index_select -- and step j is update_fused / update_reference on rows
+        [j * m, (j + 1) * m) of the copy as a [1, m] rollout with a zero bootstrap, the loss hooks reading that slice's adv / ret / logp_old."""
         self._require_ppo()
         self._check_ppo(epochs, clip, lam)
+        T, N, K = idx_buf.shape
+        M = T * N
+        k = self._check_minibatches(M, epochs, minibatches, target_kl, rows)
+        m = M // k
+        permuted = k > 1 or rows is not None      # else: an epoch is one step on the batch as it lies, the code path of the full-batch PPO
         if fused is None:
             fused = self.fused_update and self.dev.type == "cuda"
+        step = self.update_fused if fused else self.update_reference
         adv, ret, logp_old = self._ppo_prepare(idx_buf, act_buf, rew_buf, boot, float(lam), bool(normalize_adv), fused)
         self._ppo = {"adv": adv, "ret": ret, "logp_old": logp_old, "clip": float(clip)}
+        kls, early_stop = [], False
         try:
-            for _ in range(int(epochs)):
-                self._ppo.update(cursor=0, n_clipped=0.0, kl_sum=0.0)
-                stats = (self.update_fused if fused else self.update_reference)(idx_buf, act_buf, rew_buf, boot)
-                self._fwd_valid = False                                    # the weights have moved: later epochs recompute the forward pass
+            if permuted:
+                self._fwd_valid = False            # every step recomputes its forward pass, on its own rows
+                src = (idx_buf.reshape(M, K).contiguous(), act_buf.reshape(M).contiguous(), adv, ret, logp_old)
+                zero_rew, zero_boot = torch.zeros((1, m), dtype=rew_buf.dtype, device=rew_buf.device), torch.zeros(m, dtype=boot.dtype, device=boot.device)
+                mean_reward = float(rew_buf.mean())
+            for e in range(int(epochs)):
+                if permuted:
+                    perm = rows[e].to(self.dev) if rows is not None else torch.randperm(M, generator=self.gen, device=self.dev)
+                    if fused:
+                        from . import _agent_capi as A
+
+                        cp = A.ppo_shuffle_rows(perm.contiguous(), *src, out=self._minibatch_buffers(M, K, src[0]))
+                    else:
+                        cp = tuple(t.index_select(0, perm) for t in src)
+                clip_e = kl_e = 0.0
+                for j in range(k):
+                    if permuted:
+                        lo, hi = j * m, (j + 1) * m
+                        self._ppo = {"adv": cp[2][lo:hi], "ret": cp[3][lo:hi], "logp_old": cp[4][lo:hi], "clip": float(clip)}
+                        args = (cp[0][lo:hi].view(1, m, K), cp[1][lo:hi].view(1, m), zero_rew, zero_boot)
+                    else:
+                        args = (idx_buf, act_buf, rew_buf, boot)
+                    self._ppo.update(cursor=0, n_clipped=0.0, kl_sum=0.0)
+                    stats = step(*args)
+                    self._fwd_valid = False                                # the weights have moved: later steps recompute the forward pass
+                    if fused:
+                        loss = self._upd["loss"].cpu()
+                        clip_j, kl_j = float(loss[3]), float(loss[4])
+                    else:
+                        clip_j, kl_j = self._ppo["n_clipped"] / m, self._ppo["kl_sum"] / m
+                    clip_e, kl_e = clip_e + clip_j, kl_e + kl_j
+                if k > 1:
+                    clip_e, kl_e = clip_e / k, kl_e / k
+                stats["clip_fraction"], stats["approx_kl"] = clip_e, kl_e
+                if target_kl is not None:
+                    kl_e = self._mean_over_ranks(kl_e)                     # every rank compares the same number: all stop in the same epoch
+                kls.append(kl_e)
+                if target_kl is not None and kl_e > float(target_kl) and e + 1 < int(epochs):
+                    early_stop = True
+                    break
+            if permuted:
+                stats["mean_reward"] = mean_reward                         # (the steps saw the zero rewards of their [1, m] views)
                 if fused:
-                    loss = self._upd["loss"].cpu()
-                    stats["clip_fraction"], stats["approx_kl"] = float(loss[3]), float(loss[4])
-                else:
-                    stats["clip_fraction"], stats["approx_kl"] = self._ppo["n_clipped"] / adv.numel(), self._ppo["kl_sum"] / adv.numel()
-            stats["epochs"] = int(epochs)
+                    stats["forward_reused"] = False
+            stats.update(epochs=len(kls), minibatches=k, early_stop=early_stop, approx_kl_epochs=kls)
         finally:
             self._ppo = None
         return stats

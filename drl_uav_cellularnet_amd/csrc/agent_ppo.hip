@@ -4,6 +4,8 @@
 //   logp_factored_f32         log pi(a | s) = sum_b log(p_b[d_b] + 1e-5) of the joint action of every row: the OLD log-probabilities of a batch
 //   ppo_loss_grad_factored    the clipped surrogate with the entropy bonus and the critic's squared error: d a_loss / d logits in place, dv, the
 //                             bias gradient (column sums) and five loss sums
+//   ppo_shuffle_rows          the five per-row arrays of a batch copied in the order of a row list: one launch per epoch makes every minibatch
+//                             a contiguous slice; a plain copy, for either head
 // The logits' layout, the per-head softmax, the digit decode with its clamp, the per-head tail, the workgroup epilogue and the second launch are
 // agent_loss_factored.h's, shared with agent_factored.hip: ONE LANE PER (row, head), a workgroup of 256 lanes holds RPB = 256 / n_heads whole
 // rows, lane t = (row t / n_heads, head t % n_heads).  What is PPO's is the outer loop, because the probability ratio
@@ -148,6 +150,52 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_grad_factored_kernel(float *_
     factored_epilogue<kSums>(csum, {la, lc, sdv, nclip, skl}, B, A, rpb, col_partial, loss_partial);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// ppo_shuffle_rows.  out[i] = src[clamp(rows[i])] for idx (ppr pieces of sizeof(V) bytes per row: V = 16 bytes where k is even and both
+// bases are 16-byte aligned, else 8) and for the four scalars of the row, which ride as slots ppr .. ppr + 3 behind the pieces.  A row's
+// ppr + 4 slots go to a group of L = min(64, ppr + 4) lanes, 64 / L rows to a wavefront (k = 44: 22 + 4 slots, two rows; k = 216: 112 slots,
+// two passes of the one row's 64 lanes).  Wavefronts grid-stride over the groups of rows; lanes past the last group of a wavefront, and past
+// the last row, move nothing.  The row number is clamped before it is used.  No LDS, no atomics, nothing but loads and stores.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kShuffleBlocks = 2048;                          // x 4 wavefronts: 32 resident wavefronts on each of the 256 CUs
+
+template <typename V>
+__global__ __launch_bounds__(kBlock) void ppo_shuffle_rows_kernel(const long long *__restrict__ rows, long long n_rows, long long n_src,
+                                                                  const V *__restrict__ idx_src, int ppr, int L, int rpw,
+                                                                  const long long *__restrict__ act_src, const uint32_t *__restrict__ adv_src,
+                                                                  const uint32_t *__restrict__ ret_src, const uint32_t *__restrict__ logp_src,
+                                                                  V *__restrict__ idx_out, long long *__restrict__ act_out,
+                                                                  uint32_t *__restrict__ adv_out, uint32_t *__restrict__ ret_out,
+                                                                  uint32_t *__restrict__ logp_out) {
+    const int lane = threadIdx.x & 63;
+    const int lr = lane / L, g = lane - lr * L;               // the row of the wavefront's group this lane serves, and its first slot
+    const long long n_waves = (long long)gridDim.x * (kBlock / 64);
+    const long long n_groups = (n_rows + rpw - 1) / rpw;
+    const int slots = ppr + 4;
+    for (long long w = (long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); w < n_groups; w += n_waves) {
+        const long long i = w * rpw + lr;
+        if (lr >= rpw || i >= n_rows) continue;               // (no barrier in this kernel)
+        long long r = rows[i];
+        r = r < 0 ? 0 : (r > n_src - 1 ? n_src - 1 : r);
+        const V *src = idx_src + r * ppr;
+        V *dst = idx_out + i * ppr;
+        for (int s = g; s < slots; s += L) {
+            const int q = s - ppr;
+            if (q < 0) dst[s] = src[s];
+            else if (q == 0) act_out[i] = act_src[r];
+            else if (q == 1) adv_out[i] = adv_src[r];
+            else if (q == 2) ret_out[i] = ret_src[r];
+            else logp_out[i] = logp_src[r];
+        }
+    }
+}
+
+// [a, a + na) and [b, b + nb) share a byte
+bool overlap(const void *a, unsigned long long na, const void *b, unsigned long long nb) {
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return na != 0 && nb != 0 && pa < pb + nb && pb < pa + na;
+}
+
 bool unit(float x) { return x >= 0.f && x <= 1.f; }          // false for a NaN
 
 }  // namespace
@@ -209,4 +257,38 @@ extern "C" int uavagent_ppo_loss_grad_factored(float *logits_inout, int64_t ld_l
     hipLaunchKernelGGL(reduce_factored_kernel<kSums>, dim3((C + 63) / 64 + 1), dim3(kBlock), 0, s, colp, lossp, kFBlocks, C, 1.0 / (double)m_rows,
                        dbias_out, loss_out, 0.0);
     return launch_ok(what);
+}
+
+extern "C" int uavagent_ppo_shuffle_rows(const int64_t *rows, int64_t n_rows, int64_t n_src_rows, const int64_t *idx_src, int32_t k,
+                                         const int64_t *act_src, const float *adv_src, const float *ret_src, const float *logp_src,
+                                         int64_t *idx_out, int64_t *act_out, float *adv_out, float *ret_out, float *logp_out, void *stream) {
+    if (k < 1 || k > 256) return fail(UAVAGENT_E_INVALID, "ppo_shuffle_rows: need 1 <= k <= 256");
+    if (n_rows < 0 || n_src_rows < 0) return fail(UAVAGENT_E_INVALID, "ppo_shuffle_rows: negative row count");
+    if (n_rows > (int64_t)1 << 40 || n_src_rows > (int64_t)1 << 40) return fail(UAVAGENT_E_INVALID, "ppo_shuffle_rows: row count too large");
+    if (n_rows == 0) return UAVAGENT_OK;
+    if (n_src_rows == 0) return fail(UAVAGENT_E_INVALID, "ppo_shuffle_rows: rows asked of an empty source");
+    if (!rows || !idx_src || !act_src || !adv_src || !ret_src || !logp_src || !idx_out || !act_out || !adv_out || !ret_out || !logp_out)
+        return fail(UAVAGENT_E_INVALID, "ppo_shuffle_rows: null pointer");
+    const unsigned long long no = (unsigned long long)n_rows, ns = (unsigned long long)n_src_rows;
+    if (overlap(idx_out, no * k * 8, idx_src, ns * k * 8) || overlap(act_out, no * 8, act_src, ns * 8) || overlap(adv_out, no * 4, adv_src, ns * 4) ||
+        overlap(ret_out, no * 4, ret_src, ns * 4) || overlap(logp_out, no * 4, logp_src, ns * 4))
+        return fail(UAVAGENT_E_INVALID, "ppo_shuffle_rows: an output overlaps its source");
+    const bool wide = k % 2 == 0 && aligned16(idx_src) && aligned16(idx_out);
+    const int ppr = wide ? k / 2 : k;
+    const int L = ppr + 4 < 64 ? ppr + 4 : 64, rpw = 64 / L;
+    const long long n_groups = ((long long)n_rows + rpw - 1) / rpw, need = (n_groups + kBlock / 64 - 1) / (kBlock / 64);
+    const dim3 grid((unsigned)(need < kShuffleBlocks ? need : kShuffleBlocks));
+    const long long *rw = reinterpret_cast<const long long *>(rows), *as = reinterpret_cast<const long long *>(act_src);
+    long long *ao = reinterpret_cast<long long *>(act_out);
+    auto u = [](const float *p) { return reinterpret_cast<const uint32_t *>(p); };
+    auto uo = [](float *p) { return reinterpret_cast<uint32_t *>(p); };
+    if (wide)
+        hipLaunchKernelGGL(ppo_shuffle_rows_kernel<uint4>, grid, dim3(kBlock), 0, (hipStream_t)stream, rw, (long long)n_rows, (long long)n_src_rows,
+                           reinterpret_cast<const uint4 *>(idx_src), ppr, L, rpw, as, u(adv_src), u(ret_src), u(logp_src),
+                           reinterpret_cast<uint4 *>(idx_out), ao, uo(adv_out), uo(ret_out), uo(logp_out));
+    else
+        hipLaunchKernelGGL(ppo_shuffle_rows_kernel<unsigned long long>, grid, dim3(kBlock), 0, (hipStream_t)stream, rw, (long long)n_rows,
+                           (long long)n_src_rows, reinterpret_cast<const unsigned long long *>(idx_src), ppr, L, rpw, as, u(adv_src), u(ret_src),
+                           u(logp_src), reinterpret_cast<unsigned long long *>(idx_out), ao, uo(adv_out), uo(ret_out), uo(logp_out));
+    return launch_ok("ppo_shuffle_rows");
 }

@@ -372,6 +372,21 @@ int uavagent_ppo_loss_grad(float *logits_inout, int64_t ld_logits, const float *
                            const int64_t *actions, int64_t m_rows, int32_t n_actions, float beta, float clip, float *dv_out,
                            float *dbias_out, double *loss_out /* [5] */, void *workspace, void *stream);
 
+/* ---- PPO minibatches, for either head (csrc/agent_ppo.hip; additive to ABI 5, the number stays) ---- */
+
+/* out[i] = src[clamp(rows[i], 0, n_src_rows-1)] for the five per-row arrays of a PPO batch, in one launch:
+ * idx int64 [.., k] (1 <= k <= 256), actions int64, adv / ret / logp_old f32.  n_rows may be < n_src_rows; rows may repeat.
+ * A row number is clamped, never used unchecked as an index.  Plain copies: the outputs hold the sources' bits.
+ * idx moves in 16-byte pieces when k is even and idx_src and idx_out are 16-byte aligned, in 8-byte pieces otherwise; a row's pieces and
+ * its four scalars share a group of min(64, pieces + 4) lanes, and a wavefront holds as many whole groups as fit.
+ * No LDS, no atomics, fixed grid.  Refused before any HIP call: k outside [1, 256], negative counts,
+ * n_src_rows == 0 with n_rows > 0, a null pointer with n_rows > 0, an output that overlaps its source.  n_rows == 0: no launch. */
+int uavagent_ppo_shuffle_rows(const int64_t *rows, int64_t n_rows, int64_t n_src_rows,
+                              const int64_t *idx_src, int32_t k, const int64_t *act_src,
+                              const float *adv_src, const float *ret_src, const float *logp_src,
+                              int64_t *idx_out, int64_t *act_out, float *adv_out, float *ret_out, float *logp_out,
+                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,15 @@ Writes profiles/ppo_bench.json and prints it as one line.
   rollouts, at 8192 envs x 4 UAV x 40 UE, G = 100: ppo_rollout(epochs=1) and ppo_rollout(epochs=4) against train_rollout.
 Writes profiles/ppo_joint_bench.json.
 
-  python tools/bench_ppo.py [--joint] [--rollout 50] [--repeats 7] [--inner 20]"""
+--minibatches K: PPO minibatches instead, both heads in one process; the modes above and their files are untouched:
+  (a) uavagent_ppo_shuffle_rows against the five index_select calls that make the same tensors, at M = 409 600, k = 44 and M = 51 200,
+      k = 216, with the bytes per second it reaches of 2 M (8 k + 20) bytes;
+  (b) ppo_rollout(epochs=4, minibatches=K) beside ppo_rollout(epochs=4), at 8192 x 4 x 40 (joint head) and 1024 x 16 x 200 (factored).
+  (c) --default-runs OWN PARENT OWN PARENT ...: result files of the modes above written by this tree and by the parent commit's tree, taken
+      in turns; their ppo_rollout(epochs=4) timings (the default call, unchanged by minibatches) go into the file side by side.
+Writes profiles/ppo_minibatch_bench.json.
+
+  python tools/bench_ppo.py [--joint | --minibatches 4] [--rollout 50] [--repeats 7] [--inner 20]"""
 import argparse
 import json
 import os
@@ -25,6 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 KERNEL_SHAPES = [(51200, 16), (409600, 4)]
+SHUFFLE_SHAPES = [(409600, 44), (51200, 216)]      # rows of a rollout, observation nodes: 8192 x 50 of 4 UAV + 40 UE, 1024 x 50 of 16 + 200
 ROLLOUT_SHAPE = (1024, 16, 200)
 N_ACT = 5
 JOINT_KERNEL_SHAPE = (409600, 625, 640)      # rows, actions, row stride of the logits
@@ -46,10 +55,17 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--inner", type=int, default=20)
     ap.add_argument("--joint", action="store_true", help="the joint 625-way head (A2CRunner) instead of the factored one")
+    ap.add_argument("--minibatches", type=int, default=0, help="K > 1: the minibatch bench (shuffle kernel; ppo_rollout with and without K "
+                    "minibatches) instead; writes profiles/ppo_minibatch_bench.json")
+    ap.add_argument("--default-runs", nargs="*", default=[], help="with --minibatches: result files of the other modes, this tree's and the "
+                    "parent commit's in turns (own parent own parent ...)")
     ap.add_argument("--out", default=None, help="default: profiles/ppo_bench.json, with --joint profiles/ppo_joint_bench.json")
     a = ap.parse_args()
+    if a.minibatches and (a.minibatches < 2 or a.joint or len(a.default_runs) % 2):
+        ap.error("--minibatches needs K >= 2, excludes --joint, and takes --default-runs in pairs")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "ppo_joint_bench.json" if a.joint else "ppo_bench.json")
+        a.out = os.path.join(ROOT, "profiles", "ppo_minibatch_bench.json" if a.minibatches else
+                             ("ppo_joint_bench.json" if a.joint else "ppo_bench.json"))
     import torch
 
     from drl_uav_cellularnet_amd import BatchedMobiEnv
@@ -102,6 +118,58 @@ def main():
             f.write(line + "\n")
         for r in runners.values():
             r.env.close()
+
+    if a.minibatches:
+        K = a.minibatches
+        result = {"bench": "ppo_minibatch", "minibatches": K, "rollout": T, "repeats": a.repeats, "inner": a.inner,
+                  "device": torch.cuda.get_device_name(0), "shuffle_us": [], "rollouts_ms": [], "default_against_parent": []}
+        g = torch.Generator().manual_seed(23)
+        for M, k in SHUFFLE_SHAPES:
+            idx = torch.randint(0, 50000, (M, k), generator=g).to(dev)
+            act = torch.randint(0, 625, (M,), generator=g).to(dev)
+            adv, ret, logp = (torch.randn(M, generator=g).to(dev) for _ in range(3))
+            rows = torch.randperm(M, generator=g).to(dev)
+            src = (idx, act, adv, ret, logp)
+            out = tuple(torch.empty_like(t) for t in src)
+            forms = {"shuffle": lambda: median_us(lambda: A.ppo_shuffle_rows(rows, *src, out=out)),
+                     "index_select": lambda: median_us(lambda: [torch.index_select(t, 0, rows, out=o) for t, o in zip(src, out)])}
+            raw = {f: [] for f in forms}
+            for rep in range(a.repeats + 1):                                # turn 0 is untimed: first launches
+                for f, fn in forms.items():
+                    t = fn()
+                    if rep > 0:
+                        raw[f].append(t)
+            nbytes = 2 * M * (8 * k + 20)
+            result["shuffle_us"].append({"rows": M, "k": k, "bytes_moved": nbytes,
+                                         "shuffle_rows_over_index_select": pair(raw["shuffle"], raw["index_select"]),
+                                         "shuffle_rows_bytes_per_second": spread([nbytes / (t * 1e-6) for t in raw["shuffle"]])})
+            del idx, src, out
+        for name, (N, B, U), cls in (("joint", JOINT_ROLLOUT_SHAPE, A2CRunner), ("factored", ROLLOUT_SHAPE, FactoredA2CRunner)):
+            runners = {f: cls(BatchedMobiEnv(N, nBS=B, nUE=U, grid_n=100, device=dev), rollout=T) for f in ("full", "mini")}
+            forms = {"full": lambda: timed(lambda: runners["full"].ppo_rollout(epochs=4)),
+                     "mini": lambda: timed(lambda: runners["mini"].ppo_rollout(epochs=4, minibatches=K))}
+            raw, last = {f: [] for f in forms}, {}
+            for rep in range(a.repeats + 1):                                # turn 0 is untimed: graph capture, allocations, first launches
+                for f, fn in forms.items():
+                    t, last[f] = fn()
+                    if rep > 0:
+                        raw[f].append(t)
+            result["rollouts_ms"].append({"head": name, "envs": N, "n_bs": B, "n_ue": U, "grid": 100, "rows": N * T, "epochs": 4,
+                                          "minibatches_over_full_batch": pair(raw["mini"], raw["full"]),
+                                          "last_stats": {f: {s_: last[f].get(s_) for s_ in ("a_loss", "c_loss", "clip_fraction", "approx_kl",
+                                                                                           "approx_kl_epochs", "mean_reward")} for f in last}})
+            for r in runners.values():
+                r.env.close()
+            del runners
+        for own, parent in zip(a.default_runs[0::2], a.default_runs[1::2]):
+            both = {}
+            for side, path in (("own", own), ("parent", parent)):
+                with open(path) as f:
+                    d = json.loads(f.readline())
+                both[side] = {"bench": d["bench"], "ppo_rollout_epochs_4_ms": d["rollouts_ms"]["ppo_epochs_4_over_train_rollout"]["new"]}
+            result["default_against_parent"].append(both)
+        finish(result, {})
+        return
 
     if a.joint:
         M, NA, LD = JOINT_KERNEL_SHAPE

@@ -12,6 +12,8 @@ actor parameters (Global_A_PARA: here a named .npz, agent.save_actor_npz -- load
   python tools/train_a2c.py --net mlp-factored --n-bs 16 --n-ue 200 --workers 1024 --algo ppo --ppo-epochs 4 --ppo-clip 0.2 --gae-lambda 0.95
                                                    # PPO in place of A2C: GAE advantages, 4 clipped-surrogate epochs per rollout (ppo_rollout)
   python tools/train_a2c.py --net mlp --workers 8192 --algo ppo --ppo-epochs 4  # PPO for the joint 625-way head (A2CRunner.ppo_rollout)
+  python tools/train_a2c.py --net mlp --workers 8192 --algo ppo --ppo-epochs 4 --ppo-minibatches 4 [--ppo-target-kl 0.02]
+                                                   # 4 shuffled minibatch steps per epoch; stop a rollout's epochs once the policy has drifted
   python -m torch.distributed.run --nproc-per-node 8 tools/train_a2c.py ...     # one process per GPU, gradients all-reduced (RCCL)"""
 import argparse
 import json
@@ -87,14 +89,29 @@ def algo_refusal(checkpoint, algo):
 PPO_NETS = ("mlp", "mlp-factored")      # the runners with ppo_rollout (the CNN runners raise NotImplementedError)
 
 
-def ppo_flags_error(net, algo, ppo_epochs, ppo_clip, gae_lambda):
-    """What is wrong with --algo / --ppo-epochs / --ppo-clip / --gae-lambda for this --net, or None."""
-    ppo_flags = algo != "a2c" or ppo_epochs != 4 or ppo_clip != 0.2 or gae_lambda != 0.95
+def ppo_flags_error(net, algo, ppo_epochs, ppo_clip, gae_lambda, ppo_minibatches=1, ppo_target_kl=None):
+    """What is wrong with --algo / --ppo-epochs / --ppo-clip / --gae-lambda / --ppo-minibatches / --ppo-target-kl for this --net, or None."""
+    ppo_flags = algo != "a2c" or ppo_epochs != 4 or ppo_clip != 0.2 or gae_lambda != 0.95 or ppo_minibatches != 1 or ppo_target_kl is not None
     if ppo_flags and net not in PPO_NETS:
-        return "--algo / --ppo-epochs / --ppo-clip / --gae-lambda are for --net mlp and --net mlp-factored"
+        return "--algo / --ppo-epochs / --ppo-clip / --gae-lambda / --ppo-minibatches / --ppo-target-kl are for --net mlp and --net mlp-factored"
     if ppo_epochs < 1 or not 0.0 < ppo_clip < 1.0 or not 0.0 <= gae_lambda <= 1.0:
         return "--ppo-epochs must be >= 1, --ppo-clip in (0, 1) and --gae-lambda in [0, 1]"
+    if ppo_minibatches < 1 or (ppo_target_kl is not None and not (math.isfinite(ppo_target_kl) and ppo_target_kl > 0.0)):
+        return "--ppo-minibatches must be >= 1 and --ppo-target-kl finite and > 0"
     return None
+
+
+def ppo_settings(a):
+    """The PPO flags as the checkpoint keeps them (``a``: the parsed arguments)."""
+    return {"algo": a.algo, "ppo_epochs": a.ppo_epochs, "ppo_clip": a.ppo_clip, "gae_lambda": a.gae_lambda,
+            "ppo_minibatches": a.ppo_minibatches, "ppo_target_kl": a.ppo_target_kl}
+
+
+def ppo_minibatch_kwargs(settings):
+    """ppo_rollout's keywords beyond epochs / clip / lam from ppo_settings' dict (or a checkpoint from before the two flags): none at the
+    defaults, so that the default run makes the call it always made."""
+    k, target = int(settings.get("ppo_minibatches", 1)), settings.get("ppo_target_kl")
+    return {} if k == 1 and target is None else {"minibatches": k, "target_kl": target}
 
 
 def main():
@@ -132,6 +149,10 @@ def main():
     ap.add_argument("--ppo-epochs", type=int, default=4, help="--algo ppo: full-batch epochs per rollout")
     ap.add_argument("--ppo-clip", type=float, default=0.2, help="--algo ppo: the probability ratio is clipped to 1 +- this")
     ap.add_argument("--gae-lambda", type=float, default=0.95, help="--algo ppo: lambda of the advantage estimate")
+    ap.add_argument("--ppo-minibatches", type=int, default=1, help="--algo ppo: optimiser steps per epoch, each on 1 / K of the rollout's rows "
+                    "in a fresh random order (K must divide rollout x workers; 1 = full-batch epochs)")
+    ap.add_argument("--ppo-target-kl", type=float, default=None, help="--algo ppo: skip a rollout's remaining epochs once an epoch's mean "
+                    "logp_old - logp exceeds this (default: never)")
     ap.add_argument("--optimizer", choices=("rmsprop", "adam"), default="rmsprop", help="the step of both networks: the reference's TF1 RMSProp "
                     "or Adam (an extension; DESIGN.md section 24)")
     ap.add_argument("--max-grad-norm", type=float, default=None, help="clip each network's gradient to this global norm (default: no clip)")
@@ -156,9 +177,12 @@ def main():
         ap.error("--imitate-episodes must be >= 0 and --imitate-mix in [0, 1]")
     if a.imitate_tau is not None and (a.teacher != "coordinate" or not a.imitate_tau > 0):
         ap.error("--imitate-tau must be > 0 and needs --teacher coordinate")
-    msg = ppo_flags_error(a.net, a.algo, a.ppo_epochs, a.ppo_clip, a.gae_lambda)
+    msg = ppo_flags_error(a.net, a.algo, a.ppo_epochs, a.ppo_clip, a.gae_lambda, a.ppo_minibatches, a.ppo_target_kl)
     if msg:
         ap.error(msg)
+    if (a.rollout * a.workers) % a.ppo_minibatches:
+        ap.error("--ppo-minibatches %d does not divide the %d rows of a rollout (--rollout x --workers)" % (a.ppo_minibatches, a.rollout * a.workers))
+    mb = ppo_minibatch_kwargs(ppo_settings(a))
     if a.max_grad_norm is not None and not a.max_grad_norm > 0:
         ap.error("--max-grad-norm must be > 0")
     if not (0.0 <= a.adam_beta1 < 1.0 and 0.0 <= a.adam_beta2 < 1.0 and a.adam_eps > 0):
@@ -216,14 +240,19 @@ def main():
         check_ranks_agree(torch, world, dev, first_ep, runner)
     for ep in range(first_ep, a.episodes):
         imitating = ep < a.imitate_episodes                                # a function of the episode counter alone
-        reward_sum, agree, clip_frac, kl = 0.0, [], [], []
+        reward_sum, agree, clip_frac, kl, epochs_run, early_stops = 0.0, [], [], [], [], 0
         norms, n_clipped, n_skipped = [0.0, 0.0], [0, 0], 0                # --max-grad-norm: the episode's gradient norms before clipping
         for r in range(per_episode):
             if imitating:
                 st = runner.imitate_rollout(teacher=a.teacher, mix=a.imitate_mix, tau=a.imitate_tau, shaped_teacher=a.teacher_shaped)
                 agree.append(st["agreement"])
             elif a.algo == "ppo":
-                st = runner.ppo_rollout(epochs=a.ppo_epochs, clip=a.ppo_clip, lam=a.gae_lambda)
+                if mb:
+                    st = runner.ppo_rollout(epochs=a.ppo_epochs, clip=a.ppo_clip, lam=a.gae_lambda, **mb)
+                else:
+                    st = runner.ppo_rollout(epochs=a.ppo_epochs, clip=a.ppo_clip, lam=a.gae_lambda)
+                epochs_run.append(st["epochs"])
+                early_stops += int(st["early_stop"])
                 clip_frac.append(st["clip_fraction"])
                 kl.append(st["approx_kl"])
             else:
@@ -249,6 +278,9 @@ def main():
                     line.update({"clip_fraction": sum(clip_frac) / len(clip_frac), "approx_kl": sum(kl) / len(kl)})
             elif a.algo == "ppo":
                 line.update({"phase": "ppo", "clip_fraction": sum(clip_frac) / len(clip_frac), "approx_kl": sum(kl) / len(kl)})
+            if a.algo == "ppo" and not imitating:      # epochs_run: averaged over the episode's rollouts; early_stops: rollouts cut short by --ppo-target-kl
+                line.update({"ppo_minibatches": a.ppo_minibatches, "ppo_target_kl": a.ppo_target_kl,
+                             "epochs_run": sum(epochs_run) / len(epochs_run), "early_stops": early_stops})
             if a.max_grad_norm is not None:
                 line.update({"grad_norm_a": st["grad_norm_a"], "grad_norm_c": st["grad_norm_c"], "max_grad_norm_a": norms[0],
                              "max_grad_norm_c": norms[1], "clipped_a": n_clipped[0] / per_episode, "clipped_c": n_clipped[1] / per_episode,
@@ -258,6 +290,7 @@ def main():
             save_checkpoint(torch, world, ckpt, {"runner": runner.state_dict(), "reward": None if reward is None else reward.as_dict(),
                                                      "teacher_shaped": bool(a.teacher_shaped),
                                                      "algo": a.algo, "ppo_epochs": a.ppo_epochs, "ppo_clip": a.ppo_clip, "gae_lambda": a.gae_lambda,
+                                                     "ppo_minibatches": a.ppo_minibatches, "ppo_target_kl": a.ppo_target_kl,
                                                      "episode": ep, "returns": returns})
     if rank == 0:
         os.makedirs(a.out, exist_ok=True)
