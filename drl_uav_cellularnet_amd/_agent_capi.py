@@ -25,7 +25,7 @@ EXPORTS = ("uavagent_abi_version", "uavagent_last_error", "uavagent_sparse_rows_
            "uavagent_soft_targets_f32", "uavagent_gae_f32", "uavagent_logp_factored_f32", "uavagent_ppo_loss_grad_factored_workspace_bytes",
            "uavagent_ppo_loss_grad_factored", "uavagent_logp_f32", "uavagent_ppo_loss_grad_workspace_bytes", "uavagent_ppo_loss_grad",
            "uavagent_sumsq_workspace_bytes", "uavagent_sumsq_f32", "uavagent_adam_f32", "uavagent_rmsprop_tf1_clipped",
-           "uavagent_ppo_shuffle_rows")
+           "uavagent_ppo_shuffle_rows", "uavagent_nstep_returns_done_f32", "uavagent_gae_done_f32", "uavagent_episode_step_f32")
 ABI_VERSION = 5
 
 _lib = None
@@ -144,6 +144,9 @@ def load():
         "uavagent_sumsq_f32": [_P, _I64, _P, _P, _P],
         "uavagent_adam_f32": [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _I64, _F, _P, _F, _P],
         "uavagent_rmsprop_tf1_clipped": [_P, _P, _P, _I64, _F, _F, _F, _F, _P, _F, _P],
+        "uavagent_nstep_returns_done_f32": [_P, _P, _P, _I64, _I32, _F, _P, _P],
+        "uavagent_gae_done_f32": [_P, _P, _P, _P, _I64, _I32, _F, _F, _P, _P, _P],
+        "uavagent_episode_step_f32": [_P, _P, _P, _P, _P, _P, _P, _I64, _P],
         "uavagent_gate_prepare": [],
     }
     for wide, narrow in (("uavagent_first_layer_wide_f32", "uavagent_first_layer_f32"),
@@ -680,6 +683,76 @@ def gae(rewards, values, bootstrap, gamma, lam, adv_out=None, ret_out=None):
                                      _stream(rewards.device))
     _check(rc, "uavagent_gae_f32")
     return adv_out, ret_out
+
+
+def _u8c(t, what):
+    if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+        raise UavAgentError("%s must be a contiguous uint8 CUDA tensor" % what)
+
+
+def nstep_returns_done(rewards, done, bootstrap, gamma, out=None):
+    """nstep_returns with the return cut where ``done`` (uint8 [T, N]) is set (uavagent_nstep_returns_done_f32; agent.nstep_returns_done
+    states it)."""
+    _f32c(rewards, "rewards")
+    _f32c(bootstrap, "bootstrap")
+    _u8c(done, "done")
+    T, N = rewards.shape
+    if tuple(done.shape) != (T, N) or bootstrap.numel() != N:
+        raise UavAgentError("nstep_returns_done: done must be [T, N] like rewards and bootstrap [N]")
+    out = torch.empty_like(rewards) if out is None else out
+    _f32c(out, "out")
+    if out.numel() != T * N:
+        raise UavAgentError("nstep_returns_done: out must hold [T, N] floats")
+    _same_device("nstep_returns_done", rewards, done, bootstrap, out)
+    with torch.cuda.device(rewards.device):
+        rc = load().uavagent_nstep_returns_done_f32(_ptr(rewards), _ptr(done), _ptr(bootstrap), N, T, float(gamma), _ptr(out),
+                                                    _stream(rewards.device))
+    _check(rc, "uavagent_nstep_returns_done_f32")
+    return out
+
+
+def gae_done(rewards, values, done, bootstrap, gamma, lam, adv_out=None, ret_out=None):
+    """gae with the next value and the carried advantage cut where ``done`` (uint8 [T, N]) is set (uavagent_gae_done_f32;
+    agent.gae_done_reference states it).  Returns (adv, ret), float32 [T, N]."""
+    _f32c(rewards, "rewards")
+    _f32c(values, "values")
+    _f32c(bootstrap, "bootstrap")
+    _u8c(done, "done")
+    T, N = rewards.shape
+    if tuple(values.shape) != (T, N) or tuple(done.shape) != (T, N) or bootstrap.numel() != N:
+        raise UavAgentError("gae_done: values and done must be [T, N] like rewards and bootstrap [N]")
+    adv_out = torch.empty_like(rewards) if adv_out is None else adv_out
+    ret_out = torch.empty_like(rewards) if ret_out is None else ret_out
+    for o, what in ((adv_out, "adv_out"), (ret_out, "ret_out")):
+        _f32c(o, what)
+        if o.numel() != T * N:
+            raise UavAgentError("gae_done: %s must hold [T, N] floats" % what)
+    _same_device("gae_done", rewards, values, done, bootstrap, adv_out, ret_out)
+    with torch.cuda.device(rewards.device):
+        rc = load().uavagent_gae_done_f32(_ptr(rewards), _ptr(values), _ptr(done), _ptr(bootstrap), N, T, float(gamma), float(lam),
+                                          _ptr(adv_out), _ptr(ret_out), _stream(rewards.device))
+    _check(rc, "uavagent_gae_done_f32")
+    return adv_out, ret_out
+
+
+def episode_step(reward, done, ep_r, done_row_out, mask_out, fin_sum, fin_cnt):
+    """One step of episode bookkeeping, in place (uavagent_episode_step_f32; agent.episode_step_reference states it): reward float32, done
+    uint8, ep_r float32, done_row_out / mask_out uint8, fin_sum float64, fin_cnt int32, all contiguous [N] on one device."""
+    N = reward.numel()
+    _f32c(reward, "reward")
+    _f32c(ep_r, "ep_r")
+    for t, what in ((done, "done"), (done_row_out, "done_row_out"), (mask_out, "mask_out")):
+        _u8c(t, what)
+    for t, dt, what in ((fin_sum, torch.float64, "fin_sum"), (fin_cnt, torch.int32, "fin_cnt")):
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise UavAgentError("episode_step: %s must be a contiguous %s CUDA tensor" % (what, dt))
+    if any(t.numel() != N for t in (done, ep_r, done_row_out, mask_out, fin_sum, fin_cnt)):
+        raise UavAgentError("episode_step: every operand must hold n_envs elements")
+    _same_device("episode_step", reward, done, ep_r, done_row_out, mask_out, fin_sum, fin_cnt)
+    with torch.cuda.device(reward.device):
+        rc = load().uavagent_episode_step_f32(_ptr(reward), _ptr(done), _ptr(ep_r), _ptr(done_row_out), _ptr(mask_out), _ptr(fin_sum),
+                                              _ptr(fin_cnt), N, _stream(reward.device))
+    _check(rc, "uavagent_episode_step_f32")
 
 
 def _factored_rows(what, logits, actions, n_heads, n_act):

@@ -284,6 +284,50 @@ def nstep_returns(rewards, bootstrap, gamma=GAMMA):
     return out
 
 
+# ---- episodes that end inside a rollout: done [T, N], non-zero where step t ended env n's episode ---------------------
+def nstep_returns_done(rewards, done, bootstrap, gamma=GAMMA):
+    """nstep_returns with the running return cut at a done step, as uavagent_nstep_returns_done_f32 computes it: the cut is a select of 0
+    (``r + gamma * 0``, not ``r``), so a column's segments are nstep_returns of each segment with bootstrap 0, bit for bit."""
+    T = rewards.shape[0]
+    out = torch.empty_like(rewards)
+    run = bootstrap.to(rewards.dtype)
+    zero = torch.zeros_like(rewards[0])
+    for t in range(T - 1, -1, -1):
+        run = rewards[t] + gamma * torch.where(done[t] != 0, zero, run)
+        out[t] = run
+    return out
+
+
+def gae_done_reference(rewards, values, done, bootstrap, gamma, lam):
+    """gae_reference with the next value and the carried advantage cut at a done step, as uavagent_gae_done_f32 computes it: values[t + 1]
+    is then the value of the NEXT episode's first state and does not enter the episode that ended.  -> (adv, ret).
+    The constant gamma * lam is formed in the dtype of rewards, as the kernels form it in float32 (gae_reference forms it in float64 and
+    rounds then: in float32 the two round apart for some pairs, 0.9 * 0.95 among them, and alike whenever lam is a power of two)."""
+    T = rewards.shape[0]
+    values = values.to(rewards.dtype)
+    adv, run, next_v = torch.empty_like(rewards), torch.zeros_like(rewards[0]), bootstrap.to(rewards.dtype)
+    zero = torch.zeros_like(rewards[0])
+    gl = float(torch.tensor(gamma, dtype=rewards.dtype) * torch.tensor(lam, dtype=rewards.dtype))
+    for t in range(T - 1, -1, -1):
+        d = done[t] != 0
+        run = (rewards[t] + gamma * torch.where(d, zero, next_v)) - values[t] + gl * torch.where(d, zero, run)
+        adv[t] = run
+        next_v = values[t]
+    return adv, adv + values
+
+
+def episode_step_reference(reward, done, ep_r, done_row_out, mask_out, fin_sum, fin_cnt):
+    """One step of a runner's episode bookkeeping, in place, as uavagent_episode_step_f32 does it: ep_r += reward; the step's done row and
+    the mask of the reset that follows := done; where done, the episode's return goes to the per-env totals and ep_r starts again at 0."""
+    d = done != 0
+    r = ep_r + reward
+    done_row_out.copy_(d)
+    mask_out.copy_(d)
+    fin_sum.copy_(torch.where(d, fin_sum + r.double(), fin_sum))
+    fin_cnt.copy_(torch.where(d, fin_cnt + 1, fin_cnt))
+    ep_r.copy_(torch.where(d, torch.zeros_like(r), r))
+
+
 def allreduce_mean_grads(params):
     """One flat all-reduce of every gradient (sum / world size).  With one process per GPU and backend 'nccl' this is
     RCCL over xGMI; a no-op without an initialised process group.  Returns the number of float32 elements reduced."""
@@ -483,7 +527,9 @@ class A2CRunner:
         # True = when each half still fills the chip (>= 4096 envs), "force" = whenever the batch can be cut (tests).
         self._halves = None
         self._pipe_stream = None
-        if pipeline_halves and self.dev.type == "cuda" and self.fused_head and self.fused_obs:
+        # (not with a reward spec that terminates: the masked reset behind every step is one launch over the whole batch, and the halves'
+        #  step_range calls would need half-masks; the plain per-step loop serves it)
+        if pipeline_halves and self.dev.type == "cuda" and self.fused_head and self.fused_obs and self.done_buf is None:
             # the cut lies on a multiple of the head's 16-row tiles (half a batch runs on 16-row workgroups: 8192 envs = 2 x 256 tiles = one
             # workgroup per CU and half)
             mid = min((env.n_envs // 2 + 15) // 16 * 16, env.n_envs)
@@ -614,6 +660,17 @@ class A2CRunner:
         self.ep_r = torch.zeros(N, device=self.dev)
         self.running_r = None                                          # GLOBAL_RUNNING_R EMA, :169-172
         self.last_episode_return = None
+        # A reward spec that terminates (with_collision(.., terminate=True)): envs end and restart INSIDE the rollout (_after_step), each at
+        # its own step.  done_buf[t] = the done row of step t; the update's targets are cut there (nstep_returns_done, gae_done_reference).
+        # _reset_mask is the mask the per-step env.reset reads (persistent: a captured graph holds its address); _fin_sum / _fin_cnt are the
+        # per-env totals of the episodes that ended since _end_rollout last read them.  Without such a spec none of this exists.
+        self.done_buf = None
+        self.episodes_ended = None
+        if getattr(self.reward_spec, "terminate", False):
+            self.done_buf = torch.zeros((T, N), dtype=torch.uint8, device=self.dev)
+            self._reset_mask = torch.zeros(N, dtype=torch.uint8, device=self.dev)
+            self._fin_sum = torch.zeros(N, dtype=torch.float64, device=self.dev)
+            self._fin_cnt = torch.zeros(N, dtype=torch.int32, device=self.dev)
         self.stats = {}
         self._tuning_frozen = False
         self._fwd_valid = False
@@ -725,8 +782,38 @@ class A2CRunner:
             else:
                 self.act_buf[t] = self._draw_reference(t)
             env.step(self.act_buf[t], reward_out=self.rew_buf[t])
-            if not (cuda and self.fused_obs) or t == T - 1:
-                self._indices_into(self.idx_buf[t + 1])
+            self._after_step(t, cuda and self.fused_obs)
+
+    def _after_step(self, t, fused_next=False, lo=0, hi=None):
+        """The tail of rollout step t, behind env.step(.., reward_out=rew_buf[t]): stated once for every per-step loop (_rollout_steps and its
+        pipelined form, FactoredA2CRunner._imitate_collect, CnnA2CRunner.collect).
+        With a reward spec that terminates: the step's episode bookkeeping (uavagent_episode_step_f32: ep_r, done_buf[t], the reset mask, the
+        totals of the episodes that ended), then the masked reset of the envs that ended -- unconditionally, no host synchronisation: a
+        mask of zeros resets nothing -- and only then the next observation, so that idx_buf[t + 1], or the fused first layer of step t + 1
+        (which reads the env's observation itself), sees the first state of the new episode.
+        Then the index list of the next observation: not with ``fused_next`` (step t + 1's first layer builds it, fused_obs) unless t is the
+        last step.  ``lo`` / ``hi``: the rows of one half of the pipelined form (never with a terminating spec)."""
+        if self.done_buf is not None:
+            self._episode_step(t)
+            self.env.reset(mask=self._reset_mask)
+        if fused_next and t != self.T - 1:
+            return
+        if hi is None:
+            self._indices_into(self.idx_buf[t + 1])
+        else:
+            from . import _agent_capi as A
+
+            A.obs_indices({k: v[lo:hi] for k, v in self.env.observation().items()}, self.G, self.B, out=self.idx_buf[t + 1][lo:hi])
+
+    def _episode_step(self, t):
+        """Step t's episode bookkeeping from rew_buf[t] and the done the step returned, in place (one launch on the GPU)."""
+        args = (self.rew_buf[t], self.env.out["done"], self.ep_r, self.done_buf[t], self._reset_mask, self._fin_sum, self._fin_cnt)
+        if self.dev.type == "cuda":
+            from . import _agent_capi as A
+
+            A.episode_step(*args)
+        else:
+            episode_step_reference(*args)
 
     def _rollout_steps_persistent(self):
         """The T-step loop as two persistent launches (see persistent_rollout in __init__): the first layer of the state the rollout starts
@@ -775,6 +862,8 @@ class A2CRunner:
         env.copy_state_to(state)
         keep_out = {k: v.clone() for k, v in env.out.items()}
         keep_idx = self.idx_buf[T].clone()
+        # (a terminating spec: the steps also keep the episode bookkeeping)
+        keep_ep = [(v, v.clone()) for v in ((self.ep_r, self._fin_sum, self._fin_cnt) if self.done_buf is not None else ())]
         why = None
         try:
             run()
@@ -790,6 +879,8 @@ class A2CRunner:
             for k, v in keep_out.items():
                 env.out[k].copy_(v)
             self.idx_buf[T].copy_(keep_idx)
+            for v, kept in keep_ep:
+                v.copy_(kept)
         if why is not None:
             self._give_up_persistent("A2CRunner: the persistent rollout kernels did not run side by side (%s: %s); using the per-step launches "
                                      "instead" % (what, why))
@@ -816,8 +907,6 @@ class A2CRunner:
         layer from the observation the half's previous step left (gather), actor head, env step of the half's envs
         (uavenv_step_range).  The heads alternate: head(half 1, t) after head(half 0, t), head(half 0, t + 1) after head(half 1, t); everything
         else overlaps them.  Capturable: the second stream forks from and joins the calling stream through events."""
-        from . import _agent_capi as A
-
         env, T = self.env, self.T
         self.idx_buf[0].copy_(self.idx_buf[T])
         main = torch.cuda.current_stream(self.dev)
@@ -842,8 +931,7 @@ class A2CRunner:
                     last_head = torch.cuda.Event()
                     last_head.record(st)
                     env.step_range(self.act_buf[t], lo, hi - lo, reward_out=self.rew_buf[t])
-                    if t == T - 1:
-                        A.obs_indices({k: v[lo:hi] for k, v in env.observation().items()}, self.G, self.B, out=self.idx_buf[T][lo:hi])
+                    self._after_step(t, True, lo, hi)
         join = torch.cuda.Event()
         join.record(side)
         main.wait_event(join)
@@ -905,6 +993,8 @@ class A2CRunner:
         """After the T steps: episode returns, the bootstrap value v(s_T) (0 where done), the masked reset of the finished envs.
         -> (idx [T,N,K], actions [T,N], rewards [T,N], bootstrap [N]), views of persistent buffers valid until the next collect()."""
         env, T = self.env, self.T
+        if self.done_buf is not None:
+            return self._end_rollout_episodes()
         self.ep_r += self.rew_buf.sum(dim=0)
         boot = self.net.critic_only(self.idx_buf[T]).squeeze(1)                      # :173-176
         boot = torch.where(done, torch.zeros_like(boot), boot)                       # value_estimate = 0 when done
@@ -916,6 +1006,45 @@ class A2CRunner:
             env.reset(mask=done)
             self._indices_into(self.idx_buf[T])
         return self.idx_buf[:T], self.act_buf, self.rew_buf, boot
+
+    def _end_rollout_episodes(self):
+        """_end_rollout with a reward spec that terminates: the steps have kept ep_r, reset the envs that ended (a collision, or MAXSTEP --
+        step_n differs from env to env now, so that end arrives mid-rollout too) and written idx_buf[T] behind the last reset.  Left: the
+        bootstrap, 0 where the LAST step ended its episode (idx_buf[T] is then the next episode's first state), and the statistics of the
+        episodes that ended in this rollout from the per-env totals -- their mean return, the EMA once per rollout as ever, their count."""
+        T = self.T
+        boot = self.net.critic_only(self.idx_buf[T]).squeeze(1)
+        boot = torch.where(self.done_buf[T - 1] != 0, torch.zeros_like(boot), boot)
+        n = int(self._fin_cnt.sum())                                                 # (host sync)
+        self.episodes_ended = n
+        if n:
+            m = float(self._fin_sum.sum()) / n
+            self.last_episode_return = m
+            self.running_r = m if self.running_r is None else 0.99 * self.running_r + 0.01 * m
+            self._fin_sum.zero_()
+            self._fin_cnt.zero_()
+        return self.idx_buf[:T], self.act_buf, self.rew_buf, boot
+
+    def _batch_done(self, rew_buf):
+        """The done rows of the batch ``rew_buf`` belongs to -- the runner's done_buf when it holds one of that batch's shape -- or None:
+        update() keeps its signature, the done rows travel on the runner.  (A [1, m] minibatch view of ppo_update is no such batch: its
+        targets were cut when the whole batch's advantages were computed.)"""
+        d = self.done_buf
+        return d if d is not None and tuple(rew_buf.shape) == tuple(d.shape) else None
+
+    def _nstep_targets(self, rew_buf, boot, fused, out=None):
+        """The n-step value targets [T, N] of a batch for update_fused (``fused``: the kernel) / update_reference (the PyTorch statement):
+        cut at the batch's done rows when the runner holds them (_batch_done), else the plain recursion as ever."""
+        done = self._batch_done(rew_buf)
+        if fused:
+            from . import _agent_capi as A
+
+            if done is None:
+                return A.nstep_returns(rew_buf.contiguous(), boot.contiguous(), self.gamma, out=out)
+            return A.nstep_returns_done(rew_buf.contiguous(), done, boot.contiguous(), self.gamma, out=out)
+        if done is None:
+            return nstep_returns(rew_buf, boot, self.gamma)
+        return nstep_returns_done(rew_buf, done, boot, self.gamma)
 
     def _refresh_transposed(self):
         """The transposed / padded copies of the actor's dense layers the rollout's GEMM kernel reads (three small copies; the captured
@@ -1077,7 +1206,7 @@ class A2CRunner:
         T, N, K = idx_buf.shape
         M, H = T * N, HIDDEN
         b = self._ensure_update_buffers(M, K)
-        target = A.nstep_returns(rew_buf.contiguous(), boot.contiguous(), self.gamma, out=b["target"].view(T, N)).reshape(M)
+        target = self._nstep_targets(rew_buf, boot, True, out=b["target"].view(T, N)).reshape(M)
         idx, act = idx_buf.reshape(M, K).contiguous(), act_buf.reshape(M)
         gv = fl.gv
         hip = self.hip_gemms
@@ -1227,7 +1356,7 @@ class A2CRunner:
         """The same update through autograd (the form round 1 shipped), chunked to bound activation memory; gradients
         accumulate into the flat buffer, TFRMSProp steps on views of the same flat accumulators."""
         T, N, K = idx_buf.shape
-        target = nstep_returns(rew_buf, boot, self.gamma).reshape(T * N, 1)
+        target = self._nstep_targets(rew_buf, boot, False).reshape(T * N, 1)
         idx, act = idx_buf.reshape(T * N, K), act_buf.reshape(T * N)
         M = T * N
         self.flat.zero_grad()
@@ -1271,8 +1400,14 @@ class A2CRunner:
             s["kl_sum"] += float(-dl.sum())
         return losses(prob, v, actions, adv, s["ret"][lo:lo + n], logp_old, self.beta, s["clip"])
 
+    def _with_episodes(self, stats):
+        """``stats`` of a rollout's update; with a reward spec that terminates, ``episodes_ended`` added: the episodes that ended in it."""
+        if self.done_buf is not None:
+            stats["episodes_ended"] = self.episodes_ended
+        return stats
+
     def train_rollout(self):
-        stats = self.update(*self.collect())
+        stats = self._with_episodes(self.update(*self.collect()))
         if self.gemm_tuning and not self._tuning_frozen:
             # every GEMM shape of a rollout + update has now run once eagerly: no timing run may start later (inside a training loop, a
             # graph capture of the host application, or with another pick in another process)
@@ -1362,8 +1497,8 @@ class A2CRunner:
         self._require_ppo()
         self._check_ppo(epochs, clip, lam)
         self._check_minibatches(self.T * self.env.n_envs, epochs, minibatches, target_kl, rows)
-        return self.ppo_update(*self.collect(), epochs=epochs, clip=clip, lam=lam, normalize_adv=normalize_adv, minibatches=minibatches,
-                               target_kl=target_kl, rows=rows)
+        return self._with_episodes(self.ppo_update(*self.collect(), epochs=epochs, clip=clip, lam=lam, normalize_adv=normalize_adv,
+                                                   minibatches=minibatches, target_kl=target_kl, rows=rows))
 
     def _mean_over_ranks(self, x):
         """The mean of a host float over the ranks (itself with one rank), as _normalize_adv exchanges its sums."""
@@ -1413,7 +1548,11 @@ class A2CRunner:
             else:
                 torch.addmm(net.c_b2, b["h1c"], net.c_w2, out=b["h2c"]).clamp_(0.0, 6.0)
             A.rowdot(b["h2c"], net.c_w3, net.c_b3, b["v"])
-            adv, ret = A.gae(rew_buf.contiguous(), b["v"].view(T, N), boot.contiguous(), self.gamma, lam)
+            done = self._batch_done(rew_buf)
+            if done is None:
+                adv, ret = A.gae(rew_buf.contiguous(), b["v"].view(T, N), boot.contiguous(), self.gamma, lam)
+            else:
+                adv, ret = A.gae_done(rew_buf.contiguous(), b["v"].view(T, N), done, boot.contiguous(), self.gamma, lam)
         else:
             net, logp_old, values = self.net, [], []
             for s in range(0, M, self.update_chunk):
@@ -1421,7 +1560,11 @@ class A2CRunner:
                 logp_old.append(self._logp(net.actor_only(idx[s:e]), act[s:e], False))
                 values.append(net.critic_only(idx[s:e]).reshape(-1))
             logp_old = torch.cat(logp_old)
-            adv, ret = gae_reference(rew_buf, torch.cat(values).view(T, N), boot, self.gamma, lam)
+            done = self._batch_done(rew_buf)
+            if done is None:
+                adv, ret = gae_reference(rew_buf, torch.cat(values).view(T, N), boot, self.gamma, lam)
+            else:
+                adv, ret = gae_done_reference(rew_buf, torch.cat(values).view(T, N), done, boot, self.gamma, lam)
         adv, ret = adv.reshape(M), ret.reshape(M)
         if normalize_adv:
             adv = self._normalize_adv(adv)

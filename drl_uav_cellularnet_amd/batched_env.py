@@ -173,7 +173,10 @@ class BatchedMobiEnv:
         step_search / step_coordinate) value the step's OWN reward unless asked otherwise: search_actions, coordinate_actions,
         step_search and step_coordinate take ``shaped=True`` and then value every candidate under the spec (gradient_actions uses no
         reward).  rollout_gated computes the step's own reward inside its persistent kernel and refuses to run while a spec is set.
-        A captured graph holds the spec it was captured with."""
+        A captured graph holds the spec it was captured with.
+        A spec that terminates (``with_collision(.., terminate=True)``): the same launch is uavenv_shape_reward_done and also writes the
+        ``done`` the call returns -- the step's done OR the collision flag; a multi-step call carries the flag in block t's ``done``.  The env
+        only reports: it keeps stepping, as it does past MAXSTEP, and never resets itself; ``reset(mask=done)`` is the caller's."""
         if spec is None:
             self.reward, self._reward_ref = None, None
             return
@@ -185,9 +188,14 @@ class BatchedMobiEnv:
             self.reward_terms = torch.zeros((self.n_envs, _REWARD_TERMS), dtype=torch.float64, device=self.device)
 
     def _shape(self, src_struct, n_steps, first_env, n_envs, terms):
-        """The shaping launch behind a step that wrote through ``src_struct`` (a UavEnvOut): its reward members are overwritten."""
-        rc = self._lib.uavenv_shape_reward(self._h, self._reward_ref, C.byref(src_struct), n_steps, first_env, n_envs, src_struct.reward_dev,
-                                           src_struct.reward_f64_dev, terms.data_ptr(), self._stream())
+        """The shaping launch behind a step that wrote through ``src_struct`` (a UavEnvOut): its reward members are overwritten -- and, with a
+        spec that terminates, its ``done`` member: done | the collision flag (uavenv_shape_reward_done, aliasing the source)."""
+        if self.reward.terminate:
+            rc = self._lib.uavenv_shape_reward_done(self._h, self._reward_ref, C.byref(src_struct), n_steps, first_env, n_envs, src_struct.reward_dev,
+                                                    src_struct.reward_f64_dev, terms.data_ptr(), src_struct.done_dev, self._stream())
+        else:
+            rc = self._lib.uavenv_shape_reward(self._h, self._reward_ref, C.byref(src_struct), n_steps, first_env, n_envs, src_struct.reward_dev,
+                                               src_struct.reward_f64_dev, terms.data_ptr(), self._stream())
         if rc:
             _capi.check(rc)
 
@@ -203,13 +211,16 @@ class BatchedMobiEnv:
         self._shape(src_struct, T, 0, self.n_envs, terms)
         self.reward_terms.copy_(terms[T - 1])
 
-    def shape_reward(self, spec, src=None, out=None, terms=None, first_env=0, n_envs=None):
+    def shape_reward(self, spec, src=None, out=None, terms=None, first_env=0, n_envs=None, done=None):
         """The bare uavenv_shape_reward call on tensors of the caller; neither the env's state nor its spec is touched.  ``src``: a dict
         of device tensors named like ``self.out`` (default: ``self.out``), each [N, ...] or [T, N, ...] as step_many returns them; only
         ``mean_sinr`` / ``mean_sinr_f64``, ``n_out``, ``cur_sinr`` / ``cur_sinr_f64`` and ``bs_xy`` are read, and only those the spec
         needs must be there.  ``out``: a dict with ``reward`` (float32) and / or ``reward_f64`` tensors of shape [N] / [T, N] to write --
         they may be ``src``'s own; default: fresh ones of both.  ``terms``: a float64 [N, 4] / [T, N, 4] tensor, None for a fresh one,
-        False for none.  Only the envs [first_env, first_env + n_envs) are read and written.  Returns ``out`` with ``terms`` added."""
+        False for none.  Only the envs [first_env, first_env + n_envs) are read and written.  Returns ``out`` with ``terms`` added.
+        ``done``: a uint8 [N] / [T, N] tensor -- the call is then uavenv_shape_reward_done: ``done`` takes ``src["done"]`` OR the collision flag
+        of the spec (which needs the collision term; ``spec.terminate`` is not consulted) and may be ``src["done"]`` itself; returned as
+        ``out["done"]``."""
         if not isinstance(spec, RewardSpec):
             raise TypeError("shape_reward takes a rewards.RewardSpec")
         N = self.n_envs
@@ -248,12 +259,21 @@ class BatchedMobiEnv:
         if set(out) - {"reward", "reward_f64"}:
             raise ValueError("shape_reward: out may hold 'reward' and 'reward_f64'")
         cfg = spec.to_config()
-        rc = self._lib.uavenv_shape_reward(self._h, C.byref(cfg), C.byref(st), n_steps, int(first_env), int(N - first_env if n_envs is None else n_envs),
-                                           ptr["reward"], ptr["reward_f64"], ptr["terms"], self._stream())
+        n_envs = int(N - first_env if n_envs is None else n_envs)
+        if done is None:
+            rc = self._lib.uavenv_shape_reward(self._h, C.byref(cfg), C.byref(st), n_steps, int(first_env), n_envs,
+                                               ptr["reward"], ptr["reward_f64"], ptr["terms"], self._stream())
+        else:
+            if done.dtype != torch.uint8 or tuple(done.shape) != T + (N,) or not done.is_contiguous() or done.device != self.device:
+                raise ValueError("shape_reward: done must be a contiguous uint8 tensor of shape %s on the env's device" % (list(T + (N,)),))
+            rc = self._lib.uavenv_shape_reward_done(self._h, C.byref(cfg), C.byref(st), n_steps, int(first_env), n_envs,
+                                                    ptr["reward"], ptr["reward_f64"], ptr["terms"], done.data_ptr(), self._stream())
         if rc:
             _capi.check(rc)
         if terms is not False:
             out["terms"] = terms
+        if done is not None:
+            out["done"] = done
         return out
 
     # ---- injected randomness (parity tests) --------------------------------------------------------

@@ -26,7 +26,7 @@ ENV_EXTRA = {"uavenv_capi.hip": [os.path.join(PKG_DIR, "csrc", "uavenv_path_kern
 DEPS = ENV_SRCS + ENV_HDRS + [h for hs in ENV_EXTRA.values() for h in hs]
 LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB = os.path.join(LIB_DIR, "libuavenv.so")
-AGENT_SRCS = [os.path.join(PKG_DIR, "csrc", f) for f in ("agent_kernels.hip", "agent_learner.hip", "agent_gemm.hip", "agent_factored.hip", "agent_wide.hip", "agent_ppo.hip", "agent_ppo_joint.hip", "agent_optim.hip")]
+AGENT_SRCS = [os.path.join(PKG_DIR, "csrc", f) for f in ("agent_kernels.hip", "agent_learner.hip", "agent_gemm.hip", "agent_factored.hip", "agent_wide.hip", "agent_ppo.hip", "agent_ppo_joint.hip", "agent_optim.hip", "agent_episode.hip")]
 AGENT_SRC = AGENT_SRCS[0]
 AGENT_DEPS = AGENT_SRCS + [os.path.join(PKG_DIR, "csrc", f) for f in ("agent_common.h", "agent_loss_joint.h", "agent_loss_factored.h", "rollout_gate.h")] + [os.path.join(ROOT, "include", "uavagent.h")]
 AGENT_LIB = os.path.join(LIB_DIR, "libuavagent.so")

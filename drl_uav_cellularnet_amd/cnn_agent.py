@@ -316,7 +316,7 @@ class CnnA2CRunner(A2CRunner):
             else:
                 self.act_buf[t] = self._draw_reference(t)
             env.step(self.act_buf[t], reward_out=self.rew_buf[t])
-            self._indices_into(self.idx_buf[t + 1])
+            self._after_step(t)
         done = env.out["done"].bool()
         return self._end_rollout(done, bool(done.any()))
 
@@ -385,7 +385,7 @@ class CnnA2CRunner(A2CRunner):
         M = T * N
         chunk = min(self.update_chunk, M)
         b = self._ensure_update_buffers(chunk, Kn)
-        target = A.nstep_returns(rew_buf.contiguous(), boot.contiguous(), self.gamma).reshape(M)
+        target = self._nstep_targets(rew_buf, boot, True).reshape(M)
         idx, act = idx_buf.reshape(M, Kn).contiguous(), act_buf.reshape(M).contiguous()
         self._refresh_transposed()
         fl.zero_grad()

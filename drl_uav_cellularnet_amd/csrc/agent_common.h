@@ -1,5 +1,5 @@
-// Shared by the eight translation units of libuavagent.so (agent_kernels, agent_learner, agent_gemm, agent_factored, agent_wide, agent_ppo,
-// agent_ppo_joint, agent_optim .hip; not part of the C ABI: hidden visibility): the host helpers every entry point uses, then the device statements more
+// Shared by the nine translation units of libuavagent.so (agent_kernels, agent_learner, agent_gemm, agent_factored, agent_wide, agent_ppo,
+// agent_ppo_joint, agent_optim, agent_episode .hip; not part of the C ABI: hidden visibility): the host helpers every entry point uses, then the device statements more
 // than one unit needs bit for bit.  The loss gradients have headers of their own: agent_loss_joint.h, agent_loss_factored.h.
 #pragma once
 #include <hip/hip_runtime.h>

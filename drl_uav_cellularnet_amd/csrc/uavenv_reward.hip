@@ -36,8 +36,13 @@ struct RewardIn {                                           // block 0 of the st
 //     matrix read front to back, B^2 dependent additions of consecutive LDS words.  Adding +0.0 for the diagonal and for a pair out of range
 //     leaves every bit of S as skipping them does (S is never -0.0: it starts at +0.0, and no p_ij, a difference, is -0.0).
 // The kernel never reads the step's reward, so the outputs may alias it.
+// kDone (uavenv_shape_reward_done): lane e also stores done_out = done_in | the collision flag of env e.  A second instantiation, so that the
+// first keeps its code; its DoneIo is empty.  done_out may be done_in: each row is read and then written by the one lane that owns it.
+template <bool kDone> struct DoneIo {};
+template <> struct DoneIo<true> { const uint8_t *in; uint8_t *out; };
+template <bool kDone>
 __global__ __launch_bounds__(kRewThr) void shape_reward_kernel(UavEnvRewardConfig c, RewardIn in, long long N, int U, int B, int seg, long long first,
-                                                                long long end, float *reward, double *reward64, double *terms) {
+                                                                long long end, float *reward, double *reward64, double *terms, DoneIo<kDone> dn) {
     __shared__ double s_sum[kRewEnvs];
     __shared__ double s_p[kRewEnvs * kRewMaxCells];
     __shared__ int32_t s_bs[kRewEnvs * kRewBsStride];
@@ -121,6 +126,7 @@ __global__ __launch_bounds__(kRewThr) void shape_reward_kernel(UavEnvRewardConfi
         double *o = terms + row * 4;
         o[0] = t0; o[1] = t1; o[2] = t2; o[3] = t3;
     }
+    if constexpr (kDone) dn.out[row] = (uint8_t)((dn.in[row] != 0) | (col && s_hit[tid] != 0));   // mobile_env.py:180: done = collision
 }
 }  // namespace
 
@@ -147,31 +153,53 @@ int uavenv_internal::reward_config_refuses(const UavEnvRewardConfig *cfg, const 
     return UAVENV_OK;
 }
 
-extern "C" int uavenv_shape_reward(uavenv_t *h, const UavEnvRewardConfig *cfg, const UavEnvOut *src, int n_steps, int64_t first_env, int64_t n_envs,
-                                   float *reward_dev, double *reward_f64_dev, double *terms_dev, void *stream) {
-    if (!h || !cfg || !src) return fail(UAVENV_E_INVALID, "shape_reward: null handle, cfg or src");
-    if (!reward_dev && !reward_f64_dev && !terms_dev) return fail(UAVENV_E_INVALID, "shape_reward: no output (reward_dev, reward_f64_dev and terms_dev are all null)");
-    if (int rc = uavenv_internal::reward_config_refuses(cfg, "shape_reward")) return rc;
-    if (n_steps < 1 || n_steps > 65535) return fail(UAVENV_E_INVALID, "shape_reward: n_steps must lie in [1, 65535]");
+// uavenv_shape_reward (done_io null, who = "shape_reward") and uavenv_shape_reward_done: one set of refusals, one launch plan.
+static int shape_reward_launch(const std::string &w, uavenv_t *h, const UavEnvRewardConfig *cfg, const UavEnvOut *src, int n_steps, int64_t first_env,
+                               int64_t n_envs, float *reward_dev, double *reward_f64_dev, double *terms_dev, uint8_t *done_dev, bool with_done, void *stream) {
+    if (!h || !cfg || !src) return fail(UAVENV_E_INVALID, w + ": null handle, cfg or src");
+    if (with_done) {
+        if (!done_dev) return fail(UAVENV_E_INVALID, w + ": null done_dev");
+    } else if (!reward_dev && !reward_f64_dev && !terms_dev) {
+        return fail(UAVENV_E_INVALID, w + ": no output (reward_dev, reward_f64_dev and terms_dev are all null)");
+    }
+    if (int rc = uavenv_internal::reward_config_refuses(cfg, w.c_str())) return rc;
+    if (with_done && !(cfg->collide_threshold >= 0.0)) return fail(UAVENV_E_INVALID, w + ": the collision flag needs collide_threshold >= 0");
+    if (n_steps < 1 || n_steps > 65535) return fail(UAVENV_E_INVALID, w + ": n_steps must lie in [1, 65535]");
     const bool uav_terms = cfg->sep_threshold > 0.0 || cfg->collide_threshold >= 0.0;
-    if ((!src->mean_sinr_dev && !src->mean_sinr_f64_dev) || !src->n_out_dev) return fail(UAVENV_E_INVALID, "shape_reward: src needs mean_sinr (float32 or float64) and n_out");
-    if (cfg->kind == REW_SINR_CAPPED && !src->cur_sinr_dev && !src->cur_sinr_f64_dev) return fail(UAVENV_E_INVALID, "shape_reward: sinr_capped needs src cur_sinr (float32 or float64)");
-    if (uav_terms && !src->bs_xy_dev) return fail(UAVENV_E_INVALID, "shape_reward: the separation and collision terms need src bs_xy");
+    if ((!src->mean_sinr_dev && !src->mean_sinr_f64_dev) || !src->n_out_dev) return fail(UAVENV_E_INVALID, w + ": src needs mean_sinr (float32 or float64) and n_out");
+    if (cfg->kind == REW_SINR_CAPPED && !src->cur_sinr_dev && !src->cur_sinr_f64_dev) return fail(UAVENV_E_INVALID, w + ": sinr_capped needs src cur_sinr (float32 or float64)");
+    if (uav_terms && !src->bs_xy_dev) return fail(UAVENV_E_INVALID, w + ": the separation and collision terms need src bs_xy");
+    if (with_done && !src->done_dev) return fail(UAVENV_E_INVALID, w + ": src needs done");
     const long long N = h->N;
     if (first_env < 0 || n_envs < 0 || first_env > N || n_envs > N - first_env)
-        return fail(UAVENV_E_INVALID, "shape_reward: [first_env, first_env + n_envs) must lie inside the batch");
+        return fail(UAVENV_E_INVALID, w + ": [first_env, first_env + n_envs) must lie inside the batch");
     const int U = (int)h->cfg.n_ue, B = (int)h->cfg.n_bs;
-    if (B > UAVENV_MAX_BS) return fail(UAVENV_E_INVALID, "shape_reward: n_bs above UAVENV_MAX_BS");
+    if (B > UAVENV_MAX_BS) return fail(UAVENV_E_INVALID, w + ": n_bs above UAVENV_MAX_BS");
     DeviceGuard guard(h->device);
-    if (int rc_dev = poisoned(h, "shape_reward")) return rc_dev;
+    if (int rc_dev = poisoned(h, w.c_str())) return rc_dev;
     if (n_envs == 0) return UAVENV_OK;
     const long long blocks = (n_envs + kRewEnvs - 1) / kRewEnvs;
-    if (blocks > 0x7FFFFFFFll) return fail(UAVENV_E_INVALID, "shape_reward: range too large for one launch");
+    if (blocks > 0x7FFFFFFFll) return fail(UAVENV_E_INVALID, w + ": range too large for one launch");
     int seg = 1;
     while (seg < 64 && seg < U) seg <<= 1;
     const RewardIn in{src->mean_sinr_dev, src->mean_sinr_f64_dev, src->n_out_dev, src->cur_sinr_dev, src->cur_sinr_f64_dev, src->bs_xy_dev};
-    hipLaunchKernelGGL(shape_reward_kernel, dim3((unsigned)blocks, (unsigned)n_steps), dim3(kRewThr), 0, (hipStream_t)stream, *cfg, in, N, U, B, seg,
-                       (long long)first_env, (long long)(first_env + n_envs), reward_dev, reward_f64_dev, terms_dev);
+    const dim3 grid((unsigned)blocks, (unsigned)n_steps);
+    if (with_done)
+        hipLaunchKernelGGL(shape_reward_kernel<true>, grid, dim3(kRewThr), 0, (hipStream_t)stream, *cfg, in, N, U, B, seg, (long long)first_env,
+                           (long long)(first_env + n_envs), reward_dev, reward_f64_dev, terms_dev, DoneIo<true>{src->done_dev, done_dev});
+    else
+        hipLaunchKernelGGL(shape_reward_kernel<false>, grid, dim3(kRewThr), 0, (hipStream_t)stream, *cfg, in, N, U, B, seg, (long long)first_env,
+                           (long long)(first_env + n_envs), reward_dev, reward_f64_dev, terms_dev, DoneIo<false>{});
     HIP_TRY(hipGetLastError());
     return UAVENV_OK;
+}
+
+extern "C" int uavenv_shape_reward(uavenv_t *h, const UavEnvRewardConfig *cfg, const UavEnvOut *src, int n_steps, int64_t first_env, int64_t n_envs,
+                                   float *reward_dev, double *reward_f64_dev, double *terms_dev, void *stream) {
+    return shape_reward_launch("shape_reward", h, cfg, src, n_steps, first_env, n_envs, reward_dev, reward_f64_dev, terms_dev, nullptr, false, stream);
+}
+
+extern "C" int uavenv_shape_reward_done(uavenv_t *h, const UavEnvRewardConfig *cfg, const UavEnvOut *src, int n_steps, int64_t first_env,
+                                        int64_t n_envs, float *reward_dev, double *reward_f64_dev, double *terms_dev, uint8_t *done_dev, void *stream) {
+    return shape_reward_launch("shape_reward_done", h, cfg, src, n_steps, first_env, n_envs, reward_dev, reward_f64_dev, terms_dev, done_dev, true, stream);
 }

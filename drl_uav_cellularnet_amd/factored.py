@@ -487,8 +487,7 @@ class FactoredA2CRunner(A2CRunner):
             self._mark("teacher" if tau is None else "soft_targets")
             torch.where(from_teacher[t], self.label_buf[t], self.act_buf[t], out=self.step_buf[t])
             env.step(self.step_buf[t], reward_out=self.rew_buf[t])
-            if not (cuda and self.fused_obs) or t == T - 1:
-                self._indices_into(self.idx_buf[t + 1])
+            self._after_step(t, cuda and self.fused_obs)
             self._mark("env_step")
         done = env.out["done"].bool()
         any_done = bool(done.any())                                                  # (host sync: the rollout's kernels have finished)
@@ -522,7 +521,7 @@ class FactoredA2CRunner(A2CRunner):
             raise ValueError("mix must be in [0, 1]")
         self._imitation_buffers(tau is not None)
         idx, _, rew, boot = self._imitate_collect(teacher, mix, tau, bool(shaped_teacher))
-        return self.imitate_update(idx, rew, boot, soft=tau is not None)
+        return self._with_episodes(self.imitate_update(idx, rew, boot, soft=tau is not None))
 
     def imitate_update(self, idx_buf, rew_buf, boot, soft=False, fused=None):
         """update() in imitation mode on the batch the last imitation rollout left: the teacher's label_buf (``soft``: q_buf) takes the

@@ -16,7 +16,8 @@ Differences, all deliberate and documented in DESIGN.md:
 
 Extension: ``reward=`` a ``rewards.RewardSpec`` -- one of the reference's reward functions (reward_functions.py), optionally with the UAV
 separation and collision terms mobile_env.py:172-184 carries commented out.  ``step`` / ``step_test`` then return that reward, and
-``r_dissect`` holds its four terms [t0, t1, t2, t3] (rewards.py); ``done`` is not changed by a collision.
+``r_dissect`` holds its four terms [t0, t1, t2, t3] (rewards.py); ``done`` is not changed by a collision unless the spec says
+``with_collision(.., terminate=True)`` -- the reference's commented ``done = collision`` (:180): the collision step then returns done = True.
 """
 import copy
 import sys

@@ -19,7 +19,8 @@ AFTER the move, mobile_env.py:157) and ``U`` = nUE.  The terms, in the order of 
         (25 cells, weight 0.5).  Otherwise 0.
     t3  collision, when collide_threshold >= 0:   -collide_penalty if any pair has d_ij <= collide_threshold, else 0.
         Get_if_collide (ue_mobility.py:338-353) as mobile_env.py:176-184 uses it (MIN_BS_DIST = 2, penalty 1).  The commented
-        ``done = collision`` is not provided: ``done`` stays what the step made it.
+        ``done = collision`` (:180) is ``with_collision(.., terminate=True)``: ``done`` becomes the step's done OR that flag
+        (uavenv_shape_reward_done); without it ``done`` stays what the step made it.  ``reward_reference(.., collide=True)`` returns the flag.
 
     reward = ((0.0 + t0) + t1) + t2 + t3;   if use_floor and floor > reward: reward = floor     (max(sum(r_dissect), -1), :189)
 
@@ -52,10 +53,10 @@ class RewardSpec:
     Immutable; ``with_*`` return a new spec.  Build one with ``initial()``, ``perfect()``, ``outage()`` or ``sinr_capped(cap, div)``."""
 
     __slots__ = ("kind", "use_floor", "floor", "sinr_div", "sinr_cap", "cap_div", "sep_threshold", "sep_weight", "collide_threshold",
-                 "collide_penalty")
+                 "collide_penalty", "terminate")
 
     def __init__(self, kind="initial", floor=DEFAULT_FLOOR, sinr_div=DEFAULT_SINR_DIV, sinr_cap=0.0, cap_div=0.0, sep_threshold=0.0,
-                 sep_weight=DEFAULT_SEP_WEIGHT, collide_threshold=-1.0, collide_penalty=DEFAULT_COLLIDE_PENALTY):
+                 sep_weight=DEFAULT_SEP_WEIGHT, collide_threshold=-1.0, collide_penalty=DEFAULT_COLLIDE_PENALTY, terminate=False):
         if kind not in KINDS:
             raise ValueError("RewardSpec: kind must be one of %s (got %r)" % (", ".join(KINDS), kind))
         set_ = object.__setattr__
@@ -69,6 +70,11 @@ class RewardSpec:
         set_(self, "sep_weight", _finite("sep_weight", sep_weight))
         set_(self, "collide_threshold", _finite("collide_threshold", collide_threshold))
         set_(self, "collide_penalty", _finite("collide_penalty", collide_penalty))
+        if not isinstance(terminate, (bool, np.bool_)):
+            raise TypeError("RewardSpec: terminate must be a bool (got %r)" % (terminate,))
+        set_(self, "terminate", bool(terminate))
+        if self.terminate and not self.collide_threshold >= 0.0:
+            raise ValueError("RewardSpec: terminate needs the collision term (with_collision(threshold, penalty, terminate=True))")
         if kind == "initial" and self.sinr_div == 0.0:
             raise ValueError("RewardSpec: sinr_div must not be zero")
         if kind == "sinr_capped" and self.cap_div == 0.0:
@@ -110,11 +116,13 @@ class RewardSpec:
             raise ValueError("RewardSpec: the separation threshold must be positive")
         return self._replace(sep_threshold=threshold, sep_weight=weight)
 
-    def with_collision(self, threshold=DEFAULT_COLLIDE_THRESHOLD, penalty=DEFAULT_COLLIDE_PENALTY):
-        """+ the collision term of mobile_env.py:176-184 (``threshold`` in cells, >= 0; ``done`` is not changed)."""
+    def with_collision(self, threshold=DEFAULT_COLLIDE_THRESHOLD, penalty=DEFAULT_COLLIDE_PENALTY, terminate=False):
+        """+ the collision term of mobile_env.py:176-184 (``threshold`` in cells, >= 0).  ``terminate=True``: a collision step also ends the
+        episode -- the reference's commented ``done = collision`` (:180): the step's ``done`` is OR'd with the flag (uavenv_shape_reward_done).
+        ``penalty`` may be 0 with it: termination without a fine."""
         if not float(threshold) >= 0.0:
             raise ValueError("RewardSpec: the collision threshold must not be negative")
-        return self._replace(collide_threshold=threshold, collide_penalty=penalty)
+        return self._replace(collide_threshold=threshold, collide_penalty=penalty, terminate=terminate)
 
     # ---- what the spec needs and how it travels ----------------------------------------------------------------------
     @property
@@ -126,7 +134,9 @@ class RewardSpec:
         return self.collide_threshold >= 0.0
 
     def as_dict(self):
-        return {k: getattr(self, k) for k in self.__slots__}
+        """The fields by name.  ``terminate`` is listed only when set: a spec that does not terminate keeps the dict, and with it the
+        equality, the hash and the checkpoint entry, it had before the flag existed (from_dict reads a missing flag as False)."""
+        return {k: getattr(self, k) for k in self.__slots__ if k != "terminate" or self.terminate}
 
     @classmethod
     def from_dict(cls, d):
@@ -164,7 +174,7 @@ class RewardSpec:
         if self.has_separation:
             s += ".with_separation(%r, %r)" % (self.sep_threshold, self.sep_weight)
         if self.has_collision:
-            s += ".with_collision(%r, %r)" % (self.collide_threshold, self.collide_penalty)
+            s += ".with_collision(%r, %r%s)" % (self.collide_threshold, self.collide_penalty, ", terminate=True" if self.terminate else "")
         return s
 
 
@@ -183,6 +193,9 @@ def add_reward_arguments(parser):
 
 def spec_from_arguments(args):
     """The RewardSpec the flags of add_reward_arguments describe, or None when none of them asks for anything."""
+    terminate = bool(getattr(args, "terminate_on_collision", False))     # (tools/train_a2c.py adds the flag; the other tools have none)
+    if terminate and args.collide_threshold is None:
+        raise ValueError("--terminate-on-collision needs --collide-threshold")
     if args.reward is None and args.sep_threshold is None and args.collide_threshold is None:
         if args.sinr_cap is not None:
             raise ValueError("--sinr-cap needs --reward sinr-capped")
@@ -199,7 +212,7 @@ def spec_from_arguments(args):
     if args.sep_threshold is not None:
         spec = spec.with_separation(args.sep_threshold, args.sep_weight)
     if args.collide_threshold is not None:
-        spec = spec.with_collision(args.collide_threshold)
+        spec = spec.with_collision(args.collide_threshold, terminate=terminate)
     return spec
 
 
@@ -225,10 +238,11 @@ def _reference_one(spec, mean, n_out, cur, bs_xy, U):
         x = np.where(c > f8(spec.sinr_cap), f8(spec.sinr_cap), c)
         t0, t1 = (x.sum() / Uf) / f8(spec.cap_div), f8(0.0)
     t2, t3 = f8(0.0), f8(0.0)
+    hit = False
     if spec.has_separation or spec.has_collision:
         bs = np.asarray(bs_xy).reshape(-1, 2)
         B = bs.shape[0]
-        S, hit = f8(0.0), False
+        S = f8(0.0)
         for i in range(B):
             for j in range(B):
                 if i == j:
@@ -245,17 +259,21 @@ def _reference_one(spec, mean, n_out, cur, bs_xy, U):
     reward = ((f8(0.0) + t0) + t1) + t2 + t3
     if spec.use_floor and f8(spec.floor) > reward:
         reward = f8(spec.floor)
-    return reward, (t0, t1, t2, t3)
+    return reward, (t0, t1, t2, t3), hit
 
 
-def reward_reference(spec, mean, n_out, cur, bs_xy, n_ue):
+def reward_reference(spec, mean, n_out, cur, bs_xy, n_ue, collide=False):
     """The arithmetic of the module docstring in NumPy float64 -> (reward, terms).  One env: scalars ``mean`` / ``n_out``, ``cur`` [U] (read
     for ``sinr_capped`` only, may be None otherwise), ``bs_xy`` [B, 2] (read for the UAV terms only) -> (float64, float64 [4]).  A batch:
-    ``mean`` / ``n_out`` of any shape S, ``cur`` S + [U], ``bs_xy`` S + [B, 2] -> (float64 S, float64 S + [4])."""
+    ``mean`` / ``n_out`` of any shape S, ``cur`` S + [U], ``bs_xy`` S + [B, 2] -> (float64 S, float64 S + [4]).
+    ``collide=True``: -> (reward, terms, flag), flag = Get_if_collide's answer (a bool, or bool S): any pair with d_ij <= collide_threshold;
+    False without the collision term.  With ``spec.terminate`` it is what the step's ``done`` is OR'd with."""
     U = int(n_ue)
     with np.errstate(all="ignore"):
         if np.ndim(mean) == 0:
-            r, t = _reference_one(spec, mean, n_out, cur, bs_xy, U)
+            r, t, hit = _reference_one(spec, mean, n_out, cur, bs_xy, U)
+            if collide:
+                return np.float64(r), np.array(t, dtype=np.float64), bool(hit)
             return np.float64(r), np.array(t, dtype=np.float64)
         mean, n_out = np.asarray(mean), np.asarray(n_out)
         shape = mean.shape
@@ -263,7 +281,9 @@ def reward_reference(spec, mean, n_out, cur, bs_xy, n_ue):
         m, o = mean.reshape(n), n_out.reshape(n)
         c = None if cur is None else np.asarray(cur).reshape(n, U)
         b = None if bs_xy is None else np.asarray(bs_xy).reshape(n, -1, 2)
-        reward, terms = np.empty(n, np.float64), np.empty((n, TERMS), np.float64)
+        reward, terms, flag = np.empty(n, np.float64), np.empty((n, TERMS), np.float64), np.zeros(n, bool)
         for e in range(n):
-            reward[e], terms[e] = _reference_one(spec, m[e], o[e], None if c is None else c[e], None if b is None else b[e], U)
+            reward[e], terms[e], flag[e] = _reference_one(spec, m[e], o[e], None if c is None else c[e], None if b is None else b[e], U)
+        if collide:
+            return reward.reshape(shape), terms.reshape(shape + (TERMS,)), flag.reshape(shape)
         return reward.reshape(shape), terms.reshape(shape + (TERMS,))

@@ -387,6 +387,32 @@ int uavagent_ppo_shuffle_rows(const int64_t *rows, int64_t n_rows, int64_t n_src
                               int64_t *idx_out, int64_t *act_out, float *adv_out, float *ret_out, float *logp_out,
                               void *stream);
 
+/* ---- Episodes that end inside a rollout (csrc/agent_episode.hip; additive to ABI 5, the number stays).
+ * done u8 [n_steps, n_envs]: non-zero where the step ENDED its env's episode, so that row t + 1 of that env belongs to the next one.
+ * One lane per env, float32, no FMA contraction, no atomics.  Every cut is a select of +0.0f in place of the carried value -- the
+ * arithmetic of a done step is `r + gamma * 0.0f`, not `r` -- so agent.nstep_returns_done / agent.gae_done_reference /
+ * agent.episode_step_reference (torch.where in the same places) hold the same bits.  With done all zero the first two write what
+ * uavagent_nstep_returns_f32 / uavagent_gae_f32 write.  Refusals as for those two, and a null done.  Zero envs or steps: no launch. ---- */
+
+/* run = bootstrap[n];  for t = T-1 .. 0:  nxt = done[t, n] ? 0 : run;  run = r[t, n] + gamma * nxt;  out[t, n] = run. */
+int uavagent_nstep_returns_done_f32(const float *rewards, const uint8_t *done, const float *bootstrap, int64_t n_envs, int32_t n_steps,
+                                    float gamma, float *out, void *stream);
+
+/* next_v = bootstrap[n], adv = 0;  for t = T-1 .. 0:  nv = done ? 0 : next_v;  pa = done ? 0 : adv;  delta = (r + gamma * nv) - v;
+ * adv = delta + (gamma * lam) * pa;  adv_out[t, n] = adv;  ret_out[t, n] = adv + v;  next_v = v.  At a done step values[t + 1] is the
+ * value of the next episode's first state: it does not enter the episode that ended. */
+int uavagent_gae_done_f32(const float *rewards, const float *values, const uint8_t *done, const float *bootstrap, int64_t n_envs,
+                          int32_t n_steps, float gamma, float lam, float *adv_out, float *ret_out, void *stream);
+
+/* One step's episode bookkeeping for n_envs envs, in place of six small launches per step of a rollout loop.  Per env:
+ *   r = ep_r + reward;  d = done != 0;  done_row_out = mask_out = d;
+ *   d:  fin_sum += (double)r;  fin_cnt += 1;  ep_r = 0        else:  ep_r = r.
+ * reward f32, done u8, ep_r f32 (IN / OUT), done_row_out / mask_out u8 (mask_out: what the masked env reset behind this call reads; either
+ * may be `done` itself), fin_sum f64 and fin_cnt i32 (IN / OUT: per-env totals of the episodes that ended, so their order is the order of
+ * the calls; the caller reduces and zeroes them once per rollout); all [n_envs]. */
+int uavagent_episode_step_f32(const float *reward, const uint8_t *done, float *ep_r, uint8_t *done_row_out, uint8_t *mask_out,
+                              double *fin_sum, int32_t *fin_cnt, int64_t n_envs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

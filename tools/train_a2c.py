@@ -162,6 +162,8 @@ def main():
     from drl_uav_cellularnet_amd import rewards
 
     rewards.add_reward_arguments(ap)                                       # --reward / --sinr-cap / --sep-threshold / --sep-weight / --collide-threshold
+    ap.add_argument("--terminate-on-collision", action="store_true", help="a step that leaves two UAVs within --collide-threshold cells ends "
+                    "the env's episode: it is reset inside the rollout and the value targets are cut there (DESIGN.md section 26)")
     a = ap.parse_args()
     try:
         reward = rewards.spec_from_arguments(a)
@@ -241,6 +243,7 @@ def main():
     for ep in range(first_ep, a.episodes):
         imitating = ep < a.imitate_episodes                                # a function of the episode counter alone
         reward_sum, agree, clip_frac, kl, epochs_run, early_stops = 0.0, [], [], [], [], 0
+        episodes_ended = 0                                                 # --terminate-on-collision: env episodes that ended in these rollouts
         norms, n_clipped, n_skipped = [0.0, 0.0], [0, 0], 0                # --max-grad-norm: the episode's gradient norms before clipping
         for r in range(per_episode):
             if imitating:
@@ -258,6 +261,7 @@ def main():
             else:
                 st = runner.train_rollout()
             reward_sum += st["mean_reward"]
+            episodes_ended += st.get("episodes_ended", 0)
             if a.max_grad_norm is not None:                                # (PPO: the last epoch's)
                 n_skipped += int(st["skipped_step"])
                 for i, k in enumerate("ac"):
@@ -281,6 +285,8 @@ def main():
             if a.algo == "ppo" and not imitating:      # epochs_run: averaged over the episode's rollouts; early_stops: rollouts cut short by --ppo-target-kl
                 line.update({"ppo_minibatches": a.ppo_minibatches, "ppo_target_kl": a.ppo_target_kl,
                              "epochs_run": sum(epochs_run) / len(epochs_run), "early_stops": early_stops})
+            if reward is not None and reward.terminate:
+                line["episodes_ended"] = episodes_ended
             if a.max_grad_norm is not None:
                 line.update({"grad_norm_a": st["grad_norm_a"], "grad_norm_c": st["grad_norm_c"], "max_grad_norm_a": norms[0],
                              "max_grad_norm_c": norms[1], "clipped_a": n_clipped[0] / per_episode, "clipped_c": n_clipped[1] / per_episode,
