@@ -25,7 +25,8 @@ EXPORTS = ("uavagent_abi_version", "uavagent_last_error", "uavagent_sparse_rows_
            "uavagent_soft_targets_f32", "uavagent_gae_f32", "uavagent_logp_factored_f32", "uavagent_ppo_loss_grad_factored_workspace_bytes",
            "uavagent_ppo_loss_grad_factored", "uavagent_logp_f32", "uavagent_ppo_loss_grad_workspace_bytes", "uavagent_ppo_loss_grad",
            "uavagent_sumsq_workspace_bytes", "uavagent_sumsq_f32", "uavagent_adam_f32", "uavagent_rmsprop_tf1_clipped",
-           "uavagent_ppo_shuffle_rows", "uavagent_nstep_returns_done_f32", "uavagent_gae_done_f32", "uavagent_episode_step_f32")
+           "uavagent_ppo_shuffle_rows", "uavagent_nstep_returns_done_f32", "uavagent_gae_done_f32", "uavagent_episode_step_f32",
+           "uavagent_mask_move_logits_f32")
 ABI_VERSION = 5
 
 _lib = None
@@ -147,6 +148,7 @@ def load():
         "uavagent_nstep_returns_done_f32": [_P, _P, _P, _I64, _I32, _F, _P, _P],
         "uavagent_gae_done_f32": [_P, _P, _P, _P, _I64, _I32, _F, _F, _P, _P, _P],
         "uavagent_episode_step_f32": [_P, _P, _P, _P, _P, _P, _P, _I64, _P],
+        "uavagent_mask_move_logits_f32": [_P, _I64, _P, _I64, _P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P],
         "uavagent_gate_prepare": [],
     }
     for wide, narrow in (("uavagent_first_layer_wide_f32", "uavagent_first_layer_f32"),
@@ -780,6 +782,42 @@ def logp_factored(logits, actions, n_heads, n_act, out=None):
         rc = load().uavagent_logp_factored_f32(_ptr(logits), ld, _ptr(actions), M, int(n_heads), int(n_act), _ptr(out), _stream(logits.device))
     _check(rc, "uavagent_logp_factored_f32")
     return out
+
+
+MASKED_LOGIT = -3.0e38      # what mask_move_logits writes: the factored kernels' own padding value (csrc/move_mask.h)
+
+
+def mask_move_logits(logits, n_heads, grid_n=0, bs_step=0, min_bs_dist=0, margin=0, idx=None, bits=None, bits_out=None):
+    """The move-masking pass in front of the factored head's kernels (uavagent_mask_move_logits_f32; heuristics.move_mask states the
+    predicate): in place, the logits float32 [M, 5 * n_heads] (possibly a column slice of a wider buffer) of the digits a UAV may not take
+    become MASKED_LOGIT; nothing else is written.  The mask comes from ``idx`` (int64 [M, K >= n_heads] index rows, the UAV cells first:
+    obs_indices; a row with a negative cell stays unmasked) with grid_n / bs_step / min_bs_dist / margin, or from ``bits`` (uint8
+    [M, n_heads], BatchedMobiEnv.action_mask).  ``bits_out`` uint8 [M, n_heads]: the bits applied.  Returns logits."""
+    ld = _row_stride(logits, "logits")
+    M, C_ = logits.shape
+    B = int(n_heads)
+    if C_ != 5 * B:
+        raise UavAgentError("mask_move_logits: logits must have 5 * n_heads = %d columns, got %d" % (5 * B, C_))
+    if (idx is None) == (bits is None):
+        raise UavAgentError("mask_move_logits: exactly one of idx and bits must be given")
+    ld_idx = 0
+    if idx is not None:
+        if idx.dtype != torch.int64 or not idx.is_cuda or idx.dim() != 2 or idx.shape[0] != M or (idx.shape[1] > 1 and idx.stride(1) != 1):
+            raise UavAgentError("mask_move_logits: idx must be an int64 CUDA matrix [M, K] with contiguous rows")
+        if idx.shape[1] < B:
+            raise UavAgentError("mask_move_logits: idx rows must hold the n_heads = %d UAV cells first, got %d entries" % (B, idx.shape[1]))
+        ld_idx = idx.stride(0) if M > 1 else max(idx.stride(0), idx.shape[1])
+    for t, what in ((bits, "bits"), (bits_out, "bits_out")):
+        if t is not None:
+            _u8c(t, what)
+            if t.numel() != M * B:
+                raise UavAgentError("mask_move_logits: %s must be uint8 [M, n_heads]" % what)
+    _same_device("mask_move_logits", logits, idx, bits, bits_out)
+    with torch.cuda.device(logits.device):
+        rc = load().uavagent_mask_move_logits_f32(_ptr(logits), ld, _ptr(idx), ld_idx, _ptr(bits), M, B, int(grid_n), int(bs_step),
+                                                  int(min_bs_dist), int(margin), _ptr(bits_out), _stream(logits.device))
+    _check(rc, "uavagent_mask_move_logits_f32")
+    return logits
 
 
 def ppo_loss_grad_workspace(n_heads, n_act, device):

@@ -90,7 +90,7 @@ class UavEnvStateLayout(C.Structure):
 
 
 EXPORTS = ("uavenv_abi_version", "uavenv_last_error", "uavenv_default_config", "uavenv_create", "uavenv_destroy",
-           "uavenv_init", "uavenv_warmup", "uavenv_reset", "uavenv_reset_trace", "uavenv_step", "uavenv_step_range", "uavenv_rollout_gated", "uavenv_gradient_actions", "uavenv_step_gradient", "uavenv_search_actions", "uavenv_step_search", "uavenv_coordinate_actions", "uavenv_step_coordinate", "uavenv_eval_accumulate", "uavenv_default_rate_config", "uavenv_link_rates", "uavenv_default_reward_config", "uavenv_shape_reward", "uavenv_shape_reward_done", "uavenv_coordinate_actions_shaped", "uavenv_search_actions_shaped", "uavenv_step_coordinate_shaped", "uavenv_step_search_shaped", "uavenv_debug_shaped_variant_count", "uavenv_debug_shaped_variant_info", "uavenv_debug_shaped_variant_reset", "uavenv_step_many", "uavenv_step_seq", "uavenv_step_trace",
+           "uavenv_init", "uavenv_warmup", "uavenv_reset", "uavenv_reset_trace", "uavenv_step", "uavenv_step_range", "uavenv_rollout_gated", "uavenv_gradient_actions", "uavenv_step_gradient", "uavenv_search_actions", "uavenv_step_search", "uavenv_coordinate_actions", "uavenv_step_coordinate", "uavenv_eval_accumulate", "uavenv_default_rate_config", "uavenv_link_rates", "uavenv_default_reward_config", "uavenv_shape_reward", "uavenv_shape_reward_done", "uavenv_action_mask", "uavenv_coordinate_actions_shaped", "uavenv_search_actions_shaped", "uavenv_step_coordinate_shaped", "uavenv_step_search_shaped", "uavenv_debug_shaped_variant_count", "uavenv_debug_shaped_variant_info", "uavenv_debug_shaped_variant_reset", "uavenv_step_many", "uavenv_step_seq", "uavenv_step_trace",
            "uavenv_obs_dense", "uavenv_obs_dense_update", "uavenv_sinr_area", "uavenv_sinr_area_at",
            "uavenv_debug_variant_count", "uavenv_debug_variant_info", "uavenv_debug_variant_reset",
            "uavenv_debug_side_variant_count", "uavenv_debug_side_variant_info", "uavenv_debug_side_variant_reset", "uavenv_debug_rotation_info", "uavenv_debug_path_launches", "uavenv_debug_many_form", "uavenv_debug_many_launches", "uavenv_step_many_prepare", "uavenv_device_error", "uavenv_launch_timing", "uavenv_launch_times_us", "uavenv_debug_schedule",
@@ -144,6 +144,7 @@ def load():
     lib.uavenv_default_reward_config.argtypes = [C.POINTER(UavEnvRewardConfig)]
     lib.uavenv_shape_reward.argtypes = [_P, C.POINTER(UavEnvRewardConfig), C.POINTER(UavEnvOut), C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P]
     lib.uavenv_shape_reward_done.argtypes = [_P, C.POINTER(UavEnvRewardConfig), C.POINTER(UavEnvOut), C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P, _P]
+    lib.uavenv_action_mask.argtypes = [_P, C.c_int32, _P, _P]
     _RC = C.POINTER(UavEnvRewardConfig)
     lib.uavenv_coordinate_actions_shaped.argtypes = [_P, _RC, _P, C.POINTER(UavEnvInject), C.c_int, _P, _P, _P, _P]
     lib.uavenv_search_actions_shaped.argtypes = [_P, _RC, _P, C.POINTER(UavEnvInject), C.c_int, _P, _P, _P, _P]

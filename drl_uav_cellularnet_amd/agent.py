@@ -494,7 +494,10 @@ class A2CRunner:
     def __init__(self, env, net=None, rollout=50, gamma=GAMMA, beta=ENTROPY_BETA, lr_a=LR_A, lr_c=LR_C, seed=6,
                  update_chunk=65536, first_state="obs", collect_launch="graph", fused_update=True, tune_gemms=False, hip_gemms=True,
                  overlap_allreduce=True, fused_head=True, fused_obs=True, pipeline_halves=True, force_exchange=False,
-                 persistent_rollout="auto", optimizer="rmsprop", max_grad_norm=None, adam_betas=(0.9, 0.999), adam_eps=1e-8):
+                 persistent_rollout="auto", optimizer="rmsprop", max_grad_norm=None, adam_betas=(0.9, 0.999), adam_eps=1e-8, mask_margin=None):
+        if mask_margin is not None:      # (factored.FactoredA2CRunner takes the keyword itself and does not pass it on)
+            raise ValueError("%s: mask_margin serves the factored MLP learner (factored.FactoredA2CRunner) only: the joint head's draw is "
+                             "fused into its actor-head kernels" % type(self).__name__)
         self._init_common(env, net if net is not None else ACNet(env.observation_space_dim, env.action_space_dim, seed=seed), rollout, gamma,
                           beta, lr_a, lr_c, seed, update_chunk, first_state, tune_gemms, optimizer, max_grad_norm, adam_betas, adam_eps)
         if collect_launch not in ("graph", "eager"):
@@ -1382,6 +1385,10 @@ class A2CRunner:
         """(a_prob, v) with autograd, for update_reference."""
         return self.net(idx)
 
+    def _actor_prob(self, idx):
+        """The policy output for the index rows ``idx`` in PyTorch (factored.FactoredA2CRunner: under its move mask)."""
+        return self.net.actor_only(idx)
+
     def _losses(self, a_prob, v, actions, v_target):
         """(a_loss, c_loss) of a chunk, for update_reference (a runner with another policy head states its own)."""
         if self._ppo is not None:
@@ -1557,7 +1564,7 @@ class A2CRunner:
             net, logp_old, values = self.net, [], []
             for s in range(0, M, self.update_chunk):
                 e = min(M, s + self.update_chunk)
-                logp_old.append(self._logp(net.actor_only(idx[s:e]), act[s:e], False))
+                logp_old.append(self._logp(self._actor_prob(idx[s:e]), act[s:e], False))
                 values.append(net.critic_only(idx[s:e]).reshape(-1))
             logp_old = torch.cat(logp_old)
             done = self._batch_done(rew_buf)

@@ -762,6 +762,24 @@ class BatchedMobiEnv:
         if rc:
             _capi.check(rc)
 
+    # ---- move mask (heuristics.move_mask states the predicate) -----------------------
+    def action_mask(self, margin=0, out=None):
+        """Which digits each UAV may take from the cells the env holds now (uavenv_action_mask): uint8 [N, nBS], bit d < 4 set = BS_move
+        would commit digit d were everybody else to stay and, with ``margin`` > 0, the destination keeps more than ``margin`` cells from
+        every other UAV; bit 4 (stay) always set.  One launch, no synchronisation.  heuristics.mask_bits_to_allowed gives the
+        [N, nBS, 5] bool view."""
+        N, B = self.n_envs, self.nBS
+        if isinstance(margin, bool) or int(margin) != margin or int(margin) < 0:
+            raise ValueError("margin must be an integer >= 0")
+        if out is None:
+            out = torch.empty((N, B), dtype=torch.uint8, device=self.device)
+        elif out.dtype != torch.uint8 or out.numel() != N * B or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous uint8 [n_envs, nBS] tensor on the env's device")
+        rc = self._lib.uavenv_action_mask(self._h, int(margin), out.data_ptr(), self._stream())
+        if rc:
+            _capi.check(rc)
+        return out
+
     # ---- link rates (channel.py:178-209, 272-385) ---------------------------------------------------
     RATE_WANT = ("dl_sinr_db", "dl_rate", "dl_mcs", "ul_avg_gain", "ul_interference", "ul_sinr_db", "ul_channels", "ul_rate", "ul_mcs",
                  "dl_rate_serving", "ul_rate_serving", "dl_rate_mean", "ul_rate_mean")

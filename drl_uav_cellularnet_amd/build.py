@@ -12,7 +12,7 @@ import sys
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG_DIR)
 SRC = os.path.join(PKG_DIR, "csrc", "uavenv_capi.hip")
-ENV_SRCS = [SRC] + [os.path.join(PKG_DIR, "csrc", f) for f in ("uavenv_host.hip", "uavenv_gated.hip", "uavenv_gradient.hip", "uavenv_eval.hip", "uavenv_search.hip", "uavenv_rates.hip", "uavenv_coordinate.hip", "uavenv_reward.hip", "uavenv_shaped.hip")]     # one object per translation unit: a change to one does not rebuild the others
+ENV_SRCS = [SRC] + [os.path.join(PKG_DIR, "csrc", f) for f in ("uavenv_host.hip", "uavenv_gated.hip", "uavenv_gradient.hip", "uavenv_eval.hip", "uavenv_search.hip", "uavenv_rates.hip", "uavenv_coordinate.hip", "uavenv_reward.hip", "uavenv_shaped.hip", "uavenv_mask.hip")]     # one object per translation unit: a change to one does not rebuild the others
 ENV_HDRS = [os.path.join(PKG_DIR, "csrc", f) for f in ("uavenv_kernels.h", "uavenv_handle.h", "philox.h", "lean_math.h", "intdiv.h",
                                                         "state_layout.h")] + [os.path.join(ROOT, "include", "uavenv.h")]
 _SHAPED_H = os.path.join(PKG_DIR, "csrc", "uavenv_shaped.h")      # the shape axis of the search and coordinate bodies
@@ -22,13 +22,14 @@ ENV_EXTRA = {"uavenv_capi.hip": [os.path.join(PKG_DIR, "csrc", "uavenv_path_kern
              "uavenv_search.hip": [os.path.join(PKG_DIR, "csrc", "uavenv_search_kernel.h"), _SHAPED_H],
              "uavenv_coordinate.hip": [os.path.join(PKG_DIR, "csrc", f) for f in ("uavenv_coordinate_kernel.h", "uavenv_search_kernel.h")] + [_SHAPED_H],
              "uavenv_shaped.hip": [os.path.join(PKG_DIR, "csrc", f) for f in ("uavenv_shaped_kernel.h", "uavenv_coordinate_kernel.h", "uavenv_search_kernel.h")] + [_SHAPED_H],
-             "uavenv_rates.hip": [os.path.join(PKG_DIR, "csrc", "uavenv_rates_kernel.h")]}      # headers of one translation unit only
+             "uavenv_rates.hip": [os.path.join(PKG_DIR, "csrc", "uavenv_rates_kernel.h")],
+             "uavenv_mask.hip": [os.path.join(PKG_DIR, "csrc", "move_mask.h")]}      # headers of one translation unit only
 DEPS = ENV_SRCS + ENV_HDRS + [h for hs in ENV_EXTRA.values() for h in hs]
 LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB = os.path.join(LIB_DIR, "libuavenv.so")
-AGENT_SRCS = [os.path.join(PKG_DIR, "csrc", f) for f in ("agent_kernels.hip", "agent_learner.hip", "agent_gemm.hip", "agent_factored.hip", "agent_wide.hip", "agent_ppo.hip", "agent_ppo_joint.hip", "agent_optim.hip", "agent_episode.hip")]
+AGENT_SRCS = [os.path.join(PKG_DIR, "csrc", f) for f in ("agent_kernels.hip", "agent_learner.hip", "agent_gemm.hip", "agent_factored.hip", "agent_wide.hip", "agent_ppo.hip", "agent_ppo_joint.hip", "agent_optim.hip", "agent_episode.hip", "agent_mask.hip")]
 AGENT_SRC = AGENT_SRCS[0]
-AGENT_DEPS = AGENT_SRCS + [os.path.join(PKG_DIR, "csrc", f) for f in ("agent_common.h", "agent_loss_joint.h", "agent_loss_factored.h", "rollout_gate.h")] + [os.path.join(ROOT, "include", "uavagent.h")]
+AGENT_DEPS = AGENT_SRCS + [os.path.join(PKG_DIR, "csrc", f) for f in ("agent_common.h", "agent_loss_joint.h", "agent_loss_factored.h", "rollout_gate.h", "move_mask.h")] + [os.path.join(ROOT, "include", "uavagent.h")]
 AGENT_LIB = os.path.join(LIB_DIR, "libuavagent.so")
 CNN_SRCS = [os.path.join(PKG_DIR, "csrc", "cnn_kernels.hip")]
 CNN_DEPS = CNN_SRCS + [os.path.join(ROOT, "include", "uavcnn.h")]

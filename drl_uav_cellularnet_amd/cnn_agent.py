@@ -221,8 +221,12 @@ class CnnA2CRunner(A2CRunner):
     PPO = False                   # ppo_rollout / ppo_update raise NotImplementedError: PPO is built for the MLP runners
 
     def __init__(self, env, net=None, rollout=50, gamma=GAMMA, beta=ENTROPY_BETA, lr_a=LR_A, lr_c=LR_C, seed=6, update_chunk=4096,
-                 first_state="obs", fused_update=True, optimizer="rmsprop", max_grad_norm=None, adam_betas=(0.9, 0.999), adam_eps=1e-8):
+                 first_state="obs", fused_update=True, optimizer="rmsprop", max_grad_norm=None, adam_betas=(0.9, 0.999), adam_eps=1e-8,
+                 mask_margin=None):
         import torch.distributed as dist
+
+        if mask_margin is not None:
+            raise ValueError("%s: mask_margin serves the factored MLP learner (factored.FactoredA2CRunner) only" % type(self).__name__)
 
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise RuntimeError("CnnA2CRunner: multi-rank CNN training is not supported (world size %d)" % dist.get_world_size())

@@ -43,7 +43,7 @@ class GreedyEvaluator:
     actor table only), which bounds it to nBS + nUE <= 64 like the index-list gather.  A factored.FactoredACNet takes the MLP route up to 256
     nodes (the wide from-obs gather above 64), its two dense layers through uavagent_gemm_rows_f32 and the greedy digit per UAV.  ``hist`` = (lo, hi, bins) of the serving-SINR histogram in dB."""
 
-    def __init__(self, env, net, hist=(-50.0, 100.0, 150)):
+    def __init__(self, env, net, hist=(-50.0, 100.0, 150), mask_margin=None):
         from . import _agent_capi as A
 
         if env.device.type != "cuda":
@@ -51,6 +51,16 @@ class GreedyEvaluator:
         A.load()
         self.env, self.dev = env, env.device
         self.net = net.to(self.dev)
+        # mask_margin (a factored.FactoredACNet only): the greedy digit per UAV among the digits env.action_mask(margin)
+        # allows -- this evaluator keeps no index list, so the bits come from the env and go to the masking pass as they are
+        if mask_margin is not None:
+            from .factored import check_mask_margin
+
+            mask_margin = check_mask_margin(mask_margin)
+            if not (isinstance(net, ACNet) and getattr(net, "factored", False)):
+                raise ValueError("GreedyEvaluator: mask_margin serves a factored.FactoredACNet only")
+            self._mask_bits = torch.empty((env.n_envs, env.nBS), dtype=torch.uint8, device=self.dev)
+        self.mask_margin = mask_margin
         self.acc = env.eval_accumulators(hist)
         N, U, B = env.n_envs, env.nUE, env.nBS
         NA = int(net.n_action)
@@ -132,6 +142,8 @@ class GreedyEvaluator:
         if self.kind == "mlp_factored":
             A.gemm_rows(self._h1, self._w2t, self._h2, w_transposed=True, bias=net.a_b2, relu6=True)
             A.gemm_rows(self._h2, self._w3t, self._logits_pad, w_transposed=True, bias=self._b3p)
+            if self.mask_margin is not None:
+                A.mask_move_logits(self._logits_pad[:, :NA], net.n_heads, bits=env.action_mask(self.mask_margin, out=self._mask_bits))
             A.choose_factored(self._logits_pad[:, :NA], None, net.n_heads, net.n_act, out=act)
         elif self.kind == "mlp_fused":
             A.actor_head_greedy(self._h1, self._w2t, net.a_b2, self._w3t, self._b3p, NA, self._h2, self._logits_pad, act)

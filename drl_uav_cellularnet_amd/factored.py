@@ -16,6 +16,8 @@ head GEMMs, RMSProp, rollout, checkpoint -- is cnn_agent's (FactoredCnn*) or age
 first layer holds one table row per observation node: beyond 64 nodes (16 UAV + 200 UE = 216) it runs on the 256-node gather and table
 gradient of csrc/agent_wide.hip.  FactoredA2CRunner.ppo_rollout runs PPO on the same update path: GAE(lambda)
 advantages and several clipped-surrogate epochs per rollout on the kernels of csrc/agent_ppo.hip.
+FactoredA2CRunner(mask_margin=m) takes the moves BS_move would not commit, and those ending within m cells of another UAV, out of the
+policy's support: one masking pass (csrc/agent_mask.hip) in front of the draw and the losses.
 """
 import torch
 
@@ -99,6 +101,63 @@ def loss_grad_factored_reference(logits, v, v_target, actions, n_heads, n_act=N_
     logp = (lp * hot).sum(dim=(1, 2))
     a_loss = (-(beta * h + logp * td)).mean()
     return dz, dv, dz.sum(dim=0), (a_loss, (td ** 2).mean(), dv.sum())
+
+
+# ---- move masking: a masked digit's logit counts as -inf -- p = 0, no entropy term, no gradient ------------------------
+def allowed_from_idx(idx, n_heads, grid_n, bs_step, min_bs_dist, margin):
+    """heuristics.move_mask in torch, from index rows: idx int64 [M, K >= n_heads] whose first n_heads entries are the UAV cells x * G + y
+    (agent.obs_to_indices) -> bool [M, n_heads, 5] on idx's device.  A row with a negative cell (first_state="zeros") allows everything,
+    as uavagent_mask_move_logits_f32 leaves it alone."""
+    B, G, s, D, m = int(n_heads), int(grid_n), int(bs_step), int(min_bs_dist), int(margin)
+    c = idx[:, :B]
+    blank = (c < 0).any(dim=1)
+    c = c.clamp(min=0)
+    x, y = torch.div(c, G, rounding_mode="floor"), c % G
+    xy = torch.stack([x, y], dim=-1)                                                        # [M, B, 2]
+    ok = torch.stack([x + s < G, x - s > 1, y + s < G, y - s > 1], dim=-1)                  # [M, B, 4]
+    eye = torch.eye(B, dtype=torch.bool, device=idx.device)
+    d2 = ((xy[:, :, None, :] - xy[:, None, :, :]) ** 2).sum(-1)
+    ok = ok & ~((d2 <= D * D) & ~eye).any(-1)[:, :, None]
+    if m > 0 and B > 1:
+        delta = torch.tensor(((1, 0), (-1, 0), (0, 1), (0, -1)), dtype=torch.int64, device=idx.device) * s
+        dest = xy[:, :, None, :] + delta                                                    # [M, B, 4, 2]
+        e2 = ((dest[:, :, :, None, :] - xy[:, None, None, :, :]) ** 2).sum(-1)             # [M, B, 4, B]
+        ok = ok & ~((e2 <= m * m) & ~eye[:, None, :]).any(-1)
+    allowed = torch.cat([ok, torch.ones_like(ok[:, :, :1])], dim=-1)
+    return allowed | blank[:, None, None]
+
+
+def mask_logits(logits, allowed):
+    """logits [M, B * A] or [M, B, A] with the digits not ``allowed`` (bool [M, B, A]) at -inf, as [M, B, A]: the masked forms of every
+    function of this module are the function itself on these logits (softmax gives p = 0 there: no entropy term, no gradient)."""
+    M, B, A = allowed.shape
+    return logits.reshape(M, B, A).masked_fill(~allowed, float("-inf"))
+
+
+def masked_head_prob(logits, allowed):
+    """Per-head probabilities [M, B, A] under the mask: softmax(mask_logits(logits, allowed)) over the digits."""
+    return torch.softmax(mask_logits(logits, allowed), dim=2)
+
+
+def loss_grad_factored_reference_masked(logits, allowed, v, v_target, actions, beta=ENTROPY_BETA):
+    """loss_grad_factored_reference under the mask ``allowed`` bool [M, B, A]: dlogits is exactly 0 at the masked columns."""
+    M, B, A = allowed.shape
+    return loss_grad_factored_reference(mask_logits(logits, allowed).reshape(M, B * A), v, v_target, actions, B, A, beta)
+
+
+def ppo_loss_grad_factored_reference_masked(logits, allowed, v, ret, adv, logp_old, actions, beta=ENTROPY_BETA, clip=0.2):
+    """ppo_loss_grad_factored_reference under the mask ``allowed`` bool [M, B, A]."""
+    M, B, A = allowed.shape
+    return ppo_loss_grad_factored_reference(mask_logits(logits, allowed).reshape(M, B * A), v, ret, adv, logp_old, actions, B, A, beta, clip)
+
+
+def check_mask_margin(margin):
+    """-> None or the margin as an int >= 0; ValueError otherwise."""
+    if margin is None:
+        return None
+    if isinstance(margin, bool) or int(margin) != margin or int(margin) < 0:
+        raise ValueError("mask_margin must be None or an integer >= 0")
+    return int(margin)
 
 
 # ---- PPO (DESIGN.md section 22): GAE(lambda) advantages and the clipped surrogate in place of the chosen-action term -----------------------
@@ -264,7 +323,9 @@ class FactoredCnnA2CRunner(CnnA2CRunner):
 
     NET_KIND = "cnn-factored"
 
-    def __init__(self, env, net=None, rollout=50, *, seed=6, **kw):
+    def __init__(self, env, net=None, rollout=50, *, seed=6, mask_margin=None, **kw):
+        if mask_margin is not None:
+            raise ValueError("FactoredCnnA2CRunner: mask_margin serves the factored MLP learner (FactoredA2CRunner) only")
         if net is None:
             net = FactoredCnnACNet(env.nBS, env.grid_n, env.N_ACT, seed=seed)
         if not isinstance(net, FactoredCnnACNet):
@@ -312,9 +373,14 @@ class FactoredACNet(ACNet):
         self.n_heads, self.n_act = int(n_bs), int(n_act)
         self.joint_actions = self.n_act ** self.n_heads
 
+    allowed = None      # bool [M, n_heads, n_act] while a masked reference pass runs (FactoredA2CRunner._masked): the digits not in it count as -inf
+
     def _policy_prob(self, logits):
         M = logits.shape[0]
-        return torch.softmax(logits.reshape(M, self.n_heads, self.n_act), dim=-1).reshape(M, self.n_action)
+        z = logits.reshape(M, self.n_heads, self.n_act)
+        if self.allowed is not None:
+            z = mask_logits(z, self.allowed)
+        return torch.softmax(z, dim=-1).reshape(M, self.n_action)
 
 
 class FactoredA2CRunner(A2CRunner):
@@ -327,8 +393,19 @@ class FactoredA2CRunner(A2CRunner):
 
     NET_KIND = "mlp-factored"
     FUSED_OBS_MAX_NODES = 256     # uavagent_first_layer_wide_from_obs_f32
+    mask_margin = None            # the move mask's margin; None = no masking
+    _mask_idx = None              # while update_fused / _ppo_prepare run with a mask: the index rows [M, K] of the logits at hand
 
-    def __init__(self, env, net=None, rollout=50, *, seed=6, **kw):
+    def __init__(self, env, net=None, rollout=50, *, seed=6, mask_margin=None, **kw):
+        # mask_margin: None = no masking, exactly the launches there were; an integer m >= 0 = the digits
+        # heuristics.move_mask forbids under margin m leave the policy's support -- one uavagent_mask_move_logits_f32 launch in front of
+        # the draw (rollout, inside the captured graph), of the loss gradient and of PPO's log pi_old (update), from the batch's own idx rows
+        self.mask_margin = check_mask_margin(mask_margin)
+        if self.mask_margin is not None and int(env.N_ACT) != 5:
+            raise ValueError("FactoredA2CRunner: mask_margin is stated for n_act == 5 (four moves and stay)")
+        self._mask_consts = None      # (grid_n, bs_step, min_bs_dist) of the env's config
+        if self.mask_margin is not None:
+            self._mask_consts = (int(env.grid_n), int(env.cfg.bs_step), int(env.cfg.min_bs_dist))
         if net is None:
             net = FactoredACNet((env.nBS + 1) * env.grid_n * env.grid_n, env.nBS, env.N_ACT, seed=seed)
         if not isinstance(net, FactoredACNet):
@@ -352,14 +429,62 @@ class FactoredA2CRunner(A2CRunner):
             return super()._gather_kernels()
         return A.sparse_rows_sum_wide, A.first_layer_from_obs_wide, A.rows_grad_sort_wide, A.rows_grad_sums_wide
 
+    # ---- move masking ---------------------------------------------------------------------------------------
+    def _mask(self, logits, idx):
+        """The masking pass on ``logits`` (GPU, in place) from the index rows ``idx`` they were computed from."""
+        from . import _agent_capi as A
+
+        G, s, D = self._mask_consts
+        A.mask_move_logits(logits, self.net.n_heads, G, s, D, self.mask_margin, idx=idx)
+
+    def allowed(self, idx):
+        """bool [M, n_heads, 5]: the digits the mask allows for the index rows ``idx`` (the PyTorch statement; all True without a mask)."""
+        if self.mask_margin is None:
+            return torch.ones((idx.shape[0], self.net.n_heads, self.net.n_act), dtype=torch.bool, device=idx.device)
+        G, s, D = self._mask_consts
+        return allowed_from_idx(idx, self.net.n_heads, G, s, D, self.mask_margin)
+
+    def _masked(self, fn, idx):
+        """fn(idx) of the net with the policy output under the mask of ``idx`` (the reference paths)."""
+        if self.mask_margin is None:
+            return fn(idx)
+        self.net.allowed = self.allowed(idx)
+        try:
+            return fn(idx)
+        finally:
+            self.net.allowed = None
+
+    def _actor_prob(self, idx):
+        return self._masked(self.net.actor_only, idx)
+
+    def _reference_forward(self, idx):
+        return self._masked(self.net, idx)
+
+    def _with_mask_idx(self, fn, idx_buf, *args, **kw):
+        if self.mask_margin is None:
+            return fn(idx_buf, *args, **kw)
+        self._mask_idx = idx_buf.reshape(-1, idx_buf.shape[2])
+        try:
+            return fn(idx_buf, *args, **kw)
+        finally:
+            self._mask_idx = None
+
+    def update_fused(self, idx_buf, act_buf, rew_buf, boot):
+        return self._with_mask_idx(super().update_fused, idx_buf, act_buf, rew_buf, boot)
+
+    def _ppo_prepare(self, idx_buf, act_buf, rew_buf, boot, lam, normalize_adv, fused):
+        return self._with_mask_idx(super()._ppo_prepare, idx_buf, act_buf, rew_buf, boot, lam, normalize_adv, fused)
+
     def _draw(self, logits, t, lo, hi):
         from . import _agent_capi as A
 
+        if self.mask_margin is not None:      # (fused_obs: the first layer of this step has just written idx_buf[t])
+            self._mask(logits, self.idx_buf[t][lo:hi])
         A.choose_factored(logits, self.u_buf[t][lo:hi], self.net.n_heads, self.net.n_act, out=self.act_buf[t][lo:hi])
 
     def _draw_reference(self, t):
         net = self.net
-        prob = net.actor_only(self.idx_buf[t]).reshape(-1, net.n_heads, net.n_act)
+        prob = self._actor_prob(self.idx_buf[t]).reshape(-1, net.n_heads, net.n_act)
         return sample_actions_factored(prob, self.u_buf[t])
 
     def _loss_workspace(self):
@@ -372,6 +497,8 @@ class FactoredA2CRunner(A2CRunner):
         if fused:
             from . import _agent_capi as A
 
+            if self._mask_idx is not None:    # the recomputed logits of _ppo_prepare (the rollout's own are masked already: twice is once)
+                self._mask(x, self._mask_idx)
             return A.logp_factored(x, actions, net.n_heads, net.n_act)
         return logp_factored(x.reshape(-1, net.n_heads, net.n_act), actions)
 
@@ -379,6 +506,8 @@ class FactoredA2CRunner(A2CRunner):
         from . import _agent_capi as A
 
         net = self.net
+        if self._mask_idx is not None:
+            self._mask(logits, self._mask_idx)
         if self._ppo is not None:      # ``target`` (the n-step returns update_fused computed) is not used: the batch's GAE returns take its place
             s = self._ppo
             A.ppo_loss_grad_factored(logits, v, s["ret"], s["adv"], s["logp_old"], actions, net.n_heads, net.n_act, self.beta, s["clip"], dv,
@@ -420,7 +549,14 @@ class FactoredA2CRunner(A2CRunner):
     def state_dict(self):
         sd = super().state_dict()
         sd["net"] = self.NET_KIND
+        if self.mask_margin is not None:      # (without a mask the dict keeps exactly the keys it had)
+            sd["mask_margin"] = self.mask_margin
         return sd
+
+    def load_state_dict(self, sd):
+        if sd.get("mask_margin") != self.mask_margin:
+            raise ValueError("checkpoint was written with mask_margin %r, this runner masks with %r" % (sd.get("mask_margin"), self.mask_margin))
+        super().load_state_dict(sd)
 
     # ---- the imitation warm start.  Self-contained: what it needs of the runner is collect()'s pieces (_first_layer,
     # _policy / _draw_reference, _end_rollout), update() and the two loss hooks above. -----------------------------------------------------
@@ -505,6 +641,9 @@ class FactoredA2CRunner(A2CRunner):
         env's call; the soft targets then come from the shaped table) -- refused without a spec, for "gradient" (it uses no reward) and for
         a callable.
         Returns update()'s stats with ``agreement`` added: the fraction of (sample, UAV) pairs whose greedy digit is the teacher's."""
+        if self.mask_margin is not None:
+            raise ValueError("imitate_rollout: imitation under a move mask is not built (a teacher's label may be a masked digit); "
+                             "use a runner with mask_margin=None")
         if not callable(teacher) and teacher not in self.TEACHERS:
             raise ValueError("teacher must be one of %s or a callable teacher(env) -> int64 [n_envs]" % (self.TEACHERS,))
         if shaped_teacher:

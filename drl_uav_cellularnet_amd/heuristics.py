@@ -133,6 +133,50 @@ def frozen_uavs(bs_xy, min_bs_dist):
     return ((d2 <= int(min_bs_dist) ** 2) & ~np.eye(B, dtype=bool)).any(-1)
 
 
+MOVE_DELTAS = ((1, 0), (-1, 0), (0, 1), (0, -1))      # digits 0 .. 3 of BS_move in units of bs_step (ue_mobility.py:221-235); 4 = stay
+
+
+def move_mask(bs_xy, grid_n, bs_step, min_bs_dist, margin):
+    """The move mask of DESIGN.md section 27 (csrc/move_mask.h states it for the kernels), integers only: bs_xy [..., B, 2] integer cells ->
+    bool [..., B, 5].  For UAV b at c_b and digit d < 4 with dest = c_b moved by bs_step:
+        wall   = BS_move's guard fails (x + s < G, x - s > 1, y + s < G, y - s > 1)
+        frozen = some j != b has |c_b - c_j|^2 <= min_bs_dist^2 (frozen_uavs)
+        crowd  = margin > 0 and some j != b has |dest - c_j|^2 <= margin^2
+        allowed[b, d] = not (wall or frozen or crowd);  allowed[b, 4] = True.
+    margin = 0: "UAV b taking d while everybody else stays changes b's cell".  margin >= min_bs_dist + bs_step: from a layout without a
+    frozen pair, no joint action of allowed digits freezes a UAV or is left uncommitted."""
+    bs = np.asarray(bs_xy, np.int64)
+    G, s, m = int(grid_n), int(bs_step), int(margin)
+    if m < 0:
+        raise ValueError("margin must be >= 0")
+    B = bs.shape[-2]
+    x, y = bs[..., 0], bs[..., 1]
+    ok = np.stack([x + s < G, x - s > 1, y + s < G, y - s > 1], axis=-1)                   # [..., B, 4]
+    ok &= ~frozen_uavs(bs, min_bs_dist)[..., None]
+    if m > 0 and B > 1:
+        dest = bs[..., :, None, :] + s * np.asarray(MOVE_DELTAS, np.int64)                 # [..., B, 4, 2]
+        d2 = ((dest[..., :, :, None, :] - bs[..., None, None, :, :]) ** 2).sum(-1)         # [..., B, 4, B(j)]
+        near = (d2 <= m * m) & ~np.eye(B, dtype=bool)[:, None, :]
+        ok &= ~near.any(-1)
+    return np.concatenate([ok, np.ones(ok.shape[:-1] + (1,), dtype=bool)], axis=-1)
+
+
+def mask_bits(allowed):
+    """bool [..., 5] -> uint8 [...], bit d = digit d allowed: the storage form of uavenv_action_mask and uavagent_mask_move_logits_f32."""
+    a = np.asarray(allowed, bool)
+    return (a * (1 << np.arange(a.shape[-1]))).sum(-1).astype(np.uint8)
+
+
+def mask_bits_to_allowed(bits):
+    """uint8 [...] mask bits (NumPy array or torch tensor) -> bool [..., 5] of the same kind."""
+    if isinstance(bits, np.ndarray):
+        return ((bits[..., None] >> np.arange(5, dtype=np.uint8)) & 1).astype(bool)
+    import torch
+
+    sh = torch.arange(5, device=bits.device, dtype=torch.int32)
+    return ((bits.to(torch.int32).unsqueeze(-1) >> sh) & 1).bool()
+
+
 def search_rule(rewards):
     """The one-step search policy's choice from a table of action values: rewards [N, A] -> int64 [N], per row the FIRST maximum
     (the lowest action among equal rewards).  A NaN never wins; a row of NaNs gives 0."""

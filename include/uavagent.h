@@ -413,6 +413,25 @@ int uavagent_gae_done_f32(const float *rewards, const float *values, const uint8
 int uavagent_episode_step_f32(const float *reward, const uint8_t *done, float *ep_r, uint8_t *done_row_out, uint8_t *mask_out,
                               double *fin_sum, int32_t *fin_cnt, int64_t n_envs, void *stream);
 
+/* Move masking for the factored head (n_act == 5: digits 0 +x, 1 -x, 2 +y, 3 -y, 4 stay), a pass IN FRONT of
+ * uavagent_choose_factored_f32, uavagent_logp_factored_f32 and the factored loss gradients: the logits [n_rows, >= 5 * n_heads] of the digits
+ * a UAV may not take are overwritten with -3.0e38f, those kernels' own padding value, under which their exp is 0 exactly -- probability 0,
+ * entropy term 0, gradient 0, never drawn, never the greedy pick.  Only masked columns are written; stay is never masked; masking twice is
+ * masking once.  Exactly one source of the mask:
+ *   idx      int64 rows of ld_idx >= n_heads entries whose first n_heads hold the UAV cells as x * grid_n + y (uavagent_obs_indices).  With
+ *            c_b the cells, s = bs_step, D = min_bs_dist, m = margin, dest = c_b moved by s along digit d < 4:
+ *              wall   = BS_move's guard fails (x + s < G, x - s > 1, y + s < G, y - s > 1)
+ *              frozen = some j != b has |c_b - c_j|^2 <= D^2;   crowd = m > 0 and some j != b has |dest - c_j|^2 <= m^2
+ *              allowed = !(wall | frozen | crowd)               (integers only)
+ *            A row with a negative entry among its n_heads cells is left unmasked.
+ *   bits_in  uint8 [n_rows, n_heads], bit d = digit d allowed (uavenv_action_mask's output); the grid and distance arguments are not read.
+ * bits_out (optional) uint8 [n_rows, n_heads]: the bits applied (bit 4 always set).  One launch, no allocation, no synchronisation: capturable.
+ * Refuses n_heads outside [1, 32], ld_logits < 5 * n_heads, both or neither source, and with idx: ld_idx < n_heads, grid_n outside [1, 32767],
+ * bs_step outside [0, 32767], min_bs_dist or margin outside [0, 65535].  Additive export: the ABI version stays as it is. */
+int uavagent_mask_move_logits_f32(float *logits_inout, int64_t ld_logits, const int64_t *idx, int64_t ld_idx, const uint8_t *bits_in,
+                                  int64_t n_rows, int32_t n_heads, int32_t grid_n, int32_t bs_step, int32_t min_bs_dist, int32_t margin,
+                                  uint8_t *bits_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -437,6 +437,16 @@ int uavenv_shape_reward_done(uavenv_t *h, const UavEnvRewardConfig *cfg, const U
                              float *reward_dev, double *reward_f64_dev, double *terms_dev, uint8_t *done_dev /* [n_steps, N], required */,
                              void *stream);
 
+/* Which digits each UAV may take from the cells the handle holds now -- the cells the next step moves from; valid after reset, step,
+ * set_state and a masked reset.  bits_out_dev uint8 [N, B]: bit d < 4 set = BS_move would commit digit d were every other UAV to stay
+ * (its bound guard holds and no other UAV stands within min_bs_dist of the UAV) AND, with margin > 0, the destination keeps more than
+ * `margin` cells (Euclidean, compared as squared integers) from every other UAV's current cell; bit 4 (stay) always set.  With
+ * margin >= min_bs_dist + bs_step and a layout without a frozen pair, no joint action drawn from the allowed digits freezes a UAV or is
+ * left uncommitted (the argument: DESIGN.md section 27).  The predicate is the one uavagent_mask_move_logits_f32 applies, which takes
+ * these bits as its bits_in.  One launch, no allocation, capturable.  n_act == 5 only; margin in [0, 65535].  Additive export: the ABI
+ * version stays as it is. */
+int uavenv_action_mask(uavenv_t *h, int32_t margin, uint8_t *bits_out_dev, void *stream);
+
 /* Reward-aware look-ahead: the two reward-valuing policies with every candidate valued under `cfg` instead of the step's own reward.  Each call
  * takes the arguments of its unshaped namesake plus the config, refuses what the namesake refuses, and validates `cfg` exactly as
  * uavenv_shape_reward does, before any HIP call.  Additive exports: the ABI version stays as it is.

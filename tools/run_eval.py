@@ -91,7 +91,8 @@ def run_test(trace, out_dir, actor_npz=None, max_step=2000, n_bs=4, n_ue=40, gri
     return {k: np.array(v) for k, v in buf.items()}
 
 
-def run_batched(n_envs, out_dir, trace=None, actor_npz=None, steps=2000, n_bs=4, n_ue=40, grid=100, seed=0x5EED, area_every=500, net="mlp", rates=False, reward=None):
+def run_batched(n_envs, out_dir, trace=None, actor_npz=None, steps=2000, n_bs=4, n_ue=40, grid=100, seed=0x5EED, area_every=500, net="mlp", rates=False, reward=None,
+                mask_margin=None):
     """main_test.py's loop for n_envs envs on the device: GreedyEvaluator.run + the SINR map of env 0 every area_every steps."""
     from drl_uav_cellularnet_amd import BatchedMobiEnv
     from drl_uav_cellularnet_amd.agent import ACNet, load_actor_npz
@@ -115,7 +116,7 @@ def run_batched(n_envs, out_dir, trace=None, actor_npz=None, steps=2000, n_bs=4,
         net = ACNet(env.observation_space_dim, env.action_space_dim)
     if actor_npz:
         load_actor_npz(net, actor_npz)
-    ev = GreedyEvaluator(env, net)
+    ev = GreedyEvaluator(env, net) if mask_margin is None else GreedyEvaluator(env, net, mask_margin=mask_margin)
     areas = []
 
     def after_step(t):
@@ -148,6 +149,8 @@ if __name__ == "__main__":
     ap.add_argument("--n-ue", type=int, default=40)
     ap.add_argument("--envs", type=int, default=None, help="evaluate this many envs at once on the device (GreedyEvaluator)")
     ap.add_argument("--traces", default=None, help="with --envs: int16 cells [T+1, N, U, 2] or [T+1, U, 2] (.npy); default: group mobility")
+    ap.add_argument("--mask-margin", type=int, default=None, help="with --envs and --net mlp-factored: the greedy digit per UAV among the moves the "
+                    "move mask allows at this margin (DESIGN.md section 27; default: no mask)")
     ap.add_argument("--rates", action="store_true", help="with --envs: also report the link rates (dl_rate.npy / ul_rate.npy)")
     from drl_uav_cellularnet_amd import rewards
 
@@ -157,6 +160,8 @@ if __name__ == "__main__":
         reward = rewards.spec_from_arguments(a)
     except ValueError as ex:
         ap.error(str(ex))
+    if a.mask_margin is not None and (a.envs is None or a.net != "mlp-factored" or a.mask_margin < 0):
+        ap.error("--mask-margin (>= 0) is for --envs with --net mlp-factored (GreedyEvaluator(mask_margin=...))")
     if a.make_trace:
         np.save(a.make_trace, make_trace(a.trace_rows, n_ue=a.n_ue))
         print("wrote", a.make_trace)
@@ -165,7 +170,8 @@ if __name__ == "__main__":
         src = a.traces or a.trace
         tr = np.load(src, allow_pickle=False).astype(np.int16) if src else None
         t0 = time.time()
-        res = run_batched(a.envs, a.out, tr, a.actor, a.steps, n_bs=a.n_bs, n_ue=a.n_ue, net=a.net, rates=a.rates, reward=reward)
+        res = run_batched(a.envs, a.out, tr, a.actor, a.steps, n_bs=a.n_bs, n_ue=a.n_ue, net=a.net, rates=a.rates, reward=reward,
+                          mask_margin=a.mask_margin)
         dt = time.time() - t0
         print("eval: %d envs x %d steps in %.1f s (%.3g env-steps/s incl. set-up), mean reward %.4f, mean outage fraction %.4f -> %s" % (
             a.envs, a.steps, dt, a.envs * a.steps / dt, float(res["reward"].mean()), float(res["outage_fraction"].mean()), a.out))

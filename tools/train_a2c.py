@@ -86,6 +86,42 @@ def algo_refusal(checkpoint, algo):
     return None
 
 
+def mask_margin_error(net, mask_margin, imitate_episodes=0):
+    """What is wrong with --mask-margin for this --net, or None."""
+    if mask_margin is None:
+        return None
+    if net != "mlp-factored":
+        return "--mask-margin is for --net mlp-factored (FactoredA2CRunner(mask_margin=...)): the other learners have no move mask"
+    if mask_margin < 0:
+        return "--mask-margin must be >= 0"
+    if imitate_episodes:
+        return "--mask-margin does not go with --imitate-episodes: imitation under a move mask is not built (a teacher's label may be a masked digit)"
+    return None
+
+
+def mask_margin_refusal(checkpoint, mask_margin):
+    """Why --resume must not continue ``checkpoint`` with this --mask-margin, or None.  A checkpoint from before the flag was trained without a mask."""
+    trained = checkpoint.get("mask_margin")
+    if trained != mask_margin:
+        return "train_a2c: the checkpoint was trained with --mask-margin %s, this run asks for %s: refusing to resume" % (
+            "off" if trained is None else trained, "off" if mask_margin is None else mask_margin)
+    return None
+
+
+def mean_frozen_uavs(runner, env):
+    """Mean per env of the UAVs BS_move will not move again (heuristics.frozen_uavs), on the cells the runner's last step moved from (the
+    rollout that ends an episode resets its envs, so the cells behind that step are gone); None where that index row holds no cells."""
+    from drl_uav_cellularnet_amd.heuristics import frozen_uavs
+
+    cells = runner.idx_buf[runner.T - 1][:, :env.nBS].cpu().numpy()
+    if (cells < 0).any():
+        return None
+    G = env.grid_n
+    import numpy as np
+
+    return float(frozen_uavs(np.stack([cells // G, cells % G], axis=-1), int(env.cfg.min_bs_dist)).sum(-1).mean())
+
+
 PPO_NETS = ("mlp", "mlp-factored")      # the runners with ppo_rollout (the CNN runners raise NotImplementedError)
 
 
@@ -159,6 +195,9 @@ def main():
     ap.add_argument("--adam-eps", type=float, default=1e-8)
     ap.add_argument("--adam-beta1", type=float, default=0.9)
     ap.add_argument("--adam-beta2", type=float, default=0.999)
+    ap.add_argument("--mask-margin", type=int, default=None, help="mlp-factored: the moves BS_move would not commit, and with M > 0 those that end "
+                    "within M cells of another UAV, leave the policy's support (DESIGN.md section 27); M >= min_bs_dist + bs_step = 6 keeps "
+                    "every UAV from freezing (default: no mask)")
     from drl_uav_cellularnet_amd import rewards
 
     rewards.add_reward_arguments(ap)                                       # --reward / --sinr-cap / --sep-threshold / --sep-weight / --collide-threshold
@@ -180,6 +219,9 @@ def main():
     if a.imitate_tau is not None and (a.teacher != "coordinate" or not a.imitate_tau > 0):
         ap.error("--imitate-tau must be > 0 and needs --teacher coordinate")
     msg = ppo_flags_error(a.net, a.algo, a.ppo_epochs, a.ppo_clip, a.gae_lambda, a.ppo_minibatches, a.ppo_target_kl)
+    if msg:
+        ap.error(msg)
+    msg = mask_margin_error(a.net, a.mask_margin, a.imitate_episodes)
     if msg:
         ap.error(msg)
     if (a.rollout * a.workers) % a.ppo_minibatches:
@@ -214,7 +256,8 @@ def main():
     elif a.net == "mlp-factored":
         from drl_uav_cellularnet_amd.factored import FactoredA2CRunner
 
-        runner = FactoredA2CRunner(env, rollout=a.rollout, first_state=a.first_state, tune_gemms=not a.no_gemm_tuning, **opt)
+        mask = {} if a.mask_margin is None else {"mask_margin": a.mask_margin}      # (the default run makes the call it always made)
+        runner = FactoredA2CRunner(env, rollout=a.rollout, first_state=a.first_state, tune_gemms=not a.no_gemm_tuning, **opt, **mask)
     elif a.net == "cnn":
         from drl_uav_cellularnet_amd.cnn_agent import CnnA2CRunner
 
@@ -235,6 +278,9 @@ def main():
         if msg:
             sys.exit(msg)
         msg = algo_refusal(sd, a.algo)
+        if msg:
+            sys.exit(msg)
+        msg = mask_margin_refusal(sd, a.mask_margin)
         if msg:
             sys.exit(msg)
         runner.load_state_dict(sd["runner"])
@@ -269,13 +315,15 @@ def main():
                         norms[i] = max(norms[i], st["grad_norm_" + k])
                     n_clipped[i] += int(st["clipped_" + k])
         returns.append(runner.running_r)                                   # GLOBAL_RUNNING_R, :169-172
+        frozen = mean_frozen_uavs(runner, env) if a.net == "mlp-factored" else None
         if rank == 0:
             line = {"episode": ep, "episode_return": runner.last_episode_return, "running_return": runner.running_r,
                     "a_loss": st["a_loss"], "c_loss": st["c_loss"],
                     "mean_reward": st["mean_reward"], "env_steps": (ep + 1) * per_episode * a.rollout * a.workers * world,
                     "seconds": time.time() - t0}
             if a.net == "mlp-factored":
-                line.update({"phase": "imitate" if imitating else a.algo, "episode_mean_reward_per_step": reward_sum / per_episode})
+                line.update({"phase": "imitate" if imitating else a.algo, "episode_mean_reward_per_step": reward_sum / per_episode,
+                             "frozen_uavs": frozen, "mask_margin": a.mask_margin})
                 if imitating:
                     line["agreement"] = agree                               # the teacher agreement of every rollout of the episode
                 elif a.algo == "ppo":                                      # the last epoch's figures, averaged over the episode's rollouts
@@ -297,7 +345,7 @@ def main():
                                                      "teacher_shaped": bool(a.teacher_shaped),
                                                      "algo": a.algo, "ppo_epochs": a.ppo_epochs, "ppo_clip": a.ppo_clip, "gae_lambda": a.gae_lambda,
                                                      "ppo_minibatches": a.ppo_minibatches, "ppo_target_kl": a.ppo_target_kl,
-                                                     "episode": ep, "returns": returns})
+                                                     "mask_margin": a.mask_margin, "episode": ep, "returns": returns})
     if rank == 0:
         os.makedirs(a.out, exist_ok=True)
         np.save(os.path.join(a.out, "Global_return"), np.array([x for x in returns if x is not None], dtype=np.float64))   # :135
