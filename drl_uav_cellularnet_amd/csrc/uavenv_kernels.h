@@ -462,6 +462,18 @@ __device__ __forceinline__ void bs_move_serial(const KParams &p, unsigned a, int
     }
 }
 
+// The four ordered bounce tests and reflections that end a walker's move (ue_mobility.py:490-505).  c[k] report which tests fired.
+__device__ __forceinline__ void wall_reflect(double MAXC, double &x, double &y, bool c[4]) {
+    c[0] = x < 0.0;                           // :490-493
+    if (c[0]) x = -x;
+    c[1] = x > MAXC;                          // :494-497
+    if (c[1]) x = 2.0 * MAXC - x;
+    c[2] = y < 0.0;                           // :498-501
+    if (c[2]) y = -y;
+    c[3] = y > MAXC;                          // :502-505
+    if (c[3]) y = 2.0 * MAXC - y;
+}
+
 // One next() of reference_point_group for one walker (ue_mobility.py:455-505): own step along the heading
 // drawn last tick, group step (+ pull towards the group centre while aggregating), then the four ordered
 // bounce tests.  c[k] report which tests fired (they flip the GROUP heading, once per group and test).
@@ -507,14 +519,16 @@ __device__ __forceinline__ void walker_move(const HotConst &H, const LeanCoef &C
             y = y + H.aggr * sc;
         }
     }
-    c[0] = x < 0.0;                           // :490-493
-    if (c[0]) x = -x;
-    c[1] = x > MAXC;                          // :494-497
-    if (c[1]) x = 2.0 * MAXC - x;
-    c[2] = y < 0.0;                           // :498-501
-    if (c[2]) y = -y;
-    c[3] = y > MAXC;                          // :502-505
-    if (c[3]) y = 2.0 * MAXC - y;
+    if constexpr (ON_DEMAND) {
+        // The four tests on the position as it stands, nothing reflected: the caller reflects inside its rare branch (wall_reflect), which
+        // it enters when some live lane raises one of these.  Where none does, no live lane has x < 0 or y < 0, so the ordered tests would
+        // leave its x and y as they are and give these same four values, all false.  A lane that is not live is reflected only when the
+        // branch runs for somebody else: its position may drift outside the grid for the whole launch.  What keeps it out is the caller's
+        // live_mask on every ballot of these flags (and on the outage and candidate ballots); nothing is indexed by its cell or stored for it.
+        c[0] = x < 0.0; c[1] = x > MAXC; c[2] = y < 0.0; c[3] = y > MAXC;
+    } else {
+        wall_reflect(MAXC, x, y, c);
+    }
 }
 
 // Group owner, end of tick (ue_mobility.py:493-521), in two halves: bounce flips; remaining flight length and arrival redraw.
@@ -648,13 +662,22 @@ __device__ __forceinline__ int argmax_pg(const KParams &p, const double pg[BT], 
 // px = pg[x], supplied by the caller.  The masked sum is an fma with m in {0.0, 1.0}: pg*1 + interf rounds exactly like
 // interf + pg and pg*0 + interf is interf, so the value is that of `interf += (j != x) ? pg[j] : 0.0`; choosing between 0.0
 // and 1.0 takes one v_cndmask (their low words are both zero) where choosing between 0.0 and pg[j] takes two.
-template <int BT, bool FAST>
+// BYSHIFT (BT <= 4; the on-demand block of the pinned multi-step kernels): the same m without compares.  Byte x of `sh` holds 30, the other
+// bytes 0, and 1.0's high word 0x3FF00000 shifted right by 30 is 0: one shift for `sh`, one per UAV with the byte picked by the operand
+// select.  A v_cndmask behind its own v_cmp waits a slot for the lane mask (s_nop), and in that block nothing else is there to fill it.
+template <int BT, bool FAST, bool BYSHIFT = false>
 __device__ __forceinline__ double sinr_db_px(const KParams &p, const HotConst &H, const LeanCoef &C, const double pg[BT], int x, double px) {
     const int B = uav_count<BT, FAST>(p.B);
     double interf = 0.0;
+    static_assert(!BYSHIFT || BT <= 4, "one byte of a 32-bit word per UAV");
+    const uint32_t sh = BYSHIFT ? 30u << (8 * x) : 0u;
 #pragma unroll
     for (int j = 0; j < BT; ++j) {
-        const double m = (j != x && j < B) ? 1.0 : 0.0;
+        double m;
+        if constexpr (BYSHIFT) {
+            const unsigned long long b = (unsigned long long)(j < B ? 0x3FF00000u >> ((sh >> (8 * j)) & 0xFFu) : 0u) << 32;
+            __builtin_memcpy(&m, &b, 8);
+        } else m = (j != x && j < B) ? 1.0 : 0.0;
         interf = fma(pg[j], m, interf);
     }
     return H.db_per_ln * lm_logc(lm_div(px, H.noise + interf), C);   // 10*log10(x) = (10/ln 10) * ln x; both operands normal
@@ -679,17 +702,16 @@ __device__ __forceinline__ void fifo_handover(const HotConst &H, int depth, int 
 }
 // The same push and decision by selects, for the pinned multi-step kernels.  `depth` is a per-env value, so the three cases above are three
 // exec-masked regions of every step (about 45 instructions with their mask bookkeeping, whichever case the lanes are in); as selects the
-// rows cost four v_cndmask and `remain` three compares.  Rows the case does not write keep their value, as above.
-__device__ __forceinline__ void fifo_handover_flat(const HotConst &H, int depth, int best, double bestS, double cur,
-                                                   int &serving, int &r0, int &r1, int &r2) {
+// rows cost four v_cndmask and `remain` three compares.  Rows the case does not write keep their value, as above.  The push alone: it returns
+// whether the lane is a handover candidate (`remain && changed`); the caller decides, with the best UAV's SINR, which it takes only then.
+__device__ __forceinline__ bool fifo_push_flat(int depth, int best, int serving, int &r0, int &r1, int &r2) {
     const bool d1 = depth == 1, d2 = depth == 2, shift = !(d1 || d2);
     const int n0 = shift ? r1 : r0;
     const int n1 = d1 ? best : (shift ? r2 : r1);
     const int n2 = d1 ? r2 : best;
     const bool remain = (n1 == n0) && (d1 || n2 == n0);
     r0 = n0; r1 = n1; r2 = n2;
-    const bool changed = serving != best;
-    if (remain && changed && (bestS - cur > H.ho_thr)) serving = best;
+    return remain && serving != best;
 }
 
 // The kernarg constants of env_finish.  PINNED (the pinned multi-step kernels): held in VGPRs for the whole launch.  Read from the
@@ -1153,11 +1175,15 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
                 const unsigned long long m[4] = {__ballot(c[0]) & live_mask, __ballot(c[1]) & live_mask, __ballot(c[2]) & live_mask,
                                                  __ballot(c[3]) & live_mask};
                 if (__builtin_expect(((m[0] | m[1]) | (m[2] | m[3])) != 0ull, false)) {   // rare, wave-uniform: laid out behind the loop
+                    // walker_move left the position unreflected and c[] unordered: the reflections here, in the reference's order, and the
+                    // second and fourth flag taken again behind the first and third reflection -- the old sequence on the same values
+                    wall_reflect(MAXC, x, y, c);
+                    const unsigned long long mo[4] = {m[0], __ballot(c[1]) & live_mask, m[2], __ballot(c[3]) & live_mask};
                     for (int g = 0; g < Gr; ++g) {
                         const unsigned long long mine = __ballot(gid == g);
 #pragma unroll
                         for (int k = 0; k < 4; ++k)
-                            if ((mine & m[k] & slot_mask) != 0ull) touched[k] |= 1u << g;
+                            if ((mine & mo[k] & slot_mask) != 0ull) touched[k] |= 1u << g;
                     }
                     if (CARRY) { if (live) group_flips(gid, touched, ogc, ogs); }
                     else if (gown) group_flips(ul, touched, ogc, ogs);
@@ -1214,7 +1240,12 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
             rx_power<BT, PLC, FAST, FAST && has_mobility(MODE), X3>(p, H, C, e, tick - 1u, u, live, iu, ix, iy, bsx, bsy, q0, q1, pg);
             double best_pg;
             const int best = argmax_pg<BT, FAST>(p, pg, best_pg);
-            const double bestS = sinr_db_px<BT, FAST>(p, H, C, pg, best, best_pg);
+            // LAZY (the pinned multi-step kernels for up to 4 UAVs): the best UAV's SINR on demand.  Outside a reset its one reader is the handover
+            // test, and that reads it only in a lane whose FIFO rows agree on a UAV that is not the serving one (a candidate: 2.3 % of the
+            // lane-steps of an episode of the shipped scenario).  A step in which no live lane of the wavefront is one skips the interference
+            // sum, the divide and the logarithm (27 % of the wavefront-steps there); any other step evaluates them in all lanes, as before.
+            constexpr bool LAZY = ROOMY && !is_reset(MODE);
+            const double bestS = LAZY ? 0.0 : sinr_db_px<BT, FAST>(p, H, C, pg, best, best_pg);
             if (is_reset(MODE)) {
                 // LTEChannel.reset / GetBestDlBS (channel.py:113-124)
                 cur = bestS;
@@ -1223,8 +1254,20 @@ __device__ __forceinline__ void env_packed_body(char *blob, const long long *act
             } else {
                 // UpdateDroneNet, DL part (channel.py:141-174)
                 cur = sinr_db<BT, FAST>(p, H, C, pg, serving);       // serving UAV BEFORE any handover (:145-146)
-                if (ROOMY) fifo_handover_flat(H, depth, best, bestS, cur, serving, r0, r1, r2);
-                else fifo_handover(H, depth, best, bestS, cur, serving, r0, r1, r2);
+                if constexpr (LAZY) {
+                    const bool candidate = fifo_push_flat(depth, best, serving, r0, r1, r2);
+                    if ((__ballot(candidate) & live_mask) != 0ull) {                         // wave-uniform; a branch of the loop, not behind it
+                        // `best` from its register and not from the argmax compares: their three lane masks would stay alive across the
+                        // branch, and with them the scheduled kernels spilled 59 / 53 SGPRs (bound: 47).  The interference mask by shifts
+                        // (sinr_db_px, BYSHIFT): nothing in this block overlaps a compare's wait states.  Both lean on how this compiler
+                        // allocates: tests/test_many_on_demand_listing.py pins the result (spills <= 47, carrying <= owner lanes), and a
+                        // compiler upgrade that breaks those bounds is to be met here first.
+                        int bb = best;
+                        asm volatile("" : "+v"(bb));
+                        const double bS = sinr_db_px<BT, FAST, true>(p, H, C, pg, bb, best_pg);
+                        if (candidate && (bS - cur > H.ho_thr)) serving = bb;                // :155-167
+                    }
+                } else fifo_handover(H, depth, best, bestS, cur, serving, r0, r1, r2);
             }
             if (DIET) ob = (__ballot(cur <= H.out_thr) & live_mask & slot_mask) >> base;   // (the compare's own mask, `live` one scalar AND)
             else ob = (__ballot(live && (cur <= H.out_thr)) & slot_mask) >> base;          // :116 / :170
