@@ -5,7 +5,7 @@
 // lanes idle), lane t = (row t / n_heads, head t % n_heads); a lane keeps its head for the whole grid-stride loop, so its n_act column sums stay
 // in registers.  The loss kernels differ in their outer loops (PPO's has a barrier on every trip and therefore no `continue`; A2C's and the
 // imitation forms' have neither) and share what is here: the per-head softmax and digit, the per-head tail, the workgroup epilogue and the
-// second launch.  Dword arithmetic throughout: library expf / logf, IEEE division.
+// second launch.  Dword arithmetic throughout: library expf / logf, IEEE division; the chosen digit's log alone is a float64 one (chosen_log).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -49,13 +49,19 @@ __device__ __forceinline__ void head_softmax(int A, float mx, float (&p)[kMaxAct
         p[j] *= inv;
     }
 }
-// log(p_d + e) of digit d alone, for the logp kernel; the loss kernels take it from head_gp's pass over all elements (the same bits).
+// log(p_d + e) of the CHOSEN digit: the float64 logarithm rounded once.  This term is summed over a row's heads and then differenced against
+// another policy's sum (PPO's log rho, approx_kl), and wherever the chosen p is 0 or next to it the argument is one and the same number,
+// 1e-5f: logf returns -11.5129271 there, two float32 steps below the correctly rounded -11.5129251, an error that every such head shares and
+// that therefore adds up over heads and rows instead of averaging out (6.5e-7 per head in approx_kl against float64 on saturated heads).
+// One float64 log per (row, head); the entropy terms of all elements keep logf.
+__device__ __forceinline__ float chosen_log(float ped) { return (float)log((double)ped); }
+// log(p_d + e) of digit d alone, for the logp kernel; the loss kernels take it from head_gp (the same bits).
 __device__ __forceinline__ float head_logq(const float (&pe)[kMaxAct], int d) {
     float ped = 1.f;
 #pragma unroll
     for (int j = 0; j < kMaxAct; ++j)
         if (j == d) ped = pe[j];
-    return logf(ped);
+    return chosen_log(ped);
 }
 
 // Digit `head` of the row's joint action, clamped to [0, a_max]: no action value reaches memory as an index.
@@ -81,7 +87,7 @@ __device__ __forceinline__ long long head_weight(int head, int B, int A) {      
 template <bool SOFT>
 __device__ __forceinline__ float head_gp(const float (&p)[kMaxAct], const float (&pe)[kMaxAct], int d, const float *q, float beta,
                                          float (&gp)[kMaxAct], float &lpa, float &pa) {
-    float h = 0.f;
+    float h = 0.f, ped = 1.f;
     lpa = 0.f; pa = 0.f;
 #pragma unroll
     for (int j = 0; j < kMaxAct; ++j) {
@@ -92,9 +98,10 @@ __device__ __forceinline__ float head_gp(const float (&p)[kMaxAct], const float 
             lpa += q[j] * lp;                             // q == 0 on the padding elements
             gp[j] -= q[j] / pe[j];
         } else {
-            if (j == d) { lpa = lp; pa = p[j]; }
+            if (j == d) { ped = pe[j]; pa = p[j]; }
         }
     }
+    if constexpr (!SOFT) lpa = chosen_log(ped);           // (d lies in [0, A): head_digit)
     return h;
 }
 template <bool SOFT>

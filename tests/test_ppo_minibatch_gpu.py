@@ -90,6 +90,47 @@ def test_shuffle_rows_is_index_select(k):
     assert A.device_error() == 0
 
 
+SHUFFLE_WAVES = 2048 * 4                                                        # csrc/agent_ppo.hip: kShuffleBlocks workgroups of four wavefronts
+
+
+@pytest.mark.parametrize("k", [1, 44, 65, 216])
+def test_shuffle_rows_past_two_trips_is_index_select(k):
+    """More groups of rows than two trips of the 8192 wavefronts hold, and a ragged third trip: twelve rows to a wavefront (k = 1), two
+    (k = 44: 16-byte pieces), one row in two passes over the lanes with 8-byte (k = 65) and with 16-byte pieces (k = 216, the learner's
+    own width).  The guard words, the bit comparison, the clamped ends and the repeat call of test_shuffle_rows_is_index_select."""
+    _need_gpu()
+    from drl_uav_cellularnet_amd import _agent_capi as A
+
+    n_src = 5000
+    src = _source(n_src, k, seed=900 + k)
+    bufs_for = lambda n: [_guarded(n * k, torch.int64), _guarded(n, torch.int64)] + [_guarded(n, torch.float32) for _ in range(3)]
+    assert src[0].data_ptr() % 16 == 0 and bufs_for(1)[0][1].data_ptr() % 16 == 0       # aligned bases: 16-byte pieces where k is even
+    ppr = k // 2 if k % 2 == 0 else k
+    rpw = 64 // min(64, ppr + 4)
+    n_rows = 2 * SHUFFLE_WAVES * rpw + 37
+    n_groups = -(-n_rows // rpw)
+    print("shuffle k=%d: %d pieces per row, %d rows per wavefront, %d rows in %d groups: %.3f trips" % (k, ppr, rpw, n_rows, n_groups,
+                                                                                                     n_groups / SHUFFLE_WAVES))
+    assert n_groups > 2 * SHUFFLE_WAVES and n_groups % SHUFFLE_WAVES != 0
+    rows = _row_list(n_rows, n_src, seed=k + n_rows)
+    assert int(rows[0]) < 0 and int(rows[-1]) >= n_src                          # the clamped ends, the last of them in the ragged trip
+    want = [t.index_select(0, rows.clamp(0, n_src - 1)) for t in src]
+    bufs = bufs_for(n_rows)
+    assert bufs[0][1].data_ptr() % 16 == 0
+    out = tuple(v.view(n_rows, k) if i == 0 else v for i, (_, v) in enumerate(bufs))
+    got = A.ppo_shuffle_rows(rows, *src, out=out)
+    for i, (w, o) in enumerate(zip(want, got)):
+        assert torch.equal(_bits(o), _bits(w)), (k, i)
+    for (raw, v) in bufs:
+        assert _guards_intact(raw, v.numel() * v.element_size()), k
+    first = [o.clone() for o in got]
+    again = A.ppo_shuffle_rows(rows, *src, out=out)                             # a second call: the same bits
+    assert all(torch.equal(_bits(x), _bits(y)) for x, y in zip(first, again))
+    fresh = A.ppo_shuffle_rows(rows, *src)                                      # ... and so do outputs of its own
+    assert tuple(fresh[0].shape) == (n_rows, k) and all(torch.equal(_bits(x), _bits(y)) for x, y in zip(first, fresh))
+    assert A.device_error() == 0
+
+
 @pytest.mark.parametrize("k", [24, 44, 216])
 @pytest.mark.parametrize("where", ["source", "output", "both"])
 def test_shuffle_rows_narrow_branch_gives_the_same_bits(k, where):
